@@ -19,12 +19,25 @@ per-step RCCL observation all-gather north_star mentions is measured beside it a
 (`with_obs_allgather`: on the critical path, and overlapped with the next step through double-buffered
 observation arrays).
 
-Timing.  One timed region = EXACTLY K steps, one kernel launch per step, bracketed by barrier +
-synchronize on both sides, MAX over ranks; inputs are resident in HBM before it starts.  A K-step region
-of 7 us kernels can be as short as 0.15 ms, where host launch ramp and synchronize latency are a fifth of
-the time, so the region is REPEATED (same K, fresh bracket each time) until >= 50 ms have been timed and the
-MEDIAN repeat is reported: ms_per_step = median region wall / K, `repeats` says how many regions ran.
+Timing.  W warm-up steps, then ONE timed region of EXACTLY K steps, one kernel launch per step, bracketed by
+barrier + synchronize on both sides, MAX over ranks; inputs are resident in HBM before it starts:
+ms_per_step = region wall / K.  A K-step region of 7 us kernels can be as short as 0.15 ms, where host
+launch ramp and synchronize latency are a fifth of the time: pick K accordingly.
 Prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR) and
+print the line with its roofline (priced from the same clocks).  Everything else the benchmark measures runs
+only with --full, after the headline: the repeated-region protocol (K-step regions repeated until
+--min-seconds have been timed, median reported under `repeated_regions`), the secondary figures (fused
+rollouts, the other envs, float64, host boundary, single-instance facade, copy bandwidth, 2^27 lanes), the
+rocprofv3 --pmc child passes (roofline.traffic, the fused rollouts' VALU counts), the CPU baseline and, at
+N > 1, the per-rank evidence, the observation all-gather legs, the same-box N = 1 run and the group leg.
+
+--dump-outputs DIR writes what the timed path computed in its last step — what gymnet_vecenv_read hands a
+caller: observation [N, D], reward [N], done [N] (as 0 / 1) — as DIR/<name>.npy in float32 (float64
+observations in --dtype f64), right after the timed region.  The inputs (reset draws, action ring) are seeded,
+so two builds run with the same arguments can be compared output for output.  Above 64 MB in all, a fixed
+seeded sample of lanes is written instead, with the lane indices in DIR/lanes.npy.
 """
 import argparse
 import json
@@ -39,7 +52,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0     # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 achievable)
-MIN_TIMED_SECONDS = 0.05   # repeat the K-step region until this much has been timed
+MIN_TIMED_SECONDS = 0.05   # --full: repeat the K-step region until this much has been timed
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all (else a seeded sample of lanes)
 MAX_REPEATS = 2000
 # Exit status of every rank when a SECONDARY section (the optional observation all-gather, the teardown) hung and the watchdog
 # fired: NON-ZERO.  A GPU process whose collective hung must not leave with status 0.  The headline has been measured
@@ -66,7 +80,12 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU baseline sample")
     p.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even at world size 1 "
                    "(exercises the collective code path on a 1-GPU box)")
-    p.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS)
+    p.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS, help="--full: time repeated K-step regions until this "
+                   "much has been timed (`repeated_regions`); the headline is always ONE K-step region")
+    p.add_argument("--full", action="store_true", help="also run everything beyond the headline: repeated regions, secondary figures, "
+                   "profiler child passes, CPU baseline, N > 1 legs (off: the line carries the headline and its roofline only)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write the timed path's last-step outputs (observation, reward, "
+                   "done) as DIR/<name>.npy")
     p.add_argument("--no-overlap", action="store_true", help="N > 1: single observation buffer (no gather/step overlap)")
     p.add_argument("--no-group-leg", action="store_true", help="N > 1: skip the single-process gymnet_group_* leg")
     p.add_argument("--no-host-boundary", action="store_true", help="skip the NDArray-shaped host path figure (gymnet_vecenv_step)")
@@ -267,7 +286,7 @@ def measure_traffic(args, wide16=True, timeout=90):
     /opt/skills/guides/MI355X_MICROARCH.md prescribes — FETCH_SIZE and WRITE_SIZE in SEPARATE rocprofv3 --pmc passes (no trace
     flags beside --pmc), bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (both count KiB; on gfx950 FETCH_SIZE reports half the bytes
     of a wide coalesced streaming read).  Each pass is a fresh CHILD process (`rocprofv3 ... -- python3 bench.py ...`: the
-    program after `--` is python3 itself, started with subprocess — never an exec from this GPU process) running 10 + 3 x 100
+    program after `--` is python3 itself, started with subprocess — never an exec from this GPU process) running 10 + 100
     eager launches of the same kernel on the same batch.  Returns (bytes per launch, description); raises on any failure — the
     caller then falls back to the committed constant and says so."""
     import shutil
@@ -497,6 +516,27 @@ def median(xs):
     return s[m] if len(s) % 2 else 0.5 * (s[m - 1] + s[m])
 
 
+def dump_outputs(local, out_dir, suffix=""):
+    """--dump-outputs: the last step's outputs as a caller of the path receives them (gymnet_vecenv_read), float32 / float64 .npy
+    files; above DUMP_MAX_BYTES a fixed seeded sample of lanes (sorted, indices in lanes<suffix>.npy).  Returns the names written."""
+    import numpy as np
+    got = local.Read()
+    obs = np.asarray(got.Observation)
+    obs = obs if obs.dtype == np.float64 else obs.astype(np.float32)
+    arrays = {"observation": obs, "reward": np.asarray(got.Reward, dtype=np.float32), "done": np.asarray(got.Done, dtype=np.float32)}
+    n = obs.shape[0]
+    per_lane = sum(a.nbytes for a in arrays.values()) / max(1, n)
+    if per_lane * n > DUMP_MAX_BYTES:
+        m = int(DUMP_MAX_BYTES // (per_lane + 8))
+        lanes = np.sort(np.random.default_rng(0x5EED).choice(n, size=m, replace=False))
+        arrays = {k: a[lanes] for k, a in arrays.items()}
+        arrays["lanes"] = lanes.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+    return sorted(k + suffix for k in arrays)
+
+
 def measure_host_boundary(pkg, env_name, n, device, seed, algorithmic_bytes, steps=20):
     """ms per host-boundary step (actions in, observations / reward / done out over PCIe), median of `steps` calls."""
     import numpy as np
@@ -665,6 +705,8 @@ def main():
     n = args.num_envs
     ring = max(2, args.ring + (args.ring % 2))
     K, W = args.steps, args.warmup
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     seed = 0x5EED
     # a non-default stream: the engine orders all of its work on it, and torch.cuda.Event timing below
     # records on the same stream (the null stream would make the library create a private one)
@@ -735,14 +777,15 @@ def main():
 
     def timed_region(fn, events=True):
         """One bracketed region: barrier + synchronize, fn(), synchronize + barrier.  Returns (wall s, event ms or -1).
-        events=False leaves the two HIP-event records (a few host us each) out of the wall-clock bracket."""
+        The opening event is recorded before the wall clock starts and the closing one while the device is still busy with
+        fn()'s launches, so their host cost stays out of the wall bracket; events=False records none."""
         if events:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize(dev)
         barrier()
-        t0 = time.perf_counter()
         if events:
             e0.record(stream)
+        t0 = time.perf_counter()
         fn()
         if events:
             e1.record(stream)
@@ -769,21 +812,28 @@ def main():
             rows = [(float(a), float(b)) for a, b in tw.tolist()]
         return rows
 
-    run(W)
+    if W > 0:
+        run(W)
     torch.cuda.synchronize(dev)
     steps_before = local.Counters()["lane_steps"]
     own_rows = []
-    rows = repeat_until(lambda: run(K), args.min_seconds)
-    headline_rows = list(own_rows)                               # the headline's regions (later repeat_until calls overwrite own_rows)
-    bare = [r[0] for r in rows if r[1] < 0] or [r[0] for r in rows]          # regions without event records
-    walls = bare
-    wall = median(bare)
-    ev_ms = median([r[1] for r in rows if r[1] >= 0])
-    repeats = len(rows)
+    # the headline: ONE bracketed region of exactly K steps (MAX over ranks)
+    headline_rows = [timed_region(lambda: run(K))]               # this rank's own clocks
+    rows = headline_rows
+    if use_dist:
+        tw = torch.tensor(rows, dtype=torch.float64, device=red_dev)
+        dist.all_reduce(tw, op=dist.ReduceOp.MAX)
+        rows = [(float(a), float(b)) for a, b in tw.tolist()]
+    wall, ev_ms = rows[0]
+    walls = [wall]
+    repeats = 1
 
-    # sanity: the engine really ran K steps on every lane in every repeat
+    # sanity: the engine really ran K steps on every lane
     c = local.Counters()
-    assert c["lane_steps"] - steps_before == repeats * K * n, (c, steps_before, repeats)
+    assert c["lane_steps"] - steps_before == K * n, (c, steps_before, K)
+    # the timed path's outputs, before anything else steps this handle
+    if args.dump_outputs:
+        dump_outputs(local, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     # CartPole: 41 B; float64 mode: 73 B (32 + 4 read, 32 + 4 + 1 written).  Envs that store a state row once,
     # in the observation (Pendulum 33 of 37 B, Acrobot 57 of 65 B), are priced on the bytes they MOVE: the
@@ -829,7 +879,7 @@ def main():
                                                          (parse_policy(args.policy).get("graph", -1) != 0 and n * bytes_per_step < (24 << 20)))
                                    else "back-to-back stream launches")),
                        "launch_policy": launch_policy,
-                       "timing": f"median of {repeats} bracketed {K}-step regions (>= {args.min_seconds * 1e3:.0f} ms timed in total)",
+                       "timing": f"one bracketed {K}-step region after {W} warm-up steps (synchronize on both sides)",
                        "backend": ("rccl" if backend == "nccl" else backend + " (ranks SHARE the GPUs that exist: plumbing check, not a multi-GPU measurement)") if use_dist else "single process",
                        "barrier": ("shared-memory spin barrier (ranks of one node)" if node_barrier is not None else
                                    ("process-group barrier" if use_dist else "none (one rank)")),
@@ -857,13 +907,24 @@ def main():
     out = headline() if rank == 0 else {}
     emitted = threading.Lock()
 
+    # --full: the repeated-region protocol beside the headline — the K-step region repeated until --min-seconds have been
+    # timed, the median reported (a steadier figure at small K than the single headline region)
+    if args.full:
+        rrows = repeat_until(lambda: run(K), args.min_seconds)
+        rbare = [r[0] for r in rrows if r[1] < 0] or [r[0] for r in rrows]
+        if rank == 0:
+            out["repeated_regions"] = {"repeats": len(rrows), "ms_per_step": median(rbare) * 1e3 / K, "value": n * world * K / median(rbare),
+                                       "region_ms_median": median(rbare) * 1e3, "region_ms_min": min(rbare) * 1e3, "region_ms_max": max(rbare) * 1e3,
+                                       "launch_us_by_events": median([r[1] for r in rrows if r[1] >= 0]) * 1e3 / K,
+                                       "timing": f"median of {len(rrows)} bracketed {K}-step regions (>= {args.min_seconds * 1e3:.0f} ms timed in total)"}
+
     def emit_and_exit_on_timeout(section, seconds):
         return make_watchdog(rank, out, emitted, section, seconds)
 
     # N > 1: what each rank ran on and measured by itself, and proof that the collective backend really spans `world` ranks.
     # Nothing here may cost the headline: a rank that cannot describe itself still takes part in both collectives (so nobody
     # waits for it), and the section runs under the watchdog.
-    if use_dist:
+    if use_dist and args.full:
         watchdog = emit_and_exit_on_timeout("ranks", 90)
         mine = {"rank": rank, "local_rank": local_rank, "device": dev_index, "pid": os.getpid()}
         try:
@@ -887,7 +948,7 @@ def main():
         watchdog.cancel()
 
 
-    extras = rank == 0 and world == 1 and not args.no_extras and not gather_in_region and not f64
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and not gather_in_region and not f64
     # Cross-check of the per-launch figure: 200 single launches, each bracketed by its own HIP-event pair on the
     # engine's stream (isolated launches: no back-to-back overlap with a neighbour's ramp / drain).
     single_us = None
@@ -1129,7 +1190,7 @@ def main():
     # (a) with the gather on the critical path, (b) overlapped with the next step (double-buffered observation arrays:
     # step t+1 writes buffer B while the gather of buffer A is in flight on a side stream).
     gathered = None
-    if use_dist and not gather_in_region:
+    if use_dist and args.full and not gather_in_region:
         gathered = {}
         gs = 128
         watchdog = emit_and_exit_on_timeout("with_obs_allgather", int(os.environ.get("GYMNET_BENCH_WATCHDOG", "120")))
@@ -1261,7 +1322,7 @@ def main():
         # legs below — a fresh child process and a CPU run — can no longer lose a measurement that already exists
         sys.stderr.write("[bench] headline so far: " + json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "ms_per_step") if k in out}) + "\n")
         sys.stderr.flush()
-        if world > 1:
+        if world > 1 and args.full:
             time.sleep(1.0)                                      # the other ranks are exiting
             # N = 1 on THIS box, same kernel, same K / repeats protocol without the ranks: value / (N x this) is the weak-scaling
             # efficiency measured inside one run (the driver computes its own from its separate N = 1 run)
@@ -1290,7 +1351,7 @@ def main():
                 out["same_box_n1"] = {"error": repr(e)[:300]}
             if not args.no_group_leg and not gather_in_region:
                 out["group_single_process"] = run_group_child(args, world, timeout=180)
-        if world == 1 and not args.no_traffic and not args.no_extras and not gather_in_region:
+        if args.full and world == 1 and not args.no_traffic and not args.no_extras and not gather_in_region:
             try:
                 # the guide's 2x FETCH_SIZE correction holds for 16-byte-per-lane reads: 4 float / 2 double lanes per thread
                 wide16 = launch_policy["envs_per_thread"] * (8 if f64 else 4) == 16
@@ -1344,7 +1405,7 @@ def main():
                                                                  "256-step time; both are model fractions good to a few percent (DESIGN.md §5)")
             except Exception as e:                               # noqa: BLE001 - a secondary figure never costs the headline
                 out["fused_rollout"]["roofline_error"] = repr(e)[:300]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, args.cpu_seconds)
                 if world > 1:

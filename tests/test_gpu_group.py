@@ -295,12 +295,13 @@ def test_plain_bench_gpus_2_spawns_its_own_ranks(gpu_pkg):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--ring", "8",
-                        "--num-envs", str(1 << 18)], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+                        "--num-envs", str(1 << 18), "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
     j = json.loads(lines[0])
-    assert j["n_gpus"] == 2 and j["steps"] == 20 and j["warmup"] == 5 and j["repeats"] >= 3 and j["scaling"] == "weak"
+    assert j["n_gpus"] == 2 and j["steps"] == 20 and j["warmup"] == 5 and j["repeats"] == 1 and j["scaling"] == "weak"
+    assert j["repeated_regions"]["repeats"] >= 3 and j["repeated_regions"]["value"] > 1e8
     assert j["config"]["global_num_envs"] == 2 << 18 and j["value"] > 1e8
     import torch
     if torch.cuda.device_count() < 2:
@@ -342,7 +343,7 @@ def test_bench_under_the_launcher_the_driver_uses(gpu_pkg):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "20", "--warmup", "5", "--ring", "8", "--num-envs", str(1 << 18),
-                        "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -539,11 +540,12 @@ def test_group_flags_validation_and_bookkeeping(gpu_pkg, oracle):
 
 @pytest.mark.gpu
 def test_driver_shaped_bench_line_carries_the_contract(gpu_pkg):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` — the driver's N = 1 command — prints ONE JSON line with the contract's
-    keys, the `roofline` and `cpu_baseline` objects, and the secondary figures (none of which may ever be `value`)."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` — the driver's N = 1 command with everything beyond the headline —
+    prints ONE JSON line with the contract's keys, the `roofline` and `cpu_baseline` objects, and the secondary figures (none of
+    which may ever be `value`)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1",
+                        "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -584,3 +586,37 @@ def test_driver_shaped_bench_line_carries_the_contract(gpu_pkg):
     assert f64["kernel"] == "step_kernel_pipe2<CartPole64,4,true,15>" and f64["bytes_per_env_step"] == 73 and 0.3 < f64["frac_of_peak"] < 1.0
     assert f64["env_steps_per_sec"] < j["value"]                                          # beside, never as, `value`
     assert j["hbm_resident_2p27"]["num_envs"] == 1 << 27 and 0.5 < j["hbm_resident_2p27"]["frac_of_peak"] < 1.0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_its_outputs_repeat(gpu_pkg, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` — the plain run: exactly K timed steps in one region, the
+    contract's keys and the roofline priced from the same clock, none of the --full sections; the last step's observation / reward /
+    done land in DIR as float32 .npy, and a second run with the same arguments writes the same arrays bit for bit."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    got = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "64", "--warmup", "8",
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["metric"] == "env-steps/sec" and j["unit"] == "env-steps/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["steps"] == 64 and j["warmup"] == 8 and j["repeats"] == 1
+        assert abs(j["value"] - (1 << 20) / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        assert abs(j["region_ms_median"] - 64 * j["ms_per_step"]) < 1e-9 * j["region_ms_median"]
+        assert j["roofline"]["launch_us"] > 0 and abs(j["roofline"]["achieved"] - 41 * (1 << 20) / (j["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * j["roofline"]["achieved"]
+        for k in ("cpu_baseline", "fused_rollout", "repeated_regions", "hbm_resident_2p27", "other_configs_2p20", "host_boundary"):
+            assert k not in j, k
+        arrays = {k: np.load(d / f"{k}.npy") for k in ("observation", "reward", "done")}
+        assert sorted(os.listdir(d)) == ["done.npy", "observation.npy", "reward.npy"]
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["observation"].shape == (1 << 20, 4) and arrays["reward"].shape == arrays["done"].shape == (1 << 20,)
+        assert np.isfinite(arrays["observation"]).all() and set(np.unique(arrays["done"]).tolist()) <= {0.0, 1.0}
+        assert 0 < arrays["done"].sum() < (1 << 20)
+        got.append(arrays)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k

@@ -4,6 +4,7 @@ closed forms, symmetry, the committed golden vectors and the published Philox kn
 The reference pins nothing for CartPole (tests/Gym.Tests/Envs/Classic/CartpoleEnvironment.cs:14-35
 asserts nothing) => parity unpinned; these tests are what stands in for the missing pins.
 """
+import json
 import math
 import os
 
@@ -374,26 +375,42 @@ def test_reset_stream_is_uniform_across_lanes_and_across_ticks(oracle):
         assert np.abs(np.corrcoef(sample.astype(np.float64))[np.triu_indices(4, 1)]).max() < 4.0 / np.sqrt(x.size)
 
 
-def test_restatement_token_stream_equals_the_reference_text():
-    """oracle/check_against_reference.py: the C restatement's Step assignments, reward machine, Reset and constants against
-    the TEXT of CartPoleEnv.cs under /root/reference (build container only; the GPU box has no reference tree).  It does not
-    lift "parity unpinned" (nothing runs the C#), it removes transcription slips — and a seeded slip must be caught."""
+def _reference_text_facts():
+    """tests/golden/reference_text_facts.json: data taken from the reference's source text by
+    tests/golden/make_reference_text_facts.py (token-stream digests, evaluated constants and arguments; none of the text)."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_text_facts.json")) as f:
+        return json.load(f)
+
+
+def _token_digest(tokens):
+    import hashlib
+    return hashlib.sha256(" ".join(tokens).encode()).hexdigest()
+
+
+def test_restatement_token_stream_equals_the_reference_text(oracle):
+    """oracle/check_against_reference.py: the C restatement's Step assignments and reward machine reduce to the same canonical token
+    streams as CartPoleEnv.cs (compared through the SHA-256 digests tests/golden/reference_text_facts.json records of the reference's
+    streams), the text selects the Euler integrator, and the built oracle's constants are the text's binary32 initialisers.  It does
+    not lift "parity unpinned" (nothing runs the C#), it removes transcription slips — and a seeded slip must be caught."""
     import importlib.util
-    ref = "/root/reference/src/Gym.Environments/Envs/Classic/CartPoleEnv.cs"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present (GPU box)")
     spec = importlib.util.spec_from_file_location("check_against_reference", os.path.join(ROOT, "oracle", "check_against_reference.py"))
     chk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(chk)
-    assert chk.main() == 0
+    facts = _reference_text_facts()
+    want = facts["step_digests"]
+    assert facts["integrator"] == "euler" and set(want) == set(chk.STEP_VARS)
     c = open(os.path.join(ROOT, "oracle", "classic_control_ref.c")).read()
-    want, _, integ = chk.reference_step(open(ref, encoding="utf-8-sig").read())
-    assert integ == "euler"
+    mine, machine = chk.restatement_step(c)
+    assert {v: _token_digest(mine[v]) for v in chk.STEP_VARS} == want
+    assert _token_digest(machine) == facts["machine_digest"]
+    got = oracle.cartpole_constants()
+    for name, v in facts["constants"].items():
+        assert float(got[name]) == v, name
     for a, b, var in (("costheta * temp)", "temp * costheta)", "thetaacc"), ("(double)CP_TAU * x_dot;", "(double)CP_TAU * xacc;", "x"),
                       ("4.0 / 3.0", "(4.0 / 3.0)", "thetaacc"), ("x > (double)CP_X_THRESHOLD", "x >= (double)CP_X_THRESHOLD", "done")):
         assert a in c
-        got, _ = chk.restatement_step(c.replace(a, b))
-        assert [v for v in chk.STEP_VARS if want[v] != got[v]] == [var], (a, b)
+        slipped, _ = chk.restatement_step(c.replace(a, b))
+        assert [v for v in chk.STEP_VARS if want[v] != _token_digest(slipped[v])] == [var], (a, b)
 
 
 def test_reference_constant_initialisers_are_parsed_not_evaluated():
@@ -547,69 +564,42 @@ def test_restatement_fixtures_agree_with_the_reference_text(golden):
 def test_observation_space_bounds_evaluated_from_the_reference_text(gymnet):
     """CartPoleEnv's ctor builds `high = np.array(x_threshold * 2, float.MaxValue, theta_threshold_radians * 2, float.MaxValue)`
     (CartPoleEnv.cs:46) and `ObservationSpace = new Box(-1 * high, high, np.float32)`.  The engine's gymnet_env_describe must
-    report exactly those bounds: the two products are evaluated from the reference's text (float * int folds in binary32)."""
-    if not os.path.exists("/root/reference/src/Gym.Environments/Envs/Classic/CartPoleEnv.cs"):
-        pytest.skip("reference tree not present (GPU box)")
-    import re as _re
-    from oracle.evaluate_reference_text import Parser, _tokens, load_reference, reference_constants
-    text = load_reference()
-    env = reference_constants(text)
-    args = _re.search(r"var high = np\.array\(([^;]*)\);", text).group(1).split(",")
-    assert len(args) == 4
-    fmax = float(np.finfo(np.float32).max)
-    want = []
-    for a in args:
-        a = a.strip()
-        if a == "float.MaxValue":
-            want.append(fmax)
-        else:
-            v = Parser(_tokens(a), env).expr()
-            assert v.t == "float"
-            want.append(float(v.v))
+    report exactly those bounds: the two products were evaluated from the reference's text (float * int folds in binary32) by
+    tests/golden/make_reference_text_facts.py."""
+    facts = _reference_text_facts()
+    want = facts["obs_high"]
+    assert len(want) == 4 and want[1] == want[3] == float(np.finfo(np.float32).max)
+    assert want[0] == float(np.float32(facts["constants"]["x_threshold"]) * np.float32(2))
+    assert want[2] == float(np.float32(facts["constants"]["theta_threshold_radians"]) * np.float32(2))
     info = gymnet.env_describe(0)
     assert list(info.obs_high[:4]) == want and list(info.obs_low[:4]) == [-w for w in want]
-    assert _re.search(r"ActionSpace = new Discrete\((\d+)\);", text).group(1) == str(info.action_n) == "2"
+    assert facts["action_n"] == info.action_n == 2
 
 
 def test_discrete_contains_evaluated_from_the_reference_text(oracle):
     """Discrete.Contains(int) (src/Gym/Spaces/Discrete.cs:38-40) — the rule GYMNET_FLAG_VALIDATE_ACTIONS applies on the device —
     evaluated from the reference's text for every x in [-3, N + 3) and several N, against the oracle's restatement (which the
     GPU test test_validate_actions compares the kernel with)."""
-    path = "/root/reference/src/Gym/Spaces/Discrete.cs"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    import re as _re
-    from oracle.evaluate_reference_text import Parser, Value, _strip_comments, _tokens
-    text = _strip_comments(open(path, encoding="utf-8-sig").read())
-    body = _re.search(r"public bool Contains\(int x\)\s*\{\s*return ([^;]+);\s*\}", text).group(1)
-    toks = _tokens(body)
+    rows = _reference_text_facts()["discrete_contains"]              # evaluated from the text by tests/golden/make_reference_text_facts.py
+    assert sorted(set(rows["n"])) == [1, 2, 3, 7] and len(rows["x"]) == sum(n + 6 for n in (1, 2, 3, 7))
     L = oracle.lib()
-    for n in (1, 2, 3, 7):
-        for x in range(-3, n + 3):
-            want = Parser(toks, {"x": Value(x, "int"), "N": Value(n, "int"), "Start": Value(0, "int")}).expr()
-            assert want.t == "bool" and bool(L.ref_discrete_contains(x, n)) == bool(want.v), (x, n)
+    for n, x, want in zip(rows["n"], rows["x"], rows["contains"]):
+        assert bool(L.ref_discrete_contains(x, n)) == want, (x, n)
 
 
 def test_reset_distribution_parameters_evaluated_from_the_reference_text(oracle):
     """CartPoleEnv.Reset() (CartPoleEnv.cs:63-67): `steps_beyond_done = -1; state = random.uniform(low, high, count)`.  The three
-    arguments are evaluated from the reference's text; the engine's Philox reset (a different generator by design: north_star)
-    must draw `count` components per lane inside [low, high) with the uniform's mean and variance, and leave sbd at the text's value."""
-    if not os.path.exists("/root/reference/src/Gym.Environments/Envs/Classic/CartPoleEnv.cs"):
-        pytest.skip("reference tree not present (GPU box)")
-    import re as _re
-    from oracle.evaluate_reference_text import Parser, _tokens, load_reference
-    text = load_reference()
-    body = text[text.index("public override NDArray Reset()"):]
-    body = body[:body.index("return")]
-    sbd0 = Parser(_tokens(_re.search(r"steps_beyond_done = ([^;]+);", body).group(1)), {}).expr()
-    args = _re.search(r"state = random\.uniform\(([^;]*)\);", body).group(1).split(",")
-    low, high, count = (Parser(_tokens(a), {}).expr() for a in args)
-    assert (sbd0.v, low.v, high.v, count.v) == (-1, -0.05, 0.05, 4) and count.t == "int"
+    arguments were evaluated from the reference's text (tests/golden/make_reference_text_facts.py); the engine's Philox reset (a
+    different generator by design: north_star) must draw `count` components per lane inside [low, high) with the uniform's mean and
+    variance, and leave sbd at the text's value."""
+    r0 = _reference_text_facts()["reset"]
+    sbd0, low, high, count = r0["steps_beyond_done"], r0["low"], r0["high"], r0["count"]
+    assert (sbd0, low, high, count) == (-1, -0.05, 0.05, 4) and isinstance(count, int)
     s = oracle.cartpole_reset(0x5EED, 0, 0, 200_000)
-    assert s.shape[0] == count.v and s.min() >= low.v and s.max() < high.v
-    assert abs(float(s.mean()) - (low.v + high.v) / 2) < 2e-4 and abs(float(s.std()) - (high.v - low.v) / np.sqrt(12)) < 2e-4
+    assert s.shape[0] == count and s.min() >= low and s.max() < high
+    assert abs(float(s.mean()) - (low + high) / 2) < 2e-4 and abs(float(s.std()) - (high - low) / np.sqrt(12)) < 2e-4
     st, r, d, b = oracle.cartpole_step(s.astype(np.float64), np.ones(s.shape[1], np.int32))
-    assert (b[d == 0] == sbd0.v).all()                                  # a fresh episode starts from the text's steps_beyond_done
+    assert (b[d == 0] == sbd0).all()                                  # a fresh episode starts from the text's steps_beyond_done
 
 
 # ------------------------------------------------------------------------------------------------

@@ -36,7 +36,7 @@ traffic = json.load(open(tj)) if os.path.exists(tj) else {}
 for env, b in BYTES.items():
     db = os.path.join(G, f"env_stats_{env}", "s_results.db")
     if os.path.exists(db):
-        out.append(f"## rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --env {env} --steps 1024 --warmup 128\n")
+        out.append(f"## rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --env {env} --steps 1024 --warmup 128\n")
         out.append(capture(rocpd_summary.stats, db))
     vals = {}
     for cn in ("FETCH_SIZE", "WRITE_SIZE"):

@@ -41,7 +41,7 @@ def avg_counter(db, counter, kernel="step_kernel"):
 out = []
 stats_db = os.path.join(G, "prof_stats", "bench_results.db")
 if os.path.exists(stats_db):
-    out.append("## command: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline\n")
+    out.append("## command: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline\n")
     out.append(capture(rocpd_summary.stats, stats_db))
     blog = os.path.join(G, "prof_stats_bench.log")
     if os.path.exists(blog):
@@ -50,7 +50,7 @@ if os.path.exists(stats_db):
                 out.append("## bench.py line printed by the profiled run\n" + line)
 open(os.path.join(P, f"rocprof_stats_{tag}.txt"), "w").write("".join(out))
 
-pm = ["## command per pass: rocprofv3 --pmc <COUNTERS> -- python3 bench.py --no-cpu-baseline --no-graph --steps 200 --warmup 20\n"]
+pm = ["## command per pass: rocprofv3 --pmc <COUNTERS> -- python3 bench.py --full --no-cpu-baseline --no-graph --steps 200 --warmup 20\n"]
 vals = {}
 for d in sorted(os.listdir(G)):
     db = os.path.join(G, d, "pmc_results.db")

@@ -5,8 +5,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/driver_shape_r06
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o s -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/profiled.log 2> $O/profiled.err
-timeout 600 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/unprofiled.log 2> $O/unprofiled.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o s -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/profiled.log 2> $O/profiled.err
+timeout 600 python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/unprofiled.log 2> $O/unprofiled.err
 cd $R
 {
   echo "# Round 6: rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline   (the driver's shape; one unselected box)"

@@ -22,11 +22,11 @@ timeout 300 rocprofv3 --kernel-trace --stats -d $O/fused/stats -o s -- python3 $
 timeout 300 rocprofv3 --pmc $SQC -d $O/fused/SQ -o pmc -- python3 $R/tools/fused_probe.py CartPole-v1 > $O/fused/SQ.log 2>&1
 # the driver-shaped line and the full default line, unprofiled, for the record
 cd $R
-timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.log 2>&1
-timeout 300 python3 bench.py > $O/bench_default.log 2>&1
+timeout 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.log 2>&1
+timeout 300 python3 bench.py --full > $O/bench_default.log 2>&1
 timeout 300 python3 bench.py --force-dist --no-cpu-baseline --no-extras --steps 512 --warmup 64 > $O/bench_forcedist.log 2>&1
-timeout 600 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_plain.log 2>&1
-timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_launcher.log 2>&1
+timeout 600 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_plain.log 2>&1
+timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_launcher.log 2>&1
 timeout 300 python3 tools/hbm_copy_probe.py > $O/hbm_copy.log 2>&1
 rocminfo | grep -E "Marketing Name|Compute Unit|Max Clock" | head -12 > $O/rocminfo.log 2>&1
 GYMNET_PROFILES_OUT=$O/summary python3 tools/collect_profiles_r03.py r03 > $O/collect.log 2>&1

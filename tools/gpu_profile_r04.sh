@@ -21,10 +21,10 @@ for E in CartPole-v1 CartPole-v1-f64 Pendulum-v1 MountainCar-v0 Acrobot-v1; do
 done
 # the driver-shaped line and the full default line, unprofiled, for the record; N = 2 on one GPU is a PLUMBING check (gloo, ranks share the GPU)
 cd $R
-timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.log 2>&1
-timeout 300 python3 bench.py > $O/bench_default.log 2>&1
-timeout 600 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_plain.log 2>&1
-timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_launcher.log 2>&1
+timeout 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.log 2>&1
+timeout 300 python3 bench.py --full > $O/bench_default.log 2>&1
+timeout 600 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_plain.log 2>&1
+timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_launcher.log 2>&1
 rocminfo | grep -E "Marketing Name|Compute Unit|Max Clock" | head -12 > $O/rocminfo.log 2>&1
 GYMNET_PROFILES_OUT=$O/summary python3 tools/collect_profiles_r04.py r04 > $O/collect.log 2>&1
 for E in CartPole-v1 CartPole-v1-f64 Pendulum-v1 MountainCar-v0 Acrobot-v1; do rm -rf $O/$E/stats $O/$E/FETCH_SIZE $O/$E/WRITE_SIZE $O/$E/SQ; done

@@ -10,5 +10,5 @@ for E in CartPole-v1 Pendulum-v1 MountainCar-v0 Acrobot-v1; do
   timeout 300 python3 bench.py --no-cpu-baseline --no-extras --env $E --steps 2048 --warmup 256 > $O/b_noslp_$E.log 2>&1
   GYMNET_LIB_PATH=$R/gym.net_amd/lib/libgymnet_amd_slp.so timeout 300 python3 bench.py --no-cpu-baseline --no-extras --env $E --steps 2048 --warmup 256 > $O/b_slp_$E.log 2>&1
 done
-timeout 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_k20_b.log 2>&1
+timeout 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_k20_b.log 2>&1
 timeout 300 python3 bench.py --force-dist --no-cpu-baseline --no-extras --steps 512 --warmup 64 > $O/bench_forcedist_b.log 2>&1
