@@ -47,6 +47,8 @@ DTYPE_F32, DTYPE_F64 = 0, 1
 GATHER_NONE, GATHER_DIRECT, GATHER_RCCL = 0, 1, 2
 ABI_VERSION = 6
 RECORDS_NO_OVERFLOW = 1      # gymnet_rollout_spec.record_flags
+PIXELS_RGB8, PIXELS_GRAY8 = 1, 2     # gymnet_vecenv_render(_device) formats
+RENDER_WIDTH, RENDER_HEIGHT = 600, 400
 
 
 class Config(C.Structure):
@@ -161,6 +163,10 @@ PROTOTYPES = {
     "gymnet_vecenv_get_tick": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "gymnet_vecenv_set_tick": (C.c_int, [_H, C.c_uint64]),
     "gymnet_vecenv_counters": (C.c_int, [_H, C.POINTER(Counters)]),
+    "gymnet_vecenv_render_device": (C.c_int, [_H, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int64]),
+    "gymnet_vecenv_render": (C.c_int, [_H, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int64]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

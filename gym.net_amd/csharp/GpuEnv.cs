@@ -6,7 +6,8 @@
 // UNVERIFIED: never compiled (no .NET toolchain in the build image).  tests/test_host_api.py lexes it, checks every native
 // call against the header's arity, and that the four classes derive from Env and override every abstract member.
 //
-// What is NOT here: rendering (Render returns null — NullEnvViewer semantics; the viewers are out of scope).
+// Render("rgb_array") returns the 600x400 frame the engine rasterises on the GPU (gymnet_vecenv_render, CartPole only); Render("human")
+// returns null (NullEnvViewer semantics: no viewer window).
 // Dtype: GpuCartPoleEnv defaults to float64 = true — GymnetFlags.F64, the reference's own arithmetic (float64 state, the literal
 // CartPoleEnv.cs:141-167 sequence) and the float64 observation NDArray the reference actually returns (:166,185; SURVEY F5) — so
 // the loops above see the reference's states to the last few ulps and its exact episode lengths, free-running.  float64 = false
@@ -18,6 +19,7 @@ using Gym.Observations;
 using Gym.Spaces;
 using NumSharp;
 using SixLabors.ImageSharp;
+using SixLabors.ImageSharp.PixelFormats;
 
 namespace Gym.Envs.Amd {
     /// Env (Env.cs:13-41) over ONE lane of the engine.  Reference-faithful mode: no auto-reset, so Step after done returns
@@ -113,7 +115,16 @@ namespace Gym.Envs.Amd {
             });
         }
 
-        public override Image Render(string mode = "human") => null;              // viewers are out of scope for the engine
+        /// CartPoleEnv.Render (CartPoleEnv.cs:69-135): "rgb_array" -> the 600x400 frame of the current state, drawn by the engine
+        /// (4x4-supersampled, not ImageSharp's antialiasing: INTEGRATION.md §0); "human" -> null (no viewer window).
+        public override Image Render(string mode = "human") {
+            if (mode == "human") return null;
+            if (mode != "rgb_array") throw new ArgumentException($"unsupported render mode '{mode}'", nameof(mode));
+            var rgb = new byte[600 * 400 * 3];
+            fixed (byte* p = rgb)
+                Native.Check(Native.gymnet_vecenv_render(_h, p, (int) GymnetPixelFormat.Rgb8, 0, 1, 0, 0, 600, 400, 600, 400, 600 * 400 * 3));
+            return Image.LoadPixelData<Rgb24>(rgb, 600, 400);
+        }
 
         public override void CloseEnvironment() {                                                                 // CartPoleEnv.cs:189-194
             if (_h != IntPtr.Zero) { Native.gymnet_vecenv_destroy(_h); _h = IntPtr.Zero; }

@@ -26,6 +26,8 @@ namespace Gym.Envs.Amd {
 
     public enum GymnetDtype { F32 = 0, F64 = 1 }
 
+    public enum GymnetPixelFormat { Rgb8 = 1, Gray8 = 2 }     // gymnet_vecenv_render(_device): 3 bytes per pixel / 1 byte (BT.709 luma)
+
     public enum GymnetArrayId {
         Reward = 0, Done = 1, StepsBeyondDone = 2, EpisodeReturn = 3, EpisodeLength = 4, FinishedReturn = 5, FinishedLength = 6,
         FinalObs = 7, LaneSeeds = 8
@@ -146,6 +148,11 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_tick(IntPtr h, out ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_tick(IntPtr h, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_counters(IntPtr h, out GymnetCounters counters);
+        // CartPole frames (CartPoleEnv.Render, CartPoleEnv.cs:69-135): lane k's frame at out + (k - first_lane) * lane_stride bytes
+        [DllImport(Lib)] public static extern int gymnet_vecenv_render_device(IntPtr h, void* d_out, int format, long first_lane, long count, int crop_x, int crop_y,
+                                                                             int crop_w, int crop_h, int out_w, int out_h, long lane_stride);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_render(IntPtr h, void* out_frames, int format, long first_lane, long count, int crop_x, int crop_y,
+                                                                      int crop_w, int crop_h, int out_w, int out_h, long lane_stride);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

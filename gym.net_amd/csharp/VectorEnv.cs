@@ -20,6 +20,7 @@ using Gym.Observations;
 using Gym.Spaces;
 using NumSharp;
 using SixLabors.ImageSharp;
+using SixLabors.ImageSharp.PixelFormats;
 
 namespace Gym.Envs.Amd {
     public sealed unsafe class VectorEnv : VecEnv, IVecEnv, IDisposable {
@@ -162,6 +163,30 @@ namespace Gym.Envs.Amd {
         /// TrainingPlaySession.cs:46-52): actions from a device ring, drawn in the kernel (action_source 1: ActionSpace.Sample()) or
         /// epsilon-greedy over the ring (2); dense recording; compact (step, lane, return, length) records of the episodes that end.
         /// All pointers in `spec` are DEVICE pointers; stream-ordered, does not block.
+        /// CartPole frames of lanes [firstLane, firstLane + count) (count < 0: to the last lane) into `destination`: a crop of the
+        /// 600x400 canvas resized to outW x outH, GRAY8 (1 byte per pixel) or RGB8 (3), lane k's frame at (k - firstLane) * laneStride
+        /// bytes (0: frames back to back).  The Images runner's input (CartPoleConfiguration.cs): crop (200, 150, 200, 150) -> 40 x 20,
+        /// two frames stacked into 40 x 40 = laneStride 1600 with the second frame written at destination.Slice(800).
+        public void RenderFrames(Span<byte> destination, int outW, int outH, int cropX = 0, int cropY = 0, int cropW = 600, int cropH = 400,
+                                 long firstLane = 0, long count = -1, long laneStride = 0, GymnetPixelFormat format = GymnetPixelFormat.Gray8) {
+            if (count < 0) count = NumberOfEnvironments - firstLane;
+            long frame = (long) outW * outH * (format == GymnetPixelFormat.Rgb8 ? 3 : 1);
+            if (laneStride == 0) laneStride = frame;
+            if (count > 0 && (count - 1) * laneStride + frame > destination.Length)
+                throw new ArgumentException("destination is smaller than the frames it must hold", nameof(destination));
+            fixed (byte* p = destination)
+                Native.Check(Native.gymnet_vecenv_render(_h, p, (int) format, firstLane, count, cropX, cropY, cropW, cropH, outW, outH, laneStride));
+        }
+
+        /// CartPoleEnv.Render for one lane: "rgb_array" -> its 600x400 frame, "human" -> null (no viewer window).
+        public Image Render(int lane, string mode = "human") {
+            if (mode == "human") return null;
+            if (mode != "rgb_array") throw new ArgumentException($"unsupported render mode '{mode}'", nameof(mode));
+            var rgb = new byte[600 * 400 * 3];
+            RenderFrames(rgb, 600, 400, firstLane: lane, count: 1, format: GymnetPixelFormat.Rgb8);
+            return Image.LoadPixelData<Rgb24>(rgb, 600, 400);
+        }
+
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));
         public void RolloutFused(GymnetRolloutSpec spec) {
@@ -277,7 +302,7 @@ namespace Gym.Envs.Amd {
         public NDArray Reset() { var m = new byte[Owner.NumberOfEnvironments]; m[Lane] = 1; return Owner.ResetWhere(m)[Lane]; }   // CartPoleEnv.cs:63-67
         public Step Step(object action) => throw new NotSupportedException("step the whole batch: VectorEnv.Step(int) / Step(NDArray)");
         public Task<Step> StepAsync(object action) => throw new NotSupportedException("step the whole batch: VectorEnv.StepAsync(int)");
-        public Image Render(string mode = "human") => null;                       // rendering is out of scope (NullEnvViewer semantics)
+        public Image Render(string mode = "human") => Owner.Render(Lane, mode);   // "rgb_array": the lane's frame; "human": null
         public void CloseEnvironment() { }                                        // the batch owns the resources
         public void Seed(int seed) => Owner.SeedLaneFromProxy(Lane, seed);        // CartPoleEnv.cs:196-198
     }

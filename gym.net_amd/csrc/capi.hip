@@ -738,6 +738,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     drop_graphs(h);
     for (void *p : h->owned) (void)hipFree(p);
     if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
+    if (h->d_render) (void)hipFree(h->d_render);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1317,6 +1318,84 @@ int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity) {
     if (!h || !buf || capacity < 1) return fail(h, GYMNET_ERR_INVALID_ARG, "null handle / buffer");
     if (describe_step_kernel(h->cfg.env_id, h->f64, h->autoreset, h->extras, h->lcfg, h->n, buf, (size_t)capacity) < 0)
         return fail(h, GYMNET_ERR_INVALID_ARG, "unknown env");
+    return GYMNET_OK;
+    });
+}
+
+// ---- CartPole frames (render.hip) ------------------------------------------------------------------------------------------
+namespace {
+
+// Checks a render request (nothing is written on failure) and fills the kernel arguments; *bytes = the span the frames cover.
+int render_args(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
+                int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride, RenderArgs *a, int64_t *bytes) {
+    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "rendering exists for CartPole only (CartPoleEnv.cs:69-135)");
+    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
+    if (format != GYMNET_PIXELS_RGB8 && format != GYMNET_PIXELS_GRAY8) return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel format %d", format);
+    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
+                    (long long)count, (long long)h->n);
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > kRenderWidth - crop_w || crop_y > kRenderHeight - crop_h)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "crop (%d, %d, %d, %d) not inside the %dx%d canvas", crop_x, crop_y, crop_w, crop_h, kRenderWidth, kRenderHeight);
+    if (out_w < 1 || out_h < 1 || out_w > kRenderMaxSide || out_h > kRenderMaxSide)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "output size %dx%d not in [1, %d]", out_w, out_h, kRenderMaxSide);
+    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
+    if (lane_stride < frame) return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one frame", (long long)lane_stride, (long long)frame);
+    if (lane_stride > (INT64_MAX - frame) / count) return fail(h, GYMNET_ERR_INVALID_ARG, "count x lane_stride overflows");
+    a->obs = h->d_obs; a->obs_stride = h->ostride;
+    a->first_lane = first_lane;
+    a->out = static_cast<uint8_t *>(out); a->lane_stride = lane_stride;
+    a->waves_per_frame = render_waves_per_frame(out_w, out_h);
+    a->total_waves = count * a->waves_per_frame;
+    a->out_w = out_w; a->out_h = out_h;
+    a->x0 = (float)crop_x; a->y0 = (float)crop_y;
+    a->sxq = (float)((double)crop_w / (4.0 * out_w));
+    a->syq = (float)((double)crop_h / (4.0 * out_h));
+    *bytes = (count - 1) * lane_stride + frame;
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int gymnet_vecenv_render_device(gymnet_vecenv *h, void *d_out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x,
+                                int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    RenderArgs a{};
+    int64_t bytes = 0;
+    ST_TRY(render_args(h, d_out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
+    HIP_TRY(h, launch_render(h->f64, format == GYMNET_PIXELS_RGB8 ? 3 : 1, a, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
+                         int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    RenderArgs a{};
+    int64_t bytes = 0;
+    ST_TRY(render_args(h, out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
+    if (h->render_cap < (size_t)bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_render) (void)hipFree(h->d_render);
+        h->d_render = nullptr; h->render_cap = 0;
+        hipError_t e = hipMalloc(&h->d_render, (size_t)bytes);
+        if (e != hipSuccess) return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the render staging failed: %s", (long long)bytes, hipGetErrorString(e));
+        h->render_cap = (size_t)bytes;
+    }
+    a.out = static_cast<uint8_t *>(h->d_render);
+    HIP_TRY(h, launch_render(h->f64, format == GYMNET_PIXELS_RGB8 ? 3 : 1, a, h->stream));
+    // only the frames' own bytes cross: the caller's gaps between them (lane_stride > one frame) stay as they were
+    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
+    if (lane_stride == frame) {
+        HIP_TRY(h, hipMemcpyAsync(out, h->d_render, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return GYMNET_OK;
+    }
+    std::vector<uint8_t> span((size_t)bytes);
+    HIP_TRY(h, hipMemcpyAsync(span.data(), h->d_render, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t k = 0; k < count; ++k) std::memcpy(static_cast<uint8_t *>(out) + k * lane_stride, span.data() + k * lane_stride, (size_t)frame);
     return GYMNET_OK;
     });
 }

@@ -206,6 +206,20 @@ hipError_t launch_export_host(int obs_dim, const double *obs, int64_t stride, co
 // recompute obs from state (after set_state) for envs whose observation is derived
 hipError_t launch_observe(int env_id, const float *state, int64_t state_stride, float *obs, int64_t obs_stride,
                           int64_t n, hipStream_t st);
+// CartPole frames (render.hip; contract: gymnet_vecenv_render_device).  Frame k of lanes [first_lane, first_lane + count) is
+// out + k * lane_stride; total_waves = count * waves_per_frame, waves_per_frame = render_waves_per_frame(out_w, out_h).
+struct RenderArgs {
+    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
+    int64_t first_lane;
+    uint8_t *out; int64_t lane_stride;
+    int64_t total_waves, waves_per_frame;
+    int32_t out_w, out_h;
+    float x0, y0, sxq, syq;                   // sample (a, b) of pixel (i, j): x0 + (4 j + a + 0.5) * sxq, y0 + (4 i + b + 0.5) * syq
+};
+constexpr int32_t kRenderWidth = 600, kRenderHeight = 400;   // the reference's canvas (CartPoleEnv.cs:71-72)
+constexpr int32_t kRenderMaxSide = 16384;                    // output width / height limit (sample positions stay exact in float)
+int64_t render_waves_per_frame(int32_t out_w, int32_t out_h);
+hipError_t launch_render(bool f64, int channels, const RenderArgs &a, hipStream_t st);
 hipError_t launch_fill_i32(int32_t *p, int32_t v, int64_t n, hipStream_t st);
 // Gathers the sharded done list of one step (counter half `counts`) and the records written beside it into compact arrays
 // out_*[0 .. *out_count) (entries beyond out_capacity are dropped; the count is the true one), and / or applies the records to

@@ -330,6 +330,49 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_compose_actions_device(self._h, _ptr(d_policy_actions), float(epsilon),
                                                                   _ptr(d_actions_out), int(seed), int(tick)))
 
+    # ---- CartPole frames (CartPoleEnv.Render, CartPoleEnv.cs:69-135; contract: gymnet_vecenv_render_device) -----------------
+    _FORMATS = {"rgb": capi.PIXELS_RGB8, "gray": capi.PIXELS_GRAY8, capi.PIXELS_RGB8: capi.PIXELS_RGB8, capi.PIXELS_GRAY8: capi.PIXELS_GRAY8}
+    _CANVAS = (0, 0, capi.RENDER_WIDTH, capi.RENDER_HEIGHT)
+
+    def _render_args(self, format, first_lane, count, crop, size, lane_stride):
+        fmt = self._FORMATS.get(format)
+        if fmt is None:
+            raise ValueError(f"unknown pixel format {format!r} (\"rgb\" or \"gray\")")
+        cx, cy, cw, ch = (int(v) for v in crop)
+        w, h = (cw, ch) if size is None else (int(size[0]), int(size[1]))
+        count = self.NumberOfEnvironments - int(first_lane) if count is None else int(count)
+        frame = w * h * (3 if fmt == capi.PIXELS_RGB8 else 1)
+        return (fmt, int(first_lane), count, cx, cy, cw, ch, w, h, frame if lane_stride is None else int(lane_stride))
+
+    def RenderDevice(self, d_out, format="gray", first_lane=0, count=None, crop=_CANVAS, size=None, lane_stride=None):
+        """Frames of lanes [first_lane, first_lane + count) into device memory (a torch tensor or an int pointer), ordered on the
+        handle's stream: format "rgb" (out_h x out_w x 3 bytes) or "gray" (out_h x out_w), crop = (x, y, w, h) of the 600 x 400 canvas,
+        size = (out_w, out_h) (default: the crop's size), lane k's frame at d_out + (k - first_lane) * lane_stride bytes (default:
+        frames back to back).  CartPole only."""
+        capi.check(self._lib.gymnet_vecenv_render_device(self._h, _ptr(d_out), *self._render_args(format, first_lane, count, crop, size, lane_stride)))
+
+    def Render(self, mode="human", lanes=None):
+        """CartPoleEnv.Render (CartPoleEnv.cs:69-135): "human" -> None (no viewer); "rgb_array" -> uint8 [len(lanes), 400, 600, 3], the
+        full canvas of each lane in `lanes` (default: lane 0 only — a full frame is 720 000 bytes)."""
+        if mode == "human":
+            return None
+        if mode != "rgb_array":
+            raise ValueError(f"unsupported render mode {mode!r} (Metadata['render.modes'] = {self.Metadata['render.modes']})")
+        lanes = [0] if lanes is None else [int(k) for k in lanes]
+        out = np.empty((len(lanes), capi.RENDER_HEIGHT, capi.RENDER_WIDTH, 3), np.uint8)
+        for k, lane in enumerate(lanes):
+            capi.check(self._lib.gymnet_vecenv_render(self._h, _host(out[k]), *self._render_args("rgb", lane, 1, self._CANVAS, None, None)))
+        return out
+
+    def RenderFrames(self, size, crop=_CANVAS, lanes=None):
+        """GRAY8 frames of a crop, resized: uint8 [count, out_h, out_w] for the lane range lanes = (first, count) (default: every lane).
+        The pixel-input shape of the reference's Images runner is RenderFrames((40, 20), crop=(200, 150, 200, 150))."""
+        first, count = (0, self.NumberOfEnvironments) if lanes is None else (int(lanes[0]), int(lanes[1]))
+        w, h = int(size[0]), int(size[1])
+        out = np.empty((max(count, 0), max(h, 0), max(w, 0)), np.uint8)
+        capi.check(self._lib.gymnet_vecenv_render(self._h, _host(out), *self._render_args("gray", first, count, crop, (w, h), None)))
+        return out
+
     def PackObsDevice(self, d_obs_rowmajor):
         capi.check(self._lib.gymnet_vecenv_pack_obs_device(self._h, _ptr(d_obs_rowmajor)))
 
@@ -747,7 +790,10 @@ class GpuEnv:
         return _One()
 
     def Render(self, mode="human"):
-        return None            # rendering is out of scope for the engine (NullEnvViewer semantics)
+        """CartPoleEnv.Render (CartPoleEnv.cs:69-135): "rgb_array" -> uint8 [400, 600, 3] of the current state; "human" -> None (no
+        viewer, NullEnvViewer semantics); anything else raises ValueError.  CartPole only (the other envs raise GymNetError)."""
+        frames = self._v.Render(mode)
+        return None if frames is None else frames[0]
 
     def CloseEnvironment(self):                                                      # CartPoleEnv.cs:189-194
         self._v.Close()

@@ -406,6 +406,35 @@ int gymnet_vecenv_set_array(gymnet_vecenv *h, int32_t which, const void *in, int
 /* The Philox key in use (Env.Seed(int), CartPoleEnv.cs:196-198) and whether per-lane keys are active.  Either out may be NULL. */
 int gymnet_vecenv_get_seed(gymnet_vecenv *h, uint64_t *seed, int32_t *per_lane);
 
+/* ---- CartPole frames (CartPoleEnv.Render, CartPoleEnv.cs:69-135) ----------------------------------------------------------
+ * Frames of lanes [first_lane, first_lane + count) rasterised from the CURRENT observation buffer (what gymnet_vecenv_get_state
+ * returns at that point of the stream: after an auto-reset step a finished lane shows its reset state; with GYMNET_FLAG_DOUBLE_BUFFER
+ * the buffer d_obs points at).  Lane k's frame starts at out + (k - first_lane) * lane_stride bytes (lane_stride >= the frame's size;
+ * the bytes between frames are not written) and is out_h rows of out_w pixels, top row first: RGB8 = 3 bytes per pixel, GRAY8 = 1.
+ * The canvas is the reference's: 600 x 400, y down; scale = 600f / (2.4f * 2) and polelen = scale * (2 * 0.5f) as C# floats;
+ * cx = (float)((double)x * scale + 300.0) (x = state row 0), theta = state row 2 as float.  Painted in order, the last shape
+ * containing a sample wins: background white (255, 255, 255); track black [0, 600) x [300, 301); cart black [cx - 25, cx + 25] x
+ * [285, 315]; pole (204, 153, 102), the points whose u = dx cos(theta) + dy sin(theta) is in [-5, 5] and v = dy cos(theta) - dx sin(theta)
+ * in [5 - polelen, 5], (dx, dy) relative to the pivot (cx, 295) — positive theta leans right; axle (204, 153, 102), the disc of
+ * radius 5 about (cx, 295).  GRAY8 paints white 255, black 0, pole and axle 160 (BT.709 luma, rounded).
+ * Output pixel (i, j) of a crop (crop_x, crop_y, crop_w, crop_h) of the canvas takes the 16 samples
+ * xs = crop_x + (j + (a + 0.5) / 4) * crop_w / out_w, ys = crop_y + (i + (b + 0.5) / 4) * crop_h / out_h (a, b = 0..3) and is
+ * (sum of the 16 sample values + 8) >> 4 per channel — a supersampled box filter, not ImageSharp's scanline antialiasing.
+ * A lane whose x or theta is not finite shows what stays defined (background and track; the cart and axle for a finite x).
+ * Rendering changes nothing: state, tick, counters and the Philox stream are untouched.
+ * Errors (nothing written): GYMNET_ERR_UNSUPPORTED for an env other than CartPole; GYMNET_ERR_INVALID_ARG for a NULL out, an unknown
+ * format, lanes outside [0, num_envs) or count < 1, a crop not inside the canvas or of size <= 0, out_w / out_h outside [1, 16384],
+ * or a lane_stride below one frame. */
+enum { GYMNET_PIXELS_RGB8 = 1, GYMNET_PIXELS_GRAY8 = 2 };
+/* into device memory, ordered on the handle's stream (does not block) */
+int gymnet_vecenv_render_device(gymnet_vecenv *h, void *d_out, int32_t format, int64_t first_lane, int64_t count,
+                                int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                                int32_t out_w, int32_t out_h, int64_t lane_stride);
+/* the same into host memory, staged through a device buffer the handle owns (allocated on first use); blocks */
+int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count,
+                         int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                         int32_t out_w, int32_t out_h, int64_t lane_stride);
+
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */
 int gymnet_vecenv_done_lanes(gymnet_vecenv *h, int32_t *lanes_out, int64_t capacity, int64_t *count);
