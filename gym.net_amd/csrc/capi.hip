@@ -158,6 +158,12 @@ void *state_row(gymnet_vecenv *h, int k) {
     return m < 0 ? row_at(h->d_state, k, h->sstride, h->esz) : row_at(h->d_obs, m, h->ostride, h->esz);
 }
 
+// The step kernel a launch with configuration `c` runs: the launcher's own selection (step_kernels.hpp select_step), its name and shape.
+StepForm next_step_kernel(const gymnet_vecenv *h, const LaunchCfg &c) {
+    if (h->f64) return h->launch_f64->select_step(h->autoreset, h->extras, c, h->n);
+    return h->launch_f32->select_step(h->autoreset, h->extras, c, h->n);
+}
+
 // Applies the fields of `p` that are not -1.  strict: a value the handle cannot run — or that would not take effect for it (a
 // multi-lane form on a batch that is not whole groups, a reset form the env has no use for) — is an error and nothing changes;
 // else it is ignored (probe builds).  gymnet_vecenv_kernel_name stays the authority on what the next launch runs.
@@ -194,8 +200,7 @@ int apply_policy(gymnet_vecenv *h, const gymnet_launch_policy &p, bool strict) {
     if (strict && p.sequential_lanes > 1) {
         // an explicitly requested multi-lane form must be the one the launcher resolves to: lean variant, the lane
         // width it is defined for, whole 2 * items * 256-lane groups for the pair form
-        int rvec = 1, rseq = 1;
-        resolved_step_shape(h->cfg.env_id, h->f64, h->autoreset, h->extras, c, h->n, &rvec, &rseq);
+        const int rseq = next_step_kernel(h, c).sequential;
         if (rseq != p.sequential_lanes)
             return fail(h, GYMNET_ERR_INVALID_ARG, "launch policy: sequential_lanes = %d would not take effect for this handle (vec %d, %s variant, "
                         "%lld lanes: the launcher resolves to %d)", p.sequential_lanes, c.vec, h->extras ? "bookkeeping" : "lean", (long long)h->n, rseq);
@@ -346,11 +351,11 @@ int launch_one_step(gymnet_vecenv *h, const void *d_actions) {
     if (h->f64) {
         const StepArgsT<double> a = make_step_args<double>(h, d_actions);
         cparity = a.cparity;
-        HIP_TRY(h, launch_step(h->cfg.env_id, h->autoreset, h->extras, a, h->lcfg, h->stream));
+        HIP_TRY(h, h->launch_f64->step(h->autoreset, h->extras, a, h->lcfg, h->stream));
     } else {
         const StepArgsT<float> a = make_step_args<float>(h, d_actions);
         cparity = a.cparity;
-        HIP_TRY(h, launch_step(h->cfg.env_id, h->autoreset, h->extras, a, h->lcfg, h->stream));
+        HIP_TRY(h, h->launch_f32->step(h->autoreset, h->extras, a, h->lcfg, h->stream));
     }
     swap_buffers(h);
     h->last_cparity = cparity;
@@ -371,7 +376,7 @@ static int reset_lanes_typed(gymnet_vecenv *h, const uint8_t *d_mask) {
     r.n = h->n; r.state_stride = h->sstride; r.obs_stride = h->ostride;
     r.lane_offset = (uint64_t)h->cfg.lane_offset; r.seed = h->seed;
     r.parity = (int32_t)h->tslot;
-    HIP_TRY(h, launch_reset(h->cfg.env_id, r, h->stream));
+    HIP_TRY(h, launchers<R>(h).reset(r, h->stream));
     h->tick += 1;
     h->tslot ^= 1;
     return GYMNET_OK;
@@ -581,7 +586,7 @@ static int resident_start_typed(gymnet_vecenv *h) {
     r.tick2 = h->d_tick2; r.lane_seed = h->d_lane_seed; r.ep_ret = h->d_ep_ret; r.ep_len = h->d_ep_len;
     r.n = h->n; r.state_stride = h->sstride; r.obs_stride = h->ostride; r.lane_offset = (uint64_t)h->cfg.lane_offset; r.seed = h->seed;
     r.parity = (int32_t)h->tslot;
-    HIP_TRY(h, launch_resident(h->cfg.env_id, h->autoreset, h->extras, a, r, h->mb_dev, kResidentIdlePolls, h->stream));
+    HIP_TRY(h, launchers<R>(h).resident(h->autoreset, h->extras, a, r, h->mb_dev, kResidentIdlePolls, h->stream));
     return GYMNET_OK;
 }
 
@@ -802,6 +807,8 @@ int gymnet_vecenv_create(const gymnet_config *cfg, gymnet_vecenv **out) {
     h->double_buffer = (cfg->flags & GYMNET_FLAG_DOUBLE_BUFFER) != 0;
     h->f64 = (cfg->flags & GYMNET_FLAG_F64) != 0;
     h->esz = h->f64 ? 8 : 4;
+    // (cfg.env_id and GYMNET_FLAG_F64 were checked above: the table exists)
+    if (h->f64) h->launch_f64 = env_launchers<double>(cfg->env_id); else h->launch_f32 = env_launchers<float>(cfg->env_id);
     h->compact_only = (cfg->flags & GYMNET_FLAG_COMPACT_RECORDS_ONLY) != 0;
     const EnvDesc &d = *h->desc;
     DeviceScope dev_scope;
@@ -1183,7 +1190,7 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
         // the kShards + 1 counters, zeroed on the stream by a kernel of our own
         HIP_TRY(h, launch_fill_i32(reinterpret_cast<int32_t *>(r.ep_count), 0, (int64_t)(kShards + 1) * kCountStride, h->stream));
     }
-    HIP_TRY(h, launch_rollout_fused(h->cfg.env_id, h->autoreset, h->extras, a, r, cfg, h->stream));
+    HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
     if (episodes) {
         EpisodeGatherArgs g{};
         g.counts = r.ep_count; g.cap = r.ep_cap;
@@ -1305,9 +1312,7 @@ int gymnet_vecenv_launch_policy(gymnet_vecenv *h, int32_t *vec, int32_t *block, 
     if (block) *block = h->lcfg.block;
     if (nt) *nt = h->lcfg.nt;
     if (sequential_lanes) {      // what the launcher resolves to (lanes, or lane pairs, a thread works through one after another)
-        int rvec = 1, rseq = 1;
-        resolved_step_shape(h->cfg.env_id, h->f64, h->autoreset, h->extras, h->lcfg, h->n, &rvec, &rseq);
-        *sequential_lanes = rseq;
+        *sequential_lanes = next_step_kernel(h, h->lcfg).sequential;
     }
     return GYMNET_OK;
     });
@@ -1316,8 +1321,7 @@ int gymnet_vecenv_launch_policy(gymnet_vecenv *h, int32_t *vec, int32_t *block, 
 int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity) {
     return guarded([&]() -> int {
     if (!h || !buf || capacity < 1) return fail(h, GYMNET_ERR_INVALID_ARG, "null handle / buffer");
-    if (describe_step_kernel(h->cfg.env_id, h->f64, h->autoreset, h->extras, h->lcfg, h->n, buf, (size_t)capacity) < 0)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown env");
+    next_step_kernel(h, h->lcfg).name(buf, (size_t)capacity);
     return GYMNET_OK;
     });
 }
@@ -1420,7 +1424,7 @@ int gymnet_vecenv_set_state(gymnet_vecenv *h, const void *state_soa_v) {
     for (int k = 0; k < h->desc->state_dim; ++k)
         HIP_TRY(h, hipMemcpyAsync(state_row(h, k), static_cast<const char *>(state_soa_v) + (size_t)k * row, row, hipMemcpyHostToDevice, h->stream));
     if (!h->desc->alias)      // (float32 envs only: the float64 handle's observation IS its state)
-        HIP_TRY(h, launch_observe(h->cfg.env_id, static_cast<const float *>(h->d_state), h->sstride, static_cast<float *>(h->d_obs), h->ostride, h->n, h->stream));
+        HIP_TRY(h, h->launch_f32->observe(static_cast<const float *>(h->d_state), h->sstride, static_cast<float *>(h->d_obs), h->ostride, h->n, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GYMNET_OK;
     });

@@ -1,7 +1,12 @@
-// env_mountaincar.hip — the step / fused-rollout / reset kernels of step_kernels.hpp instantiated for MountainCar:
+// env_mountaincar.hip — MountainCar's launcher table (step_kernels.hpp launchers_of), which instantiates its step / rollout / reset kernels:
 // MountainCar-v0 (absent from the reference; upstream gym).  One translation unit per env so the build compiles them side by side.
 #include "step_kernels.hpp"
 
 #include "envs.hpp"
 
-GYMNET_DEFINE_ENV(mountaincar, gymnet::MountainCar)
+namespace gymnet {
+const EnvLaunchers<float> &mountaincar_launchers() {
+    static const EnvLaunchers<float> table = launchers_of<MountainCar>();
+    return table;
+}
+}

@@ -1,7 +1,12 @@
-// env_pendulum.hip — the step / fused-rollout / reset kernels of step_kernels.hpp instantiated for Pendulum:
+// env_pendulum.hip — Pendulum's launcher table (step_kernels.hpp launchers_of), which instantiates its step / rollout / reset kernels:
 // Pendulum-v1 (absent from the reference; upstream gym).  One translation unit per env so the build compiles them side by side.
 #include "step_kernels.hpp"
 
 #include "envs.hpp"
 
-GYMNET_DEFINE_ENV(pendulum, gymnet::Pendulum)
+namespace gymnet {
+const EnvLaunchers<float> &pendulum_launchers() {
+    static const EnvLaunchers<float> table = launchers_of<Pendulum>();
+    return table;
+}
+}

@@ -54,6 +54,9 @@ struct gymnet_vecenv {
     // elements of that type; they are kept as void* here and typed where they are used (esz = element size in bytes).
     bool f64 = false;
     size_t esz = 4;
+    // the env's kernel launchers for that state scalar (kernels.hpp EnvLaunchers, found at create; the other pointer stays NULL)
+    const gymnet::EnvLaunchers<float> *launch_f32 = nullptr;
+    const gymnet::EnvLaunchers<double> *launch_f64 = nullptr;
     // d_state / d_obs always point at the CURRENT (most recently written) buffers; with GYMNET_FLAG_DOUBLE_BUFFER
     // d_state_alt / d_obs_alt are what the next step writes, and the pairs swap after every step launch.
     void *d_state = nullptr, *d_obs = nullptr;
@@ -186,6 +189,12 @@ int guarded(F &&f) noexcept {
         set_last_error("unexpected C++ exception inside the library");
         return GYMNET_ERR_HIP;
     }
+}
+
+// the handle's launcher table, for code typed by its state scalar R
+template <class R>
+inline const EnvLaunchers<R> &launchers(const gymnet_vecenv *h) {
+    if constexpr (sizeof(R) == 8) return *h->launch_f64; else return *h->launch_f32;
 }
 
 // address of row k of a [rows][stride] structure-of-arrays buffer of esz-byte elements

@@ -1,6 +1,6 @@
 // kernels.hip — the env-INDEPENDENT HIP kernels of the batched classic-control engine (row-major packing / host export of the
-// observations, done-list gather, action validation, batched space sampling, the direct all-gather push) and the dispatch from
-// (env_id, state scalar) to the env's own translation unit (env_*.hip: the step / rollout / reset kernels, step_kernels.hpp).
+// observations, done-list gather, action validation, batched space sampling, the direct all-gather push) and the lookup from
+// (env_id, state scalar) to the env's launcher table (env_*.hip: the step / rollout / reset kernels, step_kernels.hpp).
 // Written for gfx950 (CDNA4, wave64); compiled with -ffp-contract=off.
 #include "kernels.hpp"
 
@@ -385,103 +385,21 @@ static inline unsigned grid_for(int64_t items, int block) { return (unsigned)((i
 // workgroups of a stand-alone sampler launch: one thread per group of four global lanes (my_lane_group)
 static inline unsigned group_grid(int64_t n, uint64_t lane_offset) { return grid_for((n + (int64_t)(lane_offset & 3u) + 3) / 4, 256); }
 
-hipError_t launch_step(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, LaunchCfg cfg, hipStream_t st) {
-    switch (env_id) {
-        case 0: return launch_step_cartpole(autoreset, extras, a, cfg, st);
-        case 1: return launch_step_pendulum(autoreset, extras, a, cfg, st);
-        case 2: return launch_step_mountaincar(autoreset, extras, a, cfg, st);
-        case 3: return launch_step_acrobot(autoreset, extras, a, cfg, st);
-        default: return hipErrorInvalidValue;
+template <class R>
+const EnvLaunchers<R> *env_launchers(int env_id) {
+    if constexpr (sizeof(R) == 8) {
+        return env_id == 0 ? &cartpole64_launchers() : nullptr;     // the reference defines float64 arithmetic for CartPole only
+    } else {
+        static const EnvLaunchers<float> &(*const tables[])() = {cartpole_launchers, pendulum_launchers, mountaincar_launchers, acrobot_launchers};
+        return env_id >= 0 && env_id < 4 ? &tables[env_id]() : nullptr;       // by gymnet_env_id
     }
 }
-
-hipError_t launch_step(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, LaunchCfg cfg, hipStream_t st) {
-    if (env_id != 0) return hipErrorInvalidValue;      // the reference defines float64 arithmetic for CartPole only
-    return launch_step_cartpole64(autoreset, extras, a, cfg, st);
-}
-
-int describe_step_kernel(int env_id, bool f64, bool autoreset, bool extras, LaunchCfg cfg, int64_t n, char *buf, size_t cap) {
-    if (f64) return env_id == 0 ? describe_step_cartpole64(autoreset, extras, cfg, n, buf, cap) : -1;
-    switch (env_id) {
-        case 0: return describe_step_cartpole(autoreset, extras, cfg, n, buf, cap);
-        case 1: return describe_step_pendulum(autoreset, extras, cfg, n, buf, cap);
-        case 2: return describe_step_mountaincar(autoreset, extras, cfg, n, buf, cap);
-        case 3: return describe_step_acrobot(autoreset, extras, cfg, n, buf, cap);
-        default: return -1;
-    }
-}
-
-void resolved_step_shape(int env_id, bool f64, bool autoreset, bool extras, LaunchCfg cfg, int64_t n, int *vec, int *sequential) {
-    *vec = 1; *sequential = 1;
-    if (f64) { if (env_id == 0) resolved_shape_cartpole64(autoreset, extras, cfg, n, vec, sequential); return; }
-    switch (env_id) {
-        case 0: resolved_shape_cartpole(autoreset, extras, cfg, n, vec, sequential); break;
-        case 1: resolved_shape_pendulum(autoreset, extras, cfg, n, vec, sequential); break;
-        case 2: resolved_shape_mountaincar(autoreset, extras, cfg, n, vec, sequential); break;
-        case 3: resolved_shape_acrobot(autoreset, extras, cfg, n, vec, sequential); break;
-        default: break;
-    }
-}
-
-hipError_t launch_rollout_fused(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, const RolloutArgsT<float> &r, LaunchCfg cfg, hipStream_t st) {
-    switch (env_id) {
-        case 0: return launch_rollout_cartpole(autoreset, extras, a, r, cfg, st);
-        case 1: return launch_rollout_pendulum(autoreset, extras, a, r, cfg, st);
-        case 2: return launch_rollout_mountaincar(autoreset, extras, a, r, cfg, st);
-        case 3: return launch_rollout_acrobot(autoreset, extras, a, r, cfg, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_rollout_fused(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, const RolloutArgsT<double> &r, LaunchCfg cfg, hipStream_t st) {
-    if (env_id != 0) return hipErrorInvalidValue;
-    return launch_rollout_cartpole64(autoreset, extras, a, r, cfg, st);
-}
+template const EnvLaunchers<float> *env_launchers<float>(int);
+template const EnvLaunchers<double> *env_launchers<double>(int);
 
 hipError_t launch_gather_episodes(const EpisodeGatherArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(gather_episodes_kernel, dim3(kShards + 1, kGatherSplit), dim3(256), 0, st, a);     // + 1: the overflow segment's row
     return hipGetLastError();
-}
-
-hipError_t launch_reset(int env_id, const ResetArgsT<float> &a, hipStream_t st) {
-    switch (env_id) {
-        case 0: return launch_reset_cartpole(a, st);
-        case 1: return launch_reset_pendulum(a, st);
-        case 2: return launch_reset_mountaincar(a, st);
-        case 3: return launch_reset_acrobot(a, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_reset(int env_id, const ResetArgsT<double> &a, hipStream_t st) {
-    if (env_id != 0) return hipErrorInvalidValue;
-    return launch_reset_cartpole64(a, st);
-}
-
-hipError_t launch_resident(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, const ResetArgsT<float> &r, Mailbox *mb,
-                           uint64_t idle_polls, hipStream_t st) {
-    switch (env_id) {
-        case 0: return launch_resident_cartpole(autoreset, extras, a, r, mb, idle_polls, st);
-        case 1: return launch_resident_pendulum(autoreset, extras, a, r, mb, idle_polls, st);
-        case 2: return launch_resident_mountaincar(autoreset, extras, a, r, mb, idle_polls, st);
-        case 3: return launch_resident_acrobot(autoreset, extras, a, r, mb, idle_polls, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_resident(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, const ResetArgsT<double> &r, Mailbox *mb,
-                           uint64_t idle_polls, hipStream_t st) {
-    if (env_id != 0) return hipErrorInvalidValue;
-    return launch_resident_cartpole64(autoreset, extras, a, r, mb, idle_polls, st);
-}
-
-hipError_t launch_observe(int env_id, const float *state, int64_t sstride, float *obs, int64_t ostride, int64_t n,
-                          hipStream_t st) {
-    switch (env_id) {
-        case 1: return launch_observe_pendulum(state, sstride, obs, ostride, n, st);
-        case 3: return launch_observe_acrobot(state, sstride, obs, ostride, n, st);
-        default: return hipSuccess;   // aliasing envs: nothing to recompute
-    }
 }
 
 template <class T>

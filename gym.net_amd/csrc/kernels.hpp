@@ -52,7 +52,7 @@ constexpr int kShards = 256;        // power of two; the gather kernels' workgro
 constexpr int kCountStride = 16;    // uint32 words between shard counters (64 bytes: one counter per cache line)
 constexpr int kAfterStride = 8;     // uint64 words between after_done shards (64 bytes)
 
-// lds_bytes: unused dynamic LDS requested per workgroup, for the ONE purpose of capping occupancy in probes (GYMNET_LDS)
+// lds_bytes: unused dynamic LDS requested per workgroup, for the ONE purpose of capping occupancy in probes (one-shot kernel)
 // items: lanes per thread of the fully unrolled software-pipelined kernel (envs with PIPELINED only; 1 = one-shot kernel)
 // reset_form: 1 = wave-compacted fused reset in the one-step kernel (reset_pending_wave: envs whose observation aliases the
 // state, dwordx4 lanes)
@@ -60,16 +60,6 @@ constexpr int kAfterStride = 8;     // uint64 words between after_done shards (6
 // simds: SIMD units of the handle's device (multiProcessorCount x 4; 1024 on MI355X) — sizes the resident generation of the looped
 // multi-pair kernel (step_kernels.hpp pipe2_chunks) and the policy's waves-per-SIMD windows (capi.hip default_policy)
 struct LaunchCfg { int vec; int block; int nt; int lds_bytes = 0; int items = 1; int reset_form = 0; int lds_pipe = 0; int simds = 1024; };
-
-// ---- env-dependent launchers: one translation unit per env (env_*.hip, GYMNET_DEFINE_ENV in step_kernels.hpp) ---------------
-#define GYMNET_DECLARE_ENV(tag, R)                                                                                              \
-    hipError_t launch_step_##tag(bool autoreset, bool extras, const StepArgsT<R> &a, LaunchCfg cfg, hipStream_t st);            \
-    int describe_step_##tag(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, char *buf, size_t cap);                      \
-    void resolved_shape_##tag(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, int *vec, int *sequential);                \
-    hipError_t launch_rollout_##tag(bool autoreset, bool extras, const StepArgsT<R> &a, const RolloutArgsT<R> &r, LaunchCfg cfg, hipStream_t st); \
-    hipError_t launch_reset_##tag(const ResetArgsT<R> &a, hipStream_t st);                                                      \
-    hipError_t launch_observe_##tag(const R *state, int64_t sstride, R *obs, int64_t ostride, int64_t n, hipStream_t st);            \
-    hipError_t launch_resident_##tag(bool autoreset, bool extras, const StepArgsT<R> &a, const ResetArgsT<R> &r, Mailbox *mb, uint64_t idle_polls, hipStream_t st);
 
 // Fused multi-step rollout: `steps` vector steps inside ONE launch; state stays in registers between steps.
 // Round 5: the rollout carries what its consumer needs (examples/.../PlaySessions/BasePlaySession.cs:58-69 accumulates the episode
@@ -150,27 +140,54 @@ constexpr size_t kMailboxBytes = kMailboxObsOffset + (size_t)kMailboxLanes * 8 *
 static_assert(sizeof(Mailbox) <= kMailboxObsOffset, "mailbox header overlaps the observations");
 constexpr uint32_t kMailboxStep = 1, kMailboxResetAll = 2, kMailboxResetDone = 3, kMailboxExit = 4;
 
-GYMNET_DECLARE_ENV(cartpole, float)
-GYMNET_DECLARE_ENV(pendulum, float)
-GYMNET_DECLARE_ENV(mountaincar, float)
-GYMNET_DECLARE_ENV(acrobot, float)
-GYMNET_DECLARE_ENV(cartpole64, double)      // GYMNET_FLAG_F64: CartPole in the reference's own binary64 arithmetic (cartpole64.hpp)
+// ---- env-dependent launchers: one table per env and state scalar (step_kernels.hpp launchers_of, instantiated by env_*.hip) -----
 
-// env_id: gymnet_env_id; the state scalar of the arguments selects the float32 engine or (env 0 only) the float64 one.
-// autoreset / extras select the compiled variant.  Returns hipError_t.
-hipError_t launch_step(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, LaunchCfg cfg, hipStream_t st);
-hipError_t launch_step(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, LaunchCfg cfg, hipStream_t st);
+// The step kernel instantiation a launch configuration resolves to (step_kernels.hpp select_step): launch_step_env launches exactly
+// this, and gymnet_vecenv_kernel_name / the resolved launch shape read the same decision.
+struct StepForm {
+    int vec = 1;           // lanes per thread on the wide accesses
+    int sequential = 1;    // lanes (or lane pairs) a thread works through one after another in the multi-lane forms (1 = one-shot)
+    int slices = 1;        // > 1: the step is that many launches over consecutive slices of the batch (step_kernels.hpp pipe2_chunks)
+    int (*text)(char *buf, size_t cap, int slices) = nullptr;
+    // the instantiation as text ("step_kernel<CartPole,4,true,false,15,1>", " x G" for G slices); snprintf's contract
+    int name(char *buf, size_t cap) const { return text(buf, cap, slices); }
+};
+template <class R>
+struct StepKernelT : StepForm {
+    void (*kernel)(StepArgsT<R>) = nullptr;                // step_kernel / step_kernel_pipe / step_kernel_pipe2, or
+    void (*lds_kernel)(StepArgsT<R>, int64_t) = nullptr;   // step_kernel_lds (its second argument: the batch's 512-lane tiles)
+    dim3 grid, block;                                      // the launch over the whole batch
+    size_t lds_bytes = 0;                                  // dynamic LDS
+    int64_t slice_lanes = 0, group_lanes = 0;              // slices > 1: lanes per slice, lanes per workgroup
+};
 
-// The template instantiation launch_step would run for this configuration, as text ("step_kernel<CartPole,4,true,false,15,1>");
-// returns the length, or < 0 for an unknown env.  n: the batch size (one form needs whole 2 * items * 256-lane groups).
-int describe_step_kernel(int env_id, bool f64, bool autoreset, bool extras, LaunchCfg cfg, int64_t n, char *buf, size_t cap);
-// what that instantiation is shaped like: lanes per thread on its wide accesses, and lanes (or lane pairs) a thread works through
-// one after another in the multi-lane forms (1 = one-shot kernel)
-void resolved_step_shape(int env_id, bool f64, bool autoreset, bool extras, LaunchCfg cfg, int64_t n, int *vec, int *sequential);
+template <class R>
+struct EnvLaunchers {
+    // one vector step (autoreset / extras select the compiled variant)
+    hipError_t (*step)(bool autoreset, bool extras, const StepArgsT<R> &a, LaunchCfg cfg, hipStream_t st);
+    // what `step` runs for this configuration; n: the batch size (one form needs whole 2 * items * 256-lane groups)
+    StepKernelT<R> (*select_step)(bool autoreset, bool extras, LaunchCfg cfg, int64_t n);
+    // Same results as `steps` step calls (bitwise) — with r.action_source != 0: as `steps` x (sample / compose actions, then step).
+    hipError_t (*rollout)(bool autoreset, bool extras, const StepArgsT<R> &a, const RolloutArgsT<R> &r, LaunchCfg cfg, hipStream_t st);
+    hipError_t (*reset)(const ResetArgsT<R> &a, hipStream_t st);
+    // starts the resident kernel of a small handle (a.n <= kMailboxLanes; a.action must point at mb->actions); mb: device-visible address
+    hipError_t (*resident)(bool autoreset, bool extras, const StepArgsT<R> &a, const ResetArgsT<R> &r, Mailbox *mb, uint64_t idle_polls,
+                           hipStream_t st);
+    // recompute obs from state (after set_state) for envs whose observation is derived; nothing for the others
+    hipError_t (*observe)(const R *state, int64_t sstride, R *obs, int64_t ostride, int64_t n, hipStream_t st);
+};
+// one per env_*.hip (functions, not global tables: clang would copy a constant global table into the device code object too)
+const EnvLaunchers<float> &cartpole_launchers();
+const EnvLaunchers<float> &pendulum_launchers();
+const EnvLaunchers<float> &mountaincar_launchers();
+const EnvLaunchers<float> &acrobot_launchers();
+const EnvLaunchers<double> &cartpole64_launchers();   // GYMNET_FLAG_F64: CartPole in the reference's own binary64 arithmetic
 
-// Same results as `steps` launch_step calls (bitwise) — with r.action_source != 0: as `steps` x (sample / compose actions, then step).
-hipError_t launch_rollout_fused(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, const RolloutArgsT<float> &r, LaunchCfg cfg, hipStream_t st);
-hipError_t launch_rollout_fused(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, const RolloutArgsT<double> &r, LaunchCfg cfg, hipStream_t st);
+// The launchers of env `env_id` (gymnet_env_id) in state scalar R (float, or double for the float64 engine); NULL: no such env, or no
+// float64 form of it (the reference defines float64 arithmetic for CartPole only).  kernels.hip.
+template <class R>
+const EnvLaunchers<R> *env_launchers(int env_id);
+
 // Gathers the kShards segments of a fused rollout's episode records (RolloutArgs::ep_*) into compact arrays out_*[0 .. *out_count);
 // records beyond out_capacity are dropped, the count is the number of records kept by the rollout.  Any out array may be NULL.
 struct EpisodeGatherArgs {
@@ -181,12 +198,6 @@ struct EpisodeGatherArgs {
     int64_t out_capacity; uint32_t *out_count;
 };
 hipError_t launch_gather_episodes(const EpisodeGatherArgs &a, hipStream_t st);
-
-hipError_t launch_reset(int env_id, const ResetArgsT<float> &a, hipStream_t st);
-hipError_t launch_reset(int env_id, const ResetArgsT<double> &a, hipStream_t st);
-// starts the resident kernel of a small handle (a.n <= kMailboxLanes; a.action must point at mb->actions); mb: device-visible address
-hipError_t launch_resident(int env_id, bool autoreset, bool extras, const StepArgsT<float> &a, const ResetArgsT<float> &r, Mailbox *mb, uint64_t idle_polls, hipStream_t st);
-hipError_t launch_resident(int env_id, bool autoreset, bool extras, const StepArgsT<double> &a, const ResetArgsT<double> &r, Mailbox *mb, uint64_t idle_polls, hipStream_t st);
 
 // observations: SoA [O][stride] -> row-major [n][O]; float32, or float64 for a GYMNET_FLAG_F64 handle (here and below)
 hipError_t launch_pack_obs(int obs_dim, const float *obs, int64_t stride, float *out_rowmajor, int64_t n, hipStream_t st);
@@ -203,9 +214,6 @@ hipError_t launch_export_host(int obs_dim, const float *obs, int64_t stride, con
                               float *out_obs, float *out_reward, uint8_t *out_done, int64_t n, hipStream_t st);
 hipError_t launch_export_host(int obs_dim, const double *obs, int64_t stride, const float *reward, const uint8_t *done,
                               double *out_obs, float *out_reward, uint8_t *out_done, int64_t n, hipStream_t st);
-// recompute obs from state (after set_state) for envs whose observation is derived
-hipError_t launch_observe(int env_id, const float *state, int64_t state_stride, float *obs, int64_t obs_stride,
-                          int64_t n, hipStream_t st);
 // CartPole frames (render.hip; contract: gymnet_vecenv_render_device).  Frame k of lanes [first_lane, first_lane + count) is
 // out + k * lane_stride; total_waves = count * waves_per_frame, waves_per_frame = render_waves_per_frame(out_w, out_h).
 struct RenderArgs {

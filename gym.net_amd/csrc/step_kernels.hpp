@@ -1419,33 +1419,41 @@ __global__ __launch_bounds__(64) void resident_kernel(const StepArgsT<typename E
     }
 }
 
-template <class Env>
-static hipError_t launch_resident_env(bool autoreset, bool extras, const StepArgsT<typename Env::Real> &a, const ResetArgsT<typename Env::Real> &r,
-                                      Mailbox *mb, uint64_t idle_polls, hipStream_t st) {
-    if (a.n > kMailboxLanes) return hipErrorInvalidValue;
-    const dim3 grid(1), blk(64);
-    if (autoreset) { if (extras) hipLaunchKernelGGL((resident_kernel<Env, true, true>), grid, blk, 0, st, a, r, mb, idle_polls);
-                     else hipLaunchKernelGGL((resident_kernel<Env, true, false>), grid, blk, 0, st, a, r, mb, idle_polls); }
-    else           { if (extras) hipLaunchKernelGGL((resident_kernel<Env, false, true>), grid, blk, 0, st, a, r, mb, idle_polls);
-                     else hipLaunchKernelGGL((resident_kernel<Env, false, false>), grid, blk, 0, st, a, r, mb, idle_polls); }
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
+//
+// A handle reaches its kernels through ONE table per env and state scalar (kernels.hpp EnvLaunchers): launchers_of<Env> at the end
+// of this file, instantiated by the env's translation unit (env_*.hip) and looked up once, at create.  Each launcher resolves its
+// run-time configuration to one kernel instantiation and launches that function pointer; for the step kernels the resolution is
+// select_step, whose result also carries the instantiation's name (gymnet_vecenv_kernel_name) and shape, so the name and the
+// launch cannot disagree.  Run-time values become template arguments through with_bool / with_int; the `if constexpr` guard beside
+// each selection admits only the combinations its rules can reach, which keeps the instantiated set to the selectable forms.
 // ---------------------------------------------------------------------------------------------
 static inline unsigned grid_for(int64_t items, int block) { return (unsigned)((items + block - 1) / block); }
 
-// Which instantiation a step launch resolves to: ONE function decides, the launcher dispatches on it and
-// describe_step_kernel() prints it (gymnet_vecenv_kernel_name: tests and bench.py name the kernel they ran from the library,
-// not from a copy of this policy).
-struct StepVariant {
-    int lds_tiles;      // > 1: step_kernel_lds<Env, lds_tiles, AUTORESET, 15> (producer / consumer form of the multi-lane kernel)
-    int pipe_items;     // > 1: step_kernel_pipe<Env, pipe_items, AUTORESET, 15> (or step_kernel_pipe2 with pipe_pairs); else step_kernel
-    bool pipe_pairs = false;   // the multi-lane kernel over lane PAIRS (step_kernel_pipe2)
-    int vec, nt;        // step_kernel<Env, vec, AUTORESET, EXTRAS, nt, resetf>
-    int resetf;
-};
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+template <int I> using int_c = std::integral_constant<int, I>;
+
+// f(bool_c<b>{})
+template <class F>
+static void with_bool(bool b, F &&f) { if (b) f(bool_c<true>{}); else f(bool_c<false>{}); }
+// f(int_c<v>{}) for the one of I... that equals v (none: f is not called)
+template <int... I, class F>
+static void with_int(int v, F &&f) { (void)((v == I ? (f(int_c<I>{}), true) : false) || ...); }
+
+// "FAMILY<Env,P...>" printed from the template arguments the kernel is instantiated with; " x G": the step is G launches of it over
+// consecutive slices of the batch (pipe2_chunks)
+static inline int put_targ(char *t, size_t cap, bool v) { return std::snprintf(t, cap, ",%s", v ? "true" : "false"); }
+static inline int put_targ(char *t, size_t cap, int v) { return std::snprintf(t, cap, ",%d", v); }
+template <const char *FAMILY, class Env, auto... P>
+static int kernel_text(char *buf, size_t cap, int slices) {
+    char t[160];
+    int len = std::snprintf(t, sizeof t, "%s<%s", FAMILY, Env::NAME);
+    ((len += put_targ(t + len, sizeof t - (size_t)len, P)), ...);
+    return slices > 1 ? std::snprintf(buf, cap, "%s> x %d", t, slices) : std::snprintf(buf, cap, "%s>", t);
+}
+constexpr char kStepKernel[] = "step_kernel", kStepKernelPipe[] = "step_kernel_pipe", kStepKernelPipe2[] = "step_kernel_pipe2",
+               kStepKernelLds[] = "step_kernel_lds";
 
 static LaunchCfg normalized(LaunchCfg cfg) {
     if (cfg.vec != 4 && cfg.vec != 2) cfg.vec = 1;
@@ -1459,15 +1467,41 @@ static LaunchCfg normalized(LaunchCfg cfg) {
 template <class Env>
 constexpr int wide_of() { return (sizeof(typename Env::Real) == 8 || Env::PACKED2) ? 2 : 4; }
 
+// the wave-compacted fused reset (RESETF = 1, auto-reset only) exists for V > 1 lanes per thread of an env whose observation IS its
+// state, in the unpacked form
+template <class Env, int V>
+constexpr bool has_reset_form1() { return Env::OBS_ALIASES_STATE && !Env::PACKED2 && V > 1; }
+
+// Which instantiation a step launch resolves to, and how it is launched.
 template <class Env>
-static StepVariant resolve_variant(bool autoreset, bool extras, const LaunchCfg &cfg, int64_t n) {
-    StepVariant v{};
-    v.lds_tiles = 1; v.pipe_items = 1; v.vec = 1; v.nt = cfg.nt; v.resetf = 0;
+static StepKernelT<typename Env::Real> select_step(bool autoreset, bool extras, LaunchCfg cfg, int64_t n) {
+    cfg = normalized(cfg);
+    StepKernelT<typename Env::Real> k;
     if constexpr (Env::PIPE_LANES) {       // multi-lane kernel, cfg.items lanes per thread (2..5)
         if (cfg.items > 1 && cfg.items <= 5 && !extras && cfg.vec == 1) {
-            v.nt = 15;
-            if (cfg.lds_pipe) v.lds_tiles = cfg.items; else v.pipe_items = cfg.items;
-            return v;
+            with_bool(autoreset, [&](auto ar) {
+                with_int<2, 3, 4, 5>(cfg.items, [&](auto items) {
+                    constexpr bool AR = decltype(ar)::value;
+                    constexpr int I = decltype(items)::value;
+                    if (cfg.lds_pipe) {
+                        k.lds_kernel = step_kernel_lds<Env, I, AR, 15>;
+                        k.text = kernel_text<kStepKernelLds, Env, I, AR, 15>;
+                    } else {
+                        k.kernel = step_kernel_pipe<Env, I, AR, 15>;
+                        k.text = kernel_text<kStepKernelPipe, Env, I, AR, 15>;
+                    }
+                });
+            });
+            k.sequential = cfg.items;
+            if (cfg.lds_pipe) {
+                k.grid = dim3(grid_for(n / kLdsTileMax, cfg.items));
+                k.block = dim3(kLdsTileMax + 64);
+            } else {
+                const int64_t per_block = 256 * (int64_t)cfg.items;
+                k.grid = dim3(grid_for(n > 0 ? (n + per_block - 1) / per_block : 1, 1));
+                k.block = dim3(256);
+            }
+            return k;
         }
     }
     if constexpr (Env::PIPE_PAIRS) {
@@ -1477,141 +1511,78 @@ static StepVariant resolve_variant(bool autoreset, bool extras, const LaunchCfg 
         if (cfg.items > 1 && cfg.items <= 4 && !extras && cfg.vec == 2 && !cfg.lds_pipe && n > 0 && (any_n || n % (2 * (int64_t)cfg.items * 256) == 0)) {
             // every stream non-temporal, except that the four-pair form with the deferred reset also exists with the other two masks
             // (the stream policy of a batch beyond one resident generation is a measured choice: capi.hip default_policy)
-            v.nt = (any_n && cfg.items == 4) ? cfg.nt : 15; v.vec = 2; v.pipe_items = cfg.items; v.pipe_pairs = true;
-            return v;
+            const int nt = (any_n && cfg.items == 4) ? cfg.nt : 15;
+            with_bool(autoreset, [&](auto ar) {
+                with_int<2, 3, 4>(cfg.items, [&](auto items) {
+                    with_int<0, 12, 15>(nt, [&](auto ntm) {
+                        constexpr bool AR = decltype(ar)::value;
+                        constexpr int I = decltype(items)::value, NT = decltype(ntm)::value;
+                        if constexpr (NT == 15 || (I == 4 && AR && has_split_reset<Env>())) {
+                            k.kernel = step_kernel_pipe2<Env, I, AR, NT>;
+                            k.text = kernel_text<kStepKernelPipe2, Env, I, AR, NT>;
+                        }
+                    });
+                });
+            });
+            // whole groups of 2 * items * block lanes — or, for the form with the deferred reset, any batch (the last workgroups
+            // run the guarded body) in one launch per resident generation
+            const Pipe2Chunks ch = pipe2_chunks(n, cfg.items, cfg.block, any_n, cfg.simds);
+            k.vec = 2;
+            k.sequential = cfg.items;
+            k.slices = ch.chunks;
+            k.slice_lanes = ch.lanes;
+            k.group_lanes = 2 * (int64_t)cfg.items * cfg.block;
+            k.grid = dim3((unsigned)((n + k.group_lanes - 1) / k.group_lanes));
+            k.block = dim3(cfg.block);
+            return k;
         }
     }
-    if (cfg.vec > 1) v.vec = wide_of<Env>();
-    // wave-compacted fused reset: wide variant of an env whose observation IS its state
-    if (Env::OBS_ALIASES_STATE && !Env::PACKED2 && cfg.reset_form == 1 && v.vec == wide_of<Env>() && autoreset) v.resetf = 1;
-    return v;
-}
-
-// the one-shot kernel with V lanes per thread: dispatch on (AUTORESET, EXTRAS, non-temporal mask, reset form)
-template <class Env, int V>
-static hipError_t launch_one_shot(const StepVariant &v, bool autoreset, bool extras, const LaunchCfg &cfg, const StepArgsT<typename Env::Real> &a,
-                                  hipStream_t st) {
-    const int64_t threads = (a.n + V - 1) / V;
-    const dim3 grid(grid_for(threads > 0 ? threads : 1, cfg.block)), blk(cfg.block);
-#define GYMNET_LAUNCH(AR, EX, NTM, RF) hipLaunchKernelGGL((step_kernel<Env, V, AR, EX, NTM, RF>), grid, blk, (size_t)cfg.lds_bytes, st, a)
-#define GYMNET_LAUNCH_NT(AR, EX, RF)                                  \
-    do {                                                              \
-        if (v.nt == 15) GYMNET_LAUNCH(AR, EX, 15, RF);                \
-        else if (v.nt == 12) GYMNET_LAUNCH(AR, EX, 12, RF);           \
-        else GYMNET_LAUNCH(AR, EX, 0, RF);                            \
-    } while (0)
-    if constexpr (Env::OBS_ALIASES_STATE && !Env::PACKED2 && V > 1) {
-        if (v.resetf == 1) {      // (resolve_variant: only with auto-reset)
-            if (extras) GYMNET_LAUNCH_NT(true, true, 1); else GYMNET_LAUNCH_NT(true, false, 1);
-            return hipGetLastError();
-        }
-    }
-    if (extras) {   // bookkeeping variants follow the same stream policy (their own arrays stay cacheable)
-        if (autoreset) GYMNET_LAUNCH_NT(true, true, 0); else GYMNET_LAUNCH_NT(false, true, 0);
-    } else {
-        if (autoreset) GYMNET_LAUNCH_NT(true, false, 0); else GYMNET_LAUNCH_NT(false, false, 0);
-    }
-#undef GYMNET_LAUNCH_NT
-#undef GYMNET_LAUNCH
-    return hipGetLastError();
+    // the one-shot kernel: V lanes per thread, (AUTORESET, EXTRAS, non-temporal mask, reset form); the bookkeeping variants follow
+    // the same stream policy (their own arrays stay cacheable)
+    constexpr int WIDE = wide_of<Env>();
+    k.vec = cfg.vec > 1 ? WIDE : 1;
+    const bool resetf = has_reset_form1<Env, WIDE>() && cfg.reset_form == 1 && k.vec == WIDE && autoreset;
+    const auto one_shot = [&](auto vec) {
+        with_bool(autoreset, [&](auto ar) {
+            with_bool(extras, [&](auto ex) {
+                with_bool(resetf, [&](auto rf) {
+                    with_int<0, 12, 15>(cfg.nt, [&](auto ntm) {
+                        constexpr int V = decltype(vec)::value, NT = decltype(ntm)::value, RF = decltype(rf)::value ? 1 : 0;
+                        constexpr bool AR = decltype(ar)::value, EX = decltype(ex)::value;
+                        if constexpr (RF == 0 || (AR && has_reset_form1<Env, V>())) {
+                            k.kernel = step_kernel<Env, V, AR, EX, NT, RF>;
+                            k.text = kernel_text<kStepKernel, Env, V, AR, EX, NT, RF>;
+                        }
+                    });
+                });
+            });
+        });
+    };
+    if (k.vec == 1) one_shot(int_c<1>{});
+    else one_shot(int_c<WIDE>{});
+    const int64_t threads = (n + k.vec - 1) / k.vec;
+    k.grid = dim3(grid_for(threads > 0 ? threads : 1, cfg.block));
+    k.block = dim3(cfg.block);
+    k.lds_bytes = (size_t)cfg.lds_bytes;
+    return k;
 }
 
 template <class Env>
 static hipError_t launch_step_env(bool autoreset, bool extras, const StepArgsT<typename Env::Real> &a, LaunchCfg cfg, hipStream_t st) {
-    cfg = normalized(cfg);
-    const StepVariant v = resolve_variant<Env>(autoreset, extras, cfg, a.n);
-    if constexpr (Env::PIPE_PAIRS) {
-        if (v.pipe_pairs) {
-            // whole groups of 2 * items * 256 lanes (resolve_variant: any workgroup size divides the batch) — or, for the form with
-            // the deferred reset, any batch: the last workgroups run the guarded body
-            // one launch per resident generation (pipe2_chunks): every slice reads the same tick word and writes the same successor
-            const Pipe2Chunks ch = pipe2_chunks(a.n, v.pipe_items, cfg.block, has_split_reset<Env>() && autoreset, cfg.simds);
-            const int64_t per_block = 2 * (int64_t)v.pipe_items * cfg.block;
-            for (int c = 0; c < ch.chunks; ++c) {
-                const int64_t first = (int64_t)c * ch.lanes, count = (a.n - first < ch.lanes) ? a.n - first : ch.lanes;
-                const StepArgsT<typename Env::Real> sa = ch.chunks == 1 ? a : slice_of(a, first, count);
-                const dim3 qgrid((unsigned)((count + per_block - 1) / per_block)), qblk(cfg.block);
-#define GYMNET_PIPE2(I)                                                                                                 \
-    case I:                                                                                                             \
-        if (autoreset) hipLaunchKernelGGL((step_kernel_pipe2<Env, I, true, 15>), qgrid, qblk, 0, st, sa);                \
-        else hipLaunchKernelGGL((step_kernel_pipe2<Env, I, false, 15>), qgrid, qblk, 0, st, sa);                         \
-        break;
-                if constexpr (has_split_reset<Env>()) {
-                    if (autoreset && v.pipe_items == 4 && v.nt != 15) {
-                        if (v.nt == 12) hipLaunchKernelGGL((step_kernel_pipe2<Env, 4, true, 12>), qgrid, qblk, 0, st, sa);
-                        else hipLaunchKernelGGL((step_kernel_pipe2<Env, 4, true, 0>), qgrid, qblk, 0, st, sa);
-                        continue;
-                    }
-                }
-                switch (v.pipe_items) {
-                    GYMNET_PIPE2(2) GYMNET_PIPE2(3) GYMNET_PIPE2(4)
-                    default: return hipErrorInvalidValue;
-                }
-#undef GYMNET_PIPE2
-            }
-            return hipGetLastError();
+    const StepKernelT<typename Env::Real> k = select_step<Env>(autoreset, extras, cfg, a.n);
+    if (k.lds_kernel) {
+        hipLaunchKernelGGL(k.lds_kernel, k.grid, k.block, 0, st, a, a.n / kLdsTileMax);
+    } else if (k.slices == 1) {
+        hipLaunchKernelGGL(k.kernel, k.grid, k.block, k.lds_bytes, st, a);
+    } else {
+        // every slice reads the same tick word and writes the same successor
+        for (int c = 0; c < k.slices; ++c) {
+            const int64_t first = (int64_t)c * k.slice_lanes, count = (a.n - first < k.slice_lanes) ? a.n - first : k.slice_lanes;
+            const dim3 grid((unsigned)((count + k.group_lanes - 1) / k.group_lanes));
+            hipLaunchKernelGGL(k.kernel, grid, k.block, 0, st, slice_of(a, first, count));
         }
     }
-    if constexpr (Env::PIPE_LANES) {
-        if (v.lds_tiles > 1) {
-            const int64_t tiles = a.n / kLdsTileMax;
-            const dim3 lgrid(grid_for(tiles, v.lds_tiles)), lblk(kLdsTileMax + 64);
-#define GYMNET_LDS(I)                                                                                                   \
-    case I:                                                                                                             \
-        if (autoreset) hipLaunchKernelGGL((step_kernel_lds<Env, I, true, 15>), lgrid, lblk, 0, st, a, tiles);            \
-        else hipLaunchKernelGGL((step_kernel_lds<Env, I, false, 15>), lgrid, lblk, 0, st, a, tiles);                     \
-        break;
-            switch (v.lds_tiles) {
-                GYMNET_LDS(2) GYMNET_LDS(3) GYMNET_LDS(4) GYMNET_LDS(5)
-                default: return hipErrorInvalidValue;
-            }
-#undef GYMNET_LDS
-            return hipGetLastError();
-        }
-        if (v.pipe_items > 1) {
-            const int64_t per_block = 256 * (int64_t)v.pipe_items;
-            const dim3 pgrid(grid_for(a.n > 0 ? (a.n + per_block - 1) / per_block : 1, 1)), pblk(256);
-#define GYMNET_PIPE(I)                                                                                                  \
-    case I:                                                                                                             \
-        if (autoreset) hipLaunchKernelGGL((step_kernel_pipe<Env, I, true, 15>), pgrid, pblk, 0, st, a);                  \
-        else hipLaunchKernelGGL((step_kernel_pipe<Env, I, false, 15>), pgrid, pblk, 0, st, a);                           \
-        break;
-            switch (v.pipe_items) {
-                GYMNET_PIPE(2) GYMNET_PIPE(3) GYMNET_PIPE(4) GYMNET_PIPE(5)
-                default: return hipErrorInvalidValue;
-            }
-#undef GYMNET_PIPE
-            return hipGetLastError();
-        }
-    }
-    if (v.vec == 1) return launch_one_shot<Env, 1>(v, autoreset, extras, cfg, a, st);
-    return launch_one_shot<Env, wide_of<Env>()>(v, autoreset, extras, cfg, a, st);
-}
-
-template <class Env>
-static int describe_step_env(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, char *buf, size_t cap) {
-    cfg = normalized(cfg);
-    const StepVariant v = resolve_variant<Env>(autoreset, extras, cfg, n);
-    const char *env = Env::NAME;
-    const char *ar = autoreset ? "true" : "false";
-    if (v.pipe_pairs) {
-        // " x G": the step is G launches of this kernel over consecutive slices of the batch (pipe2_chunks)
-        const Pipe2Chunks ch = pipe2_chunks(n, v.pipe_items, cfg.block, has_split_reset<Env>() && autoreset, cfg.simds);
-        if (ch.chunks > 1) return std::snprintf(buf, cap, "step_kernel_pipe2<%s,%d,%s,%d> x %d", env, v.pipe_items, ar, v.nt, ch.chunks);
-        return std::snprintf(buf, cap, "step_kernel_pipe2<%s,%d,%s,%d>", env, v.pipe_items, ar, v.nt);
-    }
-    if (v.lds_tiles > 1) return std::snprintf(buf, cap, "step_kernel_lds<%s,%d,%s,15>", env, v.lds_tiles, ar);
-    if (v.pipe_items > 1) return std::snprintf(buf, cap, "step_kernel_pipe<%s,%d,%s,15>", env, v.pipe_items, ar);
-    return std::snprintf(buf, cap, "step_kernel<%s,%d,%s,%s,%d,%d>", env, v.vec, ar, extras ? "true" : "false", v.nt, v.resetf);
-}
-
-// lanes per thread on 16-byte rows the NEXT step launch resolves to, and (multi-lane forms) lanes or lane pairs per thread
-template <class Env>
-static void resolved_shape_env(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, int *vec, int *sequential) {
-    cfg = normalized(cfg);
-    const StepVariant v = resolve_variant<Env>(autoreset, extras, cfg, n);
-    *vec = v.vec;
-    *sequential = v.lds_tiles > 1 ? v.lds_tiles : v.pipe_items;
+    return hipGetLastError();
 }
 
 // Lanes per thread of the fused rollout's FAT form — beyond the widest step-kernel form: four doubles per thread for the float64 env
@@ -1623,69 +1594,63 @@ constexpr int rollout_fat_lanes() { return (sizeof(typename Env::Real) == 8 && E
 template <class Env>
 static hipError_t launch_rollout_env(bool autoreset, bool extras, const StepArgsT<typename Env::Real> &a, const RolloutArgsT<typename Env::Real> &r,
                                      LaunchCfg cfg, hipStream_t st) {
-    constexpr int WIDE = wide_of<Env>();
-    const bool wide = cfg.vec == 4 || cfg.vec == 2;
+    using R = typename Env::Real;
     const bool sample = r.action_source != 0;
-    const int64_t threads = (a.n + (wide ? WIDE : 1) - 1) / (wide ? WIDE : 1);
-    const dim3 grid(grid_for(threads > 0 ? threads : 1, 256)), blk(256);
-    const bool records = extras && r.ep_lane != nullptr;
-#define GYMNET_ROLL(V, AR, RF)                                                                                                     \
-    do {                                                                                                                          \
-        if (records && r.records_no_overflow) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, true, RF, 2>), grid, blk, 0, st, a, r); \
-                       else hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, false, RF, 2>), grid, blk, 0, st, a, r); }        \
-        else if (records) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, true, RF, 1>), grid, blk, 0, st, a, r); \
-                       else hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, false, RF, 1>), grid, blk, 0, st, a, r); }        \
-        else if (extras) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, true, RF>), grid, blk, 0, st, a, r);   \
-                           else hipLaunchKernelGGL((rollout_kernel<Env, V, AR, true, false, RF>), grid, blk, 0, st, a, r); }       \
-        else        { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, V, AR, false, true, RF>), grid, blk, 0, st, a, r);       \
-                      else hipLaunchKernelGGL((rollout_kernel<Env, V, AR, false, false, RF>), grid, blk, 0, st, a, r); }           \
-    } while (0)
-    if constexpr (rollout_fat_lanes<Env>() > 0) {
-        // The FAT form (cfg.vec == rollout_fat_lanes: capi selects it when every stream is aligned for it): 8 floats / 4 doubles per
-        // thread.  The state lives in registers for all T steps, so the lane count per thread only decides how many lanes share one
-        // wave's per-step overheads — the wave-compacted reset pass, its LDS hand-off, the loop — and how many independent chains a
-        // thread interleaves; the rollouts are instruction-issue bound (SQ counters, profiles/pmc_rollout_r05.txt: float64 187 -> 145
-        // VALU per env-step).
-        constexpr int FAT = rollout_fat_lanes<Env>();
-        if (cfg.vec == FAT) {
-            const int64_t threads4 = (a.n + FAT - 1) / FAT;
-            const dim3 grid4(grid_for(threads4 > 0 ? threads4 : 1, 256));
-#define GYMNET_ROLL4(AR, RF)                                                                                                        \
-    do {                                                                                                                            \
-        if (records && r.records_no_overflow) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, true, RF, 2>), grid4, blk, 0, st, a, r);  \
-                       else hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, false, RF, 2>), grid4, blk, 0, st, a, r); }         \
-        else if (records) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, true, RF, 1>), grid4, blk, 0, st, a, r);  \
-                       else hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, false, RF, 1>), grid4, blk, 0, st, a, r); }         \
-        else if (extras) { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, true, RF>), grid4, blk, 0, st, a, r);    \
-                           else hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, true, false, RF>), grid4, blk, 0, st, a, r); }        \
-        else        { if (sample) hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, false, true, RF>), grid4, blk, 0, st, a, r);        \
-                      else hipLaunchKernelGGL((rollout_kernel<Env, FAT, AR, false, false, RF>), grid4, blk, 0, st, a, r); }            \
-    } while (0)
-            if (autoreset) { if (cfg.reset_form == 1) GYMNET_ROLL4(true, 1); else GYMNET_ROLL4(true, 0); }
-            else GYMNET_ROLL4(false, 0);
-#undef GYMNET_ROLL4
-            return hipGetLastError();
-        }
+    // compact episode records of a bookkeeping rollout: 1 = with the overflow segment, 2 = without it
+    const int records = (extras && r.ep_lane != nullptr) ? (r.records_no_overflow ? 2 : 1) : 0;
+    // the rollout kernel with V lanes per thread; the wave-compacted reset per step with cfg.reset_form = 1 where the env has it
+    const auto launch = [&](auto vec) {
+        constexpr int V = decltype(vec)::value;
+        const bool resetf = has_reset_form1<Env, V>() && autoreset && cfg.reset_form == 1;
+        void (*kernel)(StepArgsT<R>, RolloutArgsT<R>) = nullptr;
+        with_bool(autoreset, [&](auto ar) {
+            with_bool(extras, [&](auto ex) {
+                with_bool(sample, [&](auto smp) {
+                    with_bool(resetf, [&](auto rf) {
+                        with_int<0, 1, 2>(records, [&](auto rec) {
+                            constexpr bool AR = decltype(ar)::value, EX = decltype(ex)::value, SAMPLE = decltype(smp)::value;
+                            constexpr int RF = decltype(rf)::value ? 1 : 0, RECORDS = decltype(rec)::value;
+                            if constexpr ((RF == 0 || (AR && has_reset_form1<Env, V>())) && (RECORDS == 0 || EX))
+                                kernel = rollout_kernel<Env, V, AR, EX, SAMPLE, RF, RECORDS>;
+                        });
+                    });
+                });
+            });
+        });
+        const int64_t threads = (a.n + V - 1) / V;
+        hipLaunchKernelGGL(kernel, dim3(grid_for(threads > 0 ? threads : 1, 256)), dim3(256), 0, st, a, r);
+        return hipGetLastError();
+    };
+    // The FAT form (cfg.vec == rollout_fat_lanes: capi selects it when every stream is aligned for it): 8 floats / 4 doubles per
+    // thread.  The state lives in registers for all T steps, so the lane count per thread only decides how many lanes share one
+    // wave's per-step overheads — the wave-compacted reset pass, its LDS hand-off, the loop — and how many independent chains a
+    // thread interleaves; the rollouts are instruction-issue bound (SQ counters, profiles/pmc_rollout_r05.txt: float64 187 -> 145
+    // VALU per env-step).
+    constexpr int FAT = rollout_fat_lanes<Env>();
+    if constexpr (FAT > 0) {
+        if (cfg.vec == FAT) return launch(int_c<FAT>{});
     }
-    if (wide) {
-        if (autoreset) {
-            // the wave-compacted reset per step (cfg.reset_form = 1; envs whose observation IS the state, wide lanes)
-            if constexpr (Env::OBS_ALIASES_STATE && !Env::PACKED2 && WIDE > 1) {
-                if (cfg.reset_form == 1) { GYMNET_ROLL(WIDE, true, 1); return hipGetLastError(); }
-            }
-            GYMNET_ROLL(WIDE, true, 0);
-        } else GYMNET_ROLL(WIDE, false, 0);
-    } else {
-        if (autoreset) GYMNET_ROLL(1, true, 0); else GYMNET_ROLL(1, false, 0);
-    }
-#undef GYMNET_ROLL
-    return hipGetLastError();
+    if (cfg.vec == 4 || cfg.vec == 2) return launch(int_c<wide_of<Env>()>{});
+    return launch(int_c<1>{});
 }
 
 template <class Env>
 static hipError_t launch_reset_env(const ResetArgsT<typename Env::Real> &a, hipStream_t st) {
     const dim3 grid(grid_for(a.n > 0 ? (a.n + 3) / 4 : 1, 256)), blk(256);
     hipLaunchKernelGGL(reset_kernel<Env>, grid, blk, 0, st, a);
+    return hipGetLastError();
+}
+
+template <class Env>
+static hipError_t launch_resident_env(bool autoreset, bool extras, const StepArgsT<typename Env::Real> &a, const ResetArgsT<typename Env::Real> &r,
+                                      Mailbox *mb, uint64_t idle_polls, hipStream_t st) {
+    using R = typename Env::Real;
+    if (a.n > kMailboxLanes) return hipErrorInvalidValue;
+    void (*kernel)(StepArgsT<R>, ResetArgsT<R>, Mailbox *, uint64_t) = nullptr;
+    with_bool(autoreset, [&](auto ar) {
+        with_bool(extras, [&](auto ex) { kernel = resident_kernel<Env, decltype(ar)::value, decltype(ex)::value>; });
+    });
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, a, r, mb, idle_polls);
     return hipGetLastError();
 }
 
@@ -1700,32 +1665,10 @@ static hipError_t launch_observe_env(const typename Env::Real *state, int64_t ss
     }
 }
 
-}  // namespace gymnet
+// The table an env's translation unit exports (env_*.hip; kernels.hpp EnvLaunchers).
+template <class Env>
+constexpr EnvLaunchers<typename Env::Real> launchers_of() {
+    return {launch_step_env<Env>, select_step<Env>, launch_rollout_env<Env>, launch_reset_env<Env>, launch_resident_env<Env>, launch_observe_env<Env>};
+}
 
-// One translation unit per env (env_*.hip) instantiates the kernels above and exports them under the env's tag; kernels.hip
-// dispatches on (env_id, state scalar) — see GYMNET_DECLARE_ENV in kernels.hpp.
-#define GYMNET_DEFINE_ENV(tag, Env)                                                                                                   \
-    namespace gymnet {                                                                                                                \
-    hipError_t launch_step_##tag(bool autoreset, bool extras, const StepArgsT<Env::Real> &a, LaunchCfg cfg, hipStream_t st) {         \
-        return launch_step_env<Env>(autoreset, extras, a, cfg, st);                                                                   \
-    }                                                                                                                                 \
-    int describe_step_##tag(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, char *buf, size_t cap) {                           \
-        return describe_step_env<Env>(autoreset, extras, cfg, n, buf, cap);                                                           \
-    }                                                                                                                                 \
-    void resolved_shape_##tag(bool autoreset, bool extras, LaunchCfg cfg, int64_t n, int *vec, int *sequential) {                     \
-        resolved_shape_env<Env>(autoreset, extras, cfg, n, vec, sequential);                                                          \
-    }                                                                                                                                 \
-    hipError_t launch_rollout_##tag(bool autoreset, bool extras, const StepArgsT<Env::Real> &a, const RolloutArgsT<Env::Real> &r,    \
-                                    LaunchCfg cfg, hipStream_t st) {                                                                  \
-        return launch_rollout_env<Env>(autoreset, extras, a, r, cfg, st);                                                             \
-    }                                                                                                                                 \
-    hipError_t launch_reset_##tag(const ResetArgsT<Env::Real> &a, hipStream_t st) { return launch_reset_env<Env>(a, st); }            \
-    hipError_t launch_resident_##tag(bool autoreset, bool extras, const StepArgsT<Env::Real> &a, const ResetArgsT<Env::Real> &r,      \
-                                     Mailbox *mb, uint64_t idle_polls, hipStream_t st) {                                              \
-        return launch_resident_env<Env>(autoreset, extras, a, r, mb, idle_polls, st);                                                 \
-    }                                                                                                                                 \
-    hipError_t launch_observe_##tag(const Env::Real *state, int64_t sstride, Env::Real *obs, int64_t ostride, int64_t n,              \
-                                    hipStream_t st) {                                                                                 \
-        return launch_observe_env<Env>(state, sstride, obs, ostride, n, st);                                                          \
-    }                                                                                                                                 \
-    }
+}  // namespace gymnet

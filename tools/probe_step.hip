@@ -308,7 +308,7 @@ void LPROD(const Args &a, hipStream_t st) {
     s.tick2 = g_tick2; s.n = a.n; s.state_stride = a.s1 - a.s0; s.obs_stride = s.state_stride;
     s.seed = a.seed; s.parity = (int32_t)(g_host_tick & 1); s.cparity = s.parity;
     ++g_host_tick;
-    launch_step(0, true, false, s, LaunchCfg{VEC, 256, NT}, st);
+    cartpole_launchers().step(true, false, s, LaunchCfg{VEC, 256, NT}, st);
 }
 
 int main(int argc, char **argv) {
@@ -408,7 +408,7 @@ int main(int argc, char **argv) {
                     s.reward = a.reward + p * np; s.done = a.done + p * np;
                     s.tick2 = g_tick2; s.n = np; s.state_stride = n; s.obs_stride = n; s.lane_offset = (uint64_t)(p * np);
                     s.seed = a.seed; s.parity = 0; s.cparity = 0;
-                    launch_step(0, true, false, s, LaunchCfg{4, 256, 15}, ss[p]);
+                    cartpole_launchers().step(true, false, s, LaunchCfg{4, 256, 15}, ss[p]);
                 }
             std::vector<hipEvent_t> ends(parts);
             for (int p = 0; p < parts; ++p) { CK(hipEventCreate(&ends[p])); CK(hipEventRecord(ends[p], ss[p])); }

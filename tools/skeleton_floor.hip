@@ -218,7 +218,7 @@ static void run_env(const char *label, int moved_bytes, LaunchCfg cfg, int64_t n
     HIP_OK(hipStreamSynchronize(st));
     uint64_t tick = 0;
     char name[160];
-    describe_step_env<Env>(true, false, cfg, n, name, sizeof name);
+    select_step<Env>(true, false, cfg, n).name(name, sizeof name);
     // warm-up of both, then alternate
     time_launches<Env>(b, n, cfg, 300, st, tick);
     time_launches<Floor>(b, n, cfg, 300, st, tick);
