@@ -1221,6 +1221,8 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
     if (ring_read && !sp.d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
     if (sp.steps < 0 || (ring_read && (sp.ring < 1 || sp.action_stride < 0))) return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride");
     if (sp.steps > INT32_MAX) return fail(h, GYMNET_ERR_INVALID_ARG, "steps must fit an int32 (episode records carry the step index)");
+    // ABI 5 called this field `reserved`: a caller that left it uninitialised must not select the lossy no-overflow variant by accident
+    if (sp.record_flags & ~GYMNET_RECORDS_NO_OVERFLOW) return fail(h, GYMNET_ERR_INVALID_ARG, "unknown record_flags bits 0x%x", (unsigned)sp.record_flags);
     if (sp.action_source == GYMNET_ACTIONS_EPSILON_GREEDY) {
         if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "epsilon-greedy composition is defined for Discrete action spaces");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");

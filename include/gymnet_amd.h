@@ -329,7 +329,8 @@ typedef struct gymnet_rollout_spec {
     uint64_t action_seed;        /* SAMPLE / EPSILON_GREEDY: Philox action stream key ... */
     uint64_t action_tick0;       /* ... and tick of step 0 (step t draws with tick action_tick0 + t) */
     float    epsilon;            /* EPSILON_GREEDY: exploration probability, [0, 1] */
-    int32_t  record_flags;       /* episode records: 0, or GYMNET_RECORDS_NO_OVERFLOW (ABI 5 called this field `reserved`: 0 = the default) */
+    int32_t  record_flags;       /* episode records: 0, or GYMNET_RECORDS_NO_OVERFLOW (ABI 5 called this field `reserved`: 0 = the default).
+                                    Zero-initialise the spec: any other bit is refused with GYMNET_ERR_INVALID_ARG. */
     /* dense per-step recording (the members of gymnet_rollout_buffers); any pointer NULL = not recorded */
     void    *d_rec_obs;          /* [steps][obs_dim][num_envs] observation AFTER step t; float32 — float64 for a GYMNET_FLAG_F64 handle */
     float   *d_rec_reward;       /* [steps][num_envs] */
