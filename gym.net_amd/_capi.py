@@ -28,7 +28,7 @@ ERR_UNSUPPORTED = -8
 ERR_RCCL = -9
 
 ENV_CARTPOLE, ENV_PENDULUM, ENV_MOUNTAINCAR, ENV_ACROBOT = 0, 1, 2, 3
-ENV_IDS = {"CartPole-v1": 0, "Pendulum-v1": 1, "MountainCar-v0": 2, "Acrobot-v1": 3}
+ENV_IDS = {"CartPole-v1": 0, "Pendulum-v1": 1, "MountainCar-v0": 2, "Acrobot-v1": 3, "MountainCarContinuous-v0": 4}
 
 FLAG_AUTORESET = 0x01
 FLAG_VALIDATE_ACTIONS = 0x02

@@ -2,7 +2,7 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared csrc/*.hip -ldl -o lib/libgymnet_amd.so
 (done as one `hipcc -c` per .hip file in parallel plus one link: same flags, same result.  Every env's step / rollout / reset
-kernels are a translation unit of their own — csrc/env_*.hip instantiating csrc/step_kernels.hpp — so the eight files compile
+kernels are a translation unit of their own — csrc/env_*.hip instantiating csrc/step_kernels.hpp — so the files compile
 side by side: ~15 s wall on 8 cores instead of ~40 s for the former single kernels.hip)
 
 -ffp-contract=off is part of the numerical contract (see csrc/envs.hpp): every float32 operation
@@ -15,7 +15,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libgymnet_amd.so")
-SOURCES = ["env_cartpole.hip", "env_cartpole64.hip", "env_acrobot.hip", "env_pendulum.hip", "env_mountaincar.hip", "kernels.hip", "capi.hip",
+SOURCES = ["env_cartpole.hip", "env_cartpole64.hip", "env_acrobot.hip", "env_pendulum.hip", "env_mountaincar.hip",
+           "env_mountaincar_continuous.hip", "kernels.hip", "capi.hip",
            "group.hip", "render.hip"]
 DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "cartpole64.hpp", "philox.hpp", "handle.hpp",
                   os.path.join("..", "..", "include", "gymnet_amd.h")]

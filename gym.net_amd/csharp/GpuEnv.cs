@@ -155,4 +155,11 @@ namespace Gym.Envs.Amd {
         public GpuAcrobotEnv(int device = 0, ulong seed = 0, int maxEpisodeSteps = 0, bool validateActions = false, bool resident = false)
             : base(GymnetEnvId.Acrobot, device, seed, maxEpisodeSteps, validateActions, false, resident) { }
     }
+
+    /// MountainCarContinuous-v0 (upstream gym; absent from the reference): Box(-1, 1, (1,)) force, so no validateActions (like
+    /// GpuPendulumEnv).  Upstream registers a 999-step time limit: pass maxEpisodeSteps = 999 for it.
+    public sealed class GpuMountainCarContinuousEnv : GpuEnv {
+        public GpuMountainCarContinuousEnv(int device = 0, ulong seed = 0, int maxEpisodeSteps = 0, bool resident = false)
+            : base(GymnetEnvId.MountainCarContinuous, device, seed, maxEpisodeSteps, false, false, resident) { }
+    }
 }

@@ -13,7 +13,7 @@ namespace Gym.Envs.Amd {
         AlreadyStepping = -6, NotStepping = -7, Unsupported = -8, Rccl = -9
     }
 
-    public enum GymnetEnvId { CartPole = 0, Pendulum = 1, MountainCar = 2, Acrobot = 3 }
+    public enum GymnetEnvId { CartPole = 0, Pendulum = 1, MountainCar = 2, Acrobot = 3, MountainCarContinuous = 4 }
 
     public enum GymnetGatherMode { None = 0, Direct = 1, Rccl = 2 }
 

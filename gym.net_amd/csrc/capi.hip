@@ -27,7 +27,7 @@ namespace gymnet {
 
 // Observation bounds: CartPoleEnv.cs:46-48 (high = [x_thr*2, float.MaxValue, theta_thr*2, float.MaxValue]).
 // Algorithmic bytes per env-step: SURVEY.md §8(a)/(d).
-const EnvDesc kEnvs[4] = {
+const EnvDesc kEnvs[kNumEnvs] = {
     {"CartPole-v1", 4, 4, true, false, true, 2, 0.f, 0.f,
      {-4.8000002f, -FMAX, -0.41887903f, -FMAX}, {4.8000002f, FMAX, 0.41887903f, FMAX}, 0.f, 1.f, 41, 41, {-1, -1, -1, -1}},
     {"Pendulum-v1", 2, 3, false, true, false, 0, -2.f, 2.f,
@@ -36,6 +36,10 @@ const EnvDesc kEnvs[4] = {
      {-1.2f, -0.07f}, {0.6f, 0.07f}, -1.f, -1.f, 25, 25, {-1, -1, -1, -1}},
     {"Acrobot-v1", 4, 6, false, false, false, 3, 0.f, 0.f,
      {-1.f, -1.f, -1.f, -1.f, -4.f * PI_F, -9.f * PI_F}, {1.f, 1.f, 1.f, 1.f, 4.f * PI_F, 9.f * PI_F}, -1.f, 0.f, 65, 57, {-1, -1, 4, 5}},
+    // reward (done ? 100 : 0) - 0.1 a^2 of the RAW action: unbounded below.  25 B per env-step like MountainCar: 8 state read, 4 action
+    // read, 8 state written, 4 reward, 1 done
+    {"MountainCarContinuous-v0", 2, 2, true, true, false, 0, -1.f, 1.f,
+     {-1.2f, -0.07f}, {0.6f, 0.07f}, -INFINITY, 100.f, 25, 25, {-1, -1, -1, -1}},
 };
 
 void set_last_error(const char *msg) { g_last_error = msg ? msg : ""; }
@@ -186,7 +190,7 @@ int apply_policy(gymnet_vecenv *h, const gymnet_launch_policy &p, bool strict) {
         else ST_TRY(bad("sequential_lanes", p.sequential_lanes));
     }
     if (p.reset_form != -1) {
-        const bool has_form1 = h->desc->alias;       // the wave-compacted reset hands back the state only (CartPole, MountainCar)
+        const bool has_form1 = h->desc->alias;       // the wave-compacted reset hands back the state only (CartPole, MountainCar[Continuous])
         if (p.reset_form == 0 || (p.reset_form == 1 && (has_form1 || !strict))) c.reset_form = p.reset_form; else ST_TRY(bad("reset_form", p.reset_form));
     }
     if (p.lds_pipe != -1) {
@@ -293,6 +297,9 @@ void default_policy(gymnet_vecenv *h) {
     //   MountainCar  3 * 2^19 4.31 / 5.10   2^21 3.83 / 4.48   2^22 4.14 / 4.33   2^23 3.92 / 4.10   2^24 3.85 / 3.87
     //   Pendulum     3 * 2^19 5.93 / 5.42 and 2^21 6.05 / 5.30 (loses: two of its four written rows are never read back),
     //                2^22 5.51 / 6.27   2^23 5.68 / 5.68 — hence its later start
+    // MountainCarContinuous moves MountainCar's 25 B per env-step and takes MountainCar's rule throughout.  Measured beside it in one run
+    // (profiles/mountaincar_continuous.txt, us per step, MountainCar / MountainCarContinuous): 2^19 lanes 4.51 / 4.50, 5 * 2^18 5.84 / 5.93,
+    // 2^20 4.79 / 4.67, 2^22 18.16 / 18.09 — the same kernels of both envs land within 2 % of each other at every size.
     else if (h->n >= (cfg->env_id == GYMNET_ENV_PENDULUM ? (int64_t)3 << 20 : (int64_t)5 << 18) && step_bytes <= ((size_t)300 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 0; }
     else if (step_bytes <= ((size_t)48 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 15; }
     else if (step_bytes <= ((size_t)768 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 12; }
@@ -714,7 +721,7 @@ int gymnet_device_count(int *count) {
 int gymnet_env_describe(int env_id, gymnet_env_info *out) {
     return guarded([&]() -> int {
     if (!out) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "out is null");
-    if (env_id < 0 || env_id > 3) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", env_id);
+    if (env_id < 0 || env_id >= kNumEnvs) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", env_id);
     const EnvDesc &d = kEnvs[env_id];
     std::memset(out, 0, sizeof *out);
     out->struct_size = sizeof *out;
@@ -759,7 +766,7 @@ int gymnet_vecenv_create(const gymnet_config *cfg, gymnet_vecenv **out) {
     if (!cfg) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "cfg is null");
     if (cfg->struct_size != sizeof(gymnet_config))
         return fail(nullptr, GYMNET_ERR_INVALID_ARG, "cfg.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(gymnet_config));
-    if (cfg->env_id < 0 || cfg->env_id > 3) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
+    if (cfg->env_id < 0 || cfg->env_id >= kNumEnvs) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
     if (cfg->num_envs <= 0 || cfg->num_envs > (int64_t)1 << 31)
         return fail(nullptr, GYMNET_ERR_INVALID_ARG, "num_envs %lld out of range [1, 2^31]", (long long)cfg->num_envs);
     if (cfg->lane_offset < 0) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "lane_offset < 0");

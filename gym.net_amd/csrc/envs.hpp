@@ -6,7 +6,7 @@
 //
 // CartPole follows src/Gym.Environments/Envs/Classic/CartPoleEnv.cs (paths relative to the Gym.NET
 // tree): constants :24-36 (the C# `const float` bit patterns), Step :137-186, Reset :63-67.
-// Pendulum / MountainCar / Acrobot do not exist in the reference (README.md:69-76, unchecked roadmap
+// Pendulum / MountainCar / MountainCarContinuous / Acrobot do not exist in the reference (README.md:69-76, unchecked roadmap
 // items); they follow the upstream openai/gym classic_control algorithms.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -363,6 +363,55 @@ struct MountainCar {
         s[0] = -0.6f + 0.2f * u01_24(r.w[0]);
         s[1] = 0.0f;
     }
+
+    __device__ __forceinline__ static void observe(const float (&s)[S], float (&o)[O]) { o[0] = s[0]; o[1] = s[1]; }
+    // observation of a state reset() has just drawn (bounded by construction: an env may use cheaper trigonometry here)
+    __device__ __forceinline__ static void observe_fresh(const float (&s)[S], float (&o)[O]) { observe(s, o); }
+    __device__ __forceinline__ static void step_observe(float (&s)[S], Action a, float &reward, bool &done, float (&o)[O]) {
+        step(s, a, reward, done);
+        observe(s, o);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// MountainCarContinuous-v0  (upstream gym continuous_mountain_car.py; absent from the reference)
+// The first env with a Box action AND termination; its reward depends on the action.  State = observation = [position, velocity],
+// Box(-1, 1, (1,)) force.  Same reset draw as MountainCar (same Philox word, same conversion): p ~ U(-0.6, -0.4), v = 0.
+// ---------------------------------------------------------------------------------------------
+struct MountainCarContinuous {
+    static constexpr int S = 2;              // position, velocity
+    static constexpr int O = 2;
+    static constexpr bool OBS_ALIASES_STATE = true;
+    static constexpr bool HAS_SBD = false;   // stepping after done is allowed (upstream has no steps_beyond_done)
+    static constexpr bool BOX_ACTION = true;
+    static constexpr bool PACKED2 = false;
+    static constexpr bool PIPE_LANES = false, PIPE_PAIRS = false;
+    static constexpr bool HAS_SMALL_ANGLE_PATH = false;
+    using Action = float;                    // Box(-1, 1, (1,))
+    using Real = float;
+    static constexpr bool RESET_TAKES_KEY = false;
+    static constexpr const char *NAME = "MountainCarContinuous";
+    static constexpr float ACTION_LOW = -1.0f, ACTION_HIGH = 1.0f;  // Box(-1, 1, (1,)).Sample(): the bounded regime, uniform(low, high)  (Box.cs:85)
+    // Upstream compares the float64 position against 0.45.  0.45f = 0x3EE66666 = 0.44999998807... lies BELOW 0.45, so `p >= 0.45f`
+    // would end episodes upstream keeps running.  0x1.cccccep-2f = 0x3EE66667 is the smallest float32 >= 0.45: for every float32
+    // position p, p >= GOAL exactly when (double)p >= 0.45.
+    static constexpr float GOAL = 0x1.cccccep-2f;
+
+    __device__ __forceinline__ static void step(float (&s)[S], Action a, float &reward, bool &done) {
+        float p = s[0], v = s[1];
+        // min(max(a, -1), 1): Pendulum's clamp form, NaN passes through as in upstream's min(max(...)); the clamp feeds the force only
+        const float force = a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
+        v += force * 0.0015f - 0.0025f * cos_f32(3.0f * p);
+        v = v < -0.07f ? -0.07f : (v > 0.07f ? 0.07f : v);
+        p += v;
+        p = p < -1.2f ? -1.2f : (p > 0.6f ? 0.6f : p);
+        if (p == -1.2f && v < 0.0f) v = 0.0f;
+        s[0] = p; s[1] = v;
+        done = p >= GOAL && v >= 0.0f;
+        reward = (done ? 100.0f : 0.0f) - (a * a) * 0.1f;     // reward -= math.pow(action[0], 2) * 0.1: the RAW action
+    }
+
+    __device__ __forceinline__ static void reset(float (&s)[S], const PhiloxWords &r) { MountainCar::reset(s, r); }
 
     __device__ __forceinline__ static void observe(const float (&s)[S], float (&o)[O]) { o[0] = s[0]; o[1] = s[1]; }
     // observation of a state reset() has just drawn (bounded by construction: an env may use cheaper trigonometry here)

@@ -336,7 +336,7 @@ int gymnet_group_create(const gymnet_group_config *cfg, gymnet_group **out) {
     if (!cfg) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "cfg is null");
     if (cfg->struct_size != sizeof(gymnet_group_config))
         return fail(nullptr, GYMNET_ERR_INVALID_ARG, "cfg.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(gymnet_group_config));
-    if (cfg->env_id < 0 || cfg->env_id > 3) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
+    if (cfg->env_id < 0 || cfg->env_id >= kNumEnvs) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
     const int G = cfg->num_members;
     if (G < 1 || G > kMaxPeers + 1) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "num_members %d not in [1, %d]", G, kMaxPeers + 1);
     if (cfg->global_num_envs < G || cfg->global_num_envs % G != 0)   // equal blocks: the replica is [G][D][N/G]

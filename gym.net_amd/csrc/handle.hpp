@@ -26,7 +26,7 @@ struct EnvDesc {
     int traffic_bytes;          // bytes one env-step really moves (< algorithmic where a state row is stored once, in the observation)
     int state_row_in_obs[4];    // state row k lives in observation row state_row_in_obs[k] (-1: its own row of the state array)
 };
-extern const EnvDesc kEnvs[4];
+extern const EnvDesc kEnvs[kNumEnvs];
 
 struct GraphEntry {
     const void *actions;

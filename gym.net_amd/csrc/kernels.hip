@@ -390,8 +390,9 @@ const EnvLaunchers<R> *env_launchers(int env_id) {
     if constexpr (sizeof(R) == 8) {
         return env_id == 0 ? &cartpole64_launchers() : nullptr;     // the reference defines float64 arithmetic for CartPole only
     } else {
-        static const EnvLaunchers<float> &(*const tables[])() = {cartpole_launchers, pendulum_launchers, mountaincar_launchers, acrobot_launchers};
-        return env_id >= 0 && env_id < 4 ? &tables[env_id]() : nullptr;       // by gymnet_env_id
+        static const EnvLaunchers<float> &(*const tables[kNumEnvs])() = {cartpole_launchers, pendulum_launchers, mountaincar_launchers,
+                                                                         acrobot_launchers, mountaincar_continuous_launchers};
+        return env_id >= 0 && env_id < kNumEnvs ? &tables[env_id]() : nullptr;       // by gymnet_env_id
     }
 }
 template const EnvLaunchers<float> *env_launchers<float>(int);

@@ -181,7 +181,11 @@ const EnvLaunchers<float> &cartpole_launchers();
 const EnvLaunchers<float> &pendulum_launchers();
 const EnvLaunchers<float> &mountaincar_launchers();
 const EnvLaunchers<float> &acrobot_launchers();
+const EnvLaunchers<float> &mountaincar_continuous_launchers();
 const EnvLaunchers<double> &cartpole64_launchers();   // GYMNET_FLAG_F64: CartPole in the reference's own binary64 arithmetic
+
+// Number of gymnet_env_id values: every env id range check and the per-env tables (capi.hip kEnvs, env_launchers) use it.
+constexpr int kNumEnvs = 5;
 
 // The launchers of env `env_id` (gymnet_env_id) in state scalar R (float, or double for the float64 engine); NULL: no such env, or no
 // float64 form of it (the reference defines float64 arithmetic for CartPole only).  kernels.hip.

@@ -113,7 +113,7 @@ class ShardedVectorEnv:
             device = self.tensor_device.index if self.tensor_device.type == "cuda" else 0
         from . import _capi
         env_id = _capi.ENV_IDS[env] if isinstance(env, str) else int(env)
-        self.obs_dim = {0: 4, 1: 3, 2: 2, 3: 6}[env_id]
+        self.obs_dim = int(_capi.env_describe(env_id).obs_dim)
         n_local = self.local_num_envs
         # rank-major gather buffers [B][G][D][N/G] (B = 2 when overlapping); this rank's observation arrays ARE slice
         # [b][rank] of whichever buffer b the last step wrote

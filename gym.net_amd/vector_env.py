@@ -831,5 +831,11 @@ class AcrobotEnv(GpuEnv):
     ENV = "Acrobot-v1"
 
 
+class MountainCarContinuousEnv(GpuEnv):
+    """MountainCarContinuous-v0 (upstream gym; absent from the reference): Box(-1, 1, (1,)) force, reward 100 at the goal minus
+    0.1 * action^2 of the raw action.  Upstream registers a 999-step time limit: pass max_episode_steps=999 for it (default: none)."""
+    ENV = "MountainCarContinuous-v0"
+
+
 __all__ = ["VectorEnv", "GroupVectorEnv", "DummyVecEnv", "BatchStep", "PendingStep", "GpuEnv", "CartPoleEnv", "PendulumEnv", "MountainCarEnv",
-           "AcrobotEnv", "AlreadySteppingError", "NotSteppingError"]
+           "AcrobotEnv", "MountainCarContinuousEnv", "AlreadySteppingError", "NotSteppingError"]

@@ -82,7 +82,9 @@ typedef enum gymnet_env_id {
     GYMNET_ENV_CARTPOLE = 0,     /* CartPoleEnv.cs (the only classic env present in the reference) */
     GYMNET_ENV_PENDULUM = 1,     /* absent from the reference (README.md:69-76); upstream gym Pendulum-v1 */
     GYMNET_ENV_MOUNTAINCAR = 2,  /* absent from the reference; upstream gym MountainCar-v0 */
-    GYMNET_ENV_ACROBOT = 3       /* absent from the reference; upstream gym Acrobot-v1 */
+    GYMNET_ENV_ACROBOT = 3,      /* absent from the reference; upstream gym Acrobot-v1 */
+    GYMNET_ENV_MOUNTAINCAR_CONTINUOUS = 4  /* absent from the reference; upstream gym MountainCarContinuous-v0 (ABI 6: an added value,
+                                              compatible) */
 } gymnet_env_id;
 
 /* gymnet_config.flags */
@@ -114,7 +116,7 @@ typedef enum gymnet_env_id {
 #define GYMNET_FLAG_DOUBLE_BUFFER    0x20u /* two observation buffers, written alternately: the step launched after buffer A was
                                               written reads A and writes B, so a consumer (an all-gather of A over xGMI, a policy
                                               reading A) may still be using A while the next step runs.  For envs whose observation
-                                              IS the state (CartPole, MountainCar) the state ping-pongs with it.  Which buffer holds
+                                              IS the state (CartPole, MountainCar, MountainCarContinuous) the state ping-pongs with it.  Which buffer holds
                                               the latest observation: gymnet_device_view.obs_buffer / d_obs */
 
 typedef struct gymnet_vecenv gymnet_vecenv;   /* opaque handle: one batch ("VectorEnv") on one GPU */
@@ -132,7 +134,7 @@ typedef struct gymnet_config {
     void    *d_ext_obs;         /* optional device buffer [obs_dim][ext_obs_stride] (float32; float64 with GYMNET_FLAG_F64) to keep
                                    observations in (e.g. this
                                    rank's slice of an all-gather buffer).  It is LIVE STATE STORAGE, not an output copy: for
-                                   envs whose observation IS the state (CartPole, MountainCar) every row, and for the others
+                                   envs whose observation IS the state (CartPole, MountainCar, MountainCarContinuous) every row, and for the others
                                    the rows listed in gymnet_env_info.state_row_in_obs (Pendulum obs[2]; Acrobot obs[4], obs[5]),
                                    are read back by the next step.  A consumer must not modify them in place (normalise /
                                    clip into its own buffer).  The same holds for d_ext_obs_alt.  NULL = library allocates */

@@ -13,11 +13,11 @@ dev = torch.device("cuda", 0)
 st = torch.cuda.Stream(dev)
 torch.cuda.set_stream(st)
 out = {}
-ENVS = sys.argv[1:] or ["CartPole-v1", "Pendulum-v1", "MountainCar-v0", "Acrobot-v1"]
+ENVS = sys.argv[1:] or ["CartPole-v1", "Pendulum-v1", "MountainCar-v0", "Acrobot-v1", "MountainCarContinuous-v0"]
 for name in ENVS:
     n, ring, T = 1 << 20, 64, 1024
     env = pkg.VectorEnv(name, n, seed=1, auto_reset=True, stream=st.cuda_stream)
-    adt = torch.float32 if name == "Pendulum-v1" else torch.int32
+    adt = torch.float32 if isinstance(env.ActionSpace, pkg.Box) else torch.int32
     acts = torch.empty((ring, n), dtype=adt, device=dev)
     for t in range(ring):
         env.SampleActionsDevice(acts[t], seed=2, tick=t)

@@ -3,7 +3,8 @@
 VGPRs -> waves per SIMD (512 / VGPRs, at most 8), scratch bytes (spills), static LDS bytes.  Round 5 found two slowdowns that only this view
 explains — a float32 bookkeeping rollout that allocated 131-152 VGPRs (three waves per SIMD where 2^20 lanes need four) and a float64
 four-pair kernel that must stay at two waves per SIMD because it spills when capped for three (profiles/occupancy_hints_r05.txt).
-    python tools/kernel_resources.py [env ...]        env: cartpole cartpole64 pendulum mountaincar acrobot (default: all)
+    python tools/kernel_resources.py [env ...]        env: cartpole cartpole64 pendulum mountaincar acrobot mountaincar_continuous
+                                                      (default: all)
 Prints one line per kernel; tests/test_kernel_resources.py asserts the invariants the launch policy relies on."""
 import os
 import re
@@ -17,6 +18,9 @@ CSRC = os.path.join(ROOT, "gym.net_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--cuda-device-only", "-S"]
 ENVS = ("cartpole", "cartpole64", "pendulum", "mountaincar", "acrobot")
+# collect()'s default stays the five units tests/_instantiation_matrix.py covers; the newer units have their own recipe tables
+# (tests/_mountaincar_continuous_matrix.py) and are listed only in the command line's default
+CLI_ENVS = ENVS + ("mountaincar_continuous",)
 
 
 def assembly(env, outdir):
@@ -59,7 +63,7 @@ def collect(envs=ENVS):
 
 
 if __name__ == "__main__":
-    envs = tuple(sys.argv[1:]) or ENVS
+    envs = tuple(sys.argv[1:]) or CLI_ENVS
     res = collect(envs)
     print(f"# hipcc {' '.join(FLAGS)}  (gym.net_amd/csrc/env_*.hip)   waves per SIMD = min(8, 512 // VGPRs)")
     print(f"{'kernel':72s} {'VGPRs':>6s} {'waves/SIMD':>10s} {'scratch B':>10s} {'LDS B':>7s}")
