@@ -49,6 +49,7 @@ ABI_VERSION = 6
 RECORDS_NO_OVERFLOW = 1      # gymnet_rollout_spec.record_flags
 PIXELS_RGB8, PIXELS_GRAY8 = 1, 2     # gymnet_vecenv_render(_device) formats
 RENDER_WIDTH, RENDER_HEIGHT = 600, 400
+STACK_GRAY8, STACK_BINARY8, STACK_BINARY_F32 = 2, 3, 4     # gymnet_vecenv_pixel_stack_config formats
 
 
 class Config(C.Structure):
@@ -167,6 +168,12 @@ PROTOTYPES = {
                                              C.c_int32, C.c_int32, C.c_int64]),
     "gymnet_vecenv_render": (C.c_int, [_H, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int64]),
+    "gymnet_vecenv_pixel_stack_config": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, _P, C.c_int64]),
+    "gymnet_vecenv_pixel_stack_reset_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_pixel_stack_push_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_pixel_stack_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gymnet_vecenv_pixel_stack_read": (C.c_int, [_H, _P, C.c_int64, C.c_int64]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

@@ -28,6 +28,9 @@ namespace Gym.Envs.Amd {
 
     public enum GymnetPixelFormat { Rgb8 = 1, Gray8 = 2 }     // gymnet_vecenv_render(_device): 3 bytes per pixel / 1 byte (BT.709 luma)
 
+    // gymnet_vecenv_pixel_stack_config: GRAY8 frames; 1 where the GRAY8 pixel is below 255 (not all background), else 0, as bytes or floats
+    public enum GymnetStackFormat { Gray8 = 2, Binary8 = 3, BinaryF32 = 4 }
+
     public enum GymnetArrayId {
         Reward = 0, Done = 1, StepsBeyondDone = 2, EpisodeReturn = 3, EpisodeLength = 4, FinishedReturn = 5, FinishedLength = 6,
         FinalObs = 7, LaneSeeds = 8
@@ -153,6 +156,13 @@ namespace Gym.Envs.Amd {
                                                                              int crop_w, int crop_h, int out_w, int out_h, long lane_stride);
         [DllImport(Lib)] public static extern int gymnet_vecenv_render(IntPtr h, void* out_frames, int format, long first_lane, long count, int crop_x, int crop_y,
                                                                       int crop_w, int crop_h, int out_w, int out_h, long lane_stride);
+        // CartPole pixel frame stacks: lane k's stack at base + k * lane_stride, slot s (0 = oldest) at + s * frame_bytes
+        [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_config(IntPtr h, int format, int depth, int crop_x, int crop_y, int crop_w, int crop_h,
+                                                                                  int out_w, int out_h, IntPtr d_ext, long lane_stride);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_reset_device(IntPtr h, IntPtr d_mask);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_push_device(IntPtr h, IntPtr d_done);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_view(IntPtr h, out IntPtr d_stack, out long lane_stride, out long frame_bytes);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_read(IntPtr h, void* out_stacks, long first_lane, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

@@ -25,6 +25,8 @@ using SixLabors.ImageSharp.PixelFormats;
 namespace Gym.Envs.Amd {
     public sealed unsafe class VectorEnv : VecEnv, IVecEnv, IDisposable {
         private IntPtr _h;
+        private GymnetStackFormat _stackFormat;     // of the pixel stack ConfigurePixelStack set up (depth 0: none)
+        private int _stackDepth;
         private readonly int _obsDim;
         private readonly bool _boxAction;
         private readonly bool _f64;                 // GymnetFlags.F64 (CartPole): every observation buffer holds doubles — the reference's
@@ -185,6 +187,45 @@ namespace Gym.Envs.Amd {
             var rgb = new byte[600 * 400 * 3];
             RenderFrames(rgb, 600, 400, firstLane: lane, count: 1, format: GymnetPixelFormat.Rgb8);
             return Image.LoadPixelData<Rgb24>(rgb, 600, 400);
+        }
+
+        /// An episode-aware stack of processed frames per lane on the device (the Images runner's frame queue, ReplayMemory.cs:38-54, and its
+        /// input, ImageDataBuilder.cs:10-18): the defaults are two 40 x 20 frames of the crop (200, 150, 200, 150), oldest first, 1.0f where
+        /// a pixel is not background.  dExt: a device buffer to adopt (IntPtr.Zero: the handle allocates); laneStride 0: packed
+        /// [N][depth][outH][outW].  Replaces any stack the handle had; depth 0 releases it.  CartPole only.
+        public void ConfigurePixelStack(GymnetStackFormat format = GymnetStackFormat.BinaryF32, int depth = 2, int outW = 40, int outH = 20,
+                                        int cropX = 200, int cropY = 150, int cropW = 200, int cropH = 150, IntPtr dExt = default, long laneStride = 0) {
+            Native.Check(Native.gymnet_vecenv_pixel_stack_config(_h, (int) format, depth, cropX, cropY, cropW, cropH, outW, outH, dExt, laneStride));
+            _stackFormat = format;
+            _stackDepth = depth;
+        }
+
+        /// After ResetDevice / a masked reset: the lanes whose device mask byte is set (IntPtr.Zero: every lane) get their current frame in
+        /// every slot.
+        public void ResetPixelStack(IntPtr dMask = default) => Native.Check(Native.gymnet_vecenv_pixel_stack_reset_device(_h, dMask));
+
+        /// Once per step: lanes whose device done byte is set (IntPtr.Zero: the handle's own done bytes with AutoReset, none without) fill
+        /// every slot with the current frame, the others shift by one slot and take it as the newest.
+        public void PushPixelStack(IntPtr dDone = default) => Native.Check(Native.gymnet_vecenv_pixel_stack_push_device(_h, dDone));
+
+        /// The stacks of lanes [firstLane, firstLane + count) (count < 0: to the last lane) copied into host memory, packed
+        /// [count][depth][outH][outW]: bytes for Gray8 / Binary8 stacks, floats for BinaryF32.  Blocks.
+        public void ReadPixelStack(Span<byte> destination, long firstLane = 0, long count = -1) {
+            if (_stackFormat == GymnetStackFormat.BinaryF32) throw new ArgumentException("a BinaryF32 stack reads into Span<float>", nameof(destination));
+            fixed (byte* p = destination) ReadPixelStack(p, destination.Length, firstLane, count);
+        }
+
+        public void ReadPixelStack(Span<float> destination, long firstLane = 0, long count = -1) {
+            if (_stackFormat != GymnetStackFormat.BinaryF32) throw new ArgumentException("a byte stack reads into Span<byte>", nameof(destination));
+            fixed (float* p = destination) ReadPixelStack(p, (long) destination.Length * 4, firstLane, count);
+        }
+
+        private void ReadPixelStack(void* p, long capacityBytes, long firstLane, long count) {
+            if (count < 0) count = NumberOfEnvironments - firstLane;
+            Native.Check(Native.gymnet_vecenv_pixel_stack_view(_h, out IntPtr dStack, out long laneStride, out long frameBytes));
+            if (count > 0 && count * _stackDepth * frameBytes > capacityBytes)
+                throw new ArgumentException("destination is smaller than the stacks it must hold", "destination");
+            Native.Check(Native.gymnet_vecenv_pixel_stack_read(_h, p, firstLane, count));
         }
 
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe

@@ -751,6 +751,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     for (void *p : h->owned) (void)hipFree(p);
     if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
     if (h->d_render) (void)hipFree(h->d_render);
+    if (h->stack_alloc) (void)hipFree(h->stack_alloc);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1338,6 +1339,15 @@ int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity) {
 // ---- CartPole frames (render.hip) ------------------------------------------------------------------------------------------
 namespace {
 
+// the crop / output-size rules every frame request shares (gymnet_vecenv_render_device)
+int check_crop_and_size(gymnet_vecenv *h, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h) {
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > kRenderWidth - crop_w || crop_y > kRenderHeight - crop_h)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "crop (%d, %d, %d, %d) not inside the %dx%d canvas", crop_x, crop_y, crop_w, crop_h, kRenderWidth, kRenderHeight);
+    if (out_w < 1 || out_h < 1 || out_w > kRenderMaxSide || out_h > kRenderMaxSide)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "output size %dx%d not in [1, %d]", out_w, out_h, kRenderMaxSide);
+    return GYMNET_OK;
+}
+
 // Checks a render request (nothing is written on failure) and fills the kernel arguments; *bytes = the span the frames cover.
 int render_args(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
                 int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride, RenderArgs *a, int64_t *bytes) {
@@ -1347,10 +1357,7 @@ int render_args(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane,
     if (first_lane < 0 || count < 1 || first_lane > h->n - count)
         return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
                     (long long)count, (long long)h->n);
-    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > kRenderWidth - crop_w || crop_y > kRenderHeight - crop_h)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "crop (%d, %d, %d, %d) not inside the %dx%d canvas", crop_x, crop_y, crop_w, crop_h, kRenderWidth, kRenderHeight);
-    if (out_w < 1 || out_h < 1 || out_w > kRenderMaxSide || out_h > kRenderMaxSide)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "output size %dx%d not in [1, %d]", out_w, out_h, kRenderMaxSide);
+    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
     const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
     if (lane_stride < frame) return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one frame", (long long)lane_stride, (long long)frame);
     if (lane_stride > (INT64_MAX - frame) / count) return fail(h, GYMNET_ERR_INVALID_ARG, "count x lane_stride overflows");
@@ -1409,6 +1416,132 @@ int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t fi
     HIP_TRY(h, hipMemcpyAsync(span.data(), h->d_render, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (int64_t k = 0; k < count; ++k) std::memcpy(static_cast<uint8_t *>(out) + k * lane_stride, span.data() + k * lane_stride, (size_t)frame);
+    return GYMNET_OK;
+    });
+}
+
+// ---- CartPole pixel frame stacks (pixel_stack.hip) ------------------------------------------------------------------------
+namespace {
+
+constexpr int32_t kStackMaxDepth = 64;
+
+int need_stack(gymnet_vecenv *h) {
+    return h->stack.depth > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no pixel stack configured (gymnet_vecenv_pixel_stack_config)");
+}
+
+// one launch over every lane of the configured stack, from the CURRENT observation buffer: shift = 1 push, 0 reset (StackArgs)
+int launch_stack(gymnet_vecenv *h, const uint8_t *restart, int32_t shift) {
+    StackArgs a = h->stack;
+    a.obs = h->d_obs; a.obs_stride = h->ostride;
+    a.restart = restart; a.shift = shift;
+    HIP_TRY(h, launch_pixel_stack(h->f64, h->stack_format, a, h->stream));
+    return GYMNET_OK;
+}
+
+// drops the configured stack (frees it when the handle allocated it: after the stream has drained, a launch may still use it)
+int release_stack(gymnet_vecenv *h) {
+    if (h->stack_alloc) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipFree(h->stack_alloc));
+    }
+    h->stack_alloc = nullptr;
+    h->stack = StackArgs{};
+    h->stack_format = 0;
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int gymnet_vecenv_pixel_stack_config(gymnet_vecenv *h, int32_t format, int32_t depth, int32_t crop_x, int32_t crop_y, int32_t crop_w,
+                                     int32_t crop_h, int32_t out_w, int32_t out_h, void *d_ext, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel stacks exist for CartPole only (CartPoleEnv.cs:69-135)");
+    if (depth == 0) return release_stack(h);
+    if (format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel stack format %d", format);
+    if (depth < 0 || depth > kStackMaxDepth) return fail(h, GYMNET_ERR_INVALID_ARG, "depth %d not in [0, %d]", depth, kStackMaxDepth);
+    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
+    const int64_t elem = format == GYMNET_STACK_BINARY_F32 ? 4 : 1;
+    const int64_t frame = (int64_t)out_w * out_h * elem, span = (int64_t)depth * frame;
+    if (lane_stride == 0) lane_stride = span;
+    if (lane_stride < span)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one stack", (long long)lane_stride, (long long)span);
+    if (h->n > 1 && lane_stride > (INT64_MAX - span) / (h->n - 1)) return fail(h, GYMNET_ERR_INVALID_ARG, "num_envs x lane_stride overflows");
+    if (elem == 4 && ((reinterpret_cast<uintptr_t>(d_ext) & 3u) != 0 || lane_stride % 4 != 0))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 stacks need a 4-byte aligned d_ext and lane_stride");
+    const int64_t bytes = (h->n - 1) * lane_stride + span;
+    void *alloc = nullptr;
+    if (!d_ext) {
+        if (h->stack_alloc) HIP_TRY(h, hipStreamSynchronize(h->stream));      // the old stack is still there if this allocation fails
+        hipError_t e = hipMalloc(&alloc, (size_t)bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the pixel stack failed: %s", (long long)bytes, hipGetErrorString(e));
+        }
+    }
+    if (int st = release_stack(h); st != GYMNET_OK) {
+        if (alloc) (void)hipFree(alloc);
+        return st;
+    }
+    StackArgs &a = h->stack;
+    a.base = static_cast<uint8_t *>(d_ext ? d_ext : alloc);
+    a.lane_stride = lane_stride; a.frame_bytes = frame;
+    a.depth = depth;
+    a.waves_per_frame = render_waves_per_frame(out_w, out_h);
+    a.total_waves = h->n * a.waves_per_frame;
+    a.out_w = out_w; a.out_h = out_h;
+    a.x0 = (float)crop_x; a.y0 = (float)crop_y;                        // the sample positions of render_args
+    a.sxq = (float)((double)crop_w / (4.0 * out_w));
+    a.syq = (float)((double)crop_h / (4.0 * out_h));
+    h->stack_format = format;
+    h->stack_alloc = alloc;
+    return launch_stack(h, nullptr, 0);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    return launch_stack(h, d_mask, 0);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    // without a done array an auto-reset handle restarts the lanes its most recent step finished (and already re-drew)
+    return launch_stack(h, d_done ? d_done : (h->autoreset ? h->d_done : nullptr), 1);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_view(gymnet_vecenv *h, void **d_stack, int64_t *lane_stride, int64_t *frame_bytes) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    if (d_stack) *d_stack = h->stack.base;
+    if (lane_stride) *lane_stride = h->stack.lane_stride;
+    if (frame_bytes) *frame_bytes = h->stack.frame_bytes;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_lane, int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
+    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
+                    (long long)count, (long long)h->n);
+    const StackArgs &a = h->stack;
+    const int64_t span = (int64_t)a.depth * a.frame_bytes;
+    const uint8_t *src = a.base + first_lane * a.lane_stride;
+    if (a.lane_stride == span) HIP_TRY(h, hipMemcpyAsync(out, src, (size_t)(count * span), hipMemcpyDeviceToHost, h->stream));
+    else HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)span, src, (size_t)a.lane_stride, (size_t)span, (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GYMNET_OK;
     });
 }

@@ -106,6 +106,11 @@ struct gymnet_vecenv {
     int64_t ep_ov_cap = 0;         // records of the shared overflow segment (= the largest ep_capacity asked for so far)
     void *d_render = nullptr;      // gymnet_vecenv_render's device staging (allocated on first use, grown on demand)
     size_t render_cap = 0;
+    // gymnet_vecenv_pixel_stack_*: the per-lane stacks of processed frames (stack.depth == 0: none configured).  stack.obs / restart /
+    // shift are filled in per launch; stack_alloc is the stack's allocation when the handle made it (NULL: adopted or none)
+    gymnet::StackArgs stack{};
+    int32_t stack_format = 0;
+    void *stack_alloc = nullptr;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;

@@ -232,6 +232,21 @@ constexpr int32_t kRenderWidth = 600, kRenderHeight = 400;   // the reference's 
 constexpr int32_t kRenderMaxSide = 16384;                    // output width / height limit (sample positions stay exact in float)
 int64_t render_waves_per_frame(int32_t out_w, int32_t out_h);
 hipError_t launch_render(bool f64, int channels, const RenderArgs &a, hipStream_t st);
+// Episode-aware frame stacks (pixel_stack.hip): lane k's stack at base + k * lane_stride, slot s at + s * frame_bytes, every slot one
+// frame of out_h x out_w pixels drawn as render_kernel draws it (format GYMNET_STACK_*: GRAY8, BINARY8 or BINARY_F32).
+struct StackArgs {
+    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
+    uint8_t *base; int64_t lane_stride, frame_bytes;
+    // shift = 1 (push): slots 0..depth-2 take the old slots 1..depth-1 and the newest takes the frame, except in lanes with
+    // restart[k] != 0 (no array: none), which take the frame in every slot.  shift = 0 (reset): lanes with restart[k] != 0 (no array:
+    // every lane) take the frame in every slot, the others are not touched.
+    const uint8_t *restart;
+    int32_t depth, shift;
+    int64_t total_waves, waves_per_frame;     // num_envs * waves_per_frame, render_waves_per_frame(out_w, out_h)
+    int32_t out_w, out_h;
+    float x0, y0, sxq, syq;                   // as RenderArgs
+};
+hipError_t launch_pixel_stack(bool f64, int32_t format, const StackArgs &a, hipStream_t st);
 hipError_t launch_fill_i32(int32_t *p, int32_t v, int64_t n, hipStream_t st);
 // Gathers the sharded done list of one step (counter half `counts`) and the records written beside it into compact arrays
 // out_*[0 .. *out_count) (entries beyond out_capacity are dropped; the count is the true one), and / or applies the records to

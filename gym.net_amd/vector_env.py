@@ -110,6 +110,7 @@ class VectorEnv:
         self._bookkeeping = bool(episode_stats or max_episode_steps)
         self._final_obs = bool(final_obs)
         self.Resident = bool(resident)
+        self.Device = int(device)
         capi.check(self._lib.gymnet_vecenv_create(C.byref(cfg), C.byref(self._h)))
         self._describe(env_id, num_envs, auto_reset)
         if launch_policy:
@@ -126,6 +127,7 @@ class VectorEnv:
         self._bookkeeping = True            # a group member: flags unknown here (DoneRecords() asks for everything it may have)
         self._final_obs = False
         self.Resident = False
+        self.Device = None                  # not known here: PixelStack needs an `out` tensor
         self._dtype = np.dtype(dtype)
         self._describe(env_id, num_envs, auto_reset)
         return self
@@ -373,6 +375,14 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_render(self._h, _host(out), *self._render_args("gray", first, count, crop, (w, h), None)))
         return out
 
+    def PixelStack(self, depth=2, size=(40, 20), crop=(200, 150, 200, 150), format="binary_f32", out=None):
+        """An episode-aware stack of processed frames per lane, kept on the device (gymnet_vecenv_pixel_stack_config): the Images runner's
+        2-deep frame queue (ReplayMemory.cs:38-54) and network input (ImageDataBuilder.cs:10-18) with the defaults — two 40 x 20 frames of
+        the crop (200, 150, 200, 150), oldest first, 1.0 where a pixel is not background.  format "gray8" / "binary8" (uint8) or
+        "binary_f32" (float32).  out=None allocates a torch tensor [N, depth, h, w] on the handle's device; a caller's tensor of that
+        dtype is adopted with lane_stride = its stride(0).  Replaces any stack this handle had.  CartPole only."""
+        return PixelFrameStack(self, depth, size, crop, format, out)
+
     def PackObsDevice(self, d_obs_rowmajor):
         capi.check(self._lib.gymnet_vecenv_pack_obs_device(self._h, _ptr(d_obs_rowmajor)))
 
@@ -590,6 +600,72 @@ class VectorEnv:
 
     # python-style aliases
     reset, step, seed, close = Reset, Step, Seed, Close
+
+
+class PixelFrameStack:
+    """The handle's pixel stack (VectorEnv.PixelStack).  .Tensor is the device tensor [N, depth, h, w] (the stack itself: read it after
+    the handle's stream, e.g. after env.Sync()); Reset / Push / Step are ordered on the handle's stream and do not block."""
+    _FORMATS = {"gray8": (capi.STACK_GRAY8, "uint8"), "binary8": (capi.STACK_BINARY8, "uint8"), "binary_f32": (capi.STACK_BINARY_F32, "float32")}
+
+    def __init__(self, env, depth, size, crop, format, out):
+        if format not in self._FORMATS:
+            raise ValueError(f"unknown pixel stack format {format!r} ({', '.join(self._FORMATS)})")
+        import torch
+        fmt, dt = self._FORMATS[format]
+        w, h = int(size[0]), int(size[1])
+        n, depth = env.NumberOfEnvironments, int(depth)
+        dtype = getattr(torch, dt)
+        if out is None:
+            if env.Device is None:
+                raise ValueError("this handle's device is not known: pass out=")
+            out = torch.empty((n, depth, h, w), dtype=dtype, device=f"cuda:{env.Device}")
+            stride = 0
+        else:
+            if out.dtype != dtype or tuple(out.shape) != (n, depth, h, w) or not out[0].is_contiguous():
+                raise ValueError(f"out must be a {dt} tensor [{n}, {depth}, {h}, {w}] whose lanes are contiguous")
+            stride = out.stride(0) * out.element_size()
+        self._env, self._lib, self._h = env, env._lib, env._h
+        self.Format, self.Depth, self.Size, self.Crop = format, depth, (w, h), tuple(int(v) for v in crop)
+        capi.check(self._lib.gymnet_vecenv_pixel_stack_config(self._h, fmt, depth, *self.Crop, w, h, _ptr(out), stride))
+        prev = getattr(env, "_pixel_stack", None)
+        if prev is not None:
+            prev._h = None                      # the handle holds one stack: the previous one is gone
+        env._pixel_stack = self
+        self.Tensor = out
+
+    def _handle(self):
+        if self._h is None or not self._env._h:
+            raise ValueError("this pixel stack was replaced or closed")
+        return self._h
+
+    def Reset(self, mask=None):
+        """Every lane whose device mask byte is set (None: every lane) gets its current frame in every slot; after ResetWhere(Device)."""
+        capi.check(self._lib.gymnet_vecenv_pixel_stack_reset_device(self._handle(), _ptr(mask)))
+
+    def Push(self, done=None):
+        """Once per step: restarting lanes (device done bytes; None: the handle's own with auto_reset, none without) fill every slot with
+        the current frame, the others shift by one and take it as the newest."""
+        capi.check(self._lib.gymnet_vecenv_pixel_stack_push_device(self._handle(), _ptr(done)))
+
+    def Step(self, d_actions):
+        """StepDevice(d_actions) followed by Push()."""
+        self._env.StepDevice(d_actions)
+        self.Push()
+
+    def Read(self, lanes=None):
+        """The stacks of the lane range lanes = (first, count) (default: every lane) copied to the host: numpy [count, depth, h, w]."""
+        first, count = (0, self._env.NumberOfEnvironments) if lanes is None else (int(lanes[0]), int(lanes[1]))
+        w, h = self.Size
+        out = np.empty((max(count, 0), self.Depth, h, w), np.float32 if self.Format == "binary_f32" else np.uint8)
+        capi.check(self._lib.gymnet_vecenv_pixel_stack_read(self._handle(), _host(out), first, count))
+        return out
+
+    def Close(self):
+        """Releases the stack (the handle stops writing into .Tensor)."""
+        if self._h is not None and self._env._h:
+            capi.check(self._lib.gymnet_vecenv_pixel_stack_config(self._h, 0, 0, 0, 0, 0, 0, 0, 0, None, 0))
+            self._env._pixel_stack = None
+        self._h = None
 
 
 class GroupVectorEnv:

@@ -438,6 +438,51 @@ int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t fi
                          int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
                          int32_t out_w, int32_t out_h, int64_t lane_stride);
 
+/* ---- CartPole pixel frame stacks (the Images runner's frame queue, ReplayMemory.cs:38-54, and input, ImageDataBuilder.cs:10-18) --
+ * The handle owns at most one stack of processed frames per lane, kept on the device.  Lane k's stack starts at base + k * lane_stride
+ * bytes and has `depth` slots: slot 0 the oldest, slot depth - 1 the newest, slot s at + s * frame_bytes.  A slot is out_h rows of
+ * out_w elements, top row first; frame_bytes = out_w * out_h * (1, or 4 for BINARY_F32).  With a packed stride (lane_stride = depth *
+ * frame_bytes) the buffer is exactly [num_envs][depth][out_h][out_w]: NCHW with the frames as channels.  The reference's vertical
+ * 40 x 40 composition of two 40 x 20 frames (oldest on top) is this layout with depth = 2, crop (200, 150, 200, 150), 40 x 20.
+ * The FRAME of a lane is what gymnet_vecenv_render_device draws from the current observation buffer for the same crop and size (same
+ * samples, same rounding; float32 and float64 handles alike), processed by the format:
+ *   GYMNET_STACK_GRAY8       byte for byte the GYMNET_PIXELS_GRAY8 frame;
+ *   GYMNET_STACK_BINARY8     1 where that GRAY8 value is below 255, else 0: 1 exactly when one of the pixel's 16 samples is not
+ *                            background.  It stands in for the reference's invert -> greyscale -> `R > 0 ? 1 : 0` (Imager.cs); the
+ *                            reference resizes with ImageSharp's bicubic filter, which is not reproduced, so edge pixels may differ;
+ *   GYMNET_STACK_BINARY_F32  the same as 1.0f / 0.0f.
+ * config: checks its arguments and allocates the stack (the span (num_envs - 1) * lane_stride + depth * frame_bytes); with d_ext != NULL
+ *   it adopts that device buffer instead (the caller keeps it alive until the stack is replaced, released or the handle destroyed).
+ *   lane_stride = 0 means packed.  Then every slot of every lane gets the lane's current frame.  Calling it again replaces the stack;
+ *   depth = 0 releases it (the other arguments are then not looked at).  gymnet_vecenv_destroy frees a stack the handle allocated.
+ * reset_device: every lane with d_mask[lane] != 0 (d_mask NULL: every lane) gets its current frame in every slot; the others are not
+ *   touched.  Call it after gymnet_vecenv_reset(_device) / _reset_where(_device) with the same mask.
+ * push_device: per lane, once per step.  A lane that RESTARTS gets its current frame in every slot (gym's FrameStack reset
+ *   convention); any other lane's slots 0 .. depth-2 take the old slots 1 .. depth-1 and the newest slot takes the current frame.  A lane
+ *   restarts when d_done[lane] != 0 (either done bit: a truncation by max_episode_steps counts).  With d_done == NULL a
+ *   GYMNET_FLAG_AUTORESET handle reads its own done bytes of the most recent step (gymnet_device_view.d_done); a handle without
+ *   AUTORESET restarts no lane (its caller resets explicitly, then calls reset_device).  After a fused rollout pass the last row of its
+ *   recorded d_done.
+ * config, reset_device and push_device are ordered on the handle's stream and do not block.  None of the five calls changes anything
+ *   but the stack: state, observations, tick, counters, the Philox stream and the done bytes stay as they were.  The stack is not part
+ *   of a checkpoint (gymnet_vecenv_get_state / _get_array): after a restore, call reset_device.
+ * read: copies the stacks of lanes [first_lane, first_lane + count) to host memory, packed (count * depth * frame_bytes bytes), and
+ *   blocks: for hosts without a device allocator.
+ * view: the stack's device pointer and geometry (any out pointer may be NULL).
+ * Errors (nothing written, the previous stack unchanged): GYMNET_ERR_UNSUPPORTED for config on an env other than CartPole;
+ * GYMNET_ERR_INVALID_ARG for an unknown format (GYMNET_PIXELS_RGB8 included), depth outside [0, 64], the crop / size rules of
+ * gymnet_vecenv_render_device, a lane_stride below depth * frame_bytes or a span that overflows, for BINARY_F32 a d_ext or lane_stride
+ * that is not a multiple of 4, reset / push / view / read before a stack is configured, a NULL read destination, or read lanes outside
+ * [0, num_envs) or count < 1; GYMNET_ERR_OOM when the stack cannot be allocated. */
+enum { GYMNET_STACK_GRAY8 = 2, GYMNET_STACK_BINARY8 = 3, GYMNET_STACK_BINARY_F32 = 4 };
+int gymnet_vecenv_pixel_stack_config(gymnet_vecenv *h, int32_t format, int32_t depth,
+                                     int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                                     int32_t out_w, int32_t out_h, void *d_ext, int64_t lane_stride);
+int gymnet_vecenv_pixel_stack_reset_device(gymnet_vecenv *h, const uint8_t *d_mask);
+int gymnet_vecenv_pixel_stack_push_device(gymnet_vecenv *h, const uint8_t *d_done);
+int gymnet_vecenv_pixel_stack_view(gymnet_vecenv *h, void **d_stack, int64_t *lane_stride, int64_t *frame_bytes);
+int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_lane, int64_t count);
+
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */
 int gymnet_vecenv_done_lanes(gymnet_vecenv *h, int32_t *lanes_out, int64_t capacity, int64_t *count);

@@ -285,6 +285,28 @@ public:
     void RolloutDevice(const void *d_actions, int64_t steps, int64_t stride, int64_t ring) { check(gymnet_vecenv_rollout_device(h_, d_actions, steps, stride, ring)); }
     void Sync() { check(gymnet_vecenv_sync(h_)); }
     gymnet_device_view DeviceView() const { gymnet_device_view v{}; check(gymnet_vecenv_device_view(h_, &v)); return v; }
+    // CartPole pixel frame stacks (gymnet_vecenv_pixel_stack_config): the Images runner's frame queue and input on the device.  The
+    // defaults are its shape: two 40 x 20 frames of the crop (200, 150, 200, 150), oldest first, 1.0f where a pixel is not background.
+    void ConfigurePixelStack(int32_t format = GYMNET_STACK_BINARY_F32, int32_t depth = 2, int32_t out_w = 40, int32_t out_h = 20,
+                             int32_t crop_x = 200, int32_t crop_y = 150, int32_t crop_w = 200, int32_t crop_h = 150,
+                             void *d_ext = nullptr, int64_t lane_stride = 0) {
+        check(gymnet_vecenv_pixel_stack_config(h_, format, depth, crop_x, crop_y, crop_w, crop_h, out_w, out_h, d_ext, lane_stride));
+        stack_depth_ = depth;
+    }
+    void ResetPixelStack(const uint8_t *d_mask = nullptr) { check(gymnet_vecenv_pixel_stack_reset_device(h_, d_mask)); }
+    void PushPixelStack(const uint8_t *d_done = nullptr) { check(gymnet_vecenv_pixel_stack_push_device(h_, d_done)); }
+    struct PixelStackView { void *d_stack; int64_t lane_stride, frame_bytes; };
+    PixelStackView PixelStack() const { PixelStackView v{}; check(gymnet_vecenv_pixel_stack_view(h_, &v.d_stack, &v.lane_stride, &v.frame_bytes)); return v; }
+    /// the stacks of lanes [first, first + count) (count < 0: to the last lane), packed [count][depth][out_h][out_w]: T = uint8_t for
+    /// GRAY8 / BINARY8 stacks, float for BINARY_F32
+    template <class T> std::vector<T> ReadPixelStack(int64_t first = 0, int64_t count = -1) const {
+        if (count < 0) count = n_ - first;
+        const PixelStackView v = PixelStack();
+        if (v.frame_bytes % (int64_t)sizeof(T) != 0) throw std::invalid_argument("element type does not match the stack's format");
+        std::vector<T> out((size_t)(count > 0 ? count * stack_depth_ * v.frame_bytes / (int64_t)sizeof(T) : 0));
+        check(gymnet_vecenv_pixel_stack_read(h_, out.data(), first, count));
+        return out;
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
@@ -297,6 +319,7 @@ private:
     gymnet_vecenv *h_ = nullptr;
     gymnet_env_info info_{};
     int64_t n_ = 0;
+    int32_t stack_depth_ = 0;          // of the pixel stack ConfigurePixelStack set up
     std::unique_ptr<Discrete> action_discrete_;
     std::unique_ptr<Box> action_box_, observation_space_;
 };
