@@ -15,9 +15,9 @@ from .sharding import ShardPlan, ShardedVectorEnv
 from .spaces import Box, Discrete, Space
 from .step import Step
 from .vector_env import (AcrobotEnv, BatchStep, CartPoleEnv, DummyVecEnv, GpuEnv, GroupVectorEnv, MountainCarContinuousEnv, MountainCarEnv,
-                         PendingStep, PendulumEnv, PixelFrameStack, VectorEnv)
+                         EpisodeMemory, PendingStep, PendulumEnv, PixelFrameStack, VectorEnv)
 
-__all__ = ["VectorEnv", "PixelFrameStack", "GroupVectorEnv", "DummyVecEnv", "BatchStep", "PendingStep", "GpuEnv", "CartPoleEnv", "PendulumEnv", "MountainCarEnv",
+__all__ = ["VectorEnv", "PixelFrameStack", "EpisodeMemory", "GroupVectorEnv", "DummyVecEnv", "BatchStep", "PendingStep", "GpuEnv", "CartPoleEnv", "PendulumEnv", "MountainCarEnv",
            "AcrobotEnv", "MountainCarContinuousEnv", "Space", "Box", "Discrete", "Step", "InvalidActionError", "AlreadySteppingError",
            "NotSteppingError", "GymNetError", "NoDeviceError", "ShardPlan", "ShardedVectorEnv", "device_count",
            "env_describe", "load_library", "LIB_PATH", "ENV_IDS"]

@@ -50,6 +50,7 @@ RECORDS_NO_OVERFLOW = 1      # gymnet_rollout_spec.record_flags
 PIXELS_RGB8, PIXELS_GRAY8 = 1, 2     # gymnet_vecenv_render(_device) formats
 RENDER_WIDTH, RENDER_HEIGHT = 600, 400
 STACK_GRAY8, STACK_BINARY8, STACK_BINARY_F32 = 2, 3, 4     # gymnet_vecenv_pixel_stack_config formats
+MEMORY_PARAMS = 0            # gymnet_vecenv_memory_dataset_device format (the others are the STACK_* formats)
 
 
 class Config(C.Structure):
@@ -174,6 +175,14 @@ PROTOTYPES = {
     "gymnet_vecenv_pixel_stack_push_device": (C.c_int, [_H, _P]),
     "gymnet_vecenv_pixel_stack_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gymnet_vecenv_pixel_stack_read": (C.c_int, [_H, _P, C.c_int64, C.c_int64]),
+    "gymnet_vecenv_memory_config": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "gymnet_vecenv_memory_reset_device": (C.c_int, [_H, _P, C.c_int32]),
+    "gymnet_vecenv_memory_push_device": (C.c_int, [_H, _P, _P]),
+    "gymnet_vecenv_memory_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gymnet_vecenv_memory_episodes": (C.c_int, [_H, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "gymnet_vecenv_memory_dataset_size": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "gymnet_vecenv_memory_dataset_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                     _P, _P, _P, _P, C.c_int64]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

@@ -31,6 +31,9 @@ namespace Gym.Envs.Amd {
     // gymnet_vecenv_pixel_stack_config: GRAY8 frames; 1 where the GRAY8 pixel is below 255 (not all background), else 0, as bytes or floats
     public enum GymnetStackFormat { Gray8 = 2, Binary8 = 3, BinaryF32 = 4 }
 
+    // gymnet_vecenv_memory_dataset_device: params rows, or the frames of a GymnetStackFormat (the same values)
+    public enum GymnetDatasetFormat { MemoryParams = 0, Gray8 = 2, Binary8 = 3, BinaryF32 = 4 }
+
     public enum GymnetArrayId {
         Reward = 0, Done = 1, StepsBeyondDone = 2, EpisodeReturn = 3, EpisodeLength = 4, FinishedReturn = 5, FinishedLength = 6,
         FinalObs = 7, LaneSeeds = 8
@@ -163,6 +166,17 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_push_device(IntPtr h, IntPtr d_done);
         [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_view(IntPtr h, out IntPtr d_stack, out long lane_stride, out long frame_bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_read(IntPtr h, void* out_stacks, long first_lane, long count);
+        // episode memory: the best `capacity` episodes by (return, end tick, lane) and the dataset built from them
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_config(IntPtr h, int capacity, int max_length, int history);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_reset_device(IntPtr h, IntPtr d_mask, int clear_pool);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_push_device(IntPtr h, IntPtr d_actions, IntPtr d_done);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_stats(IntPtr h, out long kept, out long ended, out long admitted, out long too_long);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_episodes(IntPtr h, float* ret, int* len, ulong* end_tick, int* lane, long capacity,
+                                                                               out long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_dataset_size(IntPtr h, out long rows);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_dataset_device(IntPtr h, int format, int crop_x, int crop_y, int crop_w, int crop_h,
+                                                                                     int out_w, int out_h, IntPtr d_x, IntPtr d_action, IntPtr d_onehot,
+                                                                                     IntPtr d_reward, long capacity_rows);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

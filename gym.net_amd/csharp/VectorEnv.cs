@@ -228,6 +228,50 @@ namespace Gym.Envs.Amd {
             Native.Check(Native.gymnet_vecenv_pixel_stack_read(_h, p, firstLane, count));
         }
 
+        /// The trainer's episode memory on the device (ReplayMemory.Memorize / EndEpisode, MemoryTypes/ReplayMemory.cs:25-67): every step of
+        /// each lane's open episode and the best `capacity` finished episodes by (return, end tick, lane), a newer episode winning ties.
+        /// maxLength 0 = the handle's max_episode_steps; history = steps per dataset row (MemoryStates).  capacity 0 releases it.
+        public void ConfigureEpisodeMemory(int capacity = 100, int maxLength = 0, int history = 4) =>
+            Native.Check(Native.gymnet_vecenv_memory_config(_h, capacity, maxLength, history));
+
+        /// Once after each single StepDevice: dActions are the device actions that step took; dDone IntPtr.Zero = the handle's own done bytes.
+        public void PushEpisodeMemory(IntPtr dActions, IntPtr dDone = default) =>
+            Native.Check(Native.gymnet_vecenv_memory_push_device(_h, dActions, dDone));
+
+        /// After ResetDevice / a masked reset: the masked lanes (IntPtr.Zero: every lane) open a new episode; clearPool also empties the pool.
+        public void ResetEpisodeMemory(IntPtr dMask = default, bool clearPool = false) =>
+            Native.Check(Native.gymnet_vecenv_memory_reset_device(_h, dMask, clearPool ? 1 : 0));
+
+        /// The kept episodes in descending key order.  Blocks.
+        public (float[] Return, int[] Length, ulong[] EndTick, int[] Lane) ReadMemoryEpisodes() {
+            Native.Check(Native.gymnet_vecenv_memory_episodes(_h, null, null, null, null, 0, out long count));
+            var ret = new float[count]; var len = new int[count]; var tick = new ulong[count]; var lane = new int[count];
+            fixed (float* pr = ret) fixed (int* pl = len) fixed (ulong* pt = tick) fixed (int* pn = lane)
+                Native.Check(Native.gymnet_vecenv_memory_episodes(_h, pr, pl, pt, pn, count, out count));
+            return (ret, len, tick, lane);
+        }
+
+        /// DataBuilder.BuildDataset (DataBuilders/DataBuilder.cs:25-55) into device buffers the caller owns, which must hold the rows
+        /// DatasetRows() reports: dX float [rows][history * obs_dim] for MemoryParams, else [rows][history][outH][outW] frames (CartPole);
+        /// dAction int [rows]; dOneHot float [rows][n] (Discrete only); any may be IntPtr.Zero.  Returns the rows, or -1 while fewer than
+        /// minEpisodes episodes are kept (BuildDataset's `return default`).  Ordered on the handle's stream.
+        public long BuildMemoryDataset(IntPtr dX, IntPtr dAction, IntPtr dOneHot, long capacityRows, int minEpisodes,
+                                       GymnetDatasetFormat format = GymnetDatasetFormat.MemoryParams, int outW = 40, int outH = 20,
+                                       int cropX = 200, int cropY = 150, int cropW = 200, int cropH = 150) {
+            Native.Check(Native.gymnet_vecenv_memory_stats(_h, out long kept, out _, out _, out _));
+            if (kept < minEpisodes) return -1;
+            long rows = DatasetRows();
+            Native.Check(Native.gymnet_vecenv_memory_dataset_device(_h, (int) format, cropX, cropY, cropW, cropH, outW, outH, dX, dAction, dOneHot,
+                                                                    IntPtr.Zero, capacityRows));
+            return rows < capacityRows ? rows : capacityRows;
+        }
+
+        /// The rows a dataset build writes now.  Blocks.
+        public long DatasetRows() {
+            Native.Check(Native.gymnet_vecenv_memory_dataset_size(_h, out long rows));
+            return rows;
+        }
+
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));
         public void RolloutFused(GymnetRolloutSpec spec) {

@@ -5,6 +5,7 @@
 // and is never linked here.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -752,6 +753,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
     if (h->d_render) (void)hipFree(h->d_render);
     if (h->stack_alloc) (void)hipFree(h->stack_alloc);
+    for (void *p : h->mem_allocs) (void)hipFree(p);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1542,6 +1544,225 @@ int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_la
     if (a.lane_stride == span) HIP_TRY(h, hipMemcpyAsync(out, src, (size_t)(count * span), hipMemcpyDeviceToHost, h->stream));
     else HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)span, src, (size_t)a.lane_stride, (size_t)span, (size_t)count, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GYMNET_OK;
+    });
+}
+
+// ---- episode memory (episode_memory.hip) ---------------------------------------------------------------------------------
+namespace {
+
+constexpr int32_t kMemoryMaxCapacity = 65536;
+constexpr int32_t kMemoryMaxHistory = 64;
+constexpr int32_t kMemoryMaxLength = 1 << 24;
+
+int need_memory(gymnet_vecenv *h) {
+    return h->mem.capacity > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no episode memory configured (gymnet_vecenv_memory_config)");
+}
+
+// drops the configured memory after the stream has drained (a launch may still use it)
+int release_memory(gymnet_vecenv *h) {
+    if (!h->mem_allocs.empty()) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (void *p : h->mem_allocs) (void)hipFree(p);
+    h->mem_allocs.clear();
+    h->mem = MemoryArgs{};
+    h->mem_history = 0;
+    return GYMNET_OK;
+}
+
+// the kept entries [0, kept) and the control block, read back after the stream has drained
+int read_pool(gymnet_vecenv *h, MemCtl *ctl, std::vector<MemEntry> *meta) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(ctl, h->mem.ctl, sizeof *ctl, hipMemcpyDeviceToHost));
+    if (meta) {
+        meta->resize((size_t)ctl->kept);
+        if (ctl->kept > 0) HIP_TRY(h, hipMemcpy(meta->data(), h->mem.meta, sizeof(MemEntry) * (size_t)ctl->kept, hipMemcpyDeviceToHost));
+    }
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (capacity == 0) return release_memory(h);
+    if (capacity < 0 || capacity > kMemoryMaxCapacity)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %d not in [0, %d]", capacity, kMemoryMaxCapacity);
+    if (history < 1 || history > kMemoryMaxHistory) return fail(h, GYMNET_ERR_INVALID_ARG, "history %d not in [1, %d]", history, kMemoryMaxHistory);
+    const int32_t len = max_length == 0 ? h->cfg.max_episode_steps : max_length;
+    if (max_length < 0 || len < 1 || len > kMemoryMaxLength)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "max_length %d not in [1, %d] (0 = max_episode_steps, which is %d)", max_length, kMemoryMaxLength,
+                    h->cfg.max_episode_steps);
+    const int obs_dim = h->desc->obs_dim;
+    const int64_t row = (int64_t)obs_dim * (int64_t)h->esz + 8;
+    const double ring_d = (double)(len + 1) * (double)h->n * (double)row, pool_d = (double)capacity * (double)len * (double)row;
+    if (ring_d > 9.0e18 || pool_d > 9.0e18) return fail(h, GYMNET_ERR_INVALID_ARG, "episode memory of %.3g bytes overflows", ring_d + pool_d);
+    MemoryArgs m{};
+    m.n = h->n; m.obs_dim = obs_dim; m.esz = (int32_t)h->esz;
+    m.max_len = len; m.capacity = capacity;
+    m.slot_bytes = h->n * row; m.row_bytes = row;
+    m.push_blocks = memory_push_blocks(h->n);
+    // every region (ring, pool, per-lane state, candidates, control, pool entries, scratch, row offsets, counters) or none
+    std::vector<void *> got;
+    auto take = [&](void **p, int64_t bytes) -> bool {
+        hipError_t e = hipMalloc(p, (size_t)(bytes > 0 ? bytes : 1));
+        if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+        got.push_back(*p);
+        return true;
+    };
+    void *ring, *pool, *lane_len, *lane_ret, *cand, *ctl, *meta, *meta_tmp, *scratch, *row_off, *partials;
+    const bool ok = take(&ring, (int64_t)(len + 1) * m.slot_bytes) && take(&pool, (int64_t)capacity * len * row) &&
+                    take(&lane_len, 4 * h->n) && take(&lane_ret, 4 * h->n) && take(&cand, (int64_t)sizeof(MemCand) * h->n) &&
+                    take(&ctl, sizeof(MemCtl)) && take(&meta, (int64_t)sizeof(MemEntry) * capacity) &&
+                    take(&meta_tmp, (int64_t)sizeof(MemEntry) * capacity) && take(&scratch, 4 * (int64_t)capacity) &&
+                    take(&row_off, 8 * ((int64_t)capacity + 1)) && take(&partials, 16 * (int64_t)m.push_blocks);
+    if (!ok) {
+        for (void *p : got) (void)hipFree(p);
+        return fail(h, GYMNET_ERR_OOM, "hipMalloc of the episode memory (%.3g bytes) failed", ring_d + pool_d);
+    }
+    if (int st = release_memory(h); st != GYMNET_OK) {
+        for (void *p : got) (void)hipFree(p);
+        return st;
+    }
+    m.ring = static_cast<uint8_t *>(ring); m.pool = static_cast<uint8_t *>(pool);
+    m.lane_len = static_cast<int32_t *>(lane_len); m.lane_ret = static_cast<float *>(lane_ret);
+    m.cand = static_cast<MemCand *>(cand); m.ctl = static_cast<MemCtl *>(ctl);
+    m.meta = static_cast<MemEntry *>(meta); m.meta_tmp = static_cast<MemEntry *>(meta_tmp);
+    m.scratch = static_cast<int32_t *>(scratch); m.row_off = static_cast<int64_t *>(row_off);
+    m.partials = static_cast<uint64_t *>(partials);
+    h->mem = m;
+    h->mem_allocs = got;
+    h->mem_history = history;
+    h->mem_pos = 0;
+    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
+    HIP_TRY(h, launch_memory_init(h->mem, h->stream));
+    HIP_TRY(h, launch_memory_open(h->f64, h->mem, h->d_obs, h->ostride, nullptr, 0, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, int32_t clear_pool) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (clear_pool) HIP_TRY(h, launch_memory_init(h->mem, h->stream));
+    HIP_TRY(h, launch_memory_open(h->f64, h->mem, h->d_obs, h->ostride, d_mask, (int64_t)(h->mem_pos % (uint64_t)(h->mem.max_len + 1)), h->stream));
+    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (h->tick != h->mem_tick + 1 || h->step_launches != h->mem_launches + 1)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
+                    "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device", (unsigned long long)h->mem_tick,
+                    (unsigned long long)h->tick, (unsigned long long)(h->step_launches - h->mem_launches));
+    MemPushArgs p{};
+    p.obs = h->d_obs; p.obs_stride = h->ostride;
+    p.actions = d_actions; p.reward = h->d_reward; p.done = d_done ? d_done : h->d_done;
+    p.slot = (int64_t)(h->mem_pos % (uint64_t)(h->mem.max_len + 1));
+    p.end_tick = h->tick;
+    p.autoreset = h->autoreset ? 1 : 0;
+    HIP_TRY(h, launch_memory_push(h->f64, h->mem, p, h->stream));
+    h->mem_pos += 1;
+    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_stats(gymnet_vecenv *h, int64_t *kept, int64_t *ended, int64_t *admitted, int64_t *too_long) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    MemCtl ctl{};
+    ST_TRY(read_pool(h, &ctl, nullptr));
+    std::vector<uint64_t> part((size_t)h->mem.push_blocks * 2);
+    HIP_TRY(h, hipMemcpy(part.data(), h->mem.partials, part.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t e = 0, t = 0;
+    for (size_t b = 0; b < part.size(); b += 2) { e += part[b]; t += part[b + 1]; }
+    if (kept) *kept = ctl.kept;
+    if (ended) *ended = (int64_t)e;
+    if (admitted) *admitted = (int64_t)ctl.admitted;
+    if (too_long) *too_long = (int64_t)t;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, uint64_t *end_tick, int32_t *lane, int64_t capacity,
+                                  int64_t *count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (capacity < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %lld < 0", (long long)capacity);
+    MemCtl ctl{};
+    std::vector<MemEntry> meta;
+    ST_TRY(read_pool(h, &ctl, &meta));
+    auto ret_order = [](float r) { return r == 0.0f ? 0.0f : r; };
+    std::sort(meta.begin(), meta.end(), [&](const MemEntry &a, const MemEntry &b) {     // descending key (return, tick, lane)
+        if (ret_order(a.ret) != ret_order(b.ret)) return ret_order(a.ret) > ret_order(b.ret);
+        if (a.tick != b.tick) return a.tick > b.tick;
+        return a.lane > b.lane;
+    });
+    const int64_t m = (int64_t)meta.size() < capacity ? (int64_t)meta.size() : capacity;
+    for (int64_t i = 0; i < m; ++i) {
+        if (ret) ret[i] = meta[(size_t)i].ret;
+        if (len) len[i] = meta[(size_t)i].len;
+        if (end_tick) end_tick[i] = meta[(size_t)i].tick;
+        if (lane) lane[i] = meta[(size_t)i].lane;
+    }
+    if (count) *count = (int64_t)meta.size();
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_dataset_size(gymnet_vecenv *h, int64_t *rows) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (!rows) return fail(h, GYMNET_ERR_INVALID_ARG, "rows is null");
+    MemCtl ctl{};
+    std::vector<MemEntry> meta;
+    ST_TRY(read_pool(h, &ctl, &meta));
+    int64_t r = 0;
+    for (const MemEntry &e : meta) r += (int64_t)e.len * 2 / 3;
+    *rows = r;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                                        int32_t out_w, int32_t out_h, void *d_x, int32_t *d_action, float *d_onehot, float *d_reward,
+                                        int64_t capacity_rows) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (format != GYMNET_MEMORY_PARAMS && format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown dataset format %d", format);
+    if (format != GYMNET_MEMORY_PARAMS) {
+        if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel datasets exist for CartPole only (CartPoleEnv.cs:69-135)");
+        ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
+    }
+    if (capacity_rows < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity_rows %lld < 0", (long long)capacity_rows);
+    if (d_onehot && h->desc->box_action) return fail(h, GYMNET_ERR_INVALID_ARG, "a Box action has no one-hot");
+    if (format == GYMNET_STACK_BINARY_F32 && !aligned_to(d_x, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 rows need a 4-byte aligned d_x");
+    if (capacity_rows == 0) return GYMNET_OK;
+    MemDatasetArgs d{};
+    d.format = format; d.history = h->mem_history;
+    d.x = d_x; d.action = d_action; d.onehot = d_onehot; d.reward = d_reward;
+    d.capacity_rows = capacity_rows;
+    d.action_n = h->desc->box_action ? 0 : h->desc->action_n;
+    if (format != GYMNET_MEMORY_PARAMS) {
+        d.waves_per_frame = render_waves_per_frame(out_w, out_h);
+        d.out_w = out_w; d.out_h = out_h;
+        d.x0 = (float)crop_x; d.y0 = (float)crop_y;                    // the sample positions of the pixel stack
+        d.sxq = (float)((double)crop_w / (4.0 * out_w));
+        d.syq = (float)((double)crop_h / (4.0 * out_h));
+    }
+    HIP_TRY(h, launch_memory_dataset(h->f64, h->mem, d, h->stream));
     return GYMNET_OK;
     });
 }

@@ -1,6 +1,7 @@
 // cartpole_raster.hpp — the CartPole canvas (CartPoleEnv.Render, CartPoleEnv.cs:69-135) as the frame kernels see it: the per-lane
-// geometry a wave computes once (lane_geometry) and the 16-sample coverage of one output pixel (shade).  Shared by render.hip (frames)
-// and pixel_stack.hip (episode-aware frame stacks), so both draw the same pixels from the same arithmetic.  The contract is
+// geometry a wave computes once (lane_geometry), the 16-sample coverage of one output pixel (shade) and a stack pixel's value
+// (stack_value).  Shared by render.hip (frames), pixel_stack.hip (episode-aware frame stacks) and episode_memory.hip (dataset frames), so
+// all of them draw the same pixels from the same arithmetic.  The contract is
 // gymnet_vecenv_render_device in include/gymnet_amd.h; compiled with -ffp-contract=off like every unit.
 //
 // The work decomposition is shared too: one wave covers kPixPerWave consecutive pixels of ONE frame, kPixPerThread per thread.
@@ -8,6 +9,7 @@
 #include "kernels.hpp"
 
 #include "envs.hpp"
+#include "../../include/gymnet_amd.h"
 
 namespace gymnet {
 
@@ -91,6 +93,16 @@ __device__ __forceinline__ void shade(const Geo &g, float xs0, float sxq, float 
             nw += track ? 0 : 4;
         }
     }
+}
+
+// what a pixel of the stack holds, from its shade() counts: the GRAY8 value of gymnet_vecenv_render_device, or 1 where that value is
+// below 255 (a sample that is not background), as a byte or as 1.0f
+template <int FMT>
+__device__ __forceinline__ uint32_t stack_value(int nw, int np) {
+    const uint32_t y = (uint32_t)(nw * 255 + np * 160 + 8) >> 4;
+    if constexpr (FMT == GYMNET_STACK_GRAY8) return y;
+    else if constexpr (FMT == GYMNET_STACK_BINARY8) return y < 255u ? 1u : 0u;
+    else return y < 255u ? 0x3f800000u : 0u;
 }
 
 }  // namespace

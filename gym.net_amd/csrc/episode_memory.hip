@@ -1,0 +1,421 @@
+// episode_memory.hip — the trainer's episode memory on the device: every step of every lane's open episode, the best `capacity`
+// finished episodes by key (return, end tick, lane), and the dataset built from them (ReplayMemory.Memorize / EndEpisode,
+// MemoryTypes/ReplayMemory.cs:25-67, and DataBuilder.BuildDataset, DataBuilders/DataBuilder.cs:25-55).  The contract is
+// gymnet_vecenv_memory_config and its siblings in include/gymnet_amd.h; tests/_episode_memory_model.py restates it in NumPy.
+// Written for gfx950 (wave64); compiled with -ffp-contract=off.
+//
+// Push (once per vector step, one thread per lane).  Steps are staged in a dense ring of L + 1 slots indexed by the memory's push
+// count, so every lane writes the same slot and the stores coalesce like a recorded rollout's: slot s holds obs [D][N], action [N] and
+// reward [N].  The step's action and reward go to slot pos, the post-step observation (the next step's o_p, or an auto-reset's o_0) to
+// slot pos + 1; an episode of len <= L steps that ends at push pos occupies slots pos - len + 1 .. pos, and pos + 1 is never one of them.
+// A lane whose episode ends compares its return with the pool's lowest kept return (read from the previous merge): a newer episode wins
+// ties, so when the pool is full ret >= thr admits.  Survivors are appended to the candidate list with one atomic per wave.
+//
+// Merge (a second launch, one workgroup; it returns at once when no episode was admitted, which is the common case after warm-up).  It
+// keeps the top `capacity` keys of pool + candidates: a 16-digit radix select finds the K-th key, evicted pool blocks join the free
+// list, and each winner copies its rows out of the ring into a free block [L][row].  Then it publishes the new threshold.
+//
+// Dataset (not per step): rank the kept keys (count of larger keys), scan the row counts floor(len * 2 / 3) in that order, then write
+// params rows (one thread per row) or frames re-rendered from the stored observations with cartpole_raster.hpp (one wave per 1024
+// pixels of one frame, as the pixel stack draws them).
+#include "cartpole_raster.hpp"
+
+#include <type_traits>
+
+namespace gymnet {
+
+namespace {
+
+// a float's order as an unsigned integer (+0 and -0 are one value)
+__device__ __forceinline__ uint32_t ret_bits(float r) {
+    const uint32_t u = __float_as_uint(r == 0.0f ? 0.0f : r);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float bits_ret(uint32_t b) { return __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b); }
+
+struct Key { uint32_t w[4]; };      // (return, tick high, tick low, lane): 16 digits of 8 bits, most significant first
+
+__device__ __forceinline__ Key make_key(float ret, uint64_t tick, int32_t lane) {
+    Key k;
+    k.w[0] = ret_bits(ret); k.w[1] = (uint32_t)(tick >> 32); k.w[2] = (uint32_t)tick; k.w[3] = (uint32_t)lane;
+    return k;
+}
+
+__device__ __forceinline__ bool key_less(const Key &a, const Key &b) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (a.w[q] != b.w[q]) return a.w[q] < b.w[q];
+    return false;
+}
+
+__device__ __forceinline__ uint32_t digit(const Key &k, int d) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (q == (d >> 2)) w = k.w[q];
+    return (w >> (24 - 8 * (d & 3))) & 255u;
+}
+
+// digits 0 .. d-1 of k equal those of t
+__device__ __forceinline__ bool prefix_match(const Key &k, const uint32_t (&t)[4], int d) {
+    const int wd = d >> 2, b = d & 3;
+    const uint32_t mask = b ? 0xFFFFFFFFu << (32 - 8 * b) : 0u;
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < wd) ok &= k.w[q] == t[q];
+        else if (q == wd) ok &= (k.w[q] & mask) == (t[q] & mask);
+    }
+    return ok;
+}
+
+__device__ __forceinline__ uint32_t wave_rank(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+constexpr int kPushBlock = 256;
+constexpr int kMergeBlock = 1024;
+
+// an empty pool: entry i owns block i, no counts, no candidates
+__global__ __launch_bounds__(256) void memory_init_kernel(MemoryArgs m) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m.capacity) m.meta[i] = MemEntry{0.0f, 0, 0ull, -1, (int32_t)i};
+    if (i < 2 * (int64_t)m.push_blocks) m.partials[i] = 0ull;
+    if (i == 0) *m.ctl = MemCtl{};
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void memory_open_kernel(MemoryArgs m, const R *obs, int64_t ostride, const uint8_t *mask, int64_t slot) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m.n || (mask && !mask[k])) return;
+    m.lane_len[k] = 0;
+    m.lane_ret[k] = 0.0f;
+    R *o = reinterpret_cast<R *>(m.ring + slot * m.slot_bytes);
+    for (int d = 0; d < m.obs_dim; ++d) o[(int64_t)d * m.n + k] = obs[(int64_t)d * ostride + k];
+}
+
+template <class R>
+__global__ __launch_bounds__(kPushBlock) void memory_push_kernel(MemoryArgs m, MemPushArgs p) {
+    __shared__ uint32_t cnt[2];
+    if (threadIdx.x == 0) { cnt[0] = 0u; cnt[1] = 0u; }
+    __syncthreads();
+    const int64_t k = (int64_t)blockIdx.x * kPushBlock + threadIdx.x;
+    bool ended = false, too_long = false, cand = false;
+    float ret = 0.0f;
+    int32_t len = -1;
+    if (k < m.n) len = m.lane_len[k];
+    if (len >= 0) {
+        const int64_t obs_bytes = (int64_t)m.obs_dim * m.n * (int64_t)sizeof(R);
+        uint8_t *slot = m.ring + p.slot * m.slot_bytes;
+        const uint32_t a = static_cast<const uint32_t *>(p.actions)[k];
+        const float r = p.reward[k];
+        const bool done = p.done[k] != 0;
+        reinterpret_cast<uint32_t *>(slot + obs_bytes)[k] = a;
+        reinterpret_cast<float *>(slot + obs_bytes + 4 * m.n)[k] = r;
+        ret = m.lane_ret[k] + r;                          // the step kernel's EPISODE_STATS sum, in the same order
+        len += 1;
+        if (done) {
+            ended = true;
+            too_long = len > m.max_len;
+            cand = !too_long && (!m.ctl->full || ret >= m.ctl->thr);
+        }
+        if (!done || p.autoreset) {                       // the next step's o_p, or the auto-reset episode's o_0
+            const int64_t nxt = p.slot == m.max_len ? 0 : p.slot + 1;
+            R *o = reinterpret_cast<R *>(m.ring + nxt * m.slot_bytes);
+            const R *src = static_cast<const R *>(p.obs);
+            for (int d = 0; d < m.obs_dim; ++d) o[(int64_t)d * m.n + k] = src[(int64_t)d * p.obs_stride + k];
+        }
+        m.lane_len[k] = done ? (p.autoreset ? 0 : -1) : len;
+        m.lane_ret[k] = done ? 0.0f : ret;
+    }
+    const int lid = threadIdx.x & 63;
+    const uint64_t cm = __ballot(cand);
+    if (cm) {
+        const int leader = __ffsll((unsigned long long)cm) - 1;
+        uint32_t base = 0;
+        if (lid == leader) base = atomicAdd(&m.ctl->cand_count, (uint32_t)__popcll(cm));
+        base = __shfl(base, leader);
+        if (cand) m.cand[base + wave_rank(cm)] = MemCand{ret, len, (int32_t)k, 0};
+    }
+    const uint64_t em = __ballot(ended), tm = __ballot(too_long);
+    if (lid == 0 && em) {
+        atomicAdd(&cnt[0], (uint32_t)__popcll(em));
+        if (tm) atomicAdd(&cnt[1], (uint32_t)__popcll(tm));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt[0]) {                     // this workgroup's own counters: no contention
+        m.partials[2 * blockIdx.x] += cnt[0];
+        m.partials[2 * blockIdx.x + 1] += cnt[1];
+    }
+}
+
+__device__ __forceinline__ Key entry_key(const MemoryArgs &m, int64_t i, int32_t kept, uint64_t end_tick) {
+    if (i < kept) { const MemEntry e = m.meta[i]; return make_key(e.ret, e.tick, e.lane); }
+    const MemCand c = m.cand[i - kept];
+    return make_key(c.ret, end_tick, c.lane);
+}
+
+template <int ESZ>
+__global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m, int64_t slot, uint64_t end_tick) {
+    using W = typename std::conditional<ESZ == 8, uint64_t, uint32_t>::type;
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t tau[4];
+    __shared__ uint32_t need_s, min_bits;
+    __shared__ int32_t n_keep, n_free, n_win;
+    const uint32_t cands = m.ctl->cand_count;
+    if (cands == 0) return;
+    const int32_t kept = m.ctl->kept, cap = m.capacity;
+    const int64_t total = (int64_t)kept + cands;
+    const bool select = total > cap;
+    const int tid = threadIdx.x;
+    if (tid < 4) tau[tid] = 0u;
+    if (tid == 0) { need_s = (uint32_t)cap; min_bits = 0xFFFFFFFFu; n_keep = 0; n_free = 0; n_win = 0; }
+    __syncthreads();
+    // the cap-th largest key: digit by digit, the bin where the count from the top reaches the rank still needed
+    if (select) {
+        for (int d = 0; d < 16; ++d) {
+            if (tid < 256) hist[tid] = 0u;
+            __syncthreads();
+            const uint32_t t[4] = {tau[0], tau[1], tau[2], tau[3]};
+            for (int64_t i = tid; i < total; i += kMergeBlock) {
+                const Key k = entry_key(m, i, kept, end_tick);
+                if (prefix_match(k, t, d)) atomicAdd(&hist[digit(k, d)], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t cum = 0u;
+                int b = 255;
+                for (; b > 0; --b) {
+                    if (cum + hist[b] >= need_s) break;
+                    cum += hist[b];
+                }
+                need_s -= cum;
+                tau[d >> 2] |= (uint32_t)b << (24 - 8 * (d & 3));
+            }
+            __syncthreads();
+        }
+    }
+    Key t;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) t.w[q] = tau[q];
+    // kept entries at or above the threshold stay; the others' blocks, and the blocks of the unused entries, are free
+    for (int i = tid; i < cap; i += kMergeBlock) {
+        const MemEntry e = m.meta[i];
+        if (i < kept && (!select || !key_less(make_key(e.ret, e.tick, e.lane), t))) m.meta_tmp[atomicAdd(&n_keep, 1)] = e;
+        else m.scratch[atomicAdd(&n_free, 1)] = e.block;
+    }
+    __syncthreads();
+    const int32_t keep = n_keep;
+    for (int64_t j = tid; j < cands; j += kMergeBlock) {
+        const MemCand c = m.cand[j];
+        if (!select || !key_less(make_key(c.ret, end_tick, c.lane), t)) {
+            const int32_t s = atomicAdd(&n_win, 1);
+            if (keep + s < cap) m.meta_tmp[keep + s] = MemEntry{c.ret, c.len, end_tick, c.lane, m.scratch[s]};
+        }
+    }
+    __syncthreads();
+    // keys are unique while ticks only grow, so exactly cap - keep candidates pass a selection; the clamp keeps a tick that was set
+    // backwards (equal keys) inside the pool
+    const int32_t win = n_win < cap - keep ? n_win : cap - keep, live = keep + win;
+    for (int i = live + tid; i < cap; i += kMergeBlock) m.meta_tmp[i] = MemEntry{0.0f, 0, 0ull, -1, m.scratch[i - keep]};
+    __syncthreads();
+    for (int i = tid; i < cap; i += kMergeBlock) {
+        const MemEntry e = m.meta_tmp[i];
+        m.meta[i] = e;
+        if (i < live) atomicMin(&min_bits, ret_bits(e.ret));
+    }
+    // each winner's rows out of the ring into its block: one wave per winner, a lane per row
+    const int wave = tid >> 6, lid = tid & 63;
+    const int64_t obs_bytes = (int64_t)m.obs_dim * m.n * ESZ;
+    for (int w = wave; w < win; w += kMergeBlock / 64) {
+        const MemEntry e = m.meta_tmp[keep + w];
+        uint8_t *blk = m.pool + (int64_t)e.block * m.max_len * m.row_bytes;
+        for (int q = lid; q < e.len; q += 64) {
+            int64_t s = slot - e.len + 1 + q;
+            if (s < 0) s += m.max_len + 1;
+            const uint8_t *src = m.ring + s * m.slot_bytes;
+            uint8_t *row = blk + (int64_t)q * m.row_bytes;
+            for (int d = 0; d < m.obs_dim; ++d)
+                reinterpret_cast<W *>(row)[d] = reinterpret_cast<const W *>(src)[(int64_t)d * m.n + e.lane];
+            reinterpret_cast<uint32_t *>(row + m.obs_dim * ESZ)[0] = reinterpret_cast<const uint32_t *>(src + obs_bytes)[e.lane];
+            reinterpret_cast<uint32_t *>(row + m.obs_dim * ESZ)[1] = reinterpret_cast<const uint32_t *>(src + obs_bytes + 4 * m.n)[e.lane];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        m.ctl->kept = live;
+        m.ctl->full = live == cap ? 1 : 0;
+        m.ctl->thr = bits_ret(min_bits);
+        m.ctl->admitted += (uint64_t)win;
+        m.ctl->cand_count = 0u;
+    }
+}
+
+// ---- dataset -----------------------------------------------------------------------------------------------------------------
+
+// scratch[rank] = the entry of that rank, 0 the largest key
+__global__ __launch_bounds__(256) void memory_rank_kernel(MemoryArgs m) {
+    const int32_t kept = m.ctl->kept;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kept) return;
+    const MemEntry e = m.meta[i];
+    const Key ki = make_key(e.ret, e.tick, e.lane);
+    int r = 0;
+    for (int j = 0; j < kept; ++j) {
+        const MemEntry f = m.meta[j];
+        r += key_less(ki, make_key(f.ret, f.tick, f.lane)) ? 1 : 0;
+    }
+    m.scratch[r] = i;
+}
+
+__device__ __forceinline__ int64_t rows_of(int32_t len) { return (int64_t)len * 2 / 3; }     // DataBuilder.cs:33
+
+// row_off[r] = first row of the episode of rank r, row_off[kept] = ctl->rows = every row
+__global__ __launch_bounds__(1024) void memory_scan_kernel(MemoryArgs m) {
+    __shared__ int64_t part[1024];
+    const int32_t kept = m.ctl->kept;
+    const int tid = threadIdx.x;
+    const int per = (kept + 1023) / 1024;
+    const int lo = tid * per, hi = lo + per < kept ? lo + per : kept;
+    int64_t s = 0;
+    for (int r = lo; r < hi; ++r) s += rows_of(m.meta[m.scratch[r]].len);
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        int64_t acc = 0;
+        for (int q = 0; q < 1024; ++q) { const int64_t v = part[q]; part[q] = acc; acc += v; }
+        m.row_off[kept] = acc;
+        m.ctl->rows = (uint64_t)acc;
+    }
+    __syncthreads();
+    int64_t off = part[tid];
+    for (int r = lo; r < hi; ++r) { m.row_off[r] = off; off += rows_of(m.meta[m.scratch[r]].len); }
+}
+
+// the episode (rank) a dataset row belongs to: the largest r with row_off[r] <= row
+__device__ __forceinline__ int find_rank(const int64_t *row_off, int32_t kept, int64_t row) {
+    int lo = 0, hi = kept - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (row_off[mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void memory_rows_kernel(MemoryArgs m, MemDatasetArgs d) {
+    const int32_t kept = m.ctl->kept;
+    const int64_t total = m.row_off[kept];
+    const int64_t lim = total < d.capacity_rows ? total : d.capacity_rows;
+    const int S = d.history, D = m.obs_dim;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < lim; row += (int64_t)gridDim.x * 256) {
+        const int r = find_rank(m.row_off, kept, row);
+        const MemEntry e = m.meta[m.scratch[r]];
+        const int64_t p = row - m.row_off[r];
+        const uint8_t *blk = m.pool + (int64_t)e.block * m.max_len * m.row_bytes;
+        const uint8_t *rp = blk + p * m.row_bytes;
+        const uint32_t a = reinterpret_cast<const uint32_t *>(rp + D * sizeof(R))[0];
+        if (d.action) d.action[row] = (int32_t)a;
+        if (d.reward) d.reward[row] = reinterpret_cast<const float *>(rp + D * sizeof(R))[1];
+        if (d.onehot)
+            for (int j = 0; j < d.action_n; ++j) d.onehot[row * d.action_n + j] = (uint32_t)j == a ? 1.0f : 0.0f;
+        if (d.format == 0 && d.x) {
+            float *x = static_cast<float *>(d.x) + row * (int64_t)S * D;
+            for (int s = 0; s < S; ++s) {
+                const int64_t q = p - (S - 1) + s;
+                const R *o = reinterpret_cast<const R *>(blk + (q > 0 ? q : 0) * m.row_bytes);
+                for (int c = 0; c < D; ++c) x[s * D + c] = (float)o[c];
+            }
+        }
+    }
+}
+
+template <class R, int FMT>
+__global__ __launch_bounds__(256) void memory_frames_kernel(MemoryArgs m, MemDatasetArgs d) {
+    constexpr int E = FMT == GYMNET_STACK_BINARY_F32 ? 4 : 1;
+    const int32_t kept = m.ctl->kept;
+    const int64_t total = m.row_off[kept];
+    const int64_t lim = total < d.capacity_rows ? total : d.capacity_rows;
+    const int S = d.history;
+    const int64_t frame_px = (int64_t)d.out_w * d.out_h;
+    const int64_t total_waves = lim * S * d.waves_per_frame;
+    const int lid = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); w < total_waves; w += nwaves) {
+        const int64_t f = w / d.waves_per_frame, slice = w - f * d.waves_per_frame;
+        const int64_t row = f / S;
+        const int s = (int)(f - row * S);
+        const int64_t p0 = slice * kPixPerWave + (int64_t)lid * kPixPerThread;
+        if (p0 >= frame_px) continue;
+        const int r = find_rank(m.row_off, kept, row);
+        const MemEntry e = m.meta[m.scratch[r]];
+        const int64_t q = row - m.row_off[r] - (S - 1) + s;
+        const R *o = reinterpret_cast<const R *>(m.pool + ((int64_t)e.block * m.max_len + (q > 0 ? q : 0)) * m.row_bytes);
+        const Geo g = lane_geometry(o, 1, 0);
+        int i = (int)(p0 / d.out_w), j = (int)(p0 - (int64_t)i * d.out_w);
+        uint8_t *out = static_cast<uint8_t *>(d.x) + (f * frame_px + p0) * E;
+        const int cnt = frame_px - p0 < kPixPerThread ? (int)(frame_px - p0) : kPixPerThread;
+#pragma unroll 1
+        for (int v = 0; v < cnt; ++v) {
+            int nw, np;
+            shade(g, d.x0, d.sxq, d.y0, d.syq, i, j, nw, np);
+            const uint32_t val = stack_value<FMT>(nw, np);
+            if constexpr (E == 4) reinterpret_cast<uint32_t *>(out)[v] = val;
+            else out[v] = (uint8_t)val;
+            if (++j == d.out_w) { j = 0; ++i; }
+        }
+    }
+}
+
+unsigned grid_for(int64_t items, int64_t per_block, int64_t max_blocks) {
+    const int64_t b = (items + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : (b < max_blocks ? b : max_blocks));
+}
+
+template <class R>
+hipError_t launch_dataset_typed(const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st) {
+    hipLaunchKernelGGL(memory_rank_kernel, dim3(grid_for(m.capacity, 256, 1 << 20)), dim3(256), 0, st, m);
+    hipLaunchKernelGGL(memory_scan_kernel, dim3(1), dim3(1024), 0, st, m);
+    hipLaunchKernelGGL((memory_rows_kernel<R>), dim3(grid_for(d.capacity_rows, 256, 1 << 14)), dim3(256), 0, st, m, d);
+    if (d.format != 0 && d.x) {
+        const unsigned g = grid_for(d.capacity_rows * d.history * d.waves_per_frame, 4, 1 << 16);
+        if (d.format == GYMNET_STACK_GRAY8) hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_GRAY8>), dim3(g), dim3(256), 0, st, m, d);
+        else if (d.format == GYMNET_STACK_BINARY8) hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_BINARY8>), dim3(g), dim3(256), 0, st, m, d);
+        else hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_BINARY_F32>), dim3(g), dim3(256), 0, st, m, d);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_memory_init(const MemoryArgs &m, hipStream_t st) {
+    const int64_t items = m.capacity > 2 * (int64_t)m.push_blocks ? m.capacity : 2 * (int64_t)m.push_blocks;
+    hipLaunchKernelGGL(memory_init_kernel, dim3(grid_for(items, 256, INT32_MAX)), dim3(256), 0, st, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_memory_open(bool f64, const MemoryArgs &m, const void *obs, int64_t obs_stride, const uint8_t *mask, int64_t slot,
+                              hipStream_t st) {
+    const unsigned g = grid_for(m.n, 256, INT32_MAX);
+    if (f64) hipLaunchKernelGGL(memory_open_kernel<double>, dim3(g), dim3(256), 0, st, m, static_cast<const double *>(obs), obs_stride, mask, slot);
+    else hipLaunchKernelGGL(memory_open_kernel<float>, dim3(g), dim3(256), 0, st, m, static_cast<const float *>(obs), obs_stride, mask, slot);
+    return hipGetLastError();
+}
+
+hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &p, hipStream_t st) {
+    if (f64) {
+        hipLaunchKernelGGL(memory_push_kernel<double>, dim3(m.push_blocks), dim3(kPushBlock), 0, st, m, p);
+        hipLaunchKernelGGL(memory_merge_kernel<8>, dim3(1), dim3(kMergeBlock), 0, st, m, p.slot, p.end_tick);
+    } else {
+        hipLaunchKernelGGL(memory_push_kernel<float>, dim3(m.push_blocks), dim3(kPushBlock), 0, st, m, p);
+        hipLaunchKernelGGL(memory_merge_kernel<4>, dim3(1), dim3(kMergeBlock), 0, st, m, p.slot, p.end_tick);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_memory_dataset(bool f64, const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st) {
+    return f64 ? launch_dataset_typed<double>(m, d, st) : launch_dataset_typed<float>(m, d, st);
+}
+
+int32_t memory_push_blocks(int64_t n) { return (int32_t)((n + kPushBlock - 1) / kPushBlock); }
+
+}  // namespace gymnet

@@ -111,6 +111,13 @@ struct gymnet_vecenv {
     gymnet::StackArgs stack{};
     int32_t stack_format = 0;
     void *stack_alloc = nullptr;
+    // gymnet_vecenv_memory_*: the episode memory (mem.capacity == 0: none configured).  mem_pos counts its pushes (the ring slot of the
+    // next step is mem_pos % (max_len + 1)); mem_tick / mem_launches are the engine tick and step launches at its last config, reset or
+    // push, so a push can tell that exactly one vector step ran in between
+    gymnet::MemoryArgs mem{};
+    int32_t mem_history = 0;
+    uint64_t mem_pos = 0, mem_tick = 0, mem_launches = 0;
+    std::vector<void *> mem_allocs;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;

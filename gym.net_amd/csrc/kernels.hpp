@@ -247,6 +247,59 @@ struct StackArgs {
     float x0, y0, sxq, syq;                   // as RenderArgs
 };
 hipError_t launch_pixel_stack(bool f64, int32_t format, const StackArgs &a, hipStream_t st);
+// Episode memory (episode_memory.hip; contract: gymnet_vecenv_memory_config in include/gymnet_amd.h).  A kept episode's key is
+// (ret, tick, lane), ordered lexicographically; `block` is the pool block [L][row] that holds its steps.
+struct MemEntry { float ret; int32_t len; uint64_t tick; int32_t lane, block; };
+struct MemCand { float ret; int32_t len, lane, pad; };      // an episode that passed the push's admission filter
+struct MemCtl {
+    uint32_t cand_count;       // candidates of the most recent push (the merge consumes them and zeroes this)
+    int32_t kept;              // pool entries [0, kept) are live
+    int32_t full;              // kept == capacity: the push admits an ended episode only when ret >= thr
+    float thr;                 // the lowest kept return (valid when full)
+    uint64_t admitted;         // episodes the merges put into the pool
+    uint64_t rows;             // dataset rows of the most recent dataset build
+};
+struct MemoryArgs {
+    int64_t n;
+    int32_t obs_dim, esz;                      // observation values per step and their size (4 float, 8 double)
+    int32_t max_len, capacity;                 // L and K
+    // staging ring [L + 1 slots]: slot s at ring + s * slot_bytes holds obs [obs_dim][n] (esz each), action [n] (4 B), reward [n] (4 B)
+    uint8_t *ring; int64_t slot_bytes;
+    // pool: block b at pool + b * max_len * row_bytes, row p = obs [obs_dim] (esz each), action (4 B), reward (4 B)
+    uint8_t *pool; int64_t row_bytes;
+    int32_t *lane_len;                         // steps of the lane's open episode (-1: the lane is closed)
+    float *lane_ret;                           // float32 sum of its rewards in step order
+    MemCand *cand;                             // [n]
+    MemCtl *ctl;
+    MemEntry *meta, *meta_tmp;                 // [capacity] each: live entries, then free blocks
+    int32_t *scratch;                          // [capacity]: free blocks during a merge, the descending key order during a dataset build
+    int64_t *row_off;                          // [capacity + 1]: first dataset row of the episode of rank r
+    uint64_t *partials;                        // [push_blocks][2]: episodes ended / too long, per push workgroup
+    int32_t push_blocks;
+};
+struct MemPushArgs {
+    const void *obs; int64_t obs_stride;       // the CURRENT observation buffer (after the step)
+    const void *actions; const float *reward; const uint8_t *done;
+    int64_t slot;                              // ring slot of this step (pos % (L + 1)); the next step's is (pos + 1) % (L + 1)
+    uint64_t end_tick;                         // engine tick after the step: the key of the episodes that end in it
+    int32_t autoreset;
+};
+// format 0 = params rows, else GYMNET_STACK_* frames drawn as the pixel stack draws them
+struct MemDatasetArgs {
+    int32_t format, history;
+    void *x; int32_t *action; float *onehot; float *reward;
+    int64_t capacity_rows;
+    int32_t action_n;                          // one-hot width (0: Box actions, no one-hot)
+    int64_t waves_per_frame;
+    int32_t out_w, out_h;
+    float x0, y0, sxq, syq;                    // as RenderArgs
+};
+int32_t memory_push_blocks(int64_t n);                       // workgroups of a push launch (MemoryArgs.push_blocks)
+hipError_t launch_memory_init(const MemoryArgs &m, hipStream_t st);   // empty pool, zero counts
+hipError_t launch_memory_open(bool f64, const MemoryArgs &m, const void *obs, int64_t obs_stride, const uint8_t *mask, int64_t slot,
+                              hipStream_t st);
+hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &p, hipStream_t st);
+hipError_t launch_memory_dataset(bool f64, const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st);
 hipError_t launch_fill_i32(int32_t *p, int32_t v, int64_t n, hipStream_t st);
 // Gathers the sharded done list of one step (counter half `counts`) and the records written beside it into compact arrays
 // out_*[0 .. *out_count) (entries beyond out_capacity are dropped; the count is the true one), and / or applies the records to

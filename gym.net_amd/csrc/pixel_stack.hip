@@ -19,16 +19,6 @@ namespace gymnet {
 
 namespace {
 
-// what a pixel of the stack holds, from its shade() counts: the GRAY8 value of gymnet_vecenv_render_device, or 1 where that value is
-// below 255 (a sample that is not background), as a byte or as 1.0f
-template <int FMT>
-__device__ __forceinline__ uint32_t stack_value(int nw, int np) {
-    const uint32_t y = (uint32_t)(nw * 255 + np * 160 + 8) >> 4;
-    if constexpr (FMT == GYMNET_STACK_GRAY8) return y;
-    else if constexpr (FMT == GYMNET_STACK_BINARY8) return y < 255u ? 1u : 0u;
-    else return y < 255u ? 0x3f800000u : 0u;
-}
-
 __device__ __forceinline__ bool at16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // 16 pixels of E bytes in stream order: 4 * E dwords

@@ -383,6 +383,13 @@ class VectorEnv:
         dtype is adopted with lane_stride = its stride(0).  Replaces any stack this handle had.  CartPole only."""
         return PixelFrameStack(self, depth, size, crop, format, out)
 
+    def EpisodeMemory(self, capacity=100, max_length=0, history=4):
+        """The trainer's episode memory on the device (gymnet_vecenv_memory_config): every step of each lane's open episode, the best
+        `capacity` finished episodes by (return, end tick, lane) and the dataset built from them (ReplayMemory.cs:25-67,
+        DataBuilder.cs:25-55).  max_length 0 = the handle's max_episode_steps; history = steps per dataset row (MemoryStates).
+        Replaces any memory this handle had."""
+        return EpisodeMemory(self, capacity, max_length, history)
+
     def PackObsDevice(self, d_obs_rowmajor):
         capi.check(self._lib.gymnet_vecenv_pack_obs_device(self._h, _ptr(d_obs_rowmajor)))
 
@@ -665,6 +672,97 @@ class PixelFrameStack:
         if self._h is not None and self._env._h:
             capi.check(self._lib.gymnet_vecenv_pixel_stack_config(self._h, 0, 0, 0, 0, 0, 0, 0, 0, None, 0))
             self._env._pixel_stack = None
+        self._h = None
+
+
+class EpisodeMemory:
+    """The handle's episode memory (VectorEnv.EpisodeMemory).  Push / Step / Reset are ordered on the handle's stream and do not block;
+    Stats / Episodes / BuildDataset block."""
+    _FORMATS = {"params": (capi.MEMORY_PARAMS, "float32"), "gray8": (capi.STACK_GRAY8, "uint8"), "binary8": (capi.STACK_BINARY8, "uint8"),
+                "binary_f32": (capi.STACK_BINARY_F32, "float32")}
+
+    def __init__(self, env, capacity, max_length, history):
+        self._env, self._lib, self._h = env, env._lib, env._h
+        capi.check(self._lib.gymnet_vecenv_memory_config(self._h, int(capacity), int(max_length), int(history)))
+        prev = getattr(env, "_episode_memory", None)
+        if prev is not None:
+            prev._h = None                      # the handle holds one memory: the previous one is gone
+        env._episode_memory = self
+        self.Capacity, self.History = int(capacity), int(history)
+
+    def _handle(self):
+        if self._h is None or not self._env._h:
+            raise ValueError("this episode memory was replaced or closed")
+        return self._h
+
+    def Push(self, actions, done=None):
+        """Once after each single vector step: the actions that step took (device tensor / pointer) and, optionally, device done bytes
+        (None: the handle's own)."""
+        capi.check(self._lib.gymnet_vecenv_memory_push_device(self._handle(), _ptr(actions), _ptr(done)))
+
+    def Step(self, actions):
+        """StepDevice(actions) followed by Push(actions)."""
+        self._env.StepDevice(actions)
+        self.Push(actions)
+
+    def Reset(self, mask=None, clear=False):
+        """Lanes whose device mask byte is set (None: every lane) open a new episode from their current observation (after
+        ResetWhere(Device)); clear=True also empties the pool and zeroes the counters."""
+        capi.check(self._lib.gymnet_vecenv_memory_reset_device(self._handle(), _ptr(mask), 1 if clear else 0))
+
+    def Stats(self):
+        """dict kept / ended / admitted / too_long."""
+        v = [C.c_int64() for _ in range(4)]
+        capi.check(self._lib.gymnet_vecenv_memory_stats(self._handle(), *(C.byref(x) for x in v)))
+        return dict(zip(("kept", "ended", "admitted", "too_long"), (int(x.value) for x in v)))
+
+    def Episodes(self):
+        """The kept episodes in descending key order: numpy arrays (return float32, length int32, end_tick uint64, lane int32)."""
+        count = C.c_int64()
+        capi.check(self._lib.gymnet_vecenv_memory_episodes(self._handle(), None, None, None, None, 0, C.byref(count)))
+        k = int(count.value)
+        ret, ln, tick, lane = np.empty(k, np.float32), np.empty(k, np.int32), np.empty(k, np.uint64), np.empty(k, np.int32)
+        capi.check(self._lib.gymnet_vecenv_memory_episodes(self._handle(), _host(ret), _host(ln), _host(tick), _host(lane), k, C.byref(count)))
+        return ret, ln, tick, lane
+
+    def DatasetSize(self):
+        rows = C.c_int64()
+        capi.check(self._lib.gymnet_vecenv_memory_dataset_size(self._handle(), C.byref(rows)))
+        return int(rows.value)
+
+    def BuildDataset(self, format="params", size=(40, 20), crop=(200, 150, 200, 150), min_episodes=None, reward=False):
+        """DataBuilder.BuildDataset on the device: torch tensors (x, action, onehot) on the handle's device, or None while fewer than
+        min_episodes (default: the capacity) episodes are kept.  x is float32 [rows, history * obs_dim] for "params", else
+        [rows, history, h, w] frames ("gray8" / "binary8" uint8, "binary_f32" float32; CartPole only).  onehot is None for a Box
+        action.  reward=True appends the rewards (float32 [rows])."""
+        if format not in self._FORMATS:
+            raise ValueError(f"unknown dataset format {format!r} ({', '.join(self._FORMATS)})")
+        import torch
+        env = self._env
+        if env.Device is None:
+            raise ValueError("this handle's device is not known")
+        if self.Stats()["kept"] < (self.Capacity if min_episodes is None else int(min_episodes)):
+            return None
+        fmt, dt = self._FORMATS[format]
+        rows = self.DatasetSize()
+        dev = f"cuda:{env.Device}"
+        w, h = int(size[0]), int(size[1])
+        shape = (rows, self.History * env.ObsDim) if fmt == capi.MEMORY_PARAMS else (rows, self.History, h, w)
+        x = torch.empty(shape, dtype=getattr(torch, dt), device=dev)
+        action = torch.empty(rows, dtype=torch.float32 if isinstance(env.ActionSpace, Box) else torch.int32, device=dev)
+        onehot = None if isinstance(env.ActionSpace, Box) else torch.empty((rows, env.ActionSpace.N), dtype=torch.float32, device=dev)
+        rew = torch.empty(rows, dtype=torch.float32, device=dev) if reward else None
+        cx, cy, cw, ch = (int(v) for v in crop)
+        capi.check(self._lib.gymnet_vecenv_memory_dataset_device(self._handle(), fmt, cx, cy, cw, ch, w, h, _ptr(x), _ptr(action),
+                                                                 _ptr(onehot), _ptr(rew), rows))
+        env.Sync()
+        return (x, action, onehot, rew) if reward else (x, action, onehot)
+
+    def Close(self):
+        """Releases the memory."""
+        if self._h is not None and self._env._h:
+            capi.check(self._lib.gymnet_vecenv_memory_config(self._h, 0, 0, 0))
+            self._env._episode_memory = None
         self._h = None
 
 

@@ -483,6 +483,64 @@ int gymnet_vecenv_pixel_stack_push_device(gymnet_vecenv *h, const uint8_t *d_don
 int gymnet_vecenv_pixel_stack_view(gymnet_vecenv *h, void **d_stack, int64_t *lane_stride, int64_t *frame_bytes);
 int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_lane, int64_t count);
 
+/* ---- episode memory (the trainer's ReplayMemory.Memorize / EndEpisode, MemoryTypes/ReplayMemory.cs:25-67, and DataBuilder.BuildDataset,
+ * DataBuilders/DataBuilder.cs:25-55) ------------------------------------------------------------------------------------------------
+ * The handle owns at most one episode memory, kept on the device.  K = capacity (episodes kept), L = max_length (steps an episode may
+ * have to be kept), S = history (steps per dataset row).
+ * Transitions: step p of a lane's open episode stores the observation BEFORE the step (o_p), the action taken (int32 for Discrete,
+ *   float32 for Box; the 4 bytes of d_actions[lane]) and the float32 reward.  o_0 is the observation the episode started from: the
+ *   current observation at config or memory reset, or the post-step observation after an auto-reset.
+ * Episode end: a push ends a lane's episode when its done byte is non-zero (either bit: a max_episode_steps truncation counts).  On a
+ *   GYMNET_FLAG_AUTORESET handle the same push opens the next episode from the post-step observation; without AUTORESET the lane stays
+ *   closed (its pushes record nothing) until memory_reset_device opens it.  The return is the float32 sum of the rewards in step order:
+ *   bit-identical to the EPISODE_STATS finished return when the handle keeps one (the memory does not need that flag).
+ * Keeping the best K: an ended episode's key is (return, end_tick, lane), ordered lexicographically, where end_tick is the engine tick
+ *   after the step that ended it.  After every push the kept set is the top K keys of (kept set + the episodes that ended in that push).
+ *   That is the reference's rule applied to episodes in (tick, lane) order — add when fewer than K are kept or return >= the lowest kept,
+ *   then drop the lowest — with a newer episode winning ties of return.  An episode longer than L is not kept, in part or whole: it is
+ *   counted as too_long.
+ * Dataset: the kept episodes in descending key order; from each the first floor(len * 2 / 3) steps (DataBuilder.cs:33); one row per
+ *   step: x, the action, for Discrete the one-hot of the action (float32 [action_n]) and the reward.
+ *   GYMNET_MEMORY_PARAMS: x = float32 [S * obs_dim] = o_{p-S+1} .. o_p, oldest first, indices below 0 clamped to o_0 (float64
+ *     observations rounded to float32).
+ *   GYMNET_STACK_GRAY8 / _BINARY8 / _BINARY_F32 (CartPole only): x = [S][out_h][out_w] bytes (floats for BINARY_F32): the frames a
+ *     pixel stack of the same format, crop, size and depth S held when the action was chosen, re-rendered from the stored observations.
+ * Memory: (L + 1) * num_envs * row + K * L * row bytes, row = obs_dim * (4, or 8 for GYMNET_FLAG_F64) + 8, plus about 40 bytes per lane
+ *   and 60 per kept episode: 12.6 GB for 2^20 CartPole float32 lanes with L = 500.
+ * config: capacity 0 releases the memory (the other arguments are then not looked at); else K in [1, 65536], history in [1, 64],
+ *   max_length in [1, 2^24] or 0 for the handle's max_episode_steps (which must then be > 0).  Replaces any memory the handle had,
+ *   with an empty pool, and opens every lane from its current observation.
+ * reset_device: lanes with d_mask[lane] != 0 (NULL: every lane) abandon their partial episode and open one from their current
+ *   observation (call it after gymnet_vecenv_reset(_device) / _reset_where(_device)); clear_pool != 0 also empties the pool and zeroes
+ *   the counters.
+ * push_device: once after each single vector step; d_actions are the actions that step took (device, [num_envs] of 4 bytes), d_done
+ *   NULL means the handle's own done bytes.  Refused unless exactly one vector step ran since the last config, memory reset or push
+ *   (a missed push, a multi-step rollout, or a reset of the handle without a memory reset in between).
+ * stats: kept episodes, episodes ended, episodes admitted into the kept set, episodes too long (any pointer may be NULL).  Blocks.
+ * episodes: the kept episodes in descending key order, at most `capacity` of them (any array may be NULL); *count = how many are kept.
+ *   Blocks.
+ * dataset_size: the rows a dataset build writes now.  Blocks.
+ * dataset_device: writes rows [0, min(rows, capacity_rows)) of the dataset: d_x ([rows][S * obs_dim] float32, or [rows][S][out_h][out_w]
+ *   elements; crop and size follow gymnet_vecenv_render_device and are not looked at for GYMNET_MEMORY_PARAMS), d_action [rows],
+ *   d_onehot [rows][action_n], d_reward [rows]; any of them may be NULL.
+ * Everything but stats, episodes and dataset_size is ordered on the handle's stream and does not block; none of the calls changes state,
+ *   observations, tick, counters, the Philox stream or the done bytes.  The memory is not part of a checkpoint.
+ * Errors (nothing written): GYMNET_ERR_INVALID_ARG for arguments outside the ranges above, calls before a memory is configured, a null
+ *   d_actions or a refused push, an unknown dataset format, a d_onehot on a Box env, a BINARY_F32 d_x that is not 4-byte aligned, a
+ *   negative capacity; GYMNET_ERR_UNSUPPORTED for a pixel dataset on an env other than CartPole; GYMNET_ERR_OOM when the memory cannot
+ *   be allocated (the previous memory stays). */
+enum { GYMNET_MEMORY_PARAMS = 0 };
+int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history);
+int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, int32_t clear_pool);
+int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, const uint8_t *d_done);
+int gymnet_vecenv_memory_stats(gymnet_vecenv *h, int64_t *kept, int64_t *ended, int64_t *admitted, int64_t *too_long);
+int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, uint64_t *end_tick, int32_t *lane, int64_t capacity,
+                                  int64_t *count);
+int gymnet_vecenv_memory_dataset_size(gymnet_vecenv *h, int64_t *rows);
+int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                                        int32_t out_w, int32_t out_h, void *d_x, int32_t *d_action, float *d_onehot, float *d_reward,
+                                        int64_t capacity_rows);
+
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */
 int gymnet_vecenv_done_lanes(gymnet_vecenv *h, int32_t *lanes_out, int64_t capacity, int64_t *count);

@@ -307,6 +307,43 @@ public:
         check(gymnet_vecenv_pixel_stack_read(h_, out.data(), first, count));
         return out;
     }
+    // The episode memory (gymnet_vecenv_memory_config): every step of each lane's open episode, the best `capacity` finished episodes
+    // by (return, end tick, lane) and the dataset built from them.  max_length 0 = the handle's max_episode_steps.
+    void ConfigureEpisodeMemory(int32_t capacity = 100, int32_t max_length = 0, int32_t history = 4) {
+        check(gymnet_vecenv_memory_config(h_, capacity, max_length, history));
+    }
+    void PushEpisodeMemory(const void *d_actions, const uint8_t *d_done = nullptr) { check(gymnet_vecenv_memory_push_device(h_, d_actions, d_done)); }
+    void ResetEpisodeMemory(const uint8_t *d_mask = nullptr, bool clear_pool = false) {
+        check(gymnet_vecenv_memory_reset_device(h_, d_mask, clear_pool ? 1 : 0));
+    }
+    struct MemoryStats { int64_t kept, ended, admitted, too_long; };
+    MemoryStats EpisodeMemoryStats() const {
+        MemoryStats s{};
+        check(gymnet_vecenv_memory_stats(h_, &s.kept, &s.ended, &s.admitted, &s.too_long));
+        return s;
+    }
+    struct MemoryEpisodes { std::vector<float> ret; std::vector<int32_t> len; std::vector<uint64_t> end_tick; std::vector<int32_t> lane; };
+    /// the kept episodes in descending key order (blocks)
+    MemoryEpisodes ReadMemoryEpisodes() const {
+        int64_t count = 0;
+        check(gymnet_vecenv_memory_episodes(h_, nullptr, nullptr, nullptr, nullptr, 0, &count));
+        MemoryEpisodes e;
+        e.ret.resize((size_t)count); e.len.resize((size_t)count); e.end_tick.resize((size_t)count); e.lane.resize((size_t)count);
+        check(gymnet_vecenv_memory_episodes(h_, e.ret.data(), e.len.data(), e.end_tick.data(), e.lane.data(), count, &count));
+        return e;
+    }
+    int64_t MemoryDatasetRows() const { int64_t r = 0; check(gymnet_vecenv_memory_dataset_size(h_, &r)); return r; }
+    /// DataBuilder.BuildDataset into device buffers of at least capacity_rows rows (format GYMNET_MEMORY_PARAMS or GYMNET_STACK_*);
+    /// returns the rows written, or -1 while fewer than min_episodes episodes are kept
+    int64_t BuildMemoryDataset(void *d_x, int32_t *d_action, float *d_onehot, int64_t capacity_rows, int64_t min_episodes,
+                               int32_t format = GYMNET_MEMORY_PARAMS, int32_t out_w = 40, int32_t out_h = 20, int32_t crop_x = 200,
+                               int32_t crop_y = 150, int32_t crop_w = 200, int32_t crop_h = 150) {
+        if (EpisodeMemoryStats().kept < min_episodes) return -1;
+        const int64_t rows = MemoryDatasetRows();
+        check(gymnet_vecenv_memory_dataset_device(h_, format, crop_x, crop_y, crop_w, crop_h, out_w, out_h, d_x, d_action, d_onehot, nullptr,
+                                                  capacity_rows));
+        return rows < capacity_rows ? rows : capacity_rows;
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:

@@ -1,0 +1,121 @@
+"""A NumPy restatement of the episode memory contract (include/gymnet_amd.h, gymnet_vecenv_memory_*): the reference's sequential
+EndEpisode rule under the key order (return, end_tick, lane), the top-K-per-push form the device computes, and a whole memory fed with
+what the step API returned (observations after the step, actions, rewards, done bytes) that yields the kept set and the dataset.
+
+The model mirrors the device's bookkeeping: `obs[t]` is the observation stored for history index t (one index per push, plus the one
+open at config), lane k's open episode started at index start[k], and a memory reset overwrites the pending index of the masked lanes."""
+import numpy as np
+
+
+def key(e):
+    """The total order of kept episodes: (return, end_tick, lane); a later tick, then a higher lane, is newer and wins ties."""
+    return (float(e["ret"]), int(e["tick"]), int(e["lane"]))
+
+
+def end_episode_sequential(pool, episode, capacity):
+    """ReplayMemory.EndEpisode (MemoryTypes/ReplayMemory.cs:53-67) for ONE episode: add it when fewer than `capacity` are kept or its
+    return is >= the lowest kept, then drop the lowest (by key) while more than `capacity` are kept."""
+    if len(pool) < capacity or float(episode["ret"]) >= min(float(e["ret"]) for e in pool):
+        pool = pool + [episode]
+    while len(pool) > capacity:
+        low = min(range(len(pool)), key=lambda i: key(pool[i]))
+        pool = pool[:low] + pool[low + 1:]
+    return pool
+
+
+def top_k_per_push(pool, ended, capacity):
+    """What the device keeps after a push: the top `capacity` keys of (kept set + episodes that ended in that push)."""
+    return sorted(pool + list(ended), key=key, reverse=True)[:capacity]
+
+
+class EpisodeMemoryModel:
+    def __init__(self, obs0, capacity, max_length, history, autoreset=True):
+        """obs0: [N, D] observations at config; every lane opens an episode from its own."""
+        obs0 = np.asarray(obs0)
+        self.n, self.d = obs0.shape
+        self.capacity, self.max_length, self.history, self.autoreset = int(capacity), int(max_length), int(history), bool(autoreset)
+        self.obs, self.act, self.rew = [obs0.copy()], [], []
+        self.start = np.zeros(self.n, np.int64)
+        self.length = np.zeros(self.n, np.int64)
+        self.ret = np.zeros(self.n, np.float32)
+        self.open = np.ones(self.n, bool)
+        self.pool = []
+        self.ended = self.admitted = self.too_long = 0
+
+    def reset(self, obs, mask=None, clear=False):
+        """memory_reset_device: masked lanes (all for None) open a new episode from `obs` at the pending history index."""
+        sel = np.ones(self.n, bool) if mask is None else np.asarray(mask) != 0
+        self.obs[-1] = self.obs[-1].copy()
+        self.obs[-1][sel] = np.asarray(obs)[sel]
+        t = len(self.obs) - 1
+        self.start[sel], self.length[sel], self.ret[sel], self.open[sel] = t, 0, np.float32(0), True
+        if clear:
+            self.pool = []
+            self.ended = self.admitted = self.too_long = 0
+
+    def push(self, actions, rewards, done, obs_after, end_tick):
+        """One push after one vector step: actions [N], float32 rewards [N], done bytes [N], observations after the step [N, D] and the
+        engine tick after the step.  Returns the episodes that ended in it."""
+        t = len(self.obs) - 1
+        self.act.append(np.asarray(actions).copy())
+        self.rew.append(np.asarray(rewards, np.float32).copy())
+        nxt = np.asarray(obs_after).copy()
+        done = np.asarray(done) != 0
+        live = self.open.copy()
+        self.ret[live] = (self.ret[live] + self.rew[-1][live]).astype(np.float32)
+        self.length[live] += 1
+        ended = []
+        for k in np.flatnonzero(live & done):
+            self.ended += 1
+            if self.length[k] > self.max_length:
+                self.too_long += 1
+                continue
+            ended.append({"ret": np.float32(self.ret[k]), "len": int(self.length[k]), "tick": int(end_tick), "lane": int(k),
+                          "start": int(self.start[k])})
+        fin = live & done
+        if self.autoreset:
+            self.start[fin], self.length[fin], self.ret[fin] = t + 1, 0, np.float32(0)
+        else:
+            self.open[fin] = False
+        self.obs.append(nxt)
+        before = {id(e) for e in self.pool}
+        self.pool = top_k_per_push(self.pool, ended, self.capacity)
+        self.admitted += sum(1 for e in self.pool if id(e) not in before)
+        return ended
+
+    def kept(self):
+        """The kept set in descending key order: (return float32, length, end_tick, lane) arrays."""
+        p = sorted(self.pool, key=key, reverse=True)
+        return (np.array([e["ret"] for e in p], np.float32), np.array([e["len"] for e in p], np.int32),
+                np.array([e["tick"] for e in p], np.uint64), np.array([e["lane"] for e in p], np.int32))
+
+    def steps(self, e):
+        """The stored steps of a kept episode: obs [len, D], actions [len], rewards [len]."""
+        idx = e["start"] + np.arange(e["len"])
+        return (np.stack([self.obs[i][e["lane"]] for i in idx]), np.array([self.act[i][e["lane"]] for i in idx]),
+                np.array([self.rew[i][e["lane"]] for i in idx], np.float32))
+
+    def dataset_rows(self):
+        """(episode, step p, history indices of o_{p-S+1} .. o_p clamped to o_0) of every dataset row, in order (DataBuilder.cs:25-55)."""
+        rows = []
+        for e in sorted(self.pool, key=key, reverse=True):
+            for p in range(e["len"] * 2 // 3):
+                hist = [e["start"] + max(p - (self.history - 1) + s, 0) for s in range(self.history)]
+                rows.append((e, p, hist))
+        return rows
+
+    def dataset_params(self, action_n=None):
+        """x float32 [rows, S * D], actions [rows], one-hot float32 [rows, action_n] (None for Box), rewards float32 [rows]."""
+        rows = self.dataset_rows()
+        x = np.zeros((len(rows), self.history * self.d), np.float32)
+        a = np.zeros(len(rows), self.act[0].dtype if self.act else np.int32)
+        r = np.zeros(len(rows), np.float32)
+        for i, (e, p, hist) in enumerate(rows):
+            x[i] = np.concatenate([self.obs[h][e["lane"]] for h in hist]).astype(np.float32)
+            a[i] = self.act[e["start"] + p][e["lane"]]
+            r[i] = self.rew[e["start"] + p][e["lane"]]
+        onehot = None
+        if action_n:
+            onehot = np.zeros((len(rows), action_n), np.float32)
+            onehot[np.arange(len(rows)), a.astype(np.int64)] = 1.0
+        return x, a, onehot, r
