@@ -14,10 +14,10 @@ from .errors import (AlreadySteppingError, GymNetError, InvalidActionError, NoDe
 from .sharding import ShardPlan, ShardedVectorEnv
 from .spaces import Box, Discrete, Space
 from .step import Step
-from .vector_env import (AcrobotEnv, BatchStep, CartPoleEnv, DummyVecEnv, GpuEnv, GroupVectorEnv, MountainCarContinuousEnv, MountainCarEnv,
+from .vector_env import (AcrobotEnv, Actor, BatchStep, CartPoleEnv, DummyVecEnv, GpuEnv, GroupVectorEnv, MountainCarContinuousEnv, MountainCarEnv,
                          EpisodeMemory, PendingStep, PendulumEnv, PixelFrameStack, VectorEnv)
 
-__all__ = ["VectorEnv", "PixelFrameStack", "EpisodeMemory", "GroupVectorEnv", "DummyVecEnv", "BatchStep", "PendingStep", "GpuEnv", "CartPoleEnv", "PendulumEnv", "MountainCarEnv",
+__all__ = ["VectorEnv", "PixelFrameStack", "EpisodeMemory", "Actor", "GroupVectorEnv", "DummyVecEnv", "BatchStep", "PendingStep", "GpuEnv", "CartPoleEnv", "PendulumEnv", "MountainCarEnv",
            "AcrobotEnv", "MountainCarContinuousEnv", "Space", "Box", "Discrete", "Step", "InvalidActionError", "AlreadySteppingError",
            "NotSteppingError", "GymNetError", "NoDeviceError", "ShardPlan", "ShardedVectorEnv", "device_count",
            "env_describe", "load_library", "LIB_PATH", "ENV_IDS"]

@@ -104,7 +104,7 @@ class RolloutBuffers(C.Structure):
     _fields_ = [("d_obs", C.c_void_p), ("d_reward", C.c_void_p), ("d_done", C.c_void_p)]
 
 
-ACTIONS_RING, ACTIONS_SAMPLE, ACTIONS_EPSILON_GREEDY = 0, 1, 2
+ACTIONS_RING, ACTIONS_SAMPLE, ACTIONS_EPSILON_GREEDY, ACTIONS_ACTOR = 0, 1, 2, 3
 
 
 class RolloutSpec(C.Structure):
@@ -183,6 +183,12 @@ PROTOTYPES = {
     "gymnet_vecenv_memory_dataset_size": (C.c_int, [_H, C.POINTER(C.c_int64)]),
     "gymnet_vecenv_memory_dataset_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                      _P, _P, _P, _P, C.c_int64]),
+    "gymnet_vecenv_actor_config": (C.c_int, [_H, C.c_int32, C.c_int32, _P, _P, C.c_int64]),
+    "gymnet_vecenv_actor_load_device": (C.c_int, [_H, _P, C.c_int64]),
+    "gymnet_vecenv_actor_reset_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_actor_push_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_actor_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
+    "gymnet_vecenv_actor_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

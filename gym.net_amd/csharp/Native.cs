@@ -85,6 +85,8 @@ namespace Gym.Envs.Amd {
 
     /// gymnet_rollout_spec.record_flags: NoOverflow = the 8 % faster records variant that may drop records of very unevenly finishing lanes
     public static class GymnetRecordFlags { public const int None = 0, NoOverflow = 1; }
+    /// gymnet_rollout_spec.action_source; GYMNET_ACTIONS_ACTOR: the handle's actor chooses every step's action inside the kernel
+    public static class GymnetActionSource { public const int GYMNET_ACTIONS_RING = 0, GYMNET_ACTIONS_SAMPLE = 1, GYMNET_ACTIONS_EPSILON_GREEDY = 2, GYMNET_ACTIONS_ACTOR = 3; }
     /// gymnet_vecenv_rollout_fused_ex_device (ABI 5): action source (0 ring, 1 ActionSpace.Sample() drawn in the kernel, 2 epsilon-greedy
     /// over the ring as the policy's actions), dense recording, and the compact records of the episodes that end during the rollout.
     [StructLayout(LayoutKind.Sequential)]
@@ -177,6 +179,13 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_dataset_device(IntPtr h, int format, int crop_x, int crop_y, int crop_w, int crop_h,
                                                                                      int out_w, int out_h, IntPtr d_x, IntPtr d_action, IntPtr d_onehot,
                                                                                      IntPtr d_reward, long capacity_rows);
+        // the actor: a fully connected ReLU network on the device that chooses every lane's action from its observation history
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_load_device(IntPtr h, IntPtr d_weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_reset_device(IntPtr h, IntPtr d_mask);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_push_device(IntPtr h, IntPtr d_done);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, float epsilon, ulong seed, ulong tick);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_view(IntPtr h, out IntPtr d_history, out long lane_stride, out int slot);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

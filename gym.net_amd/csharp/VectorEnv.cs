@@ -272,6 +272,26 @@ namespace Gym.Envs.Amd {
             return rows;
         }
 
+        /// The actor (gymnet_vecenv_actor_config): a fully connected ReLU network on the device that replaces ComposeAction ->
+        /// Trainer.Predict -> _network.Forward + IndexOf(Max()) (BasePlaySession.cs:78-81, Trainer.cs:91-92) for every lane, from its last
+        /// `history` observations.  widths = w_0 .. w_L (w_0 = history * obs_dim, w_L = action_n); weights = per layer W [out][in] row-major,
+        /// then b [out].  NeuralNetworkNET's fully connected weights must be handed over in this [out][in] layout.  No layers releases it.
+        public void ConfigureActor(int history, int[] widths, float[] weights) {
+            if (widths == null || widths.Length == 0) { Native.Check(Native.gymnet_vecenv_actor_config(_h, 0, 0, null, null, 0)); return; }
+            fixed (int* pw = widths) fixed (float* pv = weights)
+                Native.Check(Native.gymnet_vecenv_actor_config(_h, history, widths.Length - 1, pw, pv, weights.LongLength));
+        }
+        /// New device weights of the same widths, ordered on the handle's stream; the history is kept.
+        public void LoadActorWeights(IntPtr dWeights, long count) => Native.Check(Native.gymnet_vecenv_actor_load_device(_h, dWeights, count));
+        /// After ResetDevice / a masked reset: the masked lanes (IntPtr.Zero: every lane) fill their history with the current observation.
+        public void ResetActor(IntPtr dMask = default) => Native.Check(Native.gymnet_vecenv_actor_reset_device(_h, dMask));
+        /// Once after each single StepDevice: dDone IntPtr.Zero = the handle's own done bytes.
+        public void PushActor(IntPtr dDone = default) => Native.Check(Native.gymnet_vecenv_actor_push_device(_h, dDone));
+        /// Every lane's action into dActions (int [N]): argmax of the logits, epsilon-greedy as ComposeActionsDevice would compose it
+        /// (TrainingPlaySession.cs:46-52; epsilon 0 = TestingPlaySession); dLogits float [N][action_n] or IntPtr.Zero.
+        public void ActorAct(IntPtr dActions, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dLogits = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_act_device(_h, dActions, dLogits, epsilon, seed, tick));
+
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));
         public void RolloutFused(GymnetRolloutSpec spec) {

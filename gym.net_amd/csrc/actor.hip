@@ -1,0 +1,465 @@
+// actor.hip — the on-device actor: a small fully connected ReLU network, given by the caller, that chooses every lane's action from
+// the lane's observation history (the trainer's BasePlaySession.ComposeAction -> Trainer.Predict -> _network.Forward, PlaySessions/
+// BasePlaySession.cs:78-81, Trainer.cs:91-92, and TrainingPlaySession.cs:46-52's epsilon-greedy wrapper), in the single-step path and
+// inside a fused rollout.  The contract is gymnet_vecenv_actor_config and its siblings in include/gymnet_amd.h; tests/_actor_twin.py
+// restates it with an exact fmaf.  Written for gfx950 (wave64); compiled with -ffp-contract=off, so every multiply-add below is an
+// explicit __builtin_fmaf.
+//
+// Forward (VALU form, docs/ledger.md §actor).  One env lane per thread.  The activations of a layer live in VGPRs (x[64], zero beyond the
+// layer's width), the weights are wave-uniform and come through the scalar cache: the packed weight block (actor_pack_kernel) is read
+// through an address-space-4 pointer, so each chunk of 4 neurons x 8 inputs is two s_load_dwordx16 and each multiply-add is one
+// v_fma_f32 with an SGPR operand.  Neurons go four at a time (four independent fmaf chains per thread), inputs in chunks of eight; a
+// wave-uniform branch skips the chunks and groups beyond the layer's real widths, and zero padding inside the last chunk / group only
+// adds fmaf(0, 0, acc) terms after the real ones (exact, but for the sign of a zero sum).
+//
+// History.  float32 SoA [S][obs_dim][stride], a ring: every lane pushes together, so the newest observation goes to slot (slot + 1) % S
+// for every lane and a push writes one observation per lane; a restarting lane (done byte set, or a masked reset) writes its
+// observation into every slot.  Input row s (oldest first) of the network is ring slot (slot + 1 + s) % S.
+//
+// Fused rollout (actor_rollout_kernel).  The env's step, fused reset, bookkeeping and episode records of step_kernels.hpp's
+// rollout_body, one lane per thread, with the action of step t chosen in the kernel from the history the kernel itself keeps current in
+// memory: bit-identical to steps x (act, step, push).  This unit instantiates its own kernels; the env_*.hip units are untouched.
+#include "step_kernels.hpp"
+
+#include "envs.hpp"
+#include "../../include/gymnet_amd.h"
+
+namespace gymnet {
+
+namespace {
+
+typedef __attribute__((address_space(4))) const float cfloat;   // scalar-cache (constant address space) view of the weights
+
+constexpr int kW = kActorMaxWidth;
+
+// Layer l of the packed block: ceil(wout / 4) groups of [4 biases | ceil(win / 8) chunks of [4 rows][8 inputs]], zeros where a row or
+// an input does not exist.
+__host__ __device__ __forceinline__ int64_t group_floats(int32_t win) { return 4 + 32 * (int64_t)((win + 7) >> 3); }
+
+// x: the input layer's activations, +0 beyond net.win[0]; on return x[0 .. action_n) are the logits
+__device__ __forceinline__ void actor_forward(const ActorNet &net, float (&x)[kW]) {
+    for (int l = 0; l < net.layers; ++l) {                                   // wave-uniform
+        const int32_t win = net.win[l], wout = net.wout[l];
+        const int32_t nch = (win + 7) >> 3;
+        const bool hidden = l + 1 < net.layers;
+        const int64_t gf = group_floats(win);
+        cfloat *wl = (cfloat *)(net.w + net.off[l]);
+        float y[kW];
+#pragma unroll
+        for (int g = 0; g < kW / 4; ++g) {
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (4 * g < wout) {                                              // wave-uniform
+                cfloat *blk = wl + g * gf;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) acc[jj] = blk[jj];
+#pragma unroll
+                for (int c = 0; c < kW / 8; ++c) {
+                    if (c < nch) {                                           // wave-uniform
+                        cfloat *ch = blk + 4 + 32 * c;
+#pragma unroll
+                        for (int ii = 0; ii < 8; ++ii) {
+#pragma unroll
+                            for (int jj = 0; jj < 4; ++jj) acc[jj] = __builtin_fmaf(ch[jj * 8 + ii], x[8 * c + ii], acc[jj]);
+                        }
+                    }
+                }
+                if (hidden) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) acc[jj] = acc[jj] > 0.0f ? acc[jj] : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) y[4 * g + jj] = acc[jj];
+        }
+#pragma unroll
+        for (int i = 0; i < kW; ++i) x[i] = y[i];
+    }
+}
+
+// the network input of lane i: ring slots oldest first, O values each (O compile-time, so x's indices are)
+template <int O>
+__device__ __forceinline__ void load_input(const ActorHist &hs, int32_t newest, int64_t i, float (&x)[kW]) {
+#pragma unroll
+    for (int s = 0; s < kW / O; ++s) {
+        int32_t row = 0;
+        if (s < hs.history) {                                                // wave-uniform
+            row = newest + 1 + s;
+            row = row >= hs.history ? row - hs.history : row;
+            row = row >= hs.history ? row - hs.history : row;
+        }
+#pragma unroll
+        for (int k = 0; k < O; ++k) x[s * O + k] = s < hs.history ? hs.hist[((int64_t)row * O + k) * hs.stride + i] : 0.0f;
+    }
+#pragma unroll
+    for (int i2 = (kW / O) * O; i2 < kW; ++i2) x[i2] = 0.0f;
+}
+
+// first index of the largest logit (moves only on a strictly greater value)
+__device__ __forceinline__ int32_t argmax_logits(const float (&x)[kW], int32_t action_n) {
+    int32_t best = 0;
+    float bv = x[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+        if (j < action_n && x[j] > bv) { bv = x[j]; best = j; }
+    }
+    return best;
+}
+
+// gymnet_vecenv_compose_actions_device's choice for one lane: word B of the aux stream is the coin, word A of the action stream the
+// sampled action (compose_discrete_kernel); the action word is drawn only when some lane of the wave explores
+__device__ __forceinline__ int32_t compose_one(int32_t greedy, int32_t action_n, uint32_t explore_at_or_below, uint64_t seed, uint64_t gl,
+                                               uint64_t tick) {
+    const bool explore = aux_word<true>(seed, gl, tick) <= explore_at_or_below;
+    int32_t act = greedy;
+    if (__ballot(explore)) {
+        const int32_t drawn = (int32_t)__umulhi(action_word<true>(seed, gl, tick), (uint32_t)action_n);
+        act = explore ? drawn : greedy;
+    }
+    return act;
+}
+
+}  // namespace
+
+template <int O>
+__global__ __launch_bounds__(256) void actor_act_kernel(const ActorNet net, const ActorHist hs, int32_t *__restrict__ actions,
+                                                        float *__restrict__ logits, const ActorAct aa) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hs.n) return;
+    float x[kW];
+    load_input<O>(hs, hs.slot, i, x);
+    actor_forward(net, x);
+    if (logits) {
+        for (int j = 0; j < net.action_n; ++j) {                               // (action_n <= 8: the Discrete envs' spaces)
+            float v = x[0];
+#pragma unroll
+            for (int q = 1; q < 8; ++q) v = q == j ? x[q] : v;
+            logits[i * net.action_n + j] = v;
+        }
+    }
+    const int32_t greedy = argmax_logits(x, net.action_n);
+    actions[i] = compose_one(greedy, net.action_n, coin_threshold(aa.epsilon), aa.seed, aa.lane_offset + (uint64_t)i, aa.tick);
+}
+
+// push (restart = done bytes; lanes without one write the new slot only) or fill (restart = mask, NULL: every lane; lanes without one
+// are not touched)
+template <class R, int O>
+__global__ __launch_bounds__(256) void actor_push_kernel(const ActorHist hs, const R *__restrict__ obs, int64_t obs_stride,
+                                                         const uint8_t *__restrict__ restart, int32_t push) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hs.n) return;
+    const bool all = restart ? restart[i] != 0 : !push;
+    if (!push && !all) return;
+    // the observation is loaded once, before any store (the history is not declared apart from it, so a load after a store of the
+    // ring would be issued again behind that store)
+    float v[O];
+#pragma unroll
+    for (int k = 0; k < O; ++k) v[k] = (float)obs[k * obs_stride + i];
+    float *__restrict__ h = hs.hist + i;
+    if (!all) {                                       // the common case: one slot
+#pragma unroll
+        for (int k = 0; k < O; ++k) h[((int64_t)hs.slot * O + k) * hs.stride] = v[k];
+        return;
+    }
+    for (int sl = 0; sl < hs.history; ++sl) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) h[((int64_t)sl * O + k) * hs.stride] = v[k];
+    }
+}
+
+// flat torch layout (per layer W [wout][win] row-major, then b [wout]) -> the packed block actor_forward reads
+__global__ __launch_bounds__(256) void actor_pack_kernel(const ActorNet net, const float *__restrict__ flat, float *__restrict__ packed,
+                                                         int64_t packed_count) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= packed_count) return;
+    int64_t fo = 0;
+    float v = 0.0f;
+    for (int l = 0; l < net.layers; ++l) {
+        const int32_t win = net.win[l], wout = net.wout[l];
+        const int64_t gf = group_floats(win);
+        const int64_t end = net.off[l] + (int64_t)((wout + 3) >> 2) * gf;
+        if (p >= net.off[l] && p < end) {
+            const int64_t q = p - net.off[l];
+            const int64_t g = q / gf, r = q % gf;
+            if (r < 4) {
+                const int64_t j = 4 * g + r;
+                if (j < wout) v = flat[fo + (int64_t)wout * win + j];
+            } else {
+                const int64_t c = (r - 4) / 32, e = (r - 4) % 32;
+                const int64_t j = 4 * g + e / 8, in = 8 * c + e % 8;
+                if (j < wout && in < win) v = flat[fo + j * win + in];
+            }
+        }
+        fo += (int64_t)wout * win + wout;
+    }
+    packed[p] = v;
+}
+
+// ---- the fused rollout with the actor choosing the actions -------------------------------------------------------------------------
+// rollout_body's step (step_kernels.hpp) with VEC = 1; RECORDS: the rollout keeps compact episode records, with the overflow segment.
+// KEEP IN STEP with step_kernels.hpp rollout_body: the step, the EXTRAS bookkeeping (truncation, dense views, final observations), the
+// record staging and flush_stage's overflow spill are restated here for one lane per thread; a change to either must be made to both
+// (tests/test_gpu_actor.py compares this kernel with single steps, which run the step kernels' bookkeeping).
+template <class Env, bool AUTORESET, bool EXTRAS, bool RECORDS>
+__global__ __launch_bounds__(256) void actor_rollout_kernel(const StepArgs a, const RolloutArgs ro, const ActorNet net, const ActorHist hs) {
+    constexpr int S = Env::S, O = Env::O;
+    constexpr bool RESETF = Env::OBS_ALIASES_STATE;                      // the wave-compacted reset where the env has it
+    using Real = float;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    ResetScratch<Env> *sc = nullptr;
+    if constexpr (AUTORESET && RESETF) {
+        __shared__ ResetScratch<Env> scratch[256 / 64];
+        sc = &scratch[threadIdx.x >> 6];
+    }
+    EpisodeStage *stage = nullptr;
+    if constexpr (EXTRAS && RECORDS) {
+        __shared__ EpisodeStage stages[256 / 64];
+        stage = &stages[threadIdx.x >> 6];
+    }
+    const uint64_t tick0 = a.tick2[a.parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.tick2[a.parity ^ 1] = tick0 + (uint64_t)ro.steps;
+    if constexpr (EXTRAS) {
+        if (blockIdx.x == 0 && a.done_count2)
+            for (int sh = threadIdx.x; sh < kShards; sh += blockDim.x) a.done_count2[(a.cparity ^ 1) * (kShards * kCountStride) + sh * kCountStride] = 0u;
+    }
+    const int64_t n = a.n;
+    if (i >= n) return;                     // the active lanes of the last wave are a prefix (the wave-level helpers rely on it)
+
+    Real s[S][1];
+#pragma unroll
+    for (int k = 0; k < S; ++k) s[k][0] = state_row_src<Env>(a.state, a.state_stride, a.obs_in, a.obs_stride, k)[i];
+    Real o[O][1];
+    if constexpr (!Env::OBS_ALIASES_STATE) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) o[k][0] = a.obs_in[k * a.obs_stride + i];
+    }
+    int32_t sbd[1] = {0};
+    if constexpr (!AUTORESET && Env::HAS_SBD) sbd[0] = a.sbd[i];
+    float ep_ret = 0.0f, fin_ret[1] = {0.0f};
+    int32_t ep_len = 0, fin_len[1] = {0};
+    bool stats = false;
+    if constexpr (EXTRAS) {
+        stats = a.ep_ret != nullptr;
+        if (stats) { ep_ret = a.ep_ret[i]; ep_len = a.ep_len[i]; }
+    }
+    const uint32_t explore_at_or_below = coin_threshold(ro.epsilon);
+    const uint64_t gl = a.lane_offset + (uint64_t)i;
+    int32_t newest = hs.slot;
+    float reward = 0.0f;
+    uint8_t done = 0;
+
+    uint32_t staged = 0;
+    auto flush_stage = [&]() {
+        if constexpr (EXTRAS && RECORDS) {
+            if (staged == 0) return;                                   // wave-uniform
+            wave_lds_fence();
+            const uint64_t act_mask = __ballot(1);
+            const int leader = __ffsll((unsigned long long)act_mask) - 1;
+            const uint32_t A = (uint32_t)__popcll(act_mask);
+            const uint32_t shard = wave_shard();
+            uint32_t base = 0;
+            if ((int)lane_id() == leader) base = atomicAdd(&ro.ep_count[shard * kCountStride], staged);
+            base = __shfl(base, leader);
+            const uint32_t first_ov = (int64_t)base < ro.ep_cap ? (uint32_t)min((int64_t)staged, ro.ep_cap - (int64_t)base) : 0u;
+            uint32_t ovbase = 0;
+            if (first_ov < staged) {                                   // wave-uniform: the shard's segment is full, spill to the overflow
+                if ((int)lane_id() == leader) ovbase = atomicAdd(&ro.ep_count[kShards * kCountStride], staged - first_ov);
+                ovbase = __shfl(ovbase, leader);
+            }
+            for (uint32_t b0 = 0; b0 < staged; b0 += A) {
+                const uint32_t q = b0 + lane_id();
+                if (q >= staged) continue;
+                int64_t pos = -1;
+                if (q < first_ov) pos = (int64_t)shard * ro.ep_cap + base + q;
+                else if ((int64_t)(ovbase + (q - first_ov)) < ro.ov_cap) pos = (int64_t)kShards * ro.ep_cap + ovbase + (q - first_ov);
+                if (pos >= 0) {
+                    ro.ep_t[pos] = stage->t[q];
+                    ro.ep_lane[pos] = stage->lane[q];
+                    if (ro.ep_ret) { ro.ep_ret[pos] = stage->ret[q]; ro.ep_len[pos] = stage->len[q]; }
+                }
+            }
+            wave_lds_fence();
+            staged = 0;
+        }
+    };
+
+    for (int64_t t = 0; t < ro.steps; ++t) {
+        // the actor: gymnet_vecenv_actor_act_device(epsilon, action_seed, action_tick0 + t)
+        float x[kW];
+        load_input<O>(hs, newest, i, x);
+        actor_forward(net, x);
+        int32_t act[1];
+        act[0] = compose_one(argmax_logits(x, net.action_n), net.action_n, explore_at_or_below, ro.action_seed, gl, ro.action_tick0 + (uint64_t)t);
+
+        // the env step (rollout_body, VEC = 1)
+        uint32_t pending = 0;
+        bool after[1] = {false};
+        {
+            auto one = [&](auto small_tag) {
+                Real sj[S], oj[O];
+                float rw;
+                bool dn;
+#pragma unroll
+                for (int k = 0; k < S; ++k) sj[k] = s[k][0];
+                advance_sublane<Env, AUTORESET, decltype(small_tag)::value>(sj, act[0], sbd[0], rw, dn, after[0], true, oj);
+                done = dn ? 1 : 0;
+                reward = rw;
+                if constexpr (AUTORESET && !EXTRAS) pending = dn ? 1u : 0u;
+#pragma unroll
+                for (int k = 0; k < S; ++k) s[k][0] = sj[k];
+                if constexpr (!Env::OBS_ALIASES_STATE) {
+#pragma unroll
+                    for (int k = 0; k < O; ++k) o[k][0] = oj[k];
+                }
+            };
+            if constexpr (Env::HAS_SMALL_ANGLE_PATH) {
+                if (wave_angles_small<Env, 1>(s)) one(std::true_type{});
+                else one(std::false_type{});
+            } else {
+                one(std::false_type{});
+            }
+        }
+        if constexpr (EXTRAS) {
+            bool finished[1];
+            fin_ret[0] = 0.0f; fin_len[0] = 0;
+            if (stats) {
+                ep_ret += reward;
+                ep_len += 1;
+                if (a.max_episode_steps > 0 && ep_len >= a.max_episode_steps) done |= 2;
+            }
+            const bool fin = done != 0;
+            finished[0] = fin;
+            if (fin && a.final_obs) {
+#pragma unroll
+                for (int k = 0; k < O; ++k) a.final_obs[k * n + i] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
+            }
+            if (stats && fin) {
+                fin_ret[0] = ep_ret;
+                fin_len[0] = ep_len;
+                if (a.fin_ret) { a.fin_ret[i] = ep_ret; a.fin_len[i] = ep_len; }
+                if constexpr (AUTORESET) { ep_ret = 0.0f; ep_len = 0; }
+            }
+            if constexpr (AUTORESET) pending = fin ? 1u : 0u;
+            if constexpr (RECORDS) {
+                uint32_t off[1];
+                const uint32_t total = rank_finished<1>(finished, off);
+                if (total && staged + total > kStageRecords) flush_stage();   // wave-uniform (a wave finishes at most 64 <= kStageRecords)
+                if (finished[0]) {
+                    const uint32_t q = staged + off[0];
+                    stage->t[q] = (int32_t)t; stage->lane[q] = (int32_t)i; stage->ret[q] = fin_ret[0]; stage->len[q] = fin_len[0];
+                }
+                staged += total;
+            }
+            if (a.done_list && t + 1 == ro.steps) append_done_records<Env, 1>(a, finished, i, s, o, fin_ret, fin_len, stats);
+        }
+        if constexpr (!AUTORESET && Env::HAS_SBD) count_after_done<1>(a, after);
+        if (ro.rec_reward) ro.rec_reward[t * n + i] = reward;
+        if (ro.rec_done) ro.rec_done[t * n + i] = done;
+        if (ro.rec_action) static_cast<int32_t *>(ro.rec_action)[t * n + i] = act[0];
+        if constexpr (AUTORESET && RESETF) reset_pending_wave<Env, 1, EXTRAS>(pending, s, a, i, n, tick0 + (uint64_t)t, sc);
+        else if constexpr (AUTORESET) reset_pending<Env, 1, EXTRAS>(pending, s, o, a, i, n, tick0 + (uint64_t)t);
+        // the post-step observation: recorded, and pushed into the history (every slot for a lane whose done byte is set)
+        Real ob[O];
+#pragma unroll
+        for (int k = 0; k < O; ++k) ob[k] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
+        if (ro.rec_obs) {
+#pragma unroll
+            for (int k = 0; k < O; ++k) ro.rec_obs[(t * O + k) * n + i] = ob[k];
+        }
+        newest = newest + 1 == hs.history ? 0 : newest + 1;
+        for (int sl = 0; sl < hs.history; ++sl) {
+            if (done == 0 && sl != newest) continue;
+#pragma unroll
+            for (int k = 0; k < O; ++k) hs.hist[((int64_t)sl * O + k) * hs.stride + i] = ob[k];
+        }
+    }
+    flush_stage();
+
+#pragma unroll
+    for (int k = 0; k < S; ++k)
+        if (state_row_own<Env>(k)) a.state_out[k * a.state_stride + i] = s[k][0];
+    if constexpr (!Env::OBS_ALIASES_STATE) {
+#pragma unroll
+        for (int k = 0; k < O; ++k) a.obs[k * a.obs_stride + i] = o[k][0];
+    }
+    a.reward[i] = reward;
+    a.done[i] = done;
+    if constexpr (!AUTORESET && Env::HAS_SBD) a.sbd[i] = sbd[0];
+    if constexpr (EXTRAS) {
+        if (stats) { a.ep_ret[i] = ep_ret; a.ep_len[i] = ep_len; }
+    }
+}
+
+template <class Env>
+static hipError_t launch_actor_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
+                                    const ActorHist &hs, hipStream_t st) {
+    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist) = nullptr;
+    if (autoreset) {
+        if (!extras) k = actor_rollout_kernel<Env, true, false, false>;
+        else k = records ? actor_rollout_kernel<Env, true, true, true> : actor_rollout_kernel<Env, true, true, false>;
+    } else {
+        if (!extras) k = actor_rollout_kernel<Env, false, false, false>;
+        else k = records ? actor_rollout_kernel<Env, false, true, true> : actor_rollout_kernel<Env, false, true, false>;
+    }
+    const int64_t blocks = (a.n + 255) / 256;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, st, a, r, net, hs);
+    return hipGetLastError();
+}
+
+static inline dim3 lane_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+int64_t actor_packed_floats(const int32_t *widths, int32_t layers, int32_t (&off)[kActorMaxLayers]) {
+    int64_t total = 0;
+    for (int l = 0; l < layers; ++l) {
+        off[l] = (int32_t)total;
+        total += (int64_t)((widths[l + 1] + 3) >> 2) * group_floats(widths[l]);
+    }
+    return total;
+}
+
+hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *packed, int64_t packed_count, hipStream_t st) {
+    hipLaunchKernelGGL(actor_pack_kernel, lane_grid(packed_count), dim3(256), 0, st, net, flat, packed, packed_count);
+    return hipGetLastError();
+}
+
+template <class R>
+static hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int64_t obs_stride, const uint8_t *restart, bool push,
+                                          hipStream_t st) {
+    switch (hs.obs_dim) {
+        case 2: hipLaunchKernelGGL((actor_push_kernel<R, 2>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
+        case 4: hipLaunchKernelGGL((actor_push_kernel<R, 4>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
+        case 6: hipLaunchKernelGGL((actor_push_kernel<R, 6>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_actor_push(bool f64, const ActorHist &hs, const void *obs, int64_t obs_stride, const uint8_t *restart, bool push,
+                             hipStream_t st) {
+    if (hs.n <= 0) return hipSuccess;
+    if (f64) return launch_actor_push_typed<double>(hs, static_cast<const double *>(obs), obs_stride, restart, push, st);
+    return launch_actor_push_typed<float>(hs, static_cast<const float *>(obs), obs_stride, restart, push, st);
+}
+
+hipError_t launch_actor_act(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, hipStream_t st) {
+    if (hs.n <= 0) return hipSuccess;
+    switch (hs.obs_dim) {
+        case 2: hipLaunchKernelGGL(actor_act_kernel<2>, lane_grid(hs.n), dim3(256), 0, st, net, hs, actions, logits, aa); break;
+        case 4: hipLaunchKernelGGL(actor_act_kernel<4>, lane_grid(hs.n), dim3(256), 0, st, net, hs, actions, logits, aa); break;
+        case 6: hipLaunchKernelGGL(actor_act_kernel<6>, lane_grid(hs.n), dim3(256), 0, st, net, hs, actions, logits, aa); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_actor_rollout(int env_id, bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
+                                const ActorHist &hs, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    switch (env_id) {
+        case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(autoreset, extras, records, a, r, net, hs, st);
+        case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(autoreset, extras, records, a, r, net, hs, st);
+        case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(autoreset, extras, records, a, r, net, hs, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace gymnet

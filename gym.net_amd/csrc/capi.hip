@@ -754,6 +754,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     if (h->d_render) (void)hipFree(h->d_render);
     if (h->stack_alloc) (void)hipFree(h->stack_alloc);
     for (void *p : h->mem_allocs) (void)hipFree(p);
+    for (void *p : h->actor_allocs) (void)hipFree(p);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1160,6 +1161,10 @@ int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, 
 
 namespace {
 
+int need_actor(gymnet_vecenv *h);
+bool actor_current(const gymnet_vecenv *h);
+void actor_mark(gymnet_vecenv *h);
+
 // segment buffers of the fused rollout's episode records: kShards segments of `cap` records each (t, lane, return, length) +
 // the shard counters.  Random lanes do not fill the shards evenly, so a segment gets twice its share of the caller's capacity —
 // and what a shard still cannot hold (lanes that finish very unevenly) goes to ONE shared overflow segment of `capacity` records
@@ -1200,7 +1205,15 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
         // the kShards + 1 counters, zeroed on the stream by a kernel of our own
         HIP_TRY(h, launch_fill_i32(reinterpret_cast<int32_t *>(r.ep_count), 0, (int64_t)(kShards + 1) * kCountStride, h->stream));
     }
-    HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
+    if constexpr (sizeof(R) == 4) {
+        if (sp.action_source == GYMNET_ACTIONS_ACTOR) {
+            HIP_TRY(h, launch_actor_rollout(h->cfg.env_id, h->autoreset, h->extras, episodes, a, r, h->actor, h->actor_hist, h->stream));
+        } else {
+            HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
+        }
+    } else {
+        HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
+    }
     if (episodes) {
         EpisodeGatherArgs g{};
         g.counts = r.ep_count; g.cap = r.ep_cap;
@@ -1226,8 +1239,9 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
         return fail(h, GYMNET_ERR_INVALID_ARG, "spec.struct_size %u != %zu (ABI mismatch)", spec->struct_size, sizeof(gymnet_rollout_spec));
     const gymnet_rollout_spec &sp = *spec;
     const EnvDesc &d = *h->desc;
-    if (sp.action_source < GYMNET_ACTIONS_RING || sp.action_source > GYMNET_ACTIONS_EPSILON_GREEDY) return fail(h, GYMNET_ERR_INVALID_ARG, "bad action_source %d", sp.action_source);
-    const bool ring_read = sp.action_source != GYMNET_ACTIONS_SAMPLE;
+    if (sp.action_source < GYMNET_ACTIONS_RING || sp.action_source > GYMNET_ACTIONS_ACTOR) return fail(h, GYMNET_ERR_INVALID_ARG, "bad action_source %d", sp.action_source);
+    const bool actor = sp.action_source == GYMNET_ACTIONS_ACTOR;
+    const bool ring_read = sp.action_source != GYMNET_ACTIONS_SAMPLE && !actor;
     if (ring_read && !sp.d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
     if (sp.steps < 0 || (ring_read && (sp.ring < 1 || sp.action_stride < 0))) return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride");
     if (sp.steps > INT32_MAX) return fail(h, GYMNET_ERR_INVALID_ARG, "steps must fit an int32 (episode records carry the step index)");
@@ -1236,6 +1250,13 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
     if (sp.action_source == GYMNET_ACTIONS_EPSILON_GREEDY) {
         if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "epsilon-greedy composition is defined for Discrete action spaces");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
+    }
+    if (actor) {
+        if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions");
+        if (h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout runs float32 handles (float64: act / step / push)");
+        if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
+        ST_TRY(need_actor(h));
+        if (!actor_current(h)) return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: reset the actor (or push) before an actor rollout");
     }
     if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && ring_read)
         return fail(h, GYMNET_ERR_UNSUPPORTED, "VALIDATE_ACTIONS is per step; use gymnet_vecenv_rollout_device (sampled actions are valid by construction)");
@@ -1275,6 +1296,10 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
     h->tslot ^= 1;                       // one launch: it read one half of d_tick2 and wrote the other
     h->step_launches += 1;
     h->lane_steps += (uint64_t)sp.steps * (uint64_t)h->n;
+    if (actor) {                         // the kernel pushed every step: the history is current, its newest slot moved `steps` on
+        h->actor_hist.slot = (int32_t)(((int64_t)h->actor_hist.slot + sp.steps) % h->actor_hist.history);
+        actor_mark(h);
+    }
     return GYMNET_OK;
     });
 }
@@ -1763,6 +1788,149 @@ int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_
         d.syq = (float)((double)crop_h / (4.0 * out_h));
     }
     HIP_TRY(h, launch_memory_dataset(h->f64, h->mem, d, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+// ---- the actor (actor.hip) ----------------------------------------------------------------------------------------------------
+namespace {
+
+int need_actor(gymnet_vecenv *h) {
+    return h->actor.layers > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no actor configured (gymnet_vecenv_actor_config)");
+}
+
+// the history is current: no vector step since the last actor config, reset, push or actor rollout
+bool actor_current(const gymnet_vecenv *h) { return h->tick == h->actor_tick && h->step_launches == h->actor_launches; }
+
+void actor_mark(gymnet_vecenv *h) { h->actor_tick = h->tick; h->actor_launches = h->step_launches; }
+
+// drops the configured actor after the stream has drained (a launch may still use it)
+int release_actor(gymnet_vecenv *h) {
+    if (!h->actor_allocs.empty()) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (void *p : h->actor_allocs) (void)hipFree(p);
+    h->actor_allocs.clear();
+    h->actor = ActorNet{}; h->actor_hist = ActorHist{};
+    h->actor_count = 0; h->actor_packed = 0; h->actor_flat = nullptr;
+    return GYMNET_OK;
+}
+
+int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
+    HIP_TRY(h, launch_actor_push(h->f64, h->actor_hist, h->d_obs, h->ostride, d_mask, false, h->stream));
+    actor_mark(h);
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
+                               int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (num_layers == 0) return release_actor(h);
+    const EnvDesc &d = *h->desc;
+    if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions; %s has a Box action space", d.name);
+    if (num_layers < 1 || num_layers > kActorMaxLayers) return fail(h, GYMNET_ERR_INVALID_ARG, "num_layers %d not in [0, %d]", num_layers, kActorMaxLayers);
+    if (!widths || !weights) return fail(h, GYMNET_ERR_INVALID_ARG, "widths / weights is null");
+    if (history < 1 || (int64_t)history * d.obs_dim > kActorMaxWidth)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "history %d: history * obs_dim must be in [1, %d]", history, kActorMaxWidth);
+    if (d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
+    int64_t params = 0;
+    for (int l = 0; l <= num_layers; ++l)
+        if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
+    for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
+    if (widths[0] != history * d.obs_dim) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], history * d.obs_dim);
+    if (widths[num_layers] != d.action_n) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != action_n = %d", num_layers, widths[num_layers], d.action_n);
+    if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
+    if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
+    ActorNet net{};
+    net.layers = num_layers; net.action_n = d.action_n;
+    for (int l = 0; l < num_layers; ++l) { net.win[l] = widths[l]; net.wout[l] = widths[l + 1]; }
+    const int64_t packed = actor_packed_floats(widths, num_layers, net.off);
+    ST_TRY(release_actor(h));
+    const int64_t stride = h->n;
+    const size_t sizes[3] = {sizeof(float) * (size_t)packed, sizeof(float) * (size_t)params,
+                             sizeof(float) * (size_t)history * (size_t)d.obs_dim * (size_t)(stride > 0 ? stride : 1)};
+    void *got[3] = {nullptr, nullptr, nullptr};
+    for (int q = 0; q < 3; ++q) {
+        hipError_t e = hipMalloc(&got[q], sizes[q]);
+        if (e != hipSuccess) {
+            for (void *p : got) if (p) (void)hipFree(p);
+            return fail(h, GYMNET_ERR_OOM, "hipMalloc(%zu bytes) for the actor failed: %s", sizes[q], hipGetErrorString(e));
+        }
+    }
+    h->actor_allocs.assign(got, got + 3);
+    net.w = static_cast<float *>(got[0]);
+    h->actor_flat = static_cast<float *>(got[1]);
+    ActorHist hs{};
+    hs.hist = static_cast<float *>(got[2]); hs.stride = stride; hs.history = history; hs.obs_dim = d.obs_dim; hs.slot = 0; hs.n = h->n;
+    h->actor = net; h->actor_hist = hs;
+    for (int l = 0; l <= num_layers; ++l) h->actor_widths[l] = widths[l];
+    h->actor_count = params; h->actor_packed = packed;
+    HIP_TRY(h, hipMemcpyAsync(h->actor_flat, weights, sizes[1], hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, launch_actor_pack(h->actor, h->actor_flat, const_cast<float *>(h->actor.w), packed, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));     // the caller's host weights may go away when we return
+    return actor_refill(h, nullptr);
+    });
+}
+
+int gymnet_vecenv_actor_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (!d_weights) return fail(h, GYMNET_ERR_INVALID_ARG, "d_weights is null");
+    if (count != h->actor_count) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != the actor's %lld parameters", (long long)count, (long long)h->actor_count);
+    HIP_TRY(h, launch_actor_pack(h->actor, d_weights, const_cast<float *>(h->actor.w), h->actor_packed, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    return actor_refill(h, d_mask);
+    });
+}
+
+int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (h->tick != h->actor_tick + 1 || h->step_launches != h->actor_launches + 1)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "an actor push needs exactly one vector step since the last actor config, reset or push (tick %llu -> %llu, "
+                    "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)h->actor_tick,
+                    (unsigned long long)h->tick, (unsigned long long)(h->step_launches - h->actor_launches));
+    ActorHist hs = h->actor_hist;
+    hs.slot = hs.slot + 1 == hs.history ? 0 : hs.slot + 1;
+    HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));
+    h->actor_hist = hs;
+    actor_mark(h);
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
+    if (!actor_current(h))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
+    ActorAct aa{};
+    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
+    HIP_TRY(h, launch_actor_act(h->actor, h->actor_hist, d_actions, d_logits, aa, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (d_history) *d_history = h->actor_hist.hist;
+    if (lane_stride) *lane_stride = h->actor_hist.stride;
+    if (slot) *slot = h->actor_hist.slot;
     return GYMNET_OK;
     });
 }

@@ -118,6 +118,16 @@ struct gymnet_vecenv {
     int32_t mem_history = 0;
     uint64_t mem_pos = 0, mem_tick = 0, mem_launches = 0;
     std::vector<void *> mem_allocs;
+    // gymnet_vecenv_actor_*: the actor (actor.layers == 0: none configured).  actor_hist.slot is the ring slot of the newest observation;
+    // actor_tick / actor_launches are the engine tick and step launches at the last config, reset, push or actor rollout, so act can tell
+    // that the history is current and push that exactly one vector step ran in between
+    gymnet::ActorNet actor{};
+    gymnet::ActorHist actor_hist{};
+    int32_t actor_widths[gymnet::kActorMaxLayers + 1] = {};
+    int64_t actor_count = 0, actor_packed = 0;
+    float *actor_flat = nullptr;            // [actor_count] the weights as given (torch layout), the pack kernel's input
+    uint64_t actor_tick = 0, actor_launches = 0;
+    std::vector<void *> actor_allocs;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;

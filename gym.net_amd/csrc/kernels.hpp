@@ -301,6 +301,33 @@ hipError_t launch_memory_open(bool f64, const MemoryArgs &m, const void *obs, in
 hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &p, hipStream_t st);
 hipError_t launch_memory_dataset(bool f64, const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st);
 hipError_t launch_fill_i32(int32_t *p, int32_t v, int64_t n, hipStream_t st);
+// The actor (actor.hip; contract: gymnet_vecenv_actor_config in include/gymnet_amd.h): a fully connected ReLU network of `layers`
+// linear layers whose packed weights (actor_packed_floats) are read by every lane, and the per-lane observation history it reads.
+constexpr int kActorMaxLayers = 4, kActorMaxWidth = 64, kActorMaxParams = 8192, kActorMaxActions = 8;
+struct ActorNet {
+    const float *w;                            // packed block: layer l at w + off[l] (actor.hip actor_forward)
+    int32_t layers, action_n;
+    int32_t win[kActorMaxLayers], wout[kActorMaxLayers], off[kActorMaxLayers];
+};
+struct ActorHist {
+    float *hist; int64_t stride;               // [history][obs_dim][stride] float32, a ring
+    int32_t history, obs_dim;
+    int32_t slot;                              // ring slot of the newest observation (push: the slot this push writes)
+    int64_t n;
+};
+struct ActorAct { float epsilon; uint64_t seed, lane_offset, tick; };
+// floats of the packed block for widths[0 .. layers]; off[l] = where layer l starts
+int64_t actor_packed_floats(const int32_t *widths, int32_t layers, int32_t (&off)[kActorMaxLayers]);
+hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *packed, int64_t packed_count, hipStream_t st);
+// push = true: lanes with restart[k] != 0 write every slot, the others slot hs.slot; push = false (reset): lanes with restart[k] != 0
+// (NULL: every lane) write every slot, the others nothing.  obs: the CURRENT observation buffer, float or double (f64)
+hipError_t launch_actor_push(bool f64, const ActorHist &hs, const void *obs, int64_t obs_stride, const uint8_t *restart, bool push,
+                             hipStream_t st);
+hipError_t launch_actor_act(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, hipStream_t st);
+// the fused rollout with RolloutArgs::action_source = GYMNET_ACTIONS_ACTOR (float32 CartPole / MountainCar / Acrobot); records: the
+// rollout keeps compact episode records (RolloutArgs::ep_*, with the overflow segment)
+hipError_t launch_actor_rollout(int env_id, bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r,
+                                const ActorNet &net, const ActorHist &hs, hipStream_t st);
 // Gathers the sharded done list of one step (counter half `counts`) and the records written beside it into compact arrays
 // out_*[0 .. *out_count) (entries beyond out_capacity are dropped; the count is the true one), and / or applies the records to
 // the dense per-lane arrays.  Every out / dense / rec pointer may be NULL.

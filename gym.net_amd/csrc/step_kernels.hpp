@@ -1024,6 +1024,8 @@ struct EpisodeStage { int32_t t[kStageRecords], lane[kStageRecords]; float ret[k
 //           no spill path — its mere presence costs the kernel 8 % (a call, or a cold block, inside a loop whose registers are capped
 //           at 128), and an evenly finishing batch never takes it.  A variant of its own, so that the
 //           rollouts that keep none do not carry the staging code's registers (128-VGPR budget, above)
+// KEEP IN STEP with actor.hip actor_rollout_kernel, which restates this body's step, EXTRAS bookkeeping, record staging and overflow
+// spill for one lane per thread (the closed-loop rollout, GYMNET_ACTIONS_ACTOR): a change here must be made there too.
 template <class Env, int VEC, bool AUTORESET, bool GUARD, bool EXTRAS, bool SAMPLE, int RESETF = 0, int RECORDS = 0>
 __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real> &a, const RolloutArgsT<typename Env::Real> &ro,
                                              const int64_t i0, const uint64_t tick0, ResetScratch<Env> *sc = nullptr, EpisodeStage *stage = nullptr) {

@@ -297,14 +297,17 @@ class VectorEnv:
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
           actions   "ring" (d_actions[t % ring]), "sample" (ActionSpace.Sample() drawn in the kernel: the values SampleActionsDevice
                     (seed=action_seed, tick=action_tick0 + t) would write; d_actions may be None) or "epsilon_greedy" (ComposeActionsDevice
-                    over d_actions as the policy's actions, TrainingPlaySession.cs:46-52)
+                    over d_actions as the policy's actions, TrainingPlaySession.cs:46-52) or "actor" (the handle's Actor chooses
+                    step t's action as Act(epsilon, action_seed, action_tick0 + t) would, and keeps its history current; d_actions
+                    may be None)
           rec_actions  [T][N] device buffer for the actions taken
           episodes  dict(step=, lane=, ret=, length=, capacity=, count=): device arrays for the compact records of the episodes
                     that end during the rollout (any array may be omitted; count: uint32[2] = records written, episodes ended);
                     no_overflow=True selects the 8 % faster kernel variant that may drop records of very unevenly finishing lanes
                     below `capacity` (GYMNET_RECORDS_NO_OVERFLOW; count[1] > count[0] says so);
                     needs a bookkeeping handle (BasePlaySession.cs:58-69)."""
-        src = {"ring": capi.ACTIONS_RING, "sample": capi.ACTIONS_SAMPLE, "epsilon_greedy": capi.ACTIONS_EPSILON_GREEDY}[actions]
+        src = {"ring": capi.ACTIONS_RING, "sample": capi.ACTIONS_SAMPLE, "epsilon_greedy": capi.ACTIONS_EPSILON_GREEDY,
+               "actor": capi.ACTIONS_ACTOR}[actions]
         ep = episodes or {}
         unknown = set(ep) - {"step", "lane", "ret", "length", "capacity", "count", "no_overflow"}
         if unknown:
@@ -389,6 +392,13 @@ class VectorEnv:
         DataBuilder.cs:25-55).  max_length 0 = the handle's max_episode_steps; history = steps per dataset row (MemoryStates).
         Replaces any memory this handle had."""
         return EpisodeMemory(self, capacity, max_length, history)
+
+    def Actor(self, net, history=4):
+        """A fully connected ReLU network that chooses every lane's action on the device (gymnet_vecenv_actor_config): the trainer's
+        ComposeAction -> Trainer.Predict -> argmax (BasePlaySession.cs:78-81) from the last `history` observations of each lane.  net is
+        a list of (W, b) pairs (W [out][in], torch's nn.Linear layout) or a torch nn.Sequential of Linear / ReLU layers.  Replaces
+        any actor this handle had."""
+        return Actor(self, net, history)
 
     def PackObsDevice(self, d_obs_rowmajor):
         capi.check(self._lib.gymnet_vecenv_pack_obs_device(self._h, _ptr(d_obs_rowmajor)))
@@ -763,6 +773,150 @@ class EpisodeMemory:
         if self._h is not None and self._env._h:
             capi.check(self._lib.gymnet_vecenv_memory_config(self._h, 0, 0, 0))
             self._env._episode_memory = None
+        self._h = None
+
+
+def actor_layers(net):
+    """[(W float32 [out][in], b float32 [out]), ...] from a list of (W, b) pairs or a torch nn.Sequential of Linear / ReLU layers (every
+    Linear but the last followed by one ReLU, the last by none)."""
+    if hasattr(net, "named_children") or hasattr(net, "children"):
+        import torch
+        mods = list(net.children())
+        layers, expect_relu = [], False
+        for m in mods:
+            if isinstance(m, torch.nn.Linear):
+                if expect_relu:
+                    raise ValueError("every Linear layer but the last must be followed by a ReLU")
+                w = m.weight.detach().to("cpu", torch.float32).numpy()
+                b = (m.bias.detach().to("cpu", torch.float32).numpy() if m.bias is not None else np.zeros(w.shape[0], np.float32))
+                layers.append((w, b))
+                expect_relu = True
+            elif isinstance(m, torch.nn.ReLU):
+                if not expect_relu:
+                    raise ValueError("a ReLU must follow a Linear layer")
+                expect_relu = False
+            else:
+                raise ValueError(f"unsupported layer {type(m).__name__} (Linear / ReLU only)")
+        if not layers or not expect_relu:
+            raise ValueError("the network must end with a Linear layer (its outputs are the logits)")
+        return layers
+    out = []
+    for pair in net:
+        w, b = pair
+        w = np.ascontiguousarray(np.asarray(w.detach().cpu() if hasattr(w, "detach") else w, np.float32))
+        b = np.ascontiguousarray(np.asarray(b.detach().cpu() if hasattr(b, "detach") else b, np.float32))
+        if w.ndim != 2 or b.shape != (w.shape[0],):
+            raise ValueError(f"layer {len(out)}: W must be [out][in] and b [out], got {w.shape} and {b.shape}")
+        out.append((w, b))
+    if not out:
+        raise ValueError("the network has no layer")
+    return out
+
+
+def actor_pack(net):
+    """(widths int32 [L + 1], weights float32 [count]) in gymnet_vecenv_actor_config's layout: per layer W row-major, then b."""
+    layers = actor_layers(net)
+    widths = [layers[0][0].shape[1]]
+    for k, (w, b) in enumerate(layers):
+        if w.shape[1] != widths[-1]:
+            raise ValueError(f"layer {k} takes {w.shape[1]} inputs, the previous layer gives {widths[-1]}")
+        widths.append(w.shape[0])
+    flat = np.concatenate([np.concatenate([w.reshape(-1), b]) for w, b in layers]).astype(np.float32)
+    return np.asarray(widths, np.int32), flat
+
+
+class Actor:
+    """The handle's actor (VectorEnv.Actor).  Act / Push / Reset / Load / Step are ordered on the handle's stream and do not block;
+    History blocks."""
+
+    def __init__(self, env, net, history):
+        history = int(history)
+        widths, flat = actor_pack(net)
+        if history < 1:
+            raise ValueError("history must be >= 1")
+        if widths[0] != history * env.ObsDim:
+            raise ValueError(f"the first layer takes {widths[0]} inputs; history * obs_dim = {history * env.ObsDim}")
+        self._env, self._lib, self._h = env, env._lib, env._h
+        capi.check(self._lib.gymnet_vecenv_actor_config(self._h, history, len(widths) - 1, _host(widths), _host(flat), flat.size))
+        prev = getattr(env, "_actor", None)
+        if prev is not None and prev is not self:
+            prev._h = None                      # the handle holds one actor: the previous one is gone
+        env._actor = self
+        self.History_, self.Widths, self.Count = history, tuple(int(w) for w in widths), int(flat.size)
+        self._out = None
+
+    def _handle(self):
+        if self._h is None or not self._env._h:
+            raise ValueError("this actor was replaced or closed")
+        return self._h
+
+    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None):
+        """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
+        network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
+        compose it.  logits: an optional device float32 [N, action_n]."""
+        if out is None:
+            import torch
+            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.int32, device=f"cuda:{self._env.Device}")
+        capi.check(self._lib.gymnet_vecenv_actor_act_device(self._handle(), _ptr(out), _ptr(logits), float(epsilon),
+                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+        return out
+
+    def Push(self, done=None):
+        """Once after each single vector step: lanes whose done byte is set (device bytes; None: the handle's own) refill every slot with
+        their post-step observation, the others append it."""
+        capi.check(self._lib.gymnet_vecenv_actor_push_device(self._handle(), _ptr(done)))
+
+    def Reset(self, mask=None):
+        """Lanes whose device mask byte is set (None: every lane) fill every slot with their current observation (after ResetWhere(Device))."""
+        capi.check(self._lib.gymnet_vecenv_actor_reset_device(self._handle(), _ptr(mask)))
+
+    def Load(self, net):
+        """New weights of the same widths, history kept: a flat device float32 tensor in the config layout is copied device to device,
+        anything else goes through actor_pack and the host."""
+        if hasattr(net, "data_ptr") and getattr(net, "is_cuda", False):
+            if net.numel() != self.Count or str(net.dtype) != "torch.float32" or not net.is_contiguous():
+                raise ValueError(f"a device weight tensor must be {self.Count} contiguous float32 values")
+            capi.check(self._lib.gymnet_vecenv_actor_load_device(self._handle(), _ptr(net), self.Count))
+            return
+        widths, flat = actor_pack(net)
+        if tuple(int(w) for w in widths) != self.Widths:
+            raise ValueError(f"widths {tuple(int(w) for w in widths)} != the actor's {self.Widths}")
+        import torch
+        d = torch.from_numpy(flat).to(f"cuda:{self._env.Device}")
+        capi.check(self._lib.gymnet_vecenv_actor_load_device(self._handle(), _ptr(d), self.Count))
+        self._env.Sync()
+
+    def History(self):
+        """numpy float32 [N, history, obs_dim], oldest first (blocks)."""
+        p, stride, slot = C.c_void_p(), C.c_int64(), C.c_int32()
+        capi.check(self._lib.gymnet_vecenv_actor_view(self._handle(), C.byref(p), C.byref(stride), C.byref(slot)))
+        import torch
+        env = self._env
+        env.Sync()
+        n, S, O = env.NumberOfEnvironments, self.History_, env.ObsDim
+
+        class _View:                            # the library's history buffer, seen by torch without a copy
+            __cuda_array_interface__ = {"shape": (S, O, int(stride.value)), "typestr": "<f4", "data": (int(p.value or 0), False),
+                                        "version": 2, "strides": None}
+        raw = torch.as_tensor(_View(), device=f"cuda:{env.Device}").cpu().numpy()[:, :, :n]
+        order = [(int(slot.value) + 1 + s) % S for s in range(S)]
+        return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
+
+    def Step(self, epsilon=0.0, seed=0, tick=0):
+        """Act(epsilon, seed, tick), StepDevice, Push(): one closed-loop vector step; returns the device actions taken."""
+        if self._out is None:
+            import torch
+            self._out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.int32, device=f"cuda:{self._env.Device}")
+        self.Act(epsilon, seed, tick, out=self._out)
+        self._env.StepDevice(self._out)
+        self.Push()
+        return self._out
+
+    def Close(self):
+        """Releases the actor."""
+        if self._h is not None and self._env._h:
+            capi.check(self._lib.gymnet_vecenv_actor_config(self._h, 0, 0, None, None, 0))
+            self._env._actor = None
         self._h = None
 
 

@@ -297,7 +297,8 @@ typedef struct gymnet_rollout_buffers {
 /* The same `steps` vector steps as gymnet_vecenv_rollout_device — bit-identical state, reward, done — fused into ONE
  * kernel launch: every lane keeps its state in registers across the steps, so per env-step only the action is read and
  * (optionally, rec != NULL) the recorded streams are written.  For open-loop / pre-generated action sequences only: no
- * policy can look at step t's observation before step t+1.  (Since ABI 5 also on bookkeeping handles: see
+ * policy can look at step t's observation before step t+1 (the closed-loop form is gymnet_vecenv_rollout_fused_ex_device with
+ * GYMNET_ACTIONS_ACTOR: the handle's actor chooses every step's action inside the kernel).  (Since ABI 5 also on bookkeeping handles: see
  * gymnet_vecenv_rollout_fused_ex_device below, of which this is the ring-actions, no-episode-records form.) */
 int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride,
                                        int64_t ring, const gymnet_rollout_buffers *rec);
@@ -320,7 +321,14 @@ int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, 
  * most of them — can then be dropped below ep_capacity (a per-shard limit of 2 * ceil(ep_capacity / 256) + 64 records; d_ep_count[1] > [0]
  * says so).  Evenly finishing batches, e.g. random rollouts, never notice the difference. */
 #define GYMNET_RECORDS_NO_OVERFLOW 1
-typedef enum gymnet_action_source { GYMNET_ACTIONS_RING = 0, GYMNET_ACTIONS_SAMPLE = 1, GYMNET_ACTIONS_EPSILON_GREEDY = 2 } gymnet_action_source;
+/* GYMNET_ACTIONS_ACTOR (additive in ABI 6): the handle's actor chooses step t's action as gymnet_vecenv_actor_act_device(epsilon,
+ * action_seed, action_tick0 + t) would, from the history the kernel keeps current (d_actions is ignored): bit-identical to `steps` x
+ * (actor_act_device, step_device, actor_push_device), the final history included.  Needs a configured actor whose history is current;
+ * float32 CartPole / MountainCar / Acrobot handles (GYMNET_ERR_UNSUPPORTED for float64 handles and Box envs).  Every flag combination of
+ * the other sources is accepted; GYMNET_RECORDS_NO_OVERFLOW is accepted and served by the variant with the overflow segment (nothing is
+ * dropped below ep_capacity). */
+typedef enum gymnet_action_source { GYMNET_ACTIONS_RING = 0, GYMNET_ACTIONS_SAMPLE = 1, GYMNET_ACTIONS_EPSILON_GREEDY = 2,
+                                    GYMNET_ACTIONS_ACTOR = 3 } gymnet_action_source;
 typedef struct gymnet_rollout_spec {
     uint32_t struct_size;        /* = sizeof(gymnet_rollout_spec) */
     int32_t  action_source;      /* gymnet_action_source */
@@ -540,6 +548,50 @@ int gymnet_vecenv_memory_dataset_size(gymnet_vecenv *h, int64_t *rows);
 int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
                                         int32_t out_w, int32_t out_h, void *d_x, int32_t *d_action, float *d_onehot, float *d_reward,
                                         int64_t capacity_rows);
+
+/* ---- the actor (the trainer's BasePlaySession.ComposeAction -> Trainer.Predict -> _network.Forward and IndexOf(Max()),
+ * PlaySessions/BasePlaySession.cs:78-81, Trainer.cs:91-92, and TrainingPlaySession.ComposeAction's epsilon-greedy wrapper,
+ * PlaySessions/TrainingPlaySession.cs:46-52) --------------------------------------------------------------------------------------
+ * The handle owns at most one actor: a fully connected ReLU network given by the caller and kept on the device, and a per-lane history
+ * of the last S observations.  Training stays with the caller; the engine evaluates the weights it is given.
+ * Network: L = num_layers in [1, 4] linear layers, widths w_0 .. w_L (widths[L + 1]) with w_0 = S * obs_dim, w_L = action_n, every width
+ *   in [1, 64], at most 8192 parameters.  weights: float32, layer after layer, W_l [w_{l+1}][w_l] row-major (torch's nn.Linear.weight;
+ *   NeuralNetworkNET's fully connected weights must be handed over in this [out][in] layout) followed by b_l [w_{l+1}]; count = their
+ *   number.  Neuron j of layer l: acc = b_l[j]; acc = fmaf(W_l[j][i], x[i], acc) for i = 0 .. w_l - 1 (one rounding per product,
+ *   ascending i); hidden layers then take acc > 0 ? acc : +0.0f; the last layer's values are the logits.  The action is the first index
+ *   of the largest logit (argmax, not IndexOf(Max()) of a softmax: they differ only where exp rounding ties two outputs).
+ * Input: x = o_{p-S+1} .. o_p, oldest first, each observation's obs_dim values contiguous, o_p the lane's current observation, indices
+ *   below the episode's first observation clamped to it (float64 observations rounded to float32): the GYMNET_MEMORY_PARAMS row of the
+ *   same step.
+ * History: config and reset_device (lanes with d_mask[lane] != 0; NULL: every lane) fill every slot with the current observation;
+ *   push_device, once after each single vector step: a lane whose done byte is non-zero (either bit; d_done NULL = the handle's own)
+ *   refills every slot with its post-step observation, every other lane appends it.  Kept as float32 [S][obs_dim][lane_stride], a ring:
+ *   view's *slot is the ring position of the newest observation, input row s (oldest first) is ring slot (slot + 1 + s) % S.
+ * act_device: d_actions [num_envs] int32 = exactly what gymnet_vecenv_compose_actions_device(greedy, epsilon, d_actions, seed, tick)
+ *   writes over the greedy actions (epsilon = 0: TestingPlaySession; > 0: TrainingPlaySession); d_logits [num_envs][action_n] or NULL.
+ * load_device: count floats of device weights in the config layout replace the weights, ordered on the stream; the history is kept.
+ * Staleness (GYMNET_ERR_INVALID_ARG, nothing written): act unless the history is current — no vector step since the last config,
+ *   reset, push or actor rollout; push unless exactly one vector step ran since then.  A fused rollout with GYMNET_ACTIONS_ACTOR leaves
+ *   the history current; any other rollout leaves it stale until an actor reset.  Every call that moves the engine tick without
+ *   being the one vector step a push expects — a reset of the handle (gymnet_vecenv_reset(_device), _reset_where(_device): their
+ *   draws take a tick), gymnet_vecenv_seed / _seed_lanes, set_tick, restoring a checkpoint — also leaves the history stale: call
+ *   actor_reset_device after it (the actor tells by the tick and the step-launch count, so act and push are refused after any of them
+ *   that moved the tick).  So without AUTORESET the order is step, push, masked reset of the handle, actor_reset_device(mask).  On a GYMNET_FLAG_RESIDENT handle the host-boundary steps the resident kernel serves advance the tick
+ *   but are not step launches, so a push after them is refused: drive an actor there with gymnet_vecenv_step_device (or the fused
+ *   actor rollout).
+ * Envs: Discrete-action envs (CartPole, MountainCar, Acrobot) on float32 handles, and float64 CartPole handles for config / reset /
+ *   push / act; Box-action envs: GYMNET_ERR_UNSUPPORTED.  num_layers 0 releases the actor (the other arguments are not looked at).
+ *   Every call but config is ordered on the handle's stream and does not block; none changes state, observations, tick, counters or
+ *   the done bytes.  The actor is not part of a checkpoint.
+ * Errors (nothing written): GYMNET_ERR_INVALID_ARG for widths, count, history or epsilon outside the ranges above, null pointers, calls
+ *   before an actor is configured and the staleness rules; GYMNET_ERR_UNSUPPORTED for Box-action envs; GYMNET_ERR_OOM. */
+int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
+                               int64_t count);
+int gymnet_vecenv_actor_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count);
+int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask);
+int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done);
+int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick);
+int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot);
 
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */

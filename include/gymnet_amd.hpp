@@ -344,6 +344,19 @@ public:
                                                   capacity_rows));
         return rows < capacity_rows ? rows : capacity_rows;
     }
+    // The actor (gymnet_vecenv_actor_config): a fully connected ReLU network on the device that chooses every lane's action from its
+    // last `history` observations.  widths = w_0 .. w_L; weights = per layer W [out][in] row-major, then b [out].  Empty widths release it.
+    void ConfigureActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
+        if (widths.empty()) { check(gymnet_vecenv_actor_config(h_, 0, 0, nullptr, nullptr, 0)); return; }
+        check(gymnet_vecenv_actor_config(h_, history, (int32_t)widths.size() - 1, widths.data(), weights.data(), (int64_t)weights.size()));
+    }
+    void LoadActorWeights(const float *d_weights, int64_t count) { check(gymnet_vecenv_actor_load_device(h_, d_weights, count)); }
+    void ResetActor(const uint8_t *d_mask = nullptr) { check(gymnet_vecenv_actor_reset_device(h_, d_mask)); }
+    void PushActor(const uint8_t *d_done = nullptr) { check(gymnet_vecenv_actor_push_device(h_, d_done)); }
+    /// every lane's action (argmax of the logits, epsilon-greedy as gymnet_vecenv_compose_actions_device composes it) into d_actions
+    void ActorAct(int32_t *d_actions, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_logits = nullptr) {
+        check(gymnet_vecenv_actor_act_device(h_, d_actions, d_logits, epsilon, seed, tick));
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
