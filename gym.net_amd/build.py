@@ -1,6 +1,7 @@
 """Builds gym.net_amd/lib/libgymnet_amd.so: the HIP kernels + the C ABI, for gfx950 only.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared csrc/*.hip -ldl -o lib/libgymnet_amd.so
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=14 -fPIC -shared \
+          csrc/*.hip -ldl -o lib/libgymnet_amd.so
 (done as one `hipcc -c` per .hip file in parallel plus one link: same flags, same result.  Every env's step / rollout / reset
 kernels are a translation unit of their own — csrc/env_*.hip instantiating csrc/step_kernels.hpp — so the files compile
 side by side: ~15 s wall on 8 cores instead of ~40 s for the former single kernels.hip)
@@ -25,7 +26,11 @@ DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "c
 # tools/acrobot_alu_probe.hip, tools/valu_probe.hip, profiles/*_r02.txt), so the compiler's opportunistic pairing saves
 # nothing and costs the v_mov shuffles that build the pairs (Acrobot harness: 465 VALU with it, 452 without; the four
 # bench kernels time the same either way).  Off = deterministic, purely scalar code generation.
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
+# -mllvm -amdgpu-kernarg-preload-count=14: the first 14 dwords of FLAT leading kernel arguments arrive in user SGPRs at wave launch (the
+# ceiling on gfx950; code objects carry a prologue that loads them on firmware without the feature).  The one-step kernels take their
+# first-use words that way (csrc/kernels.hpp StepKernelFn); a kernel whose first argument is a by-value struct is unaffected.
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-amdgpu-kernarg-preload-count=14",
+         "-fPIC", "-shared"]
 LIBS = ["-ldl"]          # librccl is dlopen()ed on demand by group.hip, never linked
 # (The library never reads the process environment for its launch policy: gymnet_vecenv_set_launch_policy is the interface.  The
 # GYMNET_BUILD_PROBE_ENV probe build of rounds 1-4 went away in round 5 together with the scripts that needed it.)

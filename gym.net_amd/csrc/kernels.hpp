@@ -46,6 +46,18 @@ struct StepArgsT {
 typedef StepArgsT<float> StepArgs;
 typedef StepArgsT<double> StepArgs64;
 
+// How the one-step kernels (step_kernel, step_kernel_pipe, step_kernel_pipe2) receive a StepArgsT: its FIRST-USE words as flat leading
+// arguments, the whole struct behind them.  gfx950 delivers up to 14 dwords of flat leading kernel arguments in user SGPRs at wave
+// launch (-mllvm -amdgpu-kernarg-preload-count=14, gym.net_amd/build.py) — a by-value struct is never preloaded — so what the guard,
+// the first vector loads and the tick load need is there before the first instruction, with no scalar load from the kernarg segment
+// and no wait for one (profiles/launch_floor.txt).  The words, by first use: state, action, n, state_stride (the guard and the loads),
+// tick2 and parity (the tick load), reward (the first stream stored), and `block`, the launch's workgroup size: blockDim.x is a HIDDEN
+// kernel argument, which is preloaded only when every explicit argument is, so the kernels read it from here.  The kernel rebuilds its
+// StepArgsT from `rest` and the flat words (step_kernels.hpp hot_step_args); launch_step_kernel is the one place that splits it.
+template <class R>
+using StepKernelFn = void (*)(R *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2, float *reward, int32_t block,
+                              int32_t parity, StepArgsT<R> rest);
+
 // vec: envs per thread (4 = dwordx4 streams, 1 = scalar); block: threads per workgroup;
 // nt: non-temporal mask (0 none, 12 action + reward/done streams, 15 every stream)
 constexpr int kShards = 256;        // power of two; the gather kernels' workgroup size (kernels.hip static_assert)
@@ -154,7 +166,7 @@ struct StepForm {
 };
 template <class R>
 struct StepKernelT : StepForm {
-    void (*kernel)(StepArgsT<R>) = nullptr;                // step_kernel / step_kernel_pipe / step_kernel_pipe2, or
+    StepKernelFn<R> kernel = nullptr;                      // step_kernel / step_kernel_pipe / step_kernel_pipe2, or
     void (*lds_kernel)(StepArgsT<R>, int64_t) = nullptr;   // step_kernel_lds (its second argument: the batch's 512-lane tiles)
     dim3 grid, block;                                      // the launch over the whole batch
     size_t lds_bytes = 0;                                  // dynamic LDS

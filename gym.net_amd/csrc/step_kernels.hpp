@@ -373,6 +373,17 @@ __device__ __forceinline__ void append_done_records(const StepArgsT<typename Env
     }
 }
 
+// The StepArgsT a one-step kernel works with: `rest` with its first-use words taken from the kernel's flat (preloaded) arguments
+// (kernels.hpp StepKernelFn).  The flat words ARE the struct's fields — launch_step_kernel passes both from one StepArgsT — so the body
+// templates below read one struct as before; the compiler keeps each field where it arrived (user SGPRs or the kernarg segment).
+template <class R>
+__device__ __forceinline__ StepArgsT<R> hot_step_args(R *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2, float *reward,
+                                                      int32_t parity, const StepArgsT<R> &rest) {
+    StepArgsT<R> a = rest;
+    a.state = state; a.action = action; a.n = n; a.state_stride = state_stride; a.tick2 = tick2; a.reward = reward; a.parity = parity;
+    return a;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The vector step: ONE launch advances every lane by one env-step.
 //   Env       dynamics (envs.hpp)
@@ -594,11 +605,13 @@ __device__ __forceinline__ void store_lane(const StepArgsT<typename Env::Real> &
 }
 
 template <class Env, int ITEMS, bool AUTORESET, int NT>
-__global__ __launch_bounds__(256) void step_kernel_pipe(const StepArgsT<typename Env::Real> a) {
+__global__ __launch_bounds__(256) void step_kernel_pipe(typename Env::Real *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2,
+                                                        float *reward, int32_t block, int32_t parity, const StepArgsT<typename Env::Real> rest) {
+    const StepArgsT<typename Env::Real> a = hot_step_args(state, action, n, state_stride, tick2, reward, parity, rest);
     const uint64_t tick = a.tick2[a.parity];
     if (blockIdx.x == 0 && threadIdx.x == 0) a.tick2[a.parity ^ 1] = tick + 1;
-    const int64_t T = (int64_t)gridDim.x * blockDim.x;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t T = (int64_t)gridDim.x * block;
+    const int64_t i = (int64_t)blockIdx.x * block + threadIdx.x;
     // Loads are UNCONDITIONAL (a lane past the end re-reads the last valid lane; only its stores are suppressed): a branch
     // around a group of loads makes the compiler's waitcnt bookkeeping treat the earlier groups as the most recent ones at
     // the join, and the wait for lane 0 below would then wait for every lane.
@@ -769,17 +782,19 @@ __device__ __forceinline__ void pipe2_split_body(const StepArgsT<typename Env::R
 template <class Env, int ITEMS, bool AUTORESET, int NT>
 // (No occupancy hint: the float64 four-pair kernel holds 185 VGPRs = two waves per SIMD; capped at 168 for three it spills 48 bytes and
 // runs at 14.0 instead of 11.1 us per 2^20-lane step — profiles/occupancy_hints_r05.txt.)
-__global__ __launch_bounds__(256) void step_kernel_pipe2(const StepArgsT<typename Env::Real> a) {
+__global__ __launch_bounds__(256) void step_kernel_pipe2(typename Env::Real *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2,
+                                                         float *reward, int32_t block, int32_t parity, const StepArgsT<typename Env::Real> rest) {
+    const StepArgsT<typename Env::Real> a = hot_step_args(state, action, n, state_stride, tick2, reward, parity, rest);
     const uint64_t tick = a.tick2[a.parity];
     if (blockIdx.x == 0 && threadIdx.x == 0) a.tick2[a.parity ^ 1] = tick + 1;
-    const int64_t T = (int64_t)gridDim.x * blockDim.x;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t T = (int64_t)gridDim.x * block;
+    const int64_t t = (int64_t)blockIdx.x * block + threadIdx.x;
     if constexpr (AUTORESET && has_split_reset<Env>()) {
         __shared__ DeferScratch<Env> scratch[256 / 64];            // one table per wave of the workgroup
         DeferScratch<Env> *sc = &scratch[threadIdx.x >> 6];
         // ANY batch size: the grid is ceil(n / (2 * ITEMS * block)) workgroups; a workgroup whose last pair of its last item lies
         // inside the batch runs the unguarded body (workgroup-uniform), the batch's last few run the guarded one
-        if ((((int64_t)blockIdx.x + 1) * blockDim.x + (int64_t)(ITEMS - 1) * T) * 2 <= a.n) pipe2_split_body<Env, ITEMS, NT, false>(a, t, T, tick, sc);
+        if ((((int64_t)blockIdx.x + 1) * block + (int64_t)(ITEMS - 1) * T) * 2 <= a.n) pipe2_split_body<Env, ITEMS, NT, false>(a, t, T, tick, sc);
         else pipe2_split_body<Env, ITEMS, NT, true>(a, t, T, tick, sc);
         return;
     }
@@ -929,8 +944,10 @@ __global__ __launch_bounds__(CW * 64 + 64) void step_kernel_lds(const StepArgs a
 }
 
 template <class Env, int VEC, bool AUTORESET, bool EXTRAS, int NT, int RESETF = 0>
-__global__ __launch_bounds__(256) void step_kernel(const StepArgsT<typename Env::Real> a) {
-    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+__global__ __launch_bounds__(256) void step_kernel(typename Env::Real *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2,
+                                                   float *reward, int32_t block, int32_t parity, const StepArgsT<typename Env::Real> rest) {
+    const StepArgsT<typename Env::Real> a = hot_step_args(state, action, n, state_stride, tick2, reward, parity, rest);
+    const int64_t i0 = ((int64_t)blockIdx.x * block + threadIdx.x) * VEC;
     ResetScratch<Env> *sc = nullptr;
     if constexpr (RESETF == 1) {
         __shared__ ResetScratch<Env> scratch[256 / 64];            // one table per wave of the workgroup
@@ -944,10 +961,10 @@ __global__ __launch_bounds__(256) void step_kernel(const StepArgsT<typename Env:
     }
     if constexpr (EXTRAS) {
         if (blockIdx.x == 0 && a.done_count2)     // zero the NEXT step launch's half of the shard counters
-            for (int sh = threadIdx.x; sh < kShards; sh += blockDim.x) a.done_count2[(a.cparity ^ 1) * (kShards * kCountStride) + sh * kCountStride] = 0u;
+            for (int sh = threadIdx.x; sh < kShards; sh += block) a.done_count2[(a.cparity ^ 1) * (kShards * kCountStride) + sh * kCountStride] = 0u;
     }
     // workgroup-uniform: every workgroup but (at most) the last runs the unguarded body
-    if (((int64_t)blockIdx.x + 1) * blockDim.x * VEC <= a.n) {
+    if (((int64_t)blockIdx.x + 1) * block * VEC <= a.n) {
         step_body<Env, VEC, AUTORESET, EXTRAS, NT, false, RESETF>(a, i0, tick, sc);
     } else {
         if (i0 >= a.n) return;
@@ -1569,19 +1586,25 @@ static StepKernelT<typename Env::Real> select_step(bool autoreset, bool extras, 
     return k;
 }
 
+// THE place a StepArgsT is split into the kernel's flat first-use words and the struct behind them (kernels.hpp StepKernelFn)
+template <class R>
+static void launch_step_kernel(StepKernelFn<R> kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const StepArgsT<R> &a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, a.state, a.action, a.n, a.state_stride, a.tick2, a.reward, (int32_t)block.x, a.parity, a);
+}
+
 template <class Env>
 static hipError_t launch_step_env(bool autoreset, bool extras, const StepArgsT<typename Env::Real> &a, LaunchCfg cfg, hipStream_t st) {
     const StepKernelT<typename Env::Real> k = select_step<Env>(autoreset, extras, cfg, a.n);
     if (k.lds_kernel) {
         hipLaunchKernelGGL(k.lds_kernel, k.grid, k.block, 0, st, a, a.n / kLdsTileMax);
     } else if (k.slices == 1) {
-        hipLaunchKernelGGL(k.kernel, k.grid, k.block, k.lds_bytes, st, a);
+        launch_step_kernel(k.kernel, k.grid, k.block, k.lds_bytes, st, a);
     } else {
         // every slice reads the same tick word and writes the same successor
         for (int c = 0; c < k.slices; ++c) {
             const int64_t first = (int64_t)c * k.slice_lanes, count = (a.n - first < k.slice_lanes) ? a.n - first : k.slice_lanes;
             const dim3 grid((unsigned)((count + k.group_lanes - 1) / k.group_lanes));
-            hipLaunchKernelGGL(k.kernel, grid, k.block, 0, st, slice_of(a, first, count));
+            launch_step_kernel(k.kernel, grid, k.block, 0, st, slice_of(a, first, count));
         }
     }
     return hipGetLastError();

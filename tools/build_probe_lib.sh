@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 NAME=$1; shift
 mkdir -p tools/build/obj_$NAME
 for S in env_cartpole env_cartpole64 env_acrobot env_pendulum env_mountaincar kernels capi group; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC "$@" -c gym.net_amd/csrc/$S.hip -o tools/build/obj_$NAME/$S.o &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=14 -fPIC "$@" -c gym.net_amd/csrc/$S.hip -o tools/build/obj_$NAME/$S.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared tools/build/obj_$NAME/*.o -ldl -o tools/build/libgymnet_amd_$NAME.so && rm -rf tools/build/obj_$NAME

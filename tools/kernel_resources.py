@@ -16,7 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym.net_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--cuda-device-only", "-S"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-amdgpu-kernarg-preload-count=14",
+         "--cuda-device-only", "-S"]
 ENVS = ("cartpole", "cartpole64", "pendulum", "mountaincar", "acrobot")
 # collect()'s default stays the five units tests/_instantiation_matrix.py covers; the newer units have their own recipe tables
 # (tests/_mountaincar_continuous_matrix.py) and are listed only in the command line's default

@@ -469,7 +469,7 @@ int main(int argc, char **argv) {
             for (int i = 0; i < launches; ++i) {
                 a.parity = (int32_t)(tick & 1); a.cparity = a.parity;
                 a.action = static_cast<const char *>(b.action) + (int64_t)(tick % kRing) * n * 4;
-                hipLaunchKernelGGL((step_kernel<CartPole, 4, true, false, M, 1>), grid, blk, 0, st, a);
+                launch_step_kernel<float>(step_kernel<CartPole, 4, true, false, M, 1>, grid, blk, 0, st, a);
                 ++tick;
             }
             HIP_OK(hipEventRecord(e1, st)); HIP_OK(hipEventSynchronize(e1));
