@@ -19,14 +19,33 @@
 // Fused rollout (actor_rollout_kernel).  The env's step, fused reset, bookkeeping and episode records of step_kernels.hpp's
 // rollout_body, one lane per thread, with the action of step t chosen in the kernel from the history the kernel itself keeps current in
 // memory: bit-identical to steps x (act, step, push).  This unit instantiates its own kernels; the env_*.hip units are untouched.
+//
+// The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, and the three calls the fused rollout
+// (capi.hip) makes when the actor chooses its actions.
 #include "step_kernels.hpp"
 
 #include "envs.hpp"
-#include "../../include/gymnet_amd.h"
+#include "handle.hpp"
 
 namespace gymnet {
 
 namespace {
+
+// a fully connected ReLU network of `layers` linear layers whose packed weights (actor_packed_floats) are read by every lane, and the
+// per-lane observation history it reads
+constexpr int kActorMaxLayers = 4, kActorMaxWidth = 64, kActorMaxParams = 8192, kActorMaxActions = 8;
+struct ActorNet {
+    const float *w;                            // packed block: layer l at w + off[l] (actor_forward)
+    int32_t layers, action_n;
+    int32_t win[kActorMaxLayers], wout[kActorMaxLayers], off[kActorMaxLayers];
+};
+struct ActorHist {
+    float *hist; int64_t stride;               // [history][obs_dim][stride] float32, a ring
+    int32_t history, obs_dim;
+    int32_t slot;                              // ring slot of the newest observation (push: the slot this push writes)
+    int64_t n;
+};
+struct ActorAct { float epsilon; uint64_t seed, lane_offset, tick; };
 
 typedef __attribute__((address_space(4))) const float cfloat;   // scalar-cache (constant address space) view of the weights
 
@@ -407,6 +426,9 @@ static hipError_t launch_actor_rollout_env(bool autoreset, bool extras, bool rec
 
 static inline dim3 lane_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+namespace {
+
+// floats of the packed block for widths[0 .. layers]; off[l] = where layer l starts
 int64_t actor_packed_floats(const int32_t *widths, int32_t layers, int32_t (&off)[kActorMaxLayers]) {
     int64_t total = 0;
     for (int l = 0; l < layers; ++l) {
@@ -422,8 +444,7 @@ hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *pack
 }
 
 template <class R>
-static hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int64_t obs_stride, const uint8_t *restart, bool push,
-                                          hipStream_t st) {
+hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st) {
     switch (hs.obs_dim) {
         case 2: hipLaunchKernelGGL((actor_push_kernel<R, 2>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
         case 4: hipLaunchKernelGGL((actor_push_kernel<R, 4>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
@@ -433,6 +454,8 @@ static hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int
     return hipGetLastError();
 }
 
+// push = true: lanes with restart[k] != 0 write every slot, the others slot hs.slot; push = false (reset): lanes with restart[k] != 0
+// (NULL: every lane) write every slot, the others nothing.  obs: the CURRENT observation buffer, float or double (f64)
 hipError_t launch_actor_push(bool f64, const ActorHist &hs, const void *obs, int64_t obs_stride, const uint8_t *restart, bool push,
                              hipStream_t st) {
     if (hs.n <= 0) return hipSuccess;
@@ -451,15 +474,168 @@ hipError_t launch_actor_act(const ActorNet &net, const ActorHist &hs, int32_t *a
     return hipGetLastError();
 }
 
-hipError_t launch_actor_rollout(int env_id, bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                const ActorHist &hs, hipStream_t st) {
+}  // namespace
+
+// the configured actor: hist.slot is the ring slot of the newest observation; last: the handle's step counters at the last config, reset,
+// push or actor rollout, so act can tell that the history is current and push that exactly one vector step ran in between
+struct Actor { DeviceAllocs mem; ActorNet net{}; ActorHist hist{}; int64_t count = 0, packed = 0; StepMark last; };
+
+int release_actor(gymnet_vecenv *h) { return release_attachment(h, h->actor); }
+
+namespace {
+
+int need_actor(gymnet_vecenv *h) {
+    return h->actor ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no actor configured (gymnet_vecenv_actor_config)");
+}
+
+// the history is current: no vector step since the last actor config, reset, push or actor rollout
+bool actor_current(const gymnet_vecenv *h) { return since(h, h->actor->last) == StepMark{0, 0}; }
+
+int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
+    HIP_TRY(h, launch_actor_push(h->f64, h->actor->hist, h->d_obs, h->ostride, d_mask, false, h->stream));
+    h->actor->last = mark(h);
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int actor_rollout_check(gymnet_vecenv *h) {
+    ST_TRY(need_actor(h));
+    if (!actor_current(h)) return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: reset the actor (or push) before an actor rollout");
+    return GYMNET_OK;
+}
+
+// float32 CartPole / MountainCar / Acrobot
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
+    const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
-    switch (env_id) {
-        case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(autoreset, extras, records, a, r, net, hs, st);
-        case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(autoreset, extras, records, a, r, net, hs, st);
-        case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(autoreset, extras, records, a, r, net, hs, st);
+    switch (h->cfg.env_id) {
+        case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
+        case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
+        case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
         default: return hipErrorInvalidValue;
     }
 }
 
+// the kernel pushed every step: the history is current, its newest slot moved `steps` on
+void actor_rollout_done(gymnet_vecenv *h, int64_t steps) {
+    ActorHist &hs = h->actor->hist;
+    hs.slot = (int32_t)(((int64_t)hs.slot + steps) % hs.history);
+    h->actor->last = mark(h);
+}
+
 }  // namespace gymnet
+
+using namespace gymnet;
+
+extern "C" {
+
+int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
+                               int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (num_layers == 0) return release_actor(h);
+    const EnvDesc &d = *h->desc;
+    if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions; %s has a Box action space", d.name);
+    if (num_layers < 1 || num_layers > kActorMaxLayers) return fail(h, GYMNET_ERR_INVALID_ARG, "num_layers %d not in [0, %d]", num_layers, kActorMaxLayers);
+    if (!widths || !weights) return fail(h, GYMNET_ERR_INVALID_ARG, "widths / weights is null");
+    if (history < 1 || (int64_t)history * d.obs_dim > kActorMaxWidth)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "history %d: history * obs_dim must be in [1, %d]", history, kActorMaxWidth);
+    if (d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
+    int64_t params = 0;
+    for (int l = 0; l <= num_layers; ++l)
+        if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
+    for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
+    if (widths[0] != history * d.obs_dim) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], history * d.obs_dim);
+    if (widths[num_layers] != d.action_n) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != action_n = %d", num_layers, widths[num_layers], d.action_n);
+    if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
+    if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
+    std::unique_ptr<Actor> fresh(new Actor);
+    ActorNet &net = fresh->net;
+    net.layers = num_layers; net.action_n = d.action_n;
+    for (int l = 0; l < num_layers; ++l) { net.win[l] = widths[l]; net.wout[l] = widths[l + 1]; }
+    fresh->count = params;
+    fresh->packed = actor_packed_floats(widths, num_layers, net.off);
+    // the packed block, the weights as given (torch layout: the pack kernel's input) and the history: all three, or the old actor stays
+    const size_t flat_bytes = sizeof(float) * (size_t)params;
+    float *packed = static_cast<float *>(fresh->mem.take(sizeof(float) * (size_t)fresh->packed));
+    float *flat = packed ? static_cast<float *>(fresh->mem.take(flat_bytes)) : nullptr;
+    float *hist = flat ? static_cast<float *>(fresh->mem.take(sizeof(float) * (size_t)history * (size_t)d.obs_dim * (size_t)h->n)) : nullptr;
+    if (!hist) return fail(h, GYMNET_ERR_OOM, "hipMalloc of the actor (%lld parameters, %d x %d x %lld history) failed", (long long)params, history, d.obs_dim, (long long)h->n);
+    net.w = packed;
+    ActorHist &hs = fresh->hist;
+    hs.hist = hist; hs.stride = h->n; hs.history = history; hs.obs_dim = d.obs_dim; hs.slot = 0; hs.n = h->n;
+    ST_TRY(release_actor(h));
+    h->actor = fresh.release();
+    HIP_TRY(h, hipMemcpyAsync(flat, weights, flat_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, launch_actor_pack(net, flat, packed, h->actor->packed, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));     // the caller's host weights may go away when we return
+    return actor_refill(h, nullptr);
+    });
+}
+
+int gymnet_vecenv_actor_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    const Actor &ac = *h->actor;
+    if (!d_weights) return fail(h, GYMNET_ERR_INVALID_ARG, "d_weights is null");
+    if (count != ac.count) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != the actor's %lld parameters", (long long)count, (long long)ac.count);
+    HIP_TRY(h, launch_actor_pack(ac.net, d_weights, const_cast<float *>(ac.net.w), ac.packed, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    return actor_refill(h, d_mask);
+    });
+}
+
+int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    Actor &ac = *h->actor;
+    if (!(since(h, ac.last) == StepMark{1, 1}))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "an actor push needs exactly one vector step since the last actor config, reset or push (tick %llu -> %llu, "
+                    "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)ac.last.tick,
+                    (unsigned long long)h->tick, (unsigned long long)since(h, ac.last).launches);
+    ActorHist hs = ac.hist;
+    hs.slot = hs.slot + 1 == hs.history ? 0 : hs.slot + 1;
+    HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));
+    ac.hist = hs;
+    ac.last = mark(h);
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
+    if (!actor_current(h))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
+    ActorAct aa{};
+    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
+    HIP_TRY(h, launch_actor_act(h->actor->net, h->actor->hist, d_actions, d_logits, aa, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (d_history) *d_history = h->actor->hist.hist;
+    if (lane_stride) *lane_stride = h->actor->hist.stride;
+    if (slot) *slot = h->actor->hist.slot;
+    return GYMNET_OK;
+    });
+}
+
+}  // extern "C"

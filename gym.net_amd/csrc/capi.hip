@@ -94,7 +94,6 @@ void drop_graphs(gymnet_vecenv *h) {
     h->graphs.clear();
 }
 
-int apply_policy(gymnet_vecenv *h, const gymnet_launch_policy &p, bool strict);
 template <class R>
 StepArgsT<R> make_step_args(gymnet_vecenv *h, const void *d_actions) {
     StepArgsT<R> a{};
@@ -486,10 +485,6 @@ int stage_host_actions(gymnet_vecenv *h, const void *actions, const void **d_use
     return validate_now ? validate_staged_actions(h, *d_use) : GYMNET_OK;
 }
 
-}  // namespace gymnet
-
-namespace gymnet {
-
 // `steps` vector steps, one kernel launch each (caller has ENTERed the handle)
 int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride, int64_t ring, int graph_mode) {
     if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
@@ -564,10 +559,6 @@ int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_
     for (; t < steps; ++t) ST_TRY(launch_one_step(h, slice(t)));
     return GYMNET_OK;
 }
-
-}  // namespace gymnet
-
-namespace gymnet {
 
 // ~1.5 us per poll over PCIe: the resident kernel leaves after ~4-5 ms without a command (rounds 4-5: 40000 polls = 50-75 ms).  While
 // it spins it occupies the handle's stream and one wave, and anything that waits for the WHOLE device — hipDeviceSynchronize,
@@ -751,10 +742,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     drop_graphs(h);
     for (void *p : h->owned) (void)hipFree(p);
     if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
-    if (h->d_render) (void)hipFree(h->d_render);
-    if (h->stack_alloc) (void)hipFree(h->stack_alloc);
-    for (void *p : h->mem_allocs) (void)hipFree(p);
-    for (void *p : h->actor_allocs) (void)hipFree(p);
+    (void)release_render(h); (void)release_stack(h); (void)release_memory(h); (void)release_actor(h);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1161,10 +1149,6 @@ int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, 
 
 namespace {
 
-int need_actor(gymnet_vecenv *h);
-bool actor_current(const gymnet_vecenv *h);
-void actor_mark(gymnet_vecenv *h);
-
 // segment buffers of the fused rollout's episode records: kShards segments of `cap` records each (t, lane, return, length) +
 // the shard counters.  Random lanes do not fill the shards evenly, so a segment gets twice its share of the caller's capacity —
 // and what a shard still cannot hold (lanes that finish very unevenly) goes to ONE shared overflow segment of `capacity` records
@@ -1207,7 +1191,7 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
     }
     if constexpr (sizeof(R) == 4) {
         if (sp.action_source == GYMNET_ACTIONS_ACTOR) {
-            HIP_TRY(h, launch_actor_rollout(h->cfg.env_id, h->autoreset, h->extras, episodes, a, r, h->actor, h->actor_hist, h->stream));
+            HIP_TRY(h, actor_rollout_launch(h, episodes, a, r));
         } else {
             HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
         }
@@ -1255,8 +1239,7 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
         if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions");
         if (h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout runs float32 handles (float64: act / step / push)");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-        ST_TRY(need_actor(h));
-        if (!actor_current(h)) return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: reset the actor (or push) before an actor rollout");
+        ST_TRY(actor_rollout_check(h));
     }
     if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && ring_read)
         return fail(h, GYMNET_ERR_UNSUPPORTED, "VALIDATE_ACTIONS is per step; use gymnet_vecenv_rollout_device (sampled actions are valid by construction)");
@@ -1296,10 +1279,7 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
     h->tslot ^= 1;                       // one launch: it read one half of d_tick2 and wrote the other
     h->step_launches += 1;
     h->lane_steps += (uint64_t)sp.steps * (uint64_t)h->n;
-    if (actor) {                         // the kernel pushed every step: the history is current, its newest slot moved `steps` on
-        h->actor_hist.slot = (int32_t)(((int64_t)h->actor_hist.slot + sp.steps) % h->actor_hist.history);
-        actor_mark(h);
-    }
+    if (actor) actor_rollout_done(h, sp.steps);
     return GYMNET_OK;
     });
 }
@@ -1359,578 +1339,6 @@ int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity) {
     return guarded([&]() -> int {
     if (!h || !buf || capacity < 1) return fail(h, GYMNET_ERR_INVALID_ARG, "null handle / buffer");
     next_step_kernel(h, h->lcfg).name(buf, (size_t)capacity);
-    return GYMNET_OK;
-    });
-}
-
-// ---- CartPole frames (render.hip) ------------------------------------------------------------------------------------------
-namespace {
-
-// the crop / output-size rules every frame request shares (gymnet_vecenv_render_device)
-int check_crop_and_size(gymnet_vecenv *h, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h) {
-    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > kRenderWidth - crop_w || crop_y > kRenderHeight - crop_h)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "crop (%d, %d, %d, %d) not inside the %dx%d canvas", crop_x, crop_y, crop_w, crop_h, kRenderWidth, kRenderHeight);
-    if (out_w < 1 || out_h < 1 || out_w > kRenderMaxSide || out_h > kRenderMaxSide)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "output size %dx%d not in [1, %d]", out_w, out_h, kRenderMaxSide);
-    return GYMNET_OK;
-}
-
-// Checks a render request (nothing is written on failure) and fills the kernel arguments; *bytes = the span the frames cover.
-int render_args(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
-                int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride, RenderArgs *a, int64_t *bytes) {
-    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "rendering exists for CartPole only (CartPoleEnv.cs:69-135)");
-    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
-    if (format != GYMNET_PIXELS_RGB8 && format != GYMNET_PIXELS_GRAY8) return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel format %d", format);
-    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
-                    (long long)count, (long long)h->n);
-    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
-    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
-    if (lane_stride < frame) return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one frame", (long long)lane_stride, (long long)frame);
-    if (lane_stride > (INT64_MAX - frame) / count) return fail(h, GYMNET_ERR_INVALID_ARG, "count x lane_stride overflows");
-    a->obs = h->d_obs; a->obs_stride = h->ostride;
-    a->first_lane = first_lane;
-    a->out = static_cast<uint8_t *>(out); a->lane_stride = lane_stride;
-    a->waves_per_frame = render_waves_per_frame(out_w, out_h);
-    a->total_waves = count * a->waves_per_frame;
-    a->out_w = out_w; a->out_h = out_h;
-    a->x0 = (float)crop_x; a->y0 = (float)crop_y;
-    a->sxq = (float)((double)crop_w / (4.0 * out_w));
-    a->syq = (float)((double)crop_h / (4.0 * out_h));
-    *bytes = (count - 1) * lane_stride + frame;
-    return GYMNET_OK;
-}
-
-}  // namespace
-
-int gymnet_vecenv_render_device(gymnet_vecenv *h, void *d_out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x,
-                                int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    RenderArgs a{};
-    int64_t bytes = 0;
-    ST_TRY(render_args(h, d_out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
-    HIP_TRY(h, launch_render(h->f64, format == GYMNET_PIXELS_RGB8 ? 3 : 1, a, h->stream));
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
-                         int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    RenderArgs a{};
-    int64_t bytes = 0;
-    ST_TRY(render_args(h, out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
-    if (h->render_cap < (size_t)bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_render) (void)hipFree(h->d_render);
-        h->d_render = nullptr; h->render_cap = 0;
-        hipError_t e = hipMalloc(&h->d_render, (size_t)bytes);
-        if (e != hipSuccess) return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the render staging failed: %s", (long long)bytes, hipGetErrorString(e));
-        h->render_cap = (size_t)bytes;
-    }
-    a.out = static_cast<uint8_t *>(h->d_render);
-    HIP_TRY(h, launch_render(h->f64, format == GYMNET_PIXELS_RGB8 ? 3 : 1, a, h->stream));
-    // only the frames' own bytes cross: the caller's gaps between them (lane_stride > one frame) stay as they were
-    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
-    if (lane_stride == frame) {
-        HIP_TRY(h, hipMemcpyAsync(out, h->d_render, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return GYMNET_OK;
-    }
-    std::vector<uint8_t> span((size_t)bytes);
-    HIP_TRY(h, hipMemcpyAsync(span.data(), h->d_render, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int64_t k = 0; k < count; ++k) std::memcpy(static_cast<uint8_t *>(out) + k * lane_stride, span.data() + k * lane_stride, (size_t)frame);
-    return GYMNET_OK;
-    });
-}
-
-// ---- CartPole pixel frame stacks (pixel_stack.hip) ------------------------------------------------------------------------
-namespace {
-
-constexpr int32_t kStackMaxDepth = 64;
-
-int need_stack(gymnet_vecenv *h) {
-    return h->stack.depth > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no pixel stack configured (gymnet_vecenv_pixel_stack_config)");
-}
-
-// one launch over every lane of the configured stack, from the CURRENT observation buffer: shift = 1 push, 0 reset (StackArgs)
-int launch_stack(gymnet_vecenv *h, const uint8_t *restart, int32_t shift) {
-    StackArgs a = h->stack;
-    a.obs = h->d_obs; a.obs_stride = h->ostride;
-    a.restart = restart; a.shift = shift;
-    HIP_TRY(h, launch_pixel_stack(h->f64, h->stack_format, a, h->stream));
-    return GYMNET_OK;
-}
-
-// drops the configured stack (frees it when the handle allocated it: after the stream has drained, a launch may still use it)
-int release_stack(gymnet_vecenv *h) {
-    if (h->stack_alloc) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipFree(h->stack_alloc));
-    }
-    h->stack_alloc = nullptr;
-    h->stack = StackArgs{};
-    h->stack_format = 0;
-    return GYMNET_OK;
-}
-
-}  // namespace
-
-int gymnet_vecenv_pixel_stack_config(gymnet_vecenv *h, int32_t format, int32_t depth, int32_t crop_x, int32_t crop_y, int32_t crop_w,
-                                     int32_t crop_h, int32_t out_w, int32_t out_h, void *d_ext, int64_t lane_stride) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel stacks exist for CartPole only (CartPoleEnv.cs:69-135)");
-    if (depth == 0) return release_stack(h);
-    if (format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel stack format %d", format);
-    if (depth < 0 || depth > kStackMaxDepth) return fail(h, GYMNET_ERR_INVALID_ARG, "depth %d not in [0, %d]", depth, kStackMaxDepth);
-    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
-    const int64_t elem = format == GYMNET_STACK_BINARY_F32 ? 4 : 1;
-    const int64_t frame = (int64_t)out_w * out_h * elem, span = (int64_t)depth * frame;
-    if (lane_stride == 0) lane_stride = span;
-    if (lane_stride < span)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one stack", (long long)lane_stride, (long long)span);
-    if (h->n > 1 && lane_stride > (INT64_MAX - span) / (h->n - 1)) return fail(h, GYMNET_ERR_INVALID_ARG, "num_envs x lane_stride overflows");
-    if (elem == 4 && ((reinterpret_cast<uintptr_t>(d_ext) & 3u) != 0 || lane_stride % 4 != 0))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 stacks need a 4-byte aligned d_ext and lane_stride");
-    const int64_t bytes = (h->n - 1) * lane_stride + span;
-    void *alloc = nullptr;
-    if (!d_ext) {
-        if (h->stack_alloc) HIP_TRY(h, hipStreamSynchronize(h->stream));      // the old stack is still there if this allocation fails
-        hipError_t e = hipMalloc(&alloc, (size_t)bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the pixel stack failed: %s", (long long)bytes, hipGetErrorString(e));
-        }
-    }
-    if (int st = release_stack(h); st != GYMNET_OK) {
-        if (alloc) (void)hipFree(alloc);
-        return st;
-    }
-    StackArgs &a = h->stack;
-    a.base = static_cast<uint8_t *>(d_ext ? d_ext : alloc);
-    a.lane_stride = lane_stride; a.frame_bytes = frame;
-    a.depth = depth;
-    a.waves_per_frame = render_waves_per_frame(out_w, out_h);
-    a.total_waves = h->n * a.waves_per_frame;
-    a.out_w = out_w; a.out_h = out_h;
-    a.x0 = (float)crop_x; a.y0 = (float)crop_y;                        // the sample positions of render_args
-    a.sxq = (float)((double)crop_w / (4.0 * out_w));
-    a.syq = (float)((double)crop_h / (4.0 * out_h));
-    h->stack_format = format;
-    h->stack_alloc = alloc;
-    return launch_stack(h, nullptr, 0);
-    });
-}
-
-int gymnet_vecenv_pixel_stack_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_stack(h));
-    return launch_stack(h, d_mask, 0);
-    });
-}
-
-int gymnet_vecenv_pixel_stack_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_stack(h));
-    // without a done array an auto-reset handle restarts the lanes its most recent step finished (and already re-drew)
-    return launch_stack(h, d_done ? d_done : (h->autoreset ? h->d_done : nullptr), 1);
-    });
-}
-
-int gymnet_vecenv_pixel_stack_view(gymnet_vecenv *h, void **d_stack, int64_t *lane_stride, int64_t *frame_bytes) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_stack(h));
-    if (d_stack) *d_stack = h->stack.base;
-    if (lane_stride) *lane_stride = h->stack.lane_stride;
-    if (frame_bytes) *frame_bytes = h->stack.frame_bytes;
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_lane, int64_t count) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_stack(h));
-    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
-    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
-                    (long long)count, (long long)h->n);
-    const StackArgs &a = h->stack;
-    const int64_t span = (int64_t)a.depth * a.frame_bytes;
-    const uint8_t *src = a.base + first_lane * a.lane_stride;
-    if (a.lane_stride == span) HIP_TRY(h, hipMemcpyAsync(out, src, (size_t)(count * span), hipMemcpyDeviceToHost, h->stream));
-    else HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)span, src, (size_t)a.lane_stride, (size_t)span, (size_t)count, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GYMNET_OK;
-    });
-}
-
-// ---- episode memory (episode_memory.hip) ---------------------------------------------------------------------------------
-namespace {
-
-constexpr int32_t kMemoryMaxCapacity = 65536;
-constexpr int32_t kMemoryMaxHistory = 64;
-constexpr int32_t kMemoryMaxLength = 1 << 24;
-
-int need_memory(gymnet_vecenv *h) {
-    return h->mem.capacity > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no episode memory configured (gymnet_vecenv_memory_config)");
-}
-
-// drops the configured memory after the stream has drained (a launch may still use it)
-int release_memory(gymnet_vecenv *h) {
-    if (!h->mem_allocs.empty()) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (void *p : h->mem_allocs) (void)hipFree(p);
-    h->mem_allocs.clear();
-    h->mem = MemoryArgs{};
-    h->mem_history = 0;
-    return GYMNET_OK;
-}
-
-// the kept entries [0, kept) and the control block, read back after the stream has drained
-int read_pool(gymnet_vecenv *h, MemCtl *ctl, std::vector<MemEntry> *meta) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(ctl, h->mem.ctl, sizeof *ctl, hipMemcpyDeviceToHost));
-    if (meta) {
-        meta->resize((size_t)ctl->kept);
-        if (ctl->kept > 0) HIP_TRY(h, hipMemcpy(meta->data(), h->mem.meta, sizeof(MemEntry) * (size_t)ctl->kept, hipMemcpyDeviceToHost));
-    }
-    return GYMNET_OK;
-}
-
-}  // namespace
-
-int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (capacity == 0) return release_memory(h);
-    if (capacity < 0 || capacity > kMemoryMaxCapacity)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %d not in [0, %d]", capacity, kMemoryMaxCapacity);
-    if (history < 1 || history > kMemoryMaxHistory) return fail(h, GYMNET_ERR_INVALID_ARG, "history %d not in [1, %d]", history, kMemoryMaxHistory);
-    const int32_t len = max_length == 0 ? h->cfg.max_episode_steps : max_length;
-    if (max_length < 0 || len < 1 || len > kMemoryMaxLength)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "max_length %d not in [1, %d] (0 = max_episode_steps, which is %d)", max_length, kMemoryMaxLength,
-                    h->cfg.max_episode_steps);
-    const int obs_dim = h->desc->obs_dim;
-    const int64_t row = (int64_t)obs_dim * (int64_t)h->esz + 8;
-    const double ring_d = (double)(len + 1) * (double)h->n * (double)row, pool_d = (double)capacity * (double)len * (double)row;
-    if (ring_d > 9.0e18 || pool_d > 9.0e18) return fail(h, GYMNET_ERR_INVALID_ARG, "episode memory of %.3g bytes overflows", ring_d + pool_d);
-    MemoryArgs m{};
-    m.n = h->n; m.obs_dim = obs_dim; m.esz = (int32_t)h->esz;
-    m.max_len = len; m.capacity = capacity;
-    m.slot_bytes = h->n * row; m.row_bytes = row;
-    m.push_blocks = memory_push_blocks(h->n);
-    // every region (ring, pool, per-lane state, candidates, control, pool entries, scratch, row offsets, counters) or none
-    std::vector<void *> got;
-    auto take = [&](void **p, int64_t bytes) -> bool {
-        hipError_t e = hipMalloc(p, (size_t)(bytes > 0 ? bytes : 1));
-        if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-        got.push_back(*p);
-        return true;
-    };
-    void *ring, *pool, *lane_len, *lane_ret, *cand, *ctl, *meta, *meta_tmp, *scratch, *row_off, *partials;
-    const bool ok = take(&ring, (int64_t)(len + 1) * m.slot_bytes) && take(&pool, (int64_t)capacity * len * row) &&
-                    take(&lane_len, 4 * h->n) && take(&lane_ret, 4 * h->n) && take(&cand, (int64_t)sizeof(MemCand) * h->n) &&
-                    take(&ctl, sizeof(MemCtl)) && take(&meta, (int64_t)sizeof(MemEntry) * capacity) &&
-                    take(&meta_tmp, (int64_t)sizeof(MemEntry) * capacity) && take(&scratch, 4 * (int64_t)capacity) &&
-                    take(&row_off, 8 * ((int64_t)capacity + 1)) && take(&partials, 16 * (int64_t)m.push_blocks);
-    if (!ok) {
-        for (void *p : got) (void)hipFree(p);
-        return fail(h, GYMNET_ERR_OOM, "hipMalloc of the episode memory (%.3g bytes) failed", ring_d + pool_d);
-    }
-    if (int st = release_memory(h); st != GYMNET_OK) {
-        for (void *p : got) (void)hipFree(p);
-        return st;
-    }
-    m.ring = static_cast<uint8_t *>(ring); m.pool = static_cast<uint8_t *>(pool);
-    m.lane_len = static_cast<int32_t *>(lane_len); m.lane_ret = static_cast<float *>(lane_ret);
-    m.cand = static_cast<MemCand *>(cand); m.ctl = static_cast<MemCtl *>(ctl);
-    m.meta = static_cast<MemEntry *>(meta); m.meta_tmp = static_cast<MemEntry *>(meta_tmp);
-    m.scratch = static_cast<int32_t *>(scratch); m.row_off = static_cast<int64_t *>(row_off);
-    m.partials = static_cast<uint64_t *>(partials);
-    h->mem = m;
-    h->mem_allocs = got;
-    h->mem_history = history;
-    h->mem_pos = 0;
-    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
-    HIP_TRY(h, launch_memory_init(h->mem, h->stream));
-    HIP_TRY(h, launch_memory_open(h->f64, h->mem, h->d_obs, h->ostride, nullptr, 0, h->stream));
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, int32_t clear_pool) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    if (clear_pool) HIP_TRY(h, launch_memory_init(h->mem, h->stream));
-    HIP_TRY(h, launch_memory_open(h->f64, h->mem, h->d_obs, h->ostride, d_mask, (int64_t)(h->mem_pos % (uint64_t)(h->mem.max_len + 1)), h->stream));
-    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, const uint8_t *d_done) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (h->tick != h->mem_tick + 1 || h->step_launches != h->mem_launches + 1)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
-                    "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device", (unsigned long long)h->mem_tick,
-                    (unsigned long long)h->tick, (unsigned long long)(h->step_launches - h->mem_launches));
-    MemPushArgs p{};
-    p.obs = h->d_obs; p.obs_stride = h->ostride;
-    p.actions = d_actions; p.reward = h->d_reward; p.done = d_done ? d_done : h->d_done;
-    p.slot = (int64_t)(h->mem_pos % (uint64_t)(h->mem.max_len + 1));
-    p.end_tick = h->tick;
-    p.autoreset = h->autoreset ? 1 : 0;
-    HIP_TRY(h, launch_memory_push(h->f64, h->mem, p, h->stream));
-    h->mem_pos += 1;
-    h->mem_tick = h->tick; h->mem_launches = h->step_launches;
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_stats(gymnet_vecenv *h, int64_t *kept, int64_t *ended, int64_t *admitted, int64_t *too_long) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    MemCtl ctl{};
-    ST_TRY(read_pool(h, &ctl, nullptr));
-    std::vector<uint64_t> part((size_t)h->mem.push_blocks * 2);
-    HIP_TRY(h, hipMemcpy(part.data(), h->mem.partials, part.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    uint64_t e = 0, t = 0;
-    for (size_t b = 0; b < part.size(); b += 2) { e += part[b]; t += part[b + 1]; }
-    if (kept) *kept = ctl.kept;
-    if (ended) *ended = (int64_t)e;
-    if (admitted) *admitted = (int64_t)ctl.admitted;
-    if (too_long) *too_long = (int64_t)t;
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, uint64_t *end_tick, int32_t *lane, int64_t capacity,
-                                  int64_t *count) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    if (capacity < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %lld < 0", (long long)capacity);
-    MemCtl ctl{};
-    std::vector<MemEntry> meta;
-    ST_TRY(read_pool(h, &ctl, &meta));
-    auto ret_order = [](float r) { return r == 0.0f ? 0.0f : r; };
-    std::sort(meta.begin(), meta.end(), [&](const MemEntry &a, const MemEntry &b) {     // descending key (return, tick, lane)
-        if (ret_order(a.ret) != ret_order(b.ret)) return ret_order(a.ret) > ret_order(b.ret);
-        if (a.tick != b.tick) return a.tick > b.tick;
-        return a.lane > b.lane;
-    });
-    const int64_t m = (int64_t)meta.size() < capacity ? (int64_t)meta.size() : capacity;
-    for (int64_t i = 0; i < m; ++i) {
-        if (ret) ret[i] = meta[(size_t)i].ret;
-        if (len) len[i] = meta[(size_t)i].len;
-        if (end_tick) end_tick[i] = meta[(size_t)i].tick;
-        if (lane) lane[i] = meta[(size_t)i].lane;
-    }
-    if (count) *count = (int64_t)meta.size();
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_dataset_size(gymnet_vecenv *h, int64_t *rows) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    if (!rows) return fail(h, GYMNET_ERR_INVALID_ARG, "rows is null");
-    MemCtl ctl{};
-    std::vector<MemEntry> meta;
-    ST_TRY(read_pool(h, &ctl, &meta));
-    int64_t r = 0;
-    for (const MemEntry &e : meta) r += (int64_t)e.len * 2 / 3;
-    *rows = r;
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
-                                        int32_t out_w, int32_t out_h, void *d_x, int32_t *d_action, float *d_onehot, float *d_reward,
-                                        int64_t capacity_rows) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_memory(h));
-    if (format != GYMNET_MEMORY_PARAMS && format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown dataset format %d", format);
-    if (format != GYMNET_MEMORY_PARAMS) {
-        if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel datasets exist for CartPole only (CartPoleEnv.cs:69-135)");
-        ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
-    }
-    if (capacity_rows < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity_rows %lld < 0", (long long)capacity_rows);
-    if (d_onehot && h->desc->box_action) return fail(h, GYMNET_ERR_INVALID_ARG, "a Box action has no one-hot");
-    if (format == GYMNET_STACK_BINARY_F32 && !aligned_to(d_x, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 rows need a 4-byte aligned d_x");
-    if (capacity_rows == 0) return GYMNET_OK;
-    MemDatasetArgs d{};
-    d.format = format; d.history = h->mem_history;
-    d.x = d_x; d.action = d_action; d.onehot = d_onehot; d.reward = d_reward;
-    d.capacity_rows = capacity_rows;
-    d.action_n = h->desc->box_action ? 0 : h->desc->action_n;
-    if (format != GYMNET_MEMORY_PARAMS) {
-        d.waves_per_frame = render_waves_per_frame(out_w, out_h);
-        d.out_w = out_w; d.out_h = out_h;
-        d.x0 = (float)crop_x; d.y0 = (float)crop_y;                    // the sample positions of the pixel stack
-        d.sxq = (float)((double)crop_w / (4.0 * out_w));
-        d.syq = (float)((double)crop_h / (4.0 * out_h));
-    }
-    HIP_TRY(h, launch_memory_dataset(h->f64, h->mem, d, h->stream));
-    return GYMNET_OK;
-    });
-}
-
-// ---- the actor (actor.hip) ----------------------------------------------------------------------------------------------------
-namespace {
-
-int need_actor(gymnet_vecenv *h) {
-    return h->actor.layers > 0 ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no actor configured (gymnet_vecenv_actor_config)");
-}
-
-// the history is current: no vector step since the last actor config, reset, push or actor rollout
-bool actor_current(const gymnet_vecenv *h) { return h->tick == h->actor_tick && h->step_launches == h->actor_launches; }
-
-void actor_mark(gymnet_vecenv *h) { h->actor_tick = h->tick; h->actor_launches = h->step_launches; }
-
-// drops the configured actor after the stream has drained (a launch may still use it)
-int release_actor(gymnet_vecenv *h) {
-    if (!h->actor_allocs.empty()) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (void *p : h->actor_allocs) (void)hipFree(p);
-    h->actor_allocs.clear();
-    h->actor = ActorNet{}; h->actor_hist = ActorHist{};
-    h->actor_count = 0; h->actor_packed = 0; h->actor_flat = nullptr;
-    return GYMNET_OK;
-}
-
-int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
-    HIP_TRY(h, launch_actor_push(h->f64, h->actor_hist, h->d_obs, h->ostride, d_mask, false, h->stream));
-    actor_mark(h);
-    return GYMNET_OK;
-}
-
-}  // namespace
-
-int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
-                               int64_t count) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (num_layers == 0) return release_actor(h);
-    const EnvDesc &d = *h->desc;
-    if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions; %s has a Box action space", d.name);
-    if (num_layers < 1 || num_layers > kActorMaxLayers) return fail(h, GYMNET_ERR_INVALID_ARG, "num_layers %d not in [0, %d]", num_layers, kActorMaxLayers);
-    if (!widths || !weights) return fail(h, GYMNET_ERR_INVALID_ARG, "widths / weights is null");
-    if (history < 1 || (int64_t)history * d.obs_dim > kActorMaxWidth)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "history %d: history * obs_dim must be in [1, %d]", history, kActorMaxWidth);
-    if (d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
-    int64_t params = 0;
-    for (int l = 0; l <= num_layers; ++l)
-        if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
-    for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
-    if (widths[0] != history * d.obs_dim) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], history * d.obs_dim);
-    if (widths[num_layers] != d.action_n) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != action_n = %d", num_layers, widths[num_layers], d.action_n);
-    if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
-    if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
-    ActorNet net{};
-    net.layers = num_layers; net.action_n = d.action_n;
-    for (int l = 0; l < num_layers; ++l) { net.win[l] = widths[l]; net.wout[l] = widths[l + 1]; }
-    const int64_t packed = actor_packed_floats(widths, num_layers, net.off);
-    ST_TRY(release_actor(h));
-    const int64_t stride = h->n;
-    const size_t sizes[3] = {sizeof(float) * (size_t)packed, sizeof(float) * (size_t)params,
-                             sizeof(float) * (size_t)history * (size_t)d.obs_dim * (size_t)(stride > 0 ? stride : 1)};
-    void *got[3] = {nullptr, nullptr, nullptr};
-    for (int q = 0; q < 3; ++q) {
-        hipError_t e = hipMalloc(&got[q], sizes[q]);
-        if (e != hipSuccess) {
-            for (void *p : got) if (p) (void)hipFree(p);
-            return fail(h, GYMNET_ERR_OOM, "hipMalloc(%zu bytes) for the actor failed: %s", sizes[q], hipGetErrorString(e));
-        }
-    }
-    h->actor_allocs.assign(got, got + 3);
-    net.w = static_cast<float *>(got[0]);
-    h->actor_flat = static_cast<float *>(got[1]);
-    ActorHist hs{};
-    hs.hist = static_cast<float *>(got[2]); hs.stride = stride; hs.history = history; hs.obs_dim = d.obs_dim; hs.slot = 0; hs.n = h->n;
-    h->actor = net; h->actor_hist = hs;
-    for (int l = 0; l <= num_layers; ++l) h->actor_widths[l] = widths[l];
-    h->actor_count = params; h->actor_packed = packed;
-    HIP_TRY(h, hipMemcpyAsync(h->actor_flat, weights, sizes[1], hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, launch_actor_pack(h->actor, h->actor_flat, const_cast<float *>(h->actor.w), packed, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));     // the caller's host weights may go away when we return
-    return actor_refill(h, nullptr);
-    });
-}
-
-int gymnet_vecenv_actor_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_actor(h));
-    if (!d_weights) return fail(h, GYMNET_ERR_INVALID_ARG, "d_weights is null");
-    if (count != h->actor_count) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != the actor's %lld parameters", (long long)count, (long long)h->actor_count);
-    HIP_TRY(h, launch_actor_pack(h->actor, d_weights, const_cast<float *>(h->actor.w), h->actor_packed, h->stream));
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_actor(h));
-    return actor_refill(h, d_mask);
-    });
-}
-
-int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_actor(h));
-    if (h->tick != h->actor_tick + 1 || h->step_launches != h->actor_launches + 1)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "an actor push needs exactly one vector step since the last actor config, reset or push (tick %llu -> %llu, "
-                    "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)h->actor_tick,
-                    (unsigned long long)h->tick, (unsigned long long)(h->step_launches - h->actor_launches));
-    ActorHist hs = h->actor_hist;
-    hs.slot = hs.slot + 1 == hs.history ? 0 : hs.slot + 1;
-    HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));
-    h->actor_hist = hs;
-    actor_mark(h);
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_actor(h));
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-    if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
-    ActorAct aa{};
-    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
-    HIP_TRY(h, launch_actor_act(h->actor, h->actor_hist, d_actions, d_logits, aa, h->stream));
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    ST_TRY(need_actor(h));
-    if (d_history) *d_history = h->actor_hist.hist;
-    if (lane_stride) *lane_stride = h->actor_hist.stride;
-    if (slot) *slot = h->actor_hist.slot;
     return GYMNET_OK;
     });
 }

@@ -13,6 +13,15 @@
 
 namespace gymnet {
 
+constexpr int32_t kRenderWidth = 600, kRenderHeight = 400;   // the reference's canvas (CartPoleEnv.cs:71-72)
+constexpr int32_t kRenderMaxSide = 16384;                    // output width / height limit (sample positions stay exact in float)
+
+// What every frame kernel needs to know about its frames; embedded in each one's argument struct (render.hip, pixel_stack.hip,
+// episode_memory.hip).  Sample (a, b) of pixel (i, j) is at x0 + (4 j + a + 0.5) * sxq, y0 + (4 i + b + 0.5) * syq.
+struct FrameGeom { int64_t waves_per_frame; int32_t out_w, out_h; float x0, y0, sxq, syq; };
+// the crop / output-size rules every frame request shares (gymnet_vecenv_render_device); render.hip
+int check_crop_and_size(gymnet_vecenv *h, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h);
+
 namespace {
 
 // CartPoleEnv.cs:69-135, the C# float constants: scale = screen_width / world_width, world_width = x_threshold * 2, polelen = scale * (2 * length)
@@ -22,6 +31,12 @@ constexpr float kPivotY = 295.0f;                         // the pole's pivot an
 constexpr float kVlo = 5.0f - kPoleLen;                   // pole rectangle in pole coordinates: u in [-5, 5], v in [5 - polelen, 5]
 constexpr int kPixPerThread = 16;
 constexpr int kPixPerWave = 64 * kPixPerThread;
+
+inline int64_t render_waves_per_frame(int32_t out_w, int32_t out_h) { return ((int64_t)out_w * out_h + kPixPerWave - 1) / kPixPerWave; }
+inline FrameGeom frame_geom(int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h) {
+    return {render_waves_per_frame(out_w, out_h), out_w, out_h, (float)crop_x, (float)crop_y,
+            (float)((double)crop_w / (4.0 * out_w)), (float)((double)crop_h / (4.0 * out_h))};
+}
 
 struct Geo {
     float cx, cl, cr;          // cart centre and its closed x-range [cx - 25, cx + 25]

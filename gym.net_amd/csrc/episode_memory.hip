@@ -18,13 +18,62 @@
 // Dataset (not per step): rank the kept keys (count of larger keys), scan the row counts floor(len * 2 / 3) in that order, then write
 // params rows (one thread per row) or frames re-rendered from the stored observations with cartpole_raster.hpp (one wave per 1024
 // pixels of one frame, as the pixel stack draws them).
-#include "cartpole_raster.hpp"
-
+//
+// The host side follows the kernels: gymnet_vecenv_memory_* and the handle's EpisodeMemory attachment.
+#include <algorithm>
 #include <type_traits>
+
+#include "cartpole_raster.hpp"
+#include "handle.hpp"
 
 namespace gymnet {
 
 namespace {
+
+// A kept episode's key is (ret, tick, lane), ordered lexicographically; `block` is the pool block [L][row] that holds its steps.
+struct MemEntry { float ret; int32_t len; uint64_t tick; int32_t lane, block; };
+struct MemCand { float ret; int32_t len, lane, pad; };      // an episode that passed the push's admission filter
+struct MemCtl {
+    uint32_t cand_count;       // candidates of the most recent push (the merge consumes them and zeroes this)
+    int32_t kept;              // pool entries [0, kept) are live
+    int32_t full;              // kept == capacity: the push admits an ended episode only when ret >= thr
+    float thr;                 // the lowest kept return (valid when full)
+    uint64_t admitted;         // episodes the merges put into the pool
+    uint64_t rows;             // dataset rows of the most recent dataset build
+};
+struct MemoryArgs {
+    int64_t n;
+    int32_t obs_dim, esz;                      // observation values per step and their size (4 float, 8 double)
+    int32_t max_len, capacity;                 // L and K
+    // staging ring [L + 1 slots]: slot s at ring + s * slot_bytes holds obs [obs_dim][n] (esz each), action [n] (4 B), reward [n] (4 B)
+    uint8_t *ring; int64_t slot_bytes;
+    // pool: block b at pool + b * max_len * row_bytes, row p = obs [obs_dim] (esz each), action (4 B), reward (4 B)
+    uint8_t *pool; int64_t row_bytes;
+    int32_t *lane_len;                         // steps of the lane's open episode (-1: the lane is closed)
+    float *lane_ret;                           // float32 sum of its rewards in step order
+    MemCand *cand;                             // [n]
+    MemCtl *ctl;
+    MemEntry *meta, *meta_tmp;                 // [capacity] each: live entries, then free blocks
+    int32_t *scratch;                          // [capacity]: free blocks during a merge, the descending key order during a dataset build
+    int64_t *row_off;                          // [capacity + 1]: first dataset row of the episode of rank r
+    uint64_t *partials;                        // [push_blocks][2]: episodes ended / too long, per push workgroup
+    int32_t push_blocks;                       // workgroups of a push launch
+};
+struct MemPushArgs {
+    const void *obs; int64_t obs_stride;       // the CURRENT observation buffer (after the step)
+    const void *actions; const float *reward; const uint8_t *done;
+    int64_t slot;                              // ring slot of this step (pos % (L + 1)); the next step's is (pos + 1) % (L + 1)
+    uint64_t end_tick;                         // engine tick after the step: the key of the episodes that end in it
+    int32_t autoreset;
+};
+// format 0 = params rows, else GYMNET_STACK_* frames drawn as the pixel stack draws them (geo: their sample positions)
+struct MemDatasetArgs {
+    int32_t format, history;
+    void *x; int32_t *action; float *onehot; float *reward;
+    int64_t capacity_rows;
+    int32_t action_n;                          // one-hot width (0: Box actions, no one-hot)
+    FrameGeom geo;
+};
 
 // a float's order as an unsigned integer (+0 and -0 are one value)
 __device__ __forceinline__ uint32_t ret_bits(float r) {
@@ -336,12 +385,12 @@ __global__ __launch_bounds__(256) void memory_frames_kernel(MemoryArgs m, MemDat
     const int64_t total = m.row_off[kept];
     const int64_t lim = total < d.capacity_rows ? total : d.capacity_rows;
     const int S = d.history;
-    const int64_t frame_px = (int64_t)d.out_w * d.out_h;
-    const int64_t total_waves = lim * S * d.waves_per_frame;
+    const int64_t frame_px = (int64_t)d.geo.out_w * d.geo.out_h;
+    const int64_t total_waves = lim * S * d.geo.waves_per_frame;
     const int lid = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); w < total_waves; w += nwaves) {
-        const int64_t f = w / d.waves_per_frame, slice = w - f * d.waves_per_frame;
+        const int64_t f = w / d.geo.waves_per_frame, slice = w - f * d.geo.waves_per_frame;
         const int64_t row = f / S;
         const int s = (int)(f - row * S);
         const int64_t p0 = slice * kPixPerWave + (int64_t)lid * kPixPerThread;
@@ -351,17 +400,17 @@ __global__ __launch_bounds__(256) void memory_frames_kernel(MemoryArgs m, MemDat
         const int64_t q = row - m.row_off[r] - (S - 1) + s;
         const R *o = reinterpret_cast<const R *>(m.pool + ((int64_t)e.block * m.max_len + (q > 0 ? q : 0)) * m.row_bytes);
         const Geo g = lane_geometry(o, 1, 0);
-        int i = (int)(p0 / d.out_w), j = (int)(p0 - (int64_t)i * d.out_w);
+        int i = (int)(p0 / d.geo.out_w), j = (int)(p0 - (int64_t)i * d.geo.out_w);
         uint8_t *out = static_cast<uint8_t *>(d.x) + (f * frame_px + p0) * E;
         const int cnt = frame_px - p0 < kPixPerThread ? (int)(frame_px - p0) : kPixPerThread;
 #pragma unroll 1
         for (int v = 0; v < cnt; ++v) {
             int nw, np;
-            shade(g, d.x0, d.sxq, d.y0, d.syq, i, j, nw, np);
+            shade(g, d.geo.x0, d.geo.sxq, d.geo.y0, d.geo.syq, i, j, nw, np);
             const uint32_t val = stack_value<FMT>(nw, np);
             if constexpr (E == 4) reinterpret_cast<uint32_t *>(out)[v] = val;
             else out[v] = (uint8_t)val;
-            if (++j == d.out_w) { j = 0; ++i; }
+            if (++j == d.geo.out_w) { j = 0; ++i; }
         }
     }
 }
@@ -377,7 +426,7 @@ hipError_t launch_dataset_typed(const MemoryArgs &m, const MemDatasetArgs &d, hi
     hipLaunchKernelGGL(memory_scan_kernel, dim3(1), dim3(1024), 0, st, m);
     hipLaunchKernelGGL((memory_rows_kernel<R>), dim3(grid_for(d.capacity_rows, 256, 1 << 14)), dim3(256), 0, st, m, d);
     if (d.format != 0 && d.x) {
-        const unsigned g = grid_for(d.capacity_rows * d.history * d.waves_per_frame, 4, 1 << 16);
+        const unsigned g = grid_for(d.capacity_rows * d.history * d.geo.waves_per_frame, 4, 1 << 16);
         if (d.format == GYMNET_STACK_GRAY8) hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_GRAY8>), dim3(g), dim3(256), 0, st, m, d);
         else if (d.format == GYMNET_STACK_BINARY8) hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_BINARY8>), dim3(g), dim3(256), 0, st, m, d);
         else hipLaunchKernelGGL((memory_frames_kernel<R, GYMNET_STACK_BINARY_F32>), dim3(g), dim3(256), 0, st, m, d);
@@ -385,8 +434,7 @@ hipError_t launch_dataset_typed(const MemoryArgs &m, const MemDatasetArgs &d, hi
     return hipGetLastError();
 }
 
-}  // namespace
-
+// an empty pool, zero counts
 hipError_t launch_memory_init(const MemoryArgs &m, hipStream_t st) {
     const int64_t items = m.capacity > 2 * (int64_t)m.push_blocks ? m.capacity : 2 * (int64_t)m.push_blocks;
     hipLaunchKernelGGL(memory_init_kernel, dim3(grid_for(items, 256, INT32_MAX)), dim3(256), 0, st, m);
@@ -412,10 +460,210 @@ hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &
     return hipGetLastError();
 }
 
-hipError_t launch_memory_dataset(bool f64, const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st) {
-    return f64 ? launch_dataset_typed<double>(m, d, st) : launch_dataset_typed<float>(m, d, st);
+constexpr int32_t kMemoryMaxCapacity = 65536;
+constexpr int32_t kMemoryMaxHistory = 64;
+constexpr int32_t kMemoryMaxLength = 1 << 24;
+
+}  // namespace
+
+// the configured memory: pos counts its pushes (the ring slot of the next step is pos % (max_len + 1)); last: the handle's step counters
+// at its last config, reset or push, so a push can tell that exactly one vector step ran in between
+struct EpisodeMemory { DeviceAllocs mem; MemoryArgs args{}; int32_t history = 0; uint64_t pos = 0; StepMark last; };
+
+int release_memory(gymnet_vecenv *h) { return release_attachment(h, h->memory); }
+
+namespace {
+
+int need_memory(gymnet_vecenv *h) {
+    return h->memory ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no episode memory configured (gymnet_vecenv_memory_config)");
 }
 
-int32_t memory_push_blocks(int64_t n) { return (int32_t)((n + kPushBlock - 1) / kPushBlock); }
+int64_t ring_slot(const EpisodeMemory &em) { return (int64_t)(em.pos % (uint64_t)(em.args.max_len + 1)); }
+
+// the kept entries [0, kept) and the control block, read back after the stream has drained
+int read_pool(gymnet_vecenv *h, MemCtl *ctl, std::vector<MemEntry> *meta) {
+    const MemoryArgs &m = h->memory->args;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(ctl, m.ctl, sizeof *ctl, hipMemcpyDeviceToHost));
+    if (meta) {
+        meta->resize((size_t)ctl->kept);
+        if (ctl->kept > 0) HIP_TRY(h, hipMemcpy(meta->data(), m.meta, sizeof(MemEntry) * (size_t)ctl->kept, hipMemcpyDeviceToHost));
+    }
+    return GYMNET_OK;
+}
+
+}  // namespace
 
 }  // namespace gymnet
+
+using namespace gymnet;
+
+extern "C" {
+
+int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (capacity == 0) return release_memory(h);
+    if (capacity < 0 || capacity > kMemoryMaxCapacity)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %d not in [0, %d]", capacity, kMemoryMaxCapacity);
+    if (history < 1 || history > kMemoryMaxHistory) return fail(h, GYMNET_ERR_INVALID_ARG, "history %d not in [1, %d]", history, kMemoryMaxHistory);
+    const int32_t len = max_length == 0 ? h->cfg.max_episode_steps : max_length;
+    if (max_length < 0 || len < 1 || len > kMemoryMaxLength)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "max_length %d not in [1, %d] (0 = max_episode_steps, which is %d)", max_length, kMemoryMaxLength,
+                    h->cfg.max_episode_steps);
+    const int obs_dim = h->desc->obs_dim;
+    const int64_t row = (int64_t)obs_dim * (int64_t)h->esz + 8;
+    const double ring_d = (double)(len + 1) * (double)h->n * (double)row, pool_d = (double)capacity * (double)len * (double)row;
+    if (ring_d > 9.0e18 || pool_d > 9.0e18) return fail(h, GYMNET_ERR_INVALID_ARG, "episode memory of %.3g bytes overflows", ring_d + pool_d);
+    std::unique_ptr<EpisodeMemory> fresh(new EpisodeMemory);
+    MemoryArgs &m = fresh->args;
+    m.n = h->n; m.obs_dim = obs_dim; m.esz = (int32_t)h->esz;
+    m.max_len = len; m.capacity = capacity;
+    m.slot_bytes = h->n * row; m.row_bytes = row;
+    m.push_blocks = (int32_t)((h->n + kPushBlock - 1) / kPushBlock);
+    // every region (ring, pool, per-lane state, candidates, control, pool entries, scratch, row offsets, counters) or none
+    bool ok = true;
+    auto take = [&](auto *&p, int64_t bytes) {
+        using P = std::remove_reference_t<decltype(p)>;
+        ok = ok && (p = static_cast<P>(fresh->mem.take((size_t)bytes))) != nullptr;
+    };
+    take(m.ring, (int64_t)(len + 1) * m.slot_bytes); take(m.pool, (int64_t)capacity * len * row);
+    take(m.lane_len, 4 * h->n); take(m.lane_ret, 4 * h->n); take(m.cand, (int64_t)sizeof(MemCand) * h->n);
+    take(m.ctl, sizeof(MemCtl)); take(m.meta, (int64_t)sizeof(MemEntry) * capacity);
+    take(m.meta_tmp, (int64_t)sizeof(MemEntry) * capacity); take(m.scratch, 4 * (int64_t)capacity);
+    take(m.row_off, 8 * ((int64_t)capacity + 1)); take(m.partials, 16 * (int64_t)m.push_blocks);
+    if (!ok) return fail(h, GYMNET_ERR_OOM, "hipMalloc of the episode memory (%.3g bytes) failed", ring_d + pool_d);
+    fresh->history = history;
+    fresh->last = mark(h);
+    ST_TRY(release_memory(h));
+    h->memory = fresh.release();
+    HIP_TRY(h, launch_memory_init(m, h->stream));
+    HIP_TRY(h, launch_memory_open(h->f64, m, h->d_obs, h->ostride, nullptr, 0, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, int32_t clear_pool) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    EpisodeMemory &em = *h->memory;
+    if (clear_pool) HIP_TRY(h, launch_memory_init(em.args, h->stream));
+    HIP_TRY(h, launch_memory_open(h->f64, em.args, h->d_obs, h->ostride, d_mask, ring_slot(em), h->stream));
+    em.last = mark(h);
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    EpisodeMemory &em = *h->memory;
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (!(since(h, em.last) == StepMark{1, 1}))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
+                    "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device", (unsigned long long)em.last.tick,
+                    (unsigned long long)h->tick, (unsigned long long)since(h, em.last).launches);
+    MemPushArgs p{};
+    p.obs = h->d_obs; p.obs_stride = h->ostride;
+    p.actions = d_actions; p.reward = h->d_reward; p.done = d_done ? d_done : h->d_done;
+    p.slot = ring_slot(em);
+    p.end_tick = h->tick;
+    p.autoreset = h->autoreset ? 1 : 0;
+    HIP_TRY(h, launch_memory_push(h->f64, em.args, p, h->stream));
+    em.pos += 1;
+    em.last = mark(h);
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_stats(gymnet_vecenv *h, int64_t *kept, int64_t *ended, int64_t *admitted, int64_t *too_long) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    MemCtl ctl{};
+    ST_TRY(read_pool(h, &ctl, nullptr));
+    std::vector<uint64_t> part((size_t)h->memory->args.push_blocks * 2);
+    HIP_TRY(h, hipMemcpy(part.data(), h->memory->args.partials, part.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t e = 0, t = 0;
+    for (size_t b = 0; b < part.size(); b += 2) { e += part[b]; t += part[b + 1]; }
+    if (kept) *kept = ctl.kept;
+    if (ended) *ended = (int64_t)e;
+    if (admitted) *admitted = (int64_t)ctl.admitted;
+    if (too_long) *too_long = (int64_t)t;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, uint64_t *end_tick, int32_t *lane, int64_t capacity,
+                                  int64_t *count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (capacity < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %lld < 0", (long long)capacity);
+    MemCtl ctl{};
+    std::vector<MemEntry> meta;
+    ST_TRY(read_pool(h, &ctl, &meta));
+    auto ret_order = [](float r) { return r == 0.0f ? 0.0f : r; };
+    std::sort(meta.begin(), meta.end(), [&](const MemEntry &a, const MemEntry &b) {     // descending key (return, tick, lane)
+        if (ret_order(a.ret) != ret_order(b.ret)) return ret_order(a.ret) > ret_order(b.ret);
+        if (a.tick != b.tick) return a.tick > b.tick;
+        return a.lane > b.lane;
+    });
+    const int64_t m = (int64_t)meta.size() < capacity ? (int64_t)meta.size() : capacity;
+    for (int64_t i = 0; i < m; ++i) {
+        if (ret) ret[i] = meta[(size_t)i].ret;
+        if (len) len[i] = meta[(size_t)i].len;
+        if (end_tick) end_tick[i] = meta[(size_t)i].tick;
+        if (lane) lane[i] = meta[(size_t)i].lane;
+    }
+    if (count) *count = (int64_t)meta.size();
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_dataset_size(gymnet_vecenv *h, int64_t *rows) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (!rows) return fail(h, GYMNET_ERR_INVALID_ARG, "rows is null");
+    MemCtl ctl{};
+    std::vector<MemEntry> meta;
+    ST_TRY(read_pool(h, &ctl, &meta));
+    int64_t r = 0;
+    for (const MemEntry &e : meta) r += (int64_t)e.len * 2 / 3;
+    *rows = r;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h,
+                                        int32_t out_w, int32_t out_h, void *d_x, int32_t *d_action, float *d_onehot, float *d_reward,
+                                        int64_t capacity_rows) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    if (format != GYMNET_MEMORY_PARAMS && format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown dataset format %d", format);
+    if (format != GYMNET_MEMORY_PARAMS) {
+        if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel datasets exist for CartPole only (CartPoleEnv.cs:69-135)");
+        ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
+    }
+    if (capacity_rows < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "capacity_rows %lld < 0", (long long)capacity_rows);
+    if (d_onehot && h->desc->box_action) return fail(h, GYMNET_ERR_INVALID_ARG, "a Box action has no one-hot");
+    if (format == GYMNET_STACK_BINARY_F32 && !aligned_to(d_x, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 rows need a 4-byte aligned d_x");
+    if (capacity_rows == 0) return GYMNET_OK;
+    MemDatasetArgs d{};
+    d.format = format; d.history = h->memory->history;
+    d.x = d_x; d.action = d_action; d.onehot = d_onehot; d.reward = d_reward;
+    d.capacity_rows = capacity_rows;
+    d.action_n = h->desc->box_action ? 0 : h->desc->action_n;
+    if (format != GYMNET_MEMORY_PARAMS) d.geo = frame_geom(crop_x, crop_y, crop_w, crop_h, out_w, out_h);
+    const MemoryArgs &m = h->memory->args;
+    HIP_TRY(h, h->f64 ? launch_dataset_typed<double>(m, d, h->stream) : launch_dataset_typed<float>(m, d, h->stream));
+    return GYMNET_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// handle.hpp — what a gymnet_vecenv handle IS, plus the host-side helpers capi.hip and group.hip share.
+// handle.hpp — what a gymnet_vecenv handle IS, plus the host-side helpers capi.hip, group.hip and the attachment units share.
 // Internal to the library: nothing here crosses the C ABI (include/gymnet_amd.h is the boundary).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -6,6 +6,8 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -37,6 +39,11 @@ struct GraphEntry {
     uint64_t last_use;
 };
 constexpr size_t kMaxGraphs = 8;       // per handle; least-recently-used entry is destroyed beyond this
+
+struct RenderStaging;
+struct PixelStack;
+struct EpisodeMemory;
+struct Actor;
 
 }  // namespace gymnet
 
@@ -104,30 +111,12 @@ struct gymnet_vecenv {
     void *d_ep_seg = nullptr;      // fused rollout: segmented episode records + shard counters (allocated on first use, grown on demand)
     int64_t ep_seg_cap = 0;        // records per shard segment
     int64_t ep_ov_cap = 0;         // records of the shared overflow segment (= the largest ep_capacity asked for so far)
-    void *d_render = nullptr;      // gymnet_vecenv_render's device staging (allocated on first use, grown on demand)
-    size_t render_cap = 0;
-    // gymnet_vecenv_pixel_stack_*: the per-lane stacks of processed frames (stack.depth == 0: none configured).  stack.obs / restart /
-    // shift are filled in per launch; stack_alloc is the stack's allocation when the handle made it (NULL: adopted or none)
-    gymnet::StackArgs stack{};
-    int32_t stack_format = 0;
-    void *stack_alloc = nullptr;
-    // gymnet_vecenv_memory_*: the episode memory (mem.capacity == 0: none configured).  mem_pos counts its pushes (the ring slot of the
-    // next step is mem_pos % (max_len + 1)); mem_tick / mem_launches are the engine tick and step launches at its last config, reset or
-    // push, so a push can tell that exactly one vector step ran in between
-    gymnet::MemoryArgs mem{};
-    int32_t mem_history = 0;
-    uint64_t mem_pos = 0, mem_tick = 0, mem_launches = 0;
-    std::vector<void *> mem_allocs;
-    // gymnet_vecenv_actor_*: the actor (actor.layers == 0: none configured).  actor_hist.slot is the ring slot of the newest observation;
-    // actor_tick / actor_launches are the engine tick and step launches at the last config, reset, push or actor rollout, so act can tell
-    // that the history is current and push that exactly one vector step ran in between
-    gymnet::ActorNet actor{};
-    gymnet::ActorHist actor_hist{};
-    int32_t actor_widths[gymnet::kActorMaxLayers + 1] = {};
-    int64_t actor_count = 0, actor_packed = 0;
-    float *actor_flat = nullptr;            // [actor_count] the weights as given (torch layout), the pack kernel's input
-    uint64_t actor_tick = 0, actor_launches = 0;
-    std::vector<void *> actor_allocs;
+    // the four attachments (render.hip, pixel_stack.hip, episode_memory.hip, actor.hip): each unit defines its own type, creates it on
+    // config / first use and frees it in its release function below; NULL: none configured
+    gymnet::RenderStaging *render = nullptr;
+    gymnet::PixelStack *stack = nullptr;
+    gymnet::EpisodeMemory *memory = nullptr;
+    gymnet::Actor *actor = nullptr;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;
@@ -213,6 +202,49 @@ int guarded(F &&f) noexcept {
     }
 }
 
+// The device allocations of one attachment.  A (re-)config take()s everything the new attachment needs into a fresh owner, and only then
+// release()s the old one — so a failed re-config leaves the previous attachment working, and an owner that goes out of scope before it was
+// installed frees what it took.
+struct DeviceAllocs {
+    std::vector<void *> ptrs;
+    DeviceAllocs() = default;
+    DeviceAllocs(const DeviceAllocs &) = delete; DeviceAllocs &operator=(const DeviceAllocs &) = delete;     // (the destructor frees)
+    ~DeviceAllocs() { for (void *p : ptrs) (void)hipFree(p); }
+    // NULL: out of memory (nothing is reported yet; the caller words the error)
+    void *take(size_t bytes) {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        ptrs.push_back(p);
+        return p;
+    }
+    // frees everything, after the handle's stream has drained once (a launch may still use it)
+    int release(gymnet_vecenv *h) {
+        if (!ptrs.empty()) HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (void *p : ptrs) (void)hipFree(p);
+        ptrs.clear();
+        return GYMNET_OK;
+    }
+};
+
+// drops the attachment in `slot` (a struct with a DeviceAllocs `mem`); its unit's release function is this, instantiated for its type
+template <class A>
+int release_attachment(gymnet_vecenv *h, A *&slot) {
+    if (!slot) return GYMNET_OK;
+    ST_TRY(slot->mem.release(h));
+    delete slot;
+    slot = nullptr;
+    return GYMNET_OK;
+}
+int release_render(gymnet_vecenv *h), release_stack(gymnet_vecenv *h);      // render.hip, pixel_stack.hip
+int release_memory(gymnet_vecenv *h), release_actor(gymnet_vecenv *h);      // episode_memory.hip, actor.hip
+
+// Where the handle's step counters stood at an attachment's last config / reset / push: "exactly one vector step since" is
+// since(h, m) == {1, 1}, "none" is {0, 0}.
+struct StepMark { uint64_t tick = 0, launches = 0; };
+inline StepMark mark(const gymnet_vecenv *h) { return {h->tick, h->step_launches}; }
+inline StepMark since(const gymnet_vecenv *h, StepMark m) { return {h->tick - m.tick, h->step_launches - m.launches}; }
+inline bool operator==(StepMark a, StepMark b) { return a.tick == b.tick && a.launches == b.launches; }
+
 // the handle's launcher table, for code typed by its state scalar R
 template <class R>
 inline const EnvLaunchers<R> &launchers(const gymnet_vecenv *h) {
@@ -241,5 +273,10 @@ int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_
 int write_tick(gymnet_vecenv *h);
 int seed_handle(gymnet_vecenv *h, uint64_t seed);                    // Env.Seed(int): new key, tick 0, captured graphs dropped
 int resident_stop(gymnet_vecenv *h);                                 // tells a running resident kernel to leave and waits until it has
+// the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch
+// (records: the rollout keeps compact episode records); afterwards the history's newest slot has moved `steps` on and is current
+int actor_rollout_check(gymnet_vecenv *h);
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
 
 }  // namespace gymnet

@@ -1,4 +1,5 @@
-// kernels.hpp — launch interface between the C-ABI layer (capi.hip) and the HIP kernels (kernels.hip).
+// kernels.hpp — launch interface between the C-ABI layer (capi.hip) and the HIP kernels (kernels.hip, env_*.hip).  The attachment units
+// (render.hip, pixel_stack.hip, episode_memory.hip, actor.hip) keep their kernels' argument structs and launchers to themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -230,116 +231,7 @@ hipError_t launch_export_host(int obs_dim, const float *obs, int64_t stride, con
                               float *out_obs, float *out_reward, uint8_t *out_done, int64_t n, hipStream_t st);
 hipError_t launch_export_host(int obs_dim, const double *obs, int64_t stride, const float *reward, const uint8_t *done,
                               double *out_obs, float *out_reward, uint8_t *out_done, int64_t n, hipStream_t st);
-// CartPole frames (render.hip; contract: gymnet_vecenv_render_device).  Frame k of lanes [first_lane, first_lane + count) is
-// out + k * lane_stride; total_waves = count * waves_per_frame, waves_per_frame = render_waves_per_frame(out_w, out_h).
-struct RenderArgs {
-    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
-    int64_t first_lane;
-    uint8_t *out; int64_t lane_stride;
-    int64_t total_waves, waves_per_frame;
-    int32_t out_w, out_h;
-    float x0, y0, sxq, syq;                   // sample (a, b) of pixel (i, j): x0 + (4 j + a + 0.5) * sxq, y0 + (4 i + b + 0.5) * syq
-};
-constexpr int32_t kRenderWidth = 600, kRenderHeight = 400;   // the reference's canvas (CartPoleEnv.cs:71-72)
-constexpr int32_t kRenderMaxSide = 16384;                    // output width / height limit (sample positions stay exact in float)
-int64_t render_waves_per_frame(int32_t out_w, int32_t out_h);
-hipError_t launch_render(bool f64, int channels, const RenderArgs &a, hipStream_t st);
-// Episode-aware frame stacks (pixel_stack.hip): lane k's stack at base + k * lane_stride, slot s at + s * frame_bytes, every slot one
-// frame of out_h x out_w pixels drawn as render_kernel draws it (format GYMNET_STACK_*: GRAY8, BINARY8 or BINARY_F32).
-struct StackArgs {
-    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
-    uint8_t *base; int64_t lane_stride, frame_bytes;
-    // shift = 1 (push): slots 0..depth-2 take the old slots 1..depth-1 and the newest takes the frame, except in lanes with
-    // restart[k] != 0 (no array: none), which take the frame in every slot.  shift = 0 (reset): lanes with restart[k] != 0 (no array:
-    // every lane) take the frame in every slot, the others are not touched.
-    const uint8_t *restart;
-    int32_t depth, shift;
-    int64_t total_waves, waves_per_frame;     // num_envs * waves_per_frame, render_waves_per_frame(out_w, out_h)
-    int32_t out_w, out_h;
-    float x0, y0, sxq, syq;                   // as RenderArgs
-};
-hipError_t launch_pixel_stack(bool f64, int32_t format, const StackArgs &a, hipStream_t st);
-// Episode memory (episode_memory.hip; contract: gymnet_vecenv_memory_config in include/gymnet_amd.h).  A kept episode's key is
-// (ret, tick, lane), ordered lexicographically; `block` is the pool block [L][row] that holds its steps.
-struct MemEntry { float ret; int32_t len; uint64_t tick; int32_t lane, block; };
-struct MemCand { float ret; int32_t len, lane, pad; };      // an episode that passed the push's admission filter
-struct MemCtl {
-    uint32_t cand_count;       // candidates of the most recent push (the merge consumes them and zeroes this)
-    int32_t kept;              // pool entries [0, kept) are live
-    int32_t full;              // kept == capacity: the push admits an ended episode only when ret >= thr
-    float thr;                 // the lowest kept return (valid when full)
-    uint64_t admitted;         // episodes the merges put into the pool
-    uint64_t rows;             // dataset rows of the most recent dataset build
-};
-struct MemoryArgs {
-    int64_t n;
-    int32_t obs_dim, esz;                      // observation values per step and their size (4 float, 8 double)
-    int32_t max_len, capacity;                 // L and K
-    // staging ring [L + 1 slots]: slot s at ring + s * slot_bytes holds obs [obs_dim][n] (esz each), action [n] (4 B), reward [n] (4 B)
-    uint8_t *ring; int64_t slot_bytes;
-    // pool: block b at pool + b * max_len * row_bytes, row p = obs [obs_dim] (esz each), action (4 B), reward (4 B)
-    uint8_t *pool; int64_t row_bytes;
-    int32_t *lane_len;                         // steps of the lane's open episode (-1: the lane is closed)
-    float *lane_ret;                           // float32 sum of its rewards in step order
-    MemCand *cand;                             // [n]
-    MemCtl *ctl;
-    MemEntry *meta, *meta_tmp;                 // [capacity] each: live entries, then free blocks
-    int32_t *scratch;                          // [capacity]: free blocks during a merge, the descending key order during a dataset build
-    int64_t *row_off;                          // [capacity + 1]: first dataset row of the episode of rank r
-    uint64_t *partials;                        // [push_blocks][2]: episodes ended / too long, per push workgroup
-    int32_t push_blocks;
-};
-struct MemPushArgs {
-    const void *obs; int64_t obs_stride;       // the CURRENT observation buffer (after the step)
-    const void *actions; const float *reward; const uint8_t *done;
-    int64_t slot;                              // ring slot of this step (pos % (L + 1)); the next step's is (pos + 1) % (L + 1)
-    uint64_t end_tick;                         // engine tick after the step: the key of the episodes that end in it
-    int32_t autoreset;
-};
-// format 0 = params rows, else GYMNET_STACK_* frames drawn as the pixel stack draws them
-struct MemDatasetArgs {
-    int32_t format, history;
-    void *x; int32_t *action; float *onehot; float *reward;
-    int64_t capacity_rows;
-    int32_t action_n;                          // one-hot width (0: Box actions, no one-hot)
-    int64_t waves_per_frame;
-    int32_t out_w, out_h;
-    float x0, y0, sxq, syq;                    // as RenderArgs
-};
-int32_t memory_push_blocks(int64_t n);                       // workgroups of a push launch (MemoryArgs.push_blocks)
-hipError_t launch_memory_init(const MemoryArgs &m, hipStream_t st);   // empty pool, zero counts
-hipError_t launch_memory_open(bool f64, const MemoryArgs &m, const void *obs, int64_t obs_stride, const uint8_t *mask, int64_t slot,
-                              hipStream_t st);
-hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &p, hipStream_t st);
-hipError_t launch_memory_dataset(bool f64, const MemoryArgs &m, const MemDatasetArgs &d, hipStream_t st);
 hipError_t launch_fill_i32(int32_t *p, int32_t v, int64_t n, hipStream_t st);
-// The actor (actor.hip; contract: gymnet_vecenv_actor_config in include/gymnet_amd.h): a fully connected ReLU network of `layers`
-// linear layers whose packed weights (actor_packed_floats) are read by every lane, and the per-lane observation history it reads.
-constexpr int kActorMaxLayers = 4, kActorMaxWidth = 64, kActorMaxParams = 8192, kActorMaxActions = 8;
-struct ActorNet {
-    const float *w;                            // packed block: layer l at w + off[l] (actor.hip actor_forward)
-    int32_t layers, action_n;
-    int32_t win[kActorMaxLayers], wout[kActorMaxLayers], off[kActorMaxLayers];
-};
-struct ActorHist {
-    float *hist; int64_t stride;               // [history][obs_dim][stride] float32, a ring
-    int32_t history, obs_dim;
-    int32_t slot;                              // ring slot of the newest observation (push: the slot this push writes)
-    int64_t n;
-};
-struct ActorAct { float epsilon; uint64_t seed, lane_offset, tick; };
-// floats of the packed block for widths[0 .. layers]; off[l] = where layer l starts
-int64_t actor_packed_floats(const int32_t *widths, int32_t layers, int32_t (&off)[kActorMaxLayers]);
-hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *packed, int64_t packed_count, hipStream_t st);
-// push = true: lanes with restart[k] != 0 write every slot, the others slot hs.slot; push = false (reset): lanes with restart[k] != 0
-// (NULL: every lane) write every slot, the others nothing.  obs: the CURRENT observation buffer, float or double (f64)
-hipError_t launch_actor_push(bool f64, const ActorHist &hs, const void *obs, int64_t obs_stride, const uint8_t *restart, bool push,
-                             hipStream_t st);
-hipError_t launch_actor_act(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, hipStream_t st);
-// the fused rollout with RolloutArgs::action_source = GYMNET_ACTIONS_ACTOR (float32 CartPole / MountainCar / Acrobot); records: the
-// rollout keeps compact episode records (RolloutArgs::ep_*, with the overflow segment)
-hipError_t launch_actor_rollout(int env_id, bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r,
-                                const ActorNet &net, const ActorHist &hs, hipStream_t st);
 // Gathers the sharded done list of one step (counter half `counts`) and the records written beside it into compact arrays
 // out_*[0 .. *out_count) (entries beyond out_capacity are dropped; the count is the true one), and / or applies the records to
 // the dense per-lane arrays.  Every out / dense / rec pointer may be NULL.

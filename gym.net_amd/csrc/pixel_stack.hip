@@ -11,13 +11,28 @@
 // into every slot; reset_device is the same kernel with the shift switched off and the lanes outside the mask left alone.
 // Stores are dwordx4 when the slot start is 16-byte aligned (a BINARY_F32 thread writes 64 bytes per slot), bytes (dwords for
 // BINARY_F32) at a frame's tail or in a slot that is not aligned.
+//
+// The host side follows the kernel: gymnet_vecenv_pixel_stack_* and the handle's PixelStack attachment.
 #include "cartpole_raster.hpp"
-
-#include "../../include/gymnet_amd.h"
+#include "handle.hpp"
 
 namespace gymnet {
 
 namespace {
+
+// Lane k's stack at base + k * lane_stride, slot s at + s * frame_bytes, every slot one frame of geo.out_h x geo.out_w pixels drawn as
+// render_kernel draws it (format GYMNET_STACK_*: GRAY8, BINARY8 or BINARY_F32).
+struct StackArgs {
+    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
+    uint8_t *base; int64_t lane_stride, frame_bytes;
+    // shift = 1 (push): slots 0..depth-2 take the old slots 1..depth-1 and the newest takes the frame, except in lanes with
+    // restart[k] != 0 (no array: none), which take the frame in every slot.  shift = 0 (reset): lanes with restart[k] != 0 (no array:
+    // every lane) take the frame in every slot, the others are not touched.
+    const uint8_t *restart;
+    int32_t depth, shift;
+    int64_t total_waves;                      // num_envs * geo.waves_per_frame
+    FrameGeom geo;
+};
 
 __device__ __forceinline__ bool at16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -84,10 +99,10 @@ __global__ __launch_bounds__(256) void pixel_stack_kernel(StackArgs a) {
                                                 // move the rest one slot at a time after it
     const int lid = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t frame_px = (int64_t)a.out_w * a.out_h;
+    const int64_t frame_px = (int64_t)a.geo.out_w * a.geo.out_h;
     for (int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); w < a.total_waves; w += nwaves) {
-        const int64_t k = w / a.waves_per_frame;                        // lane (wave-uniform)
-        const int64_t slice = w - k * a.waves_per_frame;
+        const int64_t k = w / a.geo.waves_per_frame;                        // lane (wave-uniform)
+        const int64_t slice = w - k * a.geo.waves_per_frame;
         // push: a lane restarts where restart[k] != 0 (none without the array); reset: the masked lanes (all without a mask) restart
         // and the others are left alone
         const int flag = a.restart ? __builtin_amdgcn_readfirstlane((int)a.restart[k]) : (a.shift ? 0 : 1);
@@ -109,16 +124,16 @@ __global__ __launch_bounds__(256) void pixel_stack_kernel(StackArgs a) {
                 load_px<E>(src, b0, m, whole && at16(src), old[s]);
             }
         const Geo g = lane_geometry(static_cast<const R *>(a.obs), a.obs_stride, k);
-        int i = (int)(p0 / a.out_w), j = (int)(p0 - (int64_t)i * a.out_w);
+        int i = (int)(p0 / a.geo.out_w), j = (int)(p0 - (int64_t)i * a.geo.out_w);
         uint32_t px[4 * E];
 #pragma unroll
         for (int v = 0; v < 4 * E; ++v) px[v] = 0u;
 #pragma unroll 1
         for (int q = 0; q < kPixPerThread; ++q) {
             int nw, np;
-            shade(g, a.x0, a.sxq, a.y0, a.syq, i, j, nw, np);
+            shade(g, a.geo.x0, a.geo.sxq, a.geo.y0, a.geo.syq, i, j, nw, np);
             append<E>(px, stack_value<FMT>(nw, np));
-            if (++j == a.out_w) { j = 0; ++i; }
+            if (++j == a.geo.out_w) { j = 0; ++i; }
         }
 #pragma unroll
         for (int s = 0; s < kAhead; ++s)
@@ -153,10 +168,117 @@ hipError_t launch_pixel_stack_typed(int32_t format, const StackArgs &a, hipStrea
     return hipGetLastError();
 }
 
+constexpr int32_t kStackMaxDepth = 64;
+
 }  // namespace
 
-hipError_t launch_pixel_stack(bool f64, int32_t format, const StackArgs &a, hipStream_t st) {
-    return f64 ? launch_pixel_stack_typed<double>(format, a, st) : launch_pixel_stack_typed<float>(format, a, st);
+// the configured stack: args.obs / restart / shift are filled in per launch; mem holds the stack when the handle allocated it (empty: adopted)
+struct PixelStack { DeviceAllocs mem; StackArgs args{}; int32_t format = 0; };
+
+int release_stack(gymnet_vecenv *h) { return release_attachment(h, h->stack); }
+
+namespace {
+
+int need_stack(gymnet_vecenv *h) {
+    return h->stack ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no pixel stack configured (gymnet_vecenv_pixel_stack_config)");
 }
 
+// one launch over every lane of the configured stack, from the CURRENT observation buffer: shift = 1 push, 0 reset (StackArgs)
+int launch_stack(gymnet_vecenv *h, const uint8_t *restart, int32_t shift) {
+    StackArgs a = h->stack->args;
+    a.obs = h->d_obs; a.obs_stride = h->ostride;
+    a.restart = restart; a.shift = shift;
+    HIP_TRY(h, h->f64 ? launch_pixel_stack_typed<double>(h->stack->format, a, h->stream) : launch_pixel_stack_typed<float>(h->stack->format, a, h->stream));
+    return GYMNET_OK;
+}
+
+}  // namespace
+
 }  // namespace gymnet
+
+using namespace gymnet;
+
+extern "C" {
+
+int gymnet_vecenv_pixel_stack_config(gymnet_vecenv *h, int32_t format, int32_t depth, int32_t crop_x, int32_t crop_y, int32_t crop_w,
+                                     int32_t crop_h, int32_t out_w, int32_t out_h, void *d_ext, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "pixel stacks exist for CartPole only (CartPoleEnv.cs:69-135)");
+    if (depth == 0) return release_stack(h);
+    if (format != GYMNET_STACK_GRAY8 && format != GYMNET_STACK_BINARY8 && format != GYMNET_STACK_BINARY_F32)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel stack format %d", format);
+    if (depth < 0 || depth > kStackMaxDepth) return fail(h, GYMNET_ERR_INVALID_ARG, "depth %d not in [0, %d]", depth, kStackMaxDepth);
+    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
+    const int64_t elem = format == GYMNET_STACK_BINARY_F32 ? 4 : 1;
+    const int64_t frame = (int64_t)out_w * out_h * elem, span = (int64_t)depth * frame;
+    if (lane_stride == 0) lane_stride = span;
+    if (lane_stride < span)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one stack", (long long)lane_stride, (long long)span);
+    if (h->n > 1 && lane_stride > (INT64_MAX - span) / (h->n - 1)) return fail(h, GYMNET_ERR_INVALID_ARG, "num_envs x lane_stride overflows");
+    if (elem == 4 && ((reinterpret_cast<uintptr_t>(d_ext) & 3u) != 0 || lane_stride % 4 != 0))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "BINARY_F32 stacks need a 4-byte aligned d_ext and lane_stride");
+    const int64_t bytes = (h->n - 1) * lane_stride + span;
+    std::unique_ptr<PixelStack> fresh(new PixelStack);
+    if (!d_ext && !(d_ext = fresh->mem.take((size_t)bytes)))
+        return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the pixel stack failed", (long long)bytes);
+    StackArgs &a = fresh->args;
+    a.base = static_cast<uint8_t *>(d_ext);
+    a.lane_stride = lane_stride; a.frame_bytes = frame;
+    a.depth = depth;
+    a.geo = frame_geom(crop_x, crop_y, crop_w, crop_h, out_w, out_h);
+    a.total_waves = h->n * a.geo.waves_per_frame;
+    fresh->format = format;
+    ST_TRY(release_stack(h));
+    h->stack = fresh.release();
+    return launch_stack(h, nullptr, 0);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_reset_device(gymnet_vecenv *h, const uint8_t *d_mask) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    return launch_stack(h, d_mask, 0);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    // without a done array an auto-reset handle restarts the lanes its most recent step finished (and already re-drew)
+    return launch_stack(h, d_done ? d_done : (h->autoreset ? h->d_done : nullptr), 1);
+    });
+}
+
+int gymnet_vecenv_pixel_stack_view(gymnet_vecenv *h, void **d_stack, int64_t *lane_stride, int64_t *frame_bytes) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    if (d_stack) *d_stack = h->stack->args.base;
+    if (lane_stride) *lane_stride = h->stack->args.lane_stride;
+    if (frame_bytes) *frame_bytes = h->stack->args.frame_bytes;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_lane, int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_stack(h));
+    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
+    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
+                    (long long)count, (long long)h->n);
+    const StackArgs &a = h->stack->args;
+    const int64_t span = (int64_t)a.depth * a.frame_bytes;
+    const uint8_t *src = a.base + first_lane * a.lane_stride;
+    if (a.lane_stride == span) HIP_TRY(h, hipMemcpyAsync(out, src, (size_t)(count * span), hipMemcpyDeviceToHost, h->stream));
+    else HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)span, src, (size_t)a.lane_stride, (size_t)span, (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GYMNET_OK;
+    });
+}
+
+}  // extern "C"

@@ -8,11 +8,29 @@
 // 16-byte aligned, byte stores only at a frame's tail).  Everything that depends on the lane alone — cart position, sin / cos of the pole
 // angle, the shapes' bounding box — is computed once per wave from two wave-uniform loads.  Per pixel, a sample row that misses the
 // bounding box costs two compares (it is background or track); only rows that cross the box test their four samples against the shapes.
+//
+// The host side follows the kernels: gymnet_vecenv_render / _render_device, the crop rules every frame request shares, and the device
+// staging of the host-boundary call (the handle's RenderStaging attachment).
+#include <cstring>
+
 #include "cartpole_raster.hpp"
+#include "handle.hpp"
 
 namespace gymnet {
 
+// gymnet_vecenv_render's device staging (allocated on first use, grown on demand)
+struct RenderStaging { DeviceAllocs mem; size_t cap = 0; };
+
 namespace {
+
+// Frame k of lanes [first_lane, first_lane + count) is out + k * lane_stride; total_waves = count * geo.waves_per_frame.
+struct RenderArgs {
+    const void *obs; int64_t obs_stride;      // the CURRENT observation buffer [4][obs_stride], float or double
+    int64_t first_lane;
+    uint8_t *out; int64_t lane_stride;
+    int64_t total_waves;
+    FrameGeom geo;
+};
 
 template <int C> struct PixelBytes;                        // 16 pixels of C bytes each, as 4 * C dwords in stream order
 template <> struct PixelBytes<1> {
@@ -42,23 +60,23 @@ template <class R, int C>
 __global__ __launch_bounds__(256) void render_kernel(RenderArgs a) {
     const int lid = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t frame_px = (int64_t)a.out_w * a.out_h;
+    const int64_t frame_px = (int64_t)a.geo.out_w * a.geo.out_h;
     const int64_t frame_bytes = frame_px * C;
     for (int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); w < a.total_waves; w += nwaves) {
-        const int64_t k = w / a.waves_per_frame;                        // frame (wave-uniform)
-        const int64_t slice = w - k * a.waves_per_frame;
+        const int64_t k = w / a.geo.waves_per_frame;                        // frame (wave-uniform)
+        const int64_t slice = w - k * a.geo.waves_per_frame;
         const Geo g = lane_geometry(static_cast<const R *>(a.obs), a.obs_stride, a.first_lane + k);
         const int64_t p0 = slice * kPixPerWave + (int64_t)lid * kPixPerThread;
         if (p0 >= frame_px) continue;
         uint8_t *frame = a.out + k * a.lane_stride;
-        int i = (int)(p0 / a.out_w), j = (int)(p0 - (int64_t)i * a.out_w);
+        int i = (int)(p0 / a.geo.out_w), j = (int)(p0 - (int64_t)i * a.geo.out_w);
         PixelBytes<C> px;
 #pragma unroll 1
         for (int q = 0; q < kPixPerThread; ++q) {
             int nw, np;
-            shade(g, a.x0, a.sxq, a.y0, a.syq, i, j, nw, np);
+            shade(g, a.geo.x0, a.geo.sxq, a.geo.y0, a.geo.syq, i, j, nw, np);
             px.push(nw, np);
-            if (++j == a.out_w) { j = 0; ++i; }
+            if (++j == a.geo.out_w) { j = 0; ++i; }
         }
         const int64_t b0 = p0 * C;
         const int64_t nb = frame_bytes - b0;                           // bytes of this frame from b0 on (> 0)
@@ -85,12 +103,93 @@ hipError_t launch_render_typed(int channels, const RenderArgs &a, hipStream_t st
     return hipGetLastError();
 }
 
-}  // namespace
-
-int64_t render_waves_per_frame(int32_t out_w, int32_t out_h) { return ((int64_t)out_w * out_h + kPixPerWave - 1) / kPixPerWave; }
-
-hipError_t launch_render(bool f64, int channels, const RenderArgs &a, hipStream_t st) {
-    return f64 ? launch_render_typed<double>(channels, a, st) : launch_render_typed<float>(channels, a, st);
+hipError_t launch_render(gymnet_vecenv *h, int32_t format, const RenderArgs &a) {
+    const int channels = format == GYMNET_PIXELS_RGB8 ? 3 : 1;
+    return h->f64 ? launch_render_typed<double>(channels, a, h->stream) : launch_render_typed<float>(channels, a, h->stream);
 }
 
+// Checks a render request (nothing is written on failure) and fills the kernel arguments; *bytes = the span the frames cover.
+int render_args(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
+                int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride, RenderArgs *a, int64_t *bytes) {
+    if (h->cfg.env_id != GYMNET_ENV_CARTPOLE) return fail(h, GYMNET_ERR_UNSUPPORTED, "rendering exists for CartPole only (CartPoleEnv.cs:69-135)");
+    if (!out) return fail(h, GYMNET_ERR_INVALID_ARG, "out is null");
+    if (format != GYMNET_PIXELS_RGB8 && format != GYMNET_PIXELS_GRAY8) return fail(h, GYMNET_ERR_INVALID_ARG, "unknown pixel format %d", format);
+    if (first_lane < 0 || count < 1 || first_lane > h->n - count)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "lanes [%lld, %lld + %lld) not inside [0, %lld)", (long long)first_lane, (long long)first_lane,
+                    (long long)count, (long long)h->n);
+    ST_TRY(check_crop_and_size(h, crop_x, crop_y, crop_w, crop_h, out_w, out_h));
+    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
+    if (lane_stride < frame) return fail(h, GYMNET_ERR_INVALID_ARG, "lane_stride %lld < %lld bytes of one frame", (long long)lane_stride, (long long)frame);
+    if (lane_stride > (INT64_MAX - frame) / count) return fail(h, GYMNET_ERR_INVALID_ARG, "count x lane_stride overflows");
+    a->obs = h->d_obs; a->obs_stride = h->ostride;
+    a->first_lane = first_lane;
+    a->out = static_cast<uint8_t *>(out); a->lane_stride = lane_stride;
+    a->geo = frame_geom(crop_x, crop_y, crop_w, crop_h, out_w, out_h);
+    a->total_waves = count * a->geo.waves_per_frame;
+    *bytes = (count - 1) * lane_stride + frame;
+    return GYMNET_OK;
+}
+
+}  // namespace
+
+int check_crop_and_size(gymnet_vecenv *h, int32_t crop_x, int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h) {
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > kRenderWidth - crop_w || crop_y > kRenderHeight - crop_h)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "crop (%d, %d, %d, %d) not inside the %dx%d canvas", crop_x, crop_y, crop_w, crop_h, kRenderWidth, kRenderHeight);
+    if (out_w < 1 || out_h < 1 || out_w > kRenderMaxSide || out_h > kRenderMaxSide)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "output size %dx%d not in [1, %d]", out_w, out_h, kRenderMaxSide);
+    return GYMNET_OK;
+}
+
+int release_render(gymnet_vecenv *h) { return release_attachment(h, h->render); }
+
 }  // namespace gymnet
+
+using namespace gymnet;
+
+extern "C" {
+
+int gymnet_vecenv_render_device(gymnet_vecenv *h, void *d_out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x,
+                                int32_t crop_y, int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    RenderArgs a{};
+    int64_t bytes = 0;
+    ST_TRY(render_args(h, d_out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
+    HIP_TRY(h, launch_render(h, format, a));
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_render(gymnet_vecenv *h, void *out, int32_t format, int64_t first_lane, int64_t count, int32_t crop_x, int32_t crop_y,
+                         int32_t crop_w, int32_t crop_h, int32_t out_w, int32_t out_h, int64_t lane_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    RenderArgs a{};
+    int64_t bytes = 0;
+    ST_TRY(render_args(h, out, format, first_lane, count, crop_x, crop_y, crop_w, crop_h, out_w, out_h, lane_stride, &a, &bytes));
+    if (!h->render || h->render->cap < (size_t)bytes) {
+        std::unique_ptr<RenderStaging> fresh(new RenderStaging);
+        if (!fresh->mem.take((size_t)bytes)) return fail(h, GYMNET_ERR_OOM, "hipMalloc(%lld bytes) for the render staging failed", (long long)bytes);
+        fresh->cap = (size_t)bytes;
+        ST_TRY(release_render(h));
+        h->render = fresh.release();
+    }
+    uint8_t *staging = static_cast<uint8_t *>(h->render->mem.ptrs[0]);
+    a.out = staging;
+    HIP_TRY(h, launch_render(h, format, a));
+    // only the frames' own bytes cross: the caller's gaps between them (lane_stride > one frame) stay as they were
+    const int64_t frame = (int64_t)out_w * out_h * (format == GYMNET_PIXELS_RGB8 ? 3 : 1);
+    if (lane_stride == frame) {
+        HIP_TRY(h, hipMemcpyAsync(out, staging, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return GYMNET_OK;
+    }
+    std::vector<uint8_t> span((size_t)bytes);
+    HIP_TRY(h, hipMemcpyAsync(span.data(), staging, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t k = 0; k < count; ++k) std::memcpy(static_cast<uint8_t *>(out) + k * lane_stride, span.data() + k * lane_stride, (size_t)frame);
+    return GYMNET_OK;
+    });
+}
+
+}  // extern "C"

@@ -5,8 +5,11 @@
 cd "$(dirname "$0")/.."
 NAME=$1; shift
 mkdir -p tools/build/obj_$NAME
-for S in env_cartpole env_cartpole64 env_acrobot env_pendulum env_mountaincar kernels capi group; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=14 -fPIC "$@" -c gym.net_amd/csrc/$S.hip -o tools/build/obj_$NAME/$S.o &
+# the product's translation units and compile flags: gym.net_amd/build.py is the one place that names them
+UNITS=$(python3 -c "import sys; sys.path.insert(0, 'gym.net_amd'); import build; print(' '.join(s[:-4] for s in build.SOURCES))")
+FLAGS=$(python3 -c "import sys; sys.path.insert(0, 'gym.net_amd'); import build; print(' '.join(f for f in build.FLAGS if f != '-shared'))")
+for S in $UNITS; do
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c gym.net_amd/csrc/$S.hip -o tools/build/obj_$NAME/$S.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared tools/build/obj_$NAME/*.o -ldl -o tools/build/libgymnet_amd_$NAME.so && rm -rf tools/build/obj_$NAME

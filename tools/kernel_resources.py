@@ -3,8 +3,7 @@
 VGPRs -> waves per SIMD (512 / VGPRs, at most 8), scratch bytes (spills), static LDS bytes.  Round 5 found two slowdowns that only this view
 explains — a float32 bookkeeping rollout that allocated 131-152 VGPRs (three waves per SIMD where 2^20 lanes need four) and a float64
 four-pair kernel that must stay at two waves per SIMD because it spills when capped for three (profiles/occupancy_hints_r05.txt).
-    python tools/kernel_resources.py [env ...]        env: cartpole cartpole64 pendulum mountaincar acrobot mountaincar_continuous
-                                                      (default: all)
+    python tools/kernel_resources.py [env ...]        env: the env_<env>.hip units of gym.net_amd/build.py's SOURCES (default: all)
 Prints one line per kernel; tests/test_kernel_resources.py asserts the invariants the launch policy relies on."""
 import os
 import re
@@ -16,12 +15,24 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym.net_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-amdgpu-kernarg-preload-count=14",
-         "--cuda-device-only", "-S"]
-ENVS = ("cartpole", "cartpole64", "pendulum", "mountaincar", "acrobot")
-# collect()'s default stays the five units tests/_instantiation_matrix.py covers; the newer units have their own recipe tables
-# (tests/_mountaincar_continuous_matrix.py) and are listed only in the command line's default
-CLI_ENVS = ENVS + ("mountaincar_continuous",)
+
+
+def _product_build():
+    """gym.net_amd/build.py: the one place that names the translation units and the product's flags"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_gymnet_build", os.path.join(ROOT, "gym.net_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_BUILD = _product_build()
+FLAGS = [f for f in _BUILD.FLAGS if f not in ("-fPIC", "-shared")] + ["--cuda-device-only", "-S"]
+# every env unit of the product (build.py SOURCES), in the command line's default ...
+CLI_ENVS = tuple(s[len("env_"):-len(".hip")] for s in _BUILD.SOURCES if s.startswith("env_"))
+# ... while collect()'s default stays the five units tests/_instantiation_matrix.py covers; the newer units have their own recipe tables
+# (tests/_mountaincar_continuous_matrix.py)
+ENVS = tuple(e for e in CLI_ENVS if e != "mountaincar_continuous")
 
 
 def assembly(env, outdir):
