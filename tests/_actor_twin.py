@@ -1,7 +1,8 @@
 """The actor's forward pass restated in C with fmaf (include/gymnet_amd.h, gymnet_vecenv_actor_config), compiled at test time with the
 host compiler and called through ctypes: neuron j of layer l is acc = b[j]; acc = fmaf(W[j][i], x[i], acc) for ascending i, hidden
 layers take acc > 0 ? acc : +0.0f, the action is the first index of the largest logit.  libm's fmaf rounds once, like v_fma_f32.
-Also the history rules (config / reset fill every slot, push appends or refills) and the epsilon-greedy composition, in NumPy."""
+Also the history rules (config / reset fill every slot, push appends or refills) and the epsilon-greedy composition, in NumPy, and
+the (W, b) pairs of a flat weight block (layers / net) that the GPU tests hand to VectorEnv.Actor."""
 import ctypes as C
 import os
 import subprocess
@@ -99,6 +100,29 @@ def random_net(rng, widths, scale=1.0):
         flat.append(rng.normal(0, scale / np.sqrt(win), (wout, win)).astype(np.float32).ravel())
         flat.append(rng.normal(0, 0.1, wout).astype(np.float32))
     return np.asarray(widths, np.int32), np.concatenate(flat).astype(np.float32)
+
+
+def layers(widths, flat):
+    """The (W [out][in], b [out]) pairs of a flat block in gymnet_vecenv_actor_config's layout: what VectorEnv.Actor takes."""
+    pairs, p = [], 0
+    for l in range(len(widths) - 1):
+        win, wout = int(widths[l]), int(widths[l + 1])
+        pairs.append((flat[p:p + win * wout].reshape(wout, win), flat[p + win * wout:p + win * wout + wout]))
+        p += win * wout + wout
+    assert p == len(flat)
+    return pairs
+
+
+def net(rng, widths, scale=2.0):
+    """(widths int32, flat float32, (W, b) pairs) of a random network."""
+    w, flat = random_net(rng, widths, scale=scale)
+    return w, flat, layers(widths, flat)
+
+
+def same(a, b):
+    """bit equality of float32 arrays with -0 == +0 (the sign of a zero sum is the one thing the kernel's zero padding may change)"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return np.array_equal(a == 0, b == 0) and np.array_equal(np.where(a == 0, 0, a).view(np.uint32), np.where(b == 0, 0, b).view(np.uint32))
 
 
 def compose(greedy, sampled_or_none, explore):

@@ -6,6 +6,23 @@ The model mirrors the device's bookkeeping: `obs[t]` is the observation stored f
 open at config), lane k's open episode started at index start[k], and a memory reset overwrites the pending index of the masked lanes."""
 import numpy as np
 
+# The scenario whose end ticks cross 2^32 (tests/test_gpu_episode_memory.py runs it on the device, tests/test_episode_memory_host.py drives
+# the model through it with the NumPy oracle): the tick is set before the memory is configured, 40 pushes before the boundary.
+TICKS_ACROSS_2_32 = dict(n=1024, capacity=100, max_steps=60, pushes=110, start_tick=2 ** 32 - 40)
+
+
+def mixed_policy(n, rng, t, action_n=2):
+    """The memory tests' Discrete actions: a fixed alternating policy, replaced by a uniform draw with probability 0.3."""
+    a = rng.integers(0, action_n, n).astype(np.int32)
+    greedy = (np.arange(n) + t) % action_n
+    return np.where(rng.random(n) < 0.3, a, greedy).astype(np.int32)
+
+
+def ticks_on_both_sides(m):
+    """the pool holds end ticks below and at or above 2^32"""
+    ticks = [e["tick"] for e in m.pool]
+    return bool(ticks) and min(ticks) < 2 ** 32 <= max(ticks)
+
 
 def key(e):
     """The total order of kept episodes: (return, end_tick, lane); a later tick, then a higher lane, is newer and wins ties."""

@@ -1,6 +1,7 @@
 """CPU checks of the actor (no GPU): the fmaf twin against a float64 forward within rounding bounds, the packing of (W, b) lists and of
 an nn.Sequential into gymnet_vecenv_actor_config's layout, the Python layer's argument checks, and the register budget of actor.hip's
-kernels read from the gfx950 assembly (the runner's CartPole kernels must not spill)."""
+kernels read from the gfx950 assembly (the runner's CartPole kernels must not spill), and the names of the actor_rollout_kernel forms in
+that assembly against the recipe table of tests/_actor_forms.py."""
 import os
 import subprocess
 import sys
@@ -90,8 +91,9 @@ def test_capi_declares_the_actor_exports(gymnet):
     assert capi.ACTIONS_ACTOR == 3
 
 
-@pytest.mark.timeout(900)
-def test_actor_kernels_do_not_spill():
+@pytest.fixture(scope="module")
+def actor_kernels():
+    """{kernel name: resources} of actor.hip compiled to gfx950 assembly with the product's flags (tools/kernel_resources.py)"""
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -101,10 +103,25 @@ def test_actor_kernels_do_not_spill():
         r = subprocess.run([kernel_resources.HIPCC] + kernel_resources.FLAGS + [os.path.join(kernel_resources.CSRC, "actor.hip"), "-o", out],
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
-        k = kernel_resources.kernels(out)
+        return kernel_resources.kernels(out)
+
+
+@pytest.mark.timeout(900)
+def test_actor_kernels_do_not_spill(actor_kernels):
+    k = actor_kernels
     names = [n for n in k if n.startswith("actor_")]
     assert any(n.startswith("actor_rollout_kernel<CartPole,") for n in names)
     for n in names:
         if n.startswith("actor_act_kernel") or n.startswith("actor_push_kernel") or n.startswith("actor_rollout_kernel<CartPole,"):
             assert k[n]["scratch"] == 0, (n, k[n])                     # the runner's shape: no spills
             assert k[n]["occupancy"] >= 2, (n, k[n])
+
+
+@pytest.mark.timeout(900)
+def test_forms_table_names_every_compiled_rollout_kernel(actor_kernels):
+    """tests/_actor_forms.py FORMS against the compiled set, by name: a 19th form, or one that is dropped, fails here"""
+    import _actor_forms as forms
+    compiled = sorted(n for n in actor_kernels if n.startswith("actor_rollout_kernel<"))
+    table = sorted(row["kernel"] for row in forms.FORMS)
+    assert len(table) == len(set(table)) == 18
+    assert compiled == table, (sorted(set(compiled) - set(table)), sorted(set(table) - set(compiled)))

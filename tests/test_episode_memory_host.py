@@ -100,6 +100,37 @@ def test_model_too_long_closed_lanes_and_reset():
     assert m.kept()[0].size == 0 and m.ended == 0
 
 
+def test_the_2_to_the_32_scenario_puts_end_ticks_on_both_sides_of_the_boundary():
+    """model.TICKS_ACROSS_2_32, the GPU test's scenario, with the NumPy oracle standing in for the device: float32 CartPole steps, the
+    engine's reset draws at the step's tick, the same policy and time limit.  At some push the pool holds end ticks below and above 2^32,
+    and the uint64 ticks survive the model's key order (a tick truncated to 32 bits would rank the newer episodes below the older)."""
+    from oracle import numpy_ref as ref
+    sc = model.TICKS_ACROSS_2_32
+    n, seed = sc["n"], 0x5EED
+    lanes = np.arange(n)
+    rng = np.random.default_rng(n + sc["capacity"])
+    s = ref.cartpole_reset(seed, lanes, 0)
+    m = model.EpisodeMemoryModel(s.T, sc["capacity"], sc["max_steps"], 4)
+    length = np.zeros(n, np.int64)
+    tick = sc["start_tick"]
+    both = []
+    for t in range(sc["pushes"]):
+        a = model.mixed_policy(n, rng, t)
+        s, r, d, _ = ref.cartpole_step(s, a, np.full(n, -1, np.int32), dtype=np.float32)
+        length += 1
+        done = d | (length >= sc["max_steps"])
+        s[:, done] = ref.cartpole_reset(seed, lanes, tick)[:, done]           # the fused reset draws at the tick the step started from
+        length[done] = 0
+        tick += 1
+        m.push(a, r, done, s.T, tick)
+        both.append(model.ticks_on_both_sides(m))
+    assert any(both) and both.index(True) == 2 ** 32 - sc["start_tick"] - 1   # push 39: the first whose end tick is 2^32
+    kept_ticks = m.kept()[2]
+    assert kept_ticks.dtype == np.uint64 and int(kept_ticks.max()) > 2 ** 32 and len(m.pool) == sc["capacity"]
+    newest = max(m.pool, key=model.key)
+    assert all(model.key(e) <= model.key(newest) for e in m.pool) and newest["tick"] >= 2 ** 32
+
+
 def test_library_and_bindings_declare_the_memory_calls(gymnet):
     lib = ctypes.CDLL(gymnet.LIB_PATH)
     hdr = re.sub(r"/\*.*?\*/", "", _read("include", "gymnet_amd.h"), flags=re.S)

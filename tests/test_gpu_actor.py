@@ -1,14 +1,17 @@
 """GPU checks of the actor (gym.net_amd/csrc/actor.hip, gymnet_vecenv_actor_*): logits and greedy actions bit-identical to the fmaf twin
 (tests/_actor_twin.py, -0 == +0) on CartPole / MountainCar / Acrobot float32 and CartPole float64 handles; epsilon-greedy actions equal
-to ComposeActionsDevice over the twin's greedy actions; the history against the NumPy model of its rules; the fused rollout with
+to ComposeActionsDevice over the twin's greedy actions; the history against the NumPy model of its rules, with the handle's done bytes and
+with the caller's own; the fused rollout (the comparison is tests/_actor_forms.py fused_equals_single_steps) with
 GYMNET_ACTIONS_ACTOR bit-identical to steps x (Act, StepDevice, Push) on plain, trainer-shaped and done-list / terminal-observation
 handles, episode records with their returns and lengths included; a closed loop against the oracle's step and Philox streams; params datasets of an
-EpisodeMemory whose rows the twin maps to the actions taken; refusals that write nothing; Load."""
+EpisodeMemory whose rows the twin maps to the actions taken; refusals that write nothing; Load.  The fused rollout's 18 kernel forms, its
+record staging, the depth, shape, 2^32 and lane-offset edges are in tests/test_gpu_actor_forms.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import _actor_forms as forms
 import _actor_twin as twin
 
 pytestmark = pytest.mark.gpu
@@ -29,14 +32,7 @@ def _host(t):
     return t.cpu().numpy()
 
 
-def _net(rng, widths):
-    w, flat = twin.random_net(rng, widths, scale=2.0)
-    pairs, p = [], 0
-    for l in range(len(widths) - 1):
-        win, wout = widths[l], widths[l + 1]
-        pairs.append((flat[p:p + win * wout].reshape(wout, win), flat[p + win * wout:p + win * wout + wout]))
-        p += win * wout + wout
-    return w, flat, pairs
+_net = twin.net
 
 
 def _warm(env, actor, steps, rng):
@@ -47,10 +43,7 @@ def _warm(env, actor, steps, rng):
         actor.Push()
 
 
-def _same(a, b):
-    """bit equality with -0 == +0"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(a == 0, b == 0) and np.array_equal(np.where(a == 0, 0, a).view(np.uint32), np.where(b == 0, 0, b).view(np.uint32))
+_same = twin.same
 
 
 CASES = [("CartPole-v1", np.float32, 4, "runner", 1000), ("CartPole-v1", np.float32, 4, "runner", 1 << 20),
@@ -98,8 +91,8 @@ def test_epsilon_greedy_equals_compose(gpu_pkg, eps):
             assert np.array_equal(_host(got), greedy)
 
 
-@pytest.mark.parametrize("auto_reset", [True, False])
-def test_history_follows_the_rules(gpu_pkg, auto_reset):
+def _history_loop(gpu_pkg, auto_reset, own_done=0.0):
+    """own_done: Push gets the caller's done bytes — the handle's OR a host-chosen mask of that density — and so does the model"""
     n, S = 2000, 3
     rng = np.random.default_rng(5)
     with gpu_pkg.VectorEnv("CartPole-v1", n, seed=SEED, auto_reset=auto_reset) as env:
@@ -111,7 +104,11 @@ def test_history_follows_the_rules(gpu_pkg, auto_reset):
         for t in range(40):
             out = env.Step(rng.integers(0, 2, n).astype(np.int32))
             d = out.Done.astype(np.uint8)
-            actor.Push()
+            if own_done:
+                d |= (rng.random(n) < own_done).astype(np.uint8)
+                actor.Push(_dev(d))
+            else:
+                actor.Push()
             model.push(out.Observation, d)
             if not auto_reset and d.any():
                 obs = env.ResetWhere(d)
@@ -120,75 +117,30 @@ def test_history_follows_the_rules(gpu_pkg, auto_reset):
             assert np.array_equal(actor.History(), model.h), t
 
 
-def _trainer(gpu_pkg, name, n, trainer):
-    """plain auto-reset; the trainer's shape (EPISODE_STATS, max_episode_steps); "full": that plus the done list and terminal observations"""
-    kw = dict(auto_reset=True)
-    if trainer:
-        kw.update(episode_stats=True, max_episode_steps=50)
-    if trainer == "full":
-        kw.update(done_list=True, final_obs=True)
-    return gpu_pkg.VectorEnv(name, n, seed=SEED, **kw)
+@pytest.mark.parametrize("auto_reset", [True, False])
+def test_history_follows_the_rules(gpu_pkg, auto_reset):
+    _history_loop(gpu_pkg, auto_reset)
+
+
+@pytest.mark.parametrize("auto_reset", [True, False])
+def test_history_follows_the_rules_with_the_callers_done_bytes(gpu_pkg, auto_reset):
+    _history_loop(gpu_pkg, auto_reset, own_done=0.05)
 
 
 @pytest.mark.parametrize("name", ["CartPole-v1", "MountainCar-v0", "Acrobot-v1"])
 @pytest.mark.parametrize("T", [1, 7, 64])
 @pytest.mark.parametrize("trainer", [False, True, "full"])
 def test_fused_actor_rollout_equals_single_steps(gpu_pkg, name, T, trainer, n=3000):
-    import torch
+    """the comparison itself is tests/_actor_forms.py fused_equals_single_steps, shared with tests/test_gpu_actor_forms.py"""
     rng = np.random.default_rng(T)
-    with _trainer(gpu_pkg, name, n, trainer) as a, _trainer(gpu_pkg, name, n, trainer) as b:
-        a.Reset(); b.Reset()
-        O, A = a.ObsDim, a.ActionSpace.N
-        w, flat, pairs = _net(rng, [4 * O] + RUNNER[name][1:-1] + [A])
-        actor_a, actor_b = a.Actor(pairs, 4), b.Actor(pairs, 4)
-        eps, seed, tick0 = 0.3, 99, 1000
-        obs_a, rew_a, done_a, act_a, fin_a = [], [], [], [], []
-        for t in range(T):
-            act_a.append(_host(actor_a.Step(eps, seed, tick0 + t)).copy())
-            r = a.Read()
-            obs_a.append(r.Observation.T.copy()); rew_a.append(r.Reward.copy()); done_a.append(a.GetArray("done").copy())
-            if trainer:                                                   # the finished episodes' (return, length) of this step
-                fin_a.append((a.GetArray("finished_return").copy(), a.GetArray("finished_length").copy()))
-        rec_obs = torch.empty((T, O, n), dtype=torch.float32, device="cuda")
-        rec_rew = torch.empty((T, n), dtype=torch.float32, device="cuda")
-        rec_done = torch.empty((T, n), dtype=torch.uint8, device="cuda")
-        rec_act = torch.empty((T, n), dtype=torch.int32, device="cuda")
-        ep = None
-        if trainer:
-            cap = T * n                                                     # at most one episode per lane and step
-            ep = dict(step=torch.empty(cap, dtype=torch.int32, device="cuda"), lane=torch.empty(cap, dtype=torch.int32, device="cuda"),
-                      ret=torch.empty(cap, dtype=torch.float32, device="cuda"), length=torch.empty(cap, dtype=torch.int32, device="cuda"),
-                      capacity=cap, count=torch.zeros(2, dtype=torch.int32, device="cuda"))
-        b.RolloutFusedDevice(None, T, actions="actor", epsilon=eps, action_seed=seed, action_tick0=tick0, rec_obs=rec_obs, rec_reward=rec_rew,
-                             rec_done=rec_done, rec_actions=rec_act, episodes=ep)
-        assert np.array_equal(_host(rec_act), np.stack(act_a))
-        assert np.array_equal(_host(rec_obs).view(np.uint32), np.stack(obs_a).astype(np.float32).view(np.uint32))
-        assert np.array_equal(_host(rec_rew).view(np.uint32), np.stack(rew_a).view(np.uint32))
-        assert np.array_equal(_host(rec_done), np.stack(done_a))
-        assert np.array_equal(a.GetState().view(np.uint32), b.GetState().view(np.uint32))
-        assert np.array_equal(a.GetArray("done"), b.GetArray("done"))
-        assert a.Tick == b.Tick
-        assert np.array_equal(actor_a.History(), actor_b.History())
-        if trainer:
-            for k in ("episode_return", "episode_length", "finished_return", "finished_length"):
-                assert np.array_equal(a.GetArray(k), b.GetArray(k)), k
-            cnt = _host(ep["count"]).astype(np.int64)
-            m = int(cnt[0])
-            got = sorted(zip(_host(ep["step"])[:m].tolist(), _host(ep["lane"])[:m].tolist(), _host(ep["ret"])[:m].tolist(), _host(ep["length"])[:m].tolist()))
-            want = []
-            for t in range(T):
-                for lane in np.nonzero(done_a[t])[0]:
-                    want.append((t, int(lane), float(fin_a[t][0][lane]), int(fin_a[t][1][lane])))
-            assert int(cnt[1]) == len(want) and got == sorted(want)              # step, lane, return and length of every record
-        if trainer == "full":                                                     # the last step's done list and terminal observations
-            assert np.array_equal(a.GetArray("final_obs").view(np.uint32), b.GetArray("final_obs").view(np.uint32))
-            assert np.array_equal(np.sort(a.DoneLanes()), np.sort(b.DoneLanes()))
-            ra, rb = a.DoneRecords(), b.DoneRecords()
-            ka, kb = np.argsort(ra["lanes"]), np.argsort(rb["lanes"])
-            for k in ("lanes", "return", "length", "final_obs"):
-                assert np.array_equal(ra[k][ka], rb[k][kb]), k
-        # the history is current after the fused rollout: the next single step is accepted on both
-        assert np.array_equal(_host(actor_a.Step(eps, seed, tick0 + T)), _host(actor_b.Step(eps, seed, tick0 + T)))
+    kw = dict(auto_reset=True)
+    if trainer:
+        kw.update(episode_stats=True, max_episode_steps=50)
+    if trainer == "full":
+        kw.update(done_list=True, final_obs=True)
+    w, flat, pairs = _net(rng, RUNNER[name])                              # history 4: RUNNER's first width is 4 * obs_dim
+    forms.fused_equals_single_steps(gpu_pkg, name, n, T, kw, bool(trainer), pairs, S=4, eps=0.3, seed=99, tick0=1000, full=trainer == "full",
+                                    env_seed=SEED)
 
 
 def test_closed_loop_matches_the_oracle(gpu_pkg, oracle):
