@@ -16,9 +16,9 @@
 // for every lane and a push writes one observation per lane; a restarting lane (done byte set, or a masked reset) writes its
 // observation into every slot.  Input row s (oldest first) of the network is ring slot (slot + 1 + s) % S.
 //
-// Fused rollout (actor_rollout_kernel).  The env's step, fused reset, bookkeeping and episode records of step_kernels.hpp's
-// rollout_body, one lane per thread, with the action of step t chosen in the kernel from the history the kernel itself keeps current in
-// memory: bit-identical to steps x (act, step, push).  This unit instantiates its own kernels; the env_*.hip units are untouched.
+// Fused rollout (actor_rollout_kernel).  step_kernels.hpp's rollout_body itself, one lane per thread, with a hook (ActorHook) that
+// chooses the action of step t from the history and keeps that history current in memory: bit-identical to steps x (act, step, push).
+// This unit instantiates its own kernels; the env_*.hip units are untouched.
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, and the three calls the fused rollout
 // (capi.hip) makes when the actor chooses its actions.
@@ -214,18 +214,60 @@ __global__ __launch_bounds__(256) void actor_pack_kernel(const ActorNet net, con
 }
 
 // ---- the fused rollout with the actor choosing the actions -------------------------------------------------------------------------
-// rollout_body's step (step_kernels.hpp) with VEC = 1; RECORDS: the rollout keeps compact episode records, with the overflow segment.
-// KEEP IN STEP with step_kernels.hpp rollout_body: the step, the EXTRAS bookkeeping (truncation, dense views, final observations), the
-// record staging and flush_stage's overflow spill are restated here for one lane per thread; a change to either must be made to both
-// (tests/test_gpu_actor.py compares this kernel with single steps, which run the step kernels' bookkeeping).
+// rollout_body's hook (step_kernels.hpp) for one lane per thread: the action of step t comes from the history, and the post-step
+// observation goes back into it.  newest: the ring slot of the newest observation
+template <class Env>
+struct ActorHook {
+    static constexpr bool CHOOSES = true;
+    static constexpr int S = Env::S, O = Env::O;
+    // choose() and after() are written for rollout_body<Env, 1, ...> of a float32 env with a Discrete action space
+    static_assert(std::is_same<typename Env::Real, float>::value && !Env::BOX_ACTION, "the actor serves float32 Discrete envs, one lane per thread");
+    const ActorNet &net;
+    const ActorHist &hs;
+    const RolloutArgs &ro;
+    uint32_t explore_at_or_below;
+    uint64_t lane_offset;
+    int32_t newest;
+
+    // gymnet_vecenv_actor_act_device(epsilon, action_seed, action_tick0 + t)
+    __device__ __forceinline__ void choose(int64_t t, int64_t i, int32_t (&act)[1]) const {
+        float x[kW];
+        load_input<O>(hs, newest, i, x);
+        actor_forward(net, x);
+        act[0] = compose_one(argmax_logits(x, net.action_n), net.action_n, explore_at_or_below, ro.action_seed, lane_offset + (uint64_t)i, ro.action_tick0 + (uint64_t)t);
+    }
+
+    // gymnet_vecenv_actor_push_device, as actor_push_kernel does it: the new slot only in the common case, every slot for a lane whose
+    // done byte is set
+    __device__ __forceinline__ void after(int64_t, int64_t i, const uint8_t (&done)[1], const float (&s)[S][1], const float (&o)[O][1]) {
+        newest = newest + 1 == hs.history ? 0 : newest + 1;
+        float v[O];
+#pragma unroll
+        for (int k = 0; k < O; ++k) v[k] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
+        float *__restrict__ h = hs.hist + i;
+        if (done[0] == 0) {
+#pragma unroll
+            for (int k = 0; k < O; ++k) h[((int64_t)newest * O + k) * hs.stride] = v[k];
+            return;
+        }
+        for (int sl = 0; sl < hs.history; ++sl) {
+#pragma unroll
+            for (int k = 0; k < O; ++k) h[((int64_t)sl * O + k) * hs.stride] = v[k];
+        }
+    }
+};
+
+// rollout_kernel's prologue (step_kernels.hpp) with one lane per thread, then rollout_body with the hook above: bit-identical to
+// steps x (act, step, push).  RECORDS: the rollout keeps compact episode records, with the overflow segment.
+// kActorMinBlocks: the lean forms fit three waves per SIMD (three workgroups of four waves per CU, 168 VGPRs) and are held to it — one
+// register more would cost a third of their occupancy; the bookkeeping forms (181-207 VGPRs, two waves) get no cap: 1 is the default.
+template <bool EXTRAS> constexpr int kActorMinBlocks = EXTRAS ? 1 : 3;
 template <class Env, bool AUTORESET, bool EXTRAS, bool RECORDS>
-__global__ __launch_bounds__(256) void actor_rollout_kernel(const StepArgs a, const RolloutArgs ro, const ActorNet net, const ActorHist hs) {
-    constexpr int S = Env::S, O = Env::O;
-    constexpr bool RESETF = Env::OBS_ALIASES_STATE;                      // the wave-compacted reset where the env has it
-    using Real = float;
+__global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_rollout_kernel(const StepArgs a, const RolloutArgs ro, const ActorNet net, const ActorHist hs) {
+    constexpr bool RESETF = Env::OBS_ALIASES_STATE && AUTORESET;         // the wave-compacted reset where the env has it
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     ResetScratch<Env> *sc = nullptr;
-    if constexpr (AUTORESET && RESETF) {
+    if constexpr (RESETF) {
         __shared__ ResetScratch<Env> scratch[256 / 64];
         sc = &scratch[threadIdx.x >> 6];
     }
@@ -240,172 +282,11 @@ __global__ __launch_bounds__(256) void actor_rollout_kernel(const StepArgs a, co
         if (blockIdx.x == 0 && a.done_count2)
             for (int sh = threadIdx.x; sh < kShards; sh += blockDim.x) a.done_count2[(a.cparity ^ 1) * (kShards * kCountStride) + sh * kCountStride] = 0u;
     }
-    const int64_t n = a.n;
-    if (i >= n) return;                     // the active lanes of the last wave are a prefix (the wave-level helpers rely on it)
-
-    Real s[S][1];
-#pragma unroll
-    for (int k = 0; k < S; ++k) s[k][0] = state_row_src<Env>(a.state, a.state_stride, a.obs_in, a.obs_stride, k)[i];
-    Real o[O][1];
-    if constexpr (!Env::OBS_ALIASES_STATE) {
-#pragma unroll
-        for (int k = 0; k < O; ++k) o[k][0] = a.obs_in[k * a.obs_stride + i];
-    }
-    int32_t sbd[1] = {0};
-    if constexpr (!AUTORESET && Env::HAS_SBD) sbd[0] = a.sbd[i];
-    float ep_ret = 0.0f, fin_ret[1] = {0.0f};
-    int32_t ep_len = 0, fin_len[1] = {0};
-    bool stats = false;
-    if constexpr (EXTRAS) {
-        stats = a.ep_ret != nullptr;
-        if (stats) { ep_ret = a.ep_ret[i]; ep_len = a.ep_len[i]; }
-    }
-    const uint32_t explore_at_or_below = coin_threshold(ro.epsilon);
-    const uint64_t gl = a.lane_offset + (uint64_t)i;
-    int32_t newest = hs.slot;
-    float reward = 0.0f;
-    uint8_t done = 0;
-
-    uint32_t staged = 0;
-    auto flush_stage = [&]() {
-        if constexpr (EXTRAS && RECORDS) {
-            if (staged == 0) return;                                   // wave-uniform
-            wave_lds_fence();
-            const uint64_t act_mask = __ballot(1);
-            const int leader = __ffsll((unsigned long long)act_mask) - 1;
-            const uint32_t A = (uint32_t)__popcll(act_mask);
-            const uint32_t shard = wave_shard();
-            uint32_t base = 0;
-            if ((int)lane_id() == leader) base = atomicAdd(&ro.ep_count[shard * kCountStride], staged);
-            base = __shfl(base, leader);
-            const uint32_t first_ov = (int64_t)base < ro.ep_cap ? (uint32_t)min((int64_t)staged, ro.ep_cap - (int64_t)base) : 0u;
-            uint32_t ovbase = 0;
-            if (first_ov < staged) {                                   // wave-uniform: the shard's segment is full, spill to the overflow
-                if ((int)lane_id() == leader) ovbase = atomicAdd(&ro.ep_count[kShards * kCountStride], staged - first_ov);
-                ovbase = __shfl(ovbase, leader);
-            }
-            for (uint32_t b0 = 0; b0 < staged; b0 += A) {
-                const uint32_t q = b0 + lane_id();
-                if (q >= staged) continue;
-                int64_t pos = -1;
-                if (q < first_ov) pos = (int64_t)shard * ro.ep_cap + base + q;
-                else if ((int64_t)(ovbase + (q - first_ov)) < ro.ov_cap) pos = (int64_t)kShards * ro.ep_cap + ovbase + (q - first_ov);
-                if (pos >= 0) {
-                    ro.ep_t[pos] = stage->t[q];
-                    ro.ep_lane[pos] = stage->lane[q];
-                    if (ro.ep_ret) { ro.ep_ret[pos] = stage->ret[q]; ro.ep_len[pos] = stage->len[q]; }
-                }
-            }
-            wave_lds_fence();
-            staged = 0;
-        }
-    };
-
-    for (int64_t t = 0; t < ro.steps; ++t) {
-        // the actor: gymnet_vecenv_actor_act_device(epsilon, action_seed, action_tick0 + t)
-        float x[kW];
-        load_input<O>(hs, newest, i, x);
-        actor_forward(net, x);
-        int32_t act[1];
-        act[0] = compose_one(argmax_logits(x, net.action_n), net.action_n, explore_at_or_below, ro.action_seed, gl, ro.action_tick0 + (uint64_t)t);
-
-        // the env step (rollout_body, VEC = 1)
-        uint32_t pending = 0;
-        bool after[1] = {false};
-        {
-            auto one = [&](auto small_tag) {
-                Real sj[S], oj[O];
-                float rw;
-                bool dn;
-#pragma unroll
-                for (int k = 0; k < S; ++k) sj[k] = s[k][0];
-                advance_sublane<Env, AUTORESET, decltype(small_tag)::value>(sj, act[0], sbd[0], rw, dn, after[0], true, oj);
-                done = dn ? 1 : 0;
-                reward = rw;
-                if constexpr (AUTORESET && !EXTRAS) pending = dn ? 1u : 0u;
-#pragma unroll
-                for (int k = 0; k < S; ++k) s[k][0] = sj[k];
-                if constexpr (!Env::OBS_ALIASES_STATE) {
-#pragma unroll
-                    for (int k = 0; k < O; ++k) o[k][0] = oj[k];
-                }
-            };
-            if constexpr (Env::HAS_SMALL_ANGLE_PATH) {
-                if (wave_angles_small<Env, 1>(s)) one(std::true_type{});
-                else one(std::false_type{});
-            } else {
-                one(std::false_type{});
-            }
-        }
-        if constexpr (EXTRAS) {
-            bool finished[1];
-            fin_ret[0] = 0.0f; fin_len[0] = 0;
-            if (stats) {
-                ep_ret += reward;
-                ep_len += 1;
-                if (a.max_episode_steps > 0 && ep_len >= a.max_episode_steps) done |= 2;
-            }
-            const bool fin = done != 0;
-            finished[0] = fin;
-            if (fin && a.final_obs) {
-#pragma unroll
-                for (int k = 0; k < O; ++k) a.final_obs[k * n + i] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
-            }
-            if (stats && fin) {
-                fin_ret[0] = ep_ret;
-                fin_len[0] = ep_len;
-                if (a.fin_ret) { a.fin_ret[i] = ep_ret; a.fin_len[i] = ep_len; }
-                if constexpr (AUTORESET) { ep_ret = 0.0f; ep_len = 0; }
-            }
-            if constexpr (AUTORESET) pending = fin ? 1u : 0u;
-            if constexpr (RECORDS) {
-                uint32_t off[1];
-                const uint32_t total = rank_finished<1>(finished, off);
-                if (total && staged + total > kStageRecords) flush_stage();   // wave-uniform (a wave finishes at most 64 <= kStageRecords)
-                if (finished[0]) {
-                    const uint32_t q = staged + off[0];
-                    stage->t[q] = (int32_t)t; stage->lane[q] = (int32_t)i; stage->ret[q] = fin_ret[0]; stage->len[q] = fin_len[0];
-                }
-                staged += total;
-            }
-            if (a.done_list && t + 1 == ro.steps) append_done_records<Env, 1>(a, finished, i, s, o, fin_ret, fin_len, stats);
-        }
-        if constexpr (!AUTORESET && Env::HAS_SBD) count_after_done<1>(a, after);
-        if (ro.rec_reward) ro.rec_reward[t * n + i] = reward;
-        if (ro.rec_done) ro.rec_done[t * n + i] = done;
-        if (ro.rec_action) static_cast<int32_t *>(ro.rec_action)[t * n + i] = act[0];
-        if constexpr (AUTORESET && RESETF) reset_pending_wave<Env, 1, EXTRAS>(pending, s, a, i, n, tick0 + (uint64_t)t, sc);
-        else if constexpr (AUTORESET) reset_pending<Env, 1, EXTRAS>(pending, s, o, a, i, n, tick0 + (uint64_t)t);
-        // the post-step observation: recorded, and pushed into the history (every slot for a lane whose done byte is set)
-        Real ob[O];
-#pragma unroll
-        for (int k = 0; k < O; ++k) ob[k] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
-        if (ro.rec_obs) {
-#pragma unroll
-            for (int k = 0; k < O; ++k) ro.rec_obs[(t * O + k) * n + i] = ob[k];
-        }
-        newest = newest + 1 == hs.history ? 0 : newest + 1;
-        for (int sl = 0; sl < hs.history; ++sl) {
-            if (done == 0 && sl != newest) continue;
-#pragma unroll
-            for (int k = 0; k < O; ++k) hs.hist[((int64_t)sl * O + k) * hs.stride + i] = ob[k];
-        }
-    }
-    flush_stage();
-
-#pragma unroll
-    for (int k = 0; k < S; ++k)
-        if (state_row_own<Env>(k)) a.state_out[k * a.state_stride + i] = s[k][0];
-    if constexpr (!Env::OBS_ALIASES_STATE) {
-#pragma unroll
-        for (int k = 0; k < O; ++k) a.obs[k * a.obs_stride + i] = o[k][0];
-    }
-    a.reward[i] = reward;
-    a.done[i] = done;
-    if constexpr (!AUTORESET && Env::HAS_SBD) a.sbd[i] = sbd[0];
-    if constexpr (EXTRAS) {
-        if (stats) { a.ep_ret[i] = ep_ret; a.ep_len[i] = ep_len; }
-    }
+    // every lane of the thread is in range past this line (no GUARD form), and the active lanes of the last wave are a prefix (the
+    // wave-level helpers rely on it)
+    if (i >= a.n) return;
+    const ActorHook<Env> hook{net, hs, ro, coin_threshold(ro.epsilon), a.lane_offset, hs.slot};
+    rollout_body<Env, 1, AUTORESET, false, EXTRAS, false, RESETF ? 1 : 0, RECORDS ? 1 : 0>(a, ro, i, tick0, sc, stage, hook);
 }
 
 template <class Env>

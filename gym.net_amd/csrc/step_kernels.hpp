@@ -1041,11 +1041,16 @@ struct EpisodeStage { int32_t t[kStageRecords], lane[kStageRecords]; float ret[k
 //           no spill path — its mere presence costs the kernel 8 % (a call, or a cold block, inside a loop whose registers are capped
 //           at 128), and an evenly finishing batch never takes it.  A variant of its own, so that the
 //           rollouts that keep none do not carry the staging code's registers (128-VGPR budget, above)
-// KEEP IN STEP with actor.hip actor_rollout_kernel, which restates this body's step, EXTRAS bookkeeping, record staging and overflow
-// spill for one lane per thread (the closed-loop rollout, GYMNET_ACTIONS_ACTOR): a change here must be made there too.
-template <class Env, int VEC, bool AUTORESET, bool GUARD, bool EXTRAS, bool SAMPLE, int RESETF = 0, int RECORDS = 0>
+//   Hook    who chooses the actions.  NoHook: the ring or the sampler, above.  A hook with CHOOSES (actor.hip's ActorHook, the closed-loop
+//           rollout GYMNET_ACTIONS_ACTOR) is called twice per step: choose(t, i0, act) fills the step's actions in place of the ring and
+//           the sampler, and after(t, i0, done, s, o) sees the post-step state once the fused reset and the rec_obs store are through.
+//           Its actions are recorded on every handle, like sampled ones.  Both calls are compiled out for NoHook.
+struct NoHook { static constexpr bool CHOOSES = false; };
+
+template <class Env, int VEC, bool AUTORESET, bool GUARD, bool EXTRAS, bool SAMPLE, int RESETF = 0, int RECORDS = 0, class Hook = NoHook>
 __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real> &a, const RolloutArgsT<typename Env::Real> &ro,
-                                             const int64_t i0, const uint64_t tick0, ResetScratch<Env> *sc = nullptr, EpisodeStage *stage = nullptr) {
+                                             const int64_t i0, const uint64_t tick0, ResetScratch<Env> *sc = nullptr, EpisodeStage *stage = nullptr,
+                                             Hook hook = Hook{}) {
     constexpr int S = Env::S, O = Env::O;
     using Act = typename Env::Action;
     using Real = typename Env::Real;
@@ -1068,12 +1073,13 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
     bool use_ring = true;                                          // kernel-uniform
     const bool one_group = (a.lane_offset % (uint64_t)VEC) == 0;   // kernel-uniform: the thread's lanes share one action-stream call
     const uint32_t explore_at_or_below = coin_threshold(ro.epsilon);   // kernel-uniform (philox.hpp): the coin is one integer compare
-    if constexpr (SAMPLE) {
+    // (under a hook that chooses there is no ring and no prefetch: hook.choose() fills act[] at the head of every step)
+    if constexpr (SAMPLE && !Hook::CHOOSES) {
         use_ring = ro.action_source == 2;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { act[j] = Act(0); act_next[j] = Act(0); }
         if (use_ring) load_action(0, act);
-    } else {
+    } else if constexpr (!Hook::CHOOSES) {
         load_action(0, act);
     }
     int64_t slice = 0;
@@ -1139,7 +1145,9 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
     for (int64_t t = 0; t < ro.steps; ++t) {
         int64_t nslice = slice + 1;
         if (nslice == ro.ring) nslice = 0;
-        if constexpr (SAMPLE) {
+        if constexpr (Hook::CHOOSES) {
+            hook.choose(t, i0, act);
+        } else if constexpr (SAMPLE) {
             if (use_ring && t + 1 < ro.steps) load_action(nslice, act_next);
             uint32_t wa[VEC], wb[VEC];
             thread_action_words<VEC>(ro.action_seed, a.lane_offset + (uint64_t)i0, ro.action_tick0 + (uint64_t)t, use_ring, one_group, wa, wb);
@@ -1261,7 +1269,7 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
         if constexpr (!AUTORESET && Env::HAS_SBD) count_after_done<VEC>(a, after);
         if (ro.rec_reward) store_f32<VEC, true, GUARD>(ro.rec_reward + t * n, i0, n, reward);
         if (ro.rec_done) store_u8<VEC, true, GUARD>(ro.rec_done + t * n, i0, n, done);
-        if constexpr (EXTRAS || SAMPLE) {
+        if constexpr (EXTRAS || SAMPLE || Hook::CHOOSES) {
             if (ro.rec_action) {
                 if constexpr (Env::BOX_ACTION) store_f32<VEC, true, GUARD>(static_cast<float *>(ro.rec_action) + t * n, i0, n, act);
                 else store_i32<VEC, true, GUARD>(static_cast<int32_t *>(ro.rec_action) + t * n, i0, n, act);
@@ -1276,9 +1284,13 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
                 else store_row<Real, VEC, true, GUARD>(ro.rec_obs + (t * O + k) * n, i0, n, o[k]);
             }
         }
+        if constexpr (Hook::CHOOSES) {
+            hook.after(t, i0, done, s, o);
+        } else {
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) act[j] = act_next[j];
-        slice = nslice;
+            for (int j = 0; j < VEC; ++j) act[j] = act_next[j];
+            slice = nslice;
+        }
     }
     flush_stage();
 
