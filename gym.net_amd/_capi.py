@@ -189,6 +189,8 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_push_device": (C.c_int, [_H, _P]),
     "gymnet_vecenv_actor_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_actor_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "gymnet_vecenv_actor_box_config": (C.c_int, [_H, C.c_int32, C.c_int32, _P, _P, C.c_int64]),
+    "gymnet_vecenv_actor_box_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

@@ -186,6 +186,9 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_push_device(IntPtr h, IntPtr d_done);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_view(IntPtr h, out IntPtr d_history, out long lane_stride, out int slot);
+        // the Box actor (Pendulum, MountainCarContinuous): the last layer's one output, clamped to the env's bounds, is the action
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

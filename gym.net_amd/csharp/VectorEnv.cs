@@ -291,6 +291,17 @@ namespace Gym.Envs.Amd {
         /// (TrainingPlaySession.cs:46-52; epsilon 0 = TestingPlaySession); dLogits float [N][action_n] or IntPtr.Zero.
         public void ActorAct(IntPtr dActions, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dLogits = default) =>
             Native.Check(Native.gymnet_vecenv_actor_act_device(_h, dActions, dLogits, epsilon, seed, tick));
+        /// The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous with w_L = 1; its one output,
+        /// clamped to the env's bounds, is the action.  No layers releases it.  LoadActorWeights / ResetActor / PushActor serve both kinds.
+        public void ConfigureBoxActor(int history, int[] widths, float[] weights) {
+            if (widths == null || widths.Length == 0) { Native.Check(Native.gymnet_vecenv_actor_box_config(_h, 0, 0, null, null, 0)); return; }
+            fixed (int* pw = widths) fixed (float* pv = weights)
+                Native.Check(Native.gymnet_vecenv_actor_box_config(_h, history, widths.Length - 1, pw, pv, weights.LongLength));
+        }
+        /// Every lane's action into dActions (float [N]): the clamped output, or ActionSpace.Sample() where the lane's coin is at or below
+        /// epsilon (TrainingPlaySession.cs:46-52 on a Box space); dRaw float [N] or IntPtr.Zero receives the unclamped outputs.
+        public void BoxActorAct(IntPtr dActions, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dRaw = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_box_act_device(_h, dActions, dRaw, epsilon, seed, tick));
 
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));

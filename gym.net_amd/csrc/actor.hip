@@ -20,98 +20,16 @@
 // chooses the action of step t from the history and keeps that history current in memory: bit-identical to steps x (act, step, push).
 // This unit instantiates its own kernels; the env_*.hip units are untouched.
 //
+// What the Box actor (actor_box.hip: Pendulum, MountainCarContinuous) shares with this unit — the network and history structs, the forward
+// pass, load_input, the ring arithmetic, the push — is in actor_net.hpp; the Discrete head (argmax_logits, compose_one) stays here.
+//
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, and the three calls the fused rollout
 // (capi.hip) makes when the actor chooses its actions.
-#include "step_kernels.hpp"
-
-#include "envs.hpp"
-#include "handle.hpp"
+#include "actor_net.hpp"
 
 namespace gymnet {
 
 namespace {
-
-// a fully connected ReLU network of `layers` linear layers whose packed weights (actor_packed_floats) are read by every lane, and the
-// per-lane observation history it reads
-constexpr int kActorMaxLayers = 4, kActorMaxWidth = 64, kActorMaxParams = 8192, kActorMaxActions = 8;
-struct ActorNet {
-    const float *w;                            // packed block: layer l at w + off[l] (actor_forward)
-    int32_t layers, action_n;
-    int32_t win[kActorMaxLayers], wout[kActorMaxLayers], off[kActorMaxLayers];
-};
-struct ActorHist {
-    float *hist; int64_t stride;               // [history][obs_dim][stride] float32, a ring
-    int32_t history, obs_dim;
-    int32_t slot;                              // ring slot of the newest observation (push: the slot this push writes)
-    int64_t n;
-};
-struct ActorAct { float epsilon; uint64_t seed, lane_offset, tick; };
-
-typedef __attribute__((address_space(4))) const float cfloat;   // scalar-cache (constant address space) view of the weights
-
-constexpr int kW = kActorMaxWidth;
-
-// Layer l of the packed block: ceil(wout / 4) groups of [4 biases | ceil(win / 8) chunks of [4 rows][8 inputs]], zeros where a row or
-// an input does not exist.
-__host__ __device__ __forceinline__ int64_t group_floats(int32_t win) { return 4 + 32 * (int64_t)((win + 7) >> 3); }
-
-// x: the input layer's activations, +0 beyond net.win[0]; on return x[0 .. action_n) are the logits
-__device__ __forceinline__ void actor_forward(const ActorNet &net, float (&x)[kW]) {
-    for (int l = 0; l < net.layers; ++l) {                                   // wave-uniform
-        const int32_t win = net.win[l], wout = net.wout[l];
-        const int32_t nch = (win + 7) >> 3;
-        const bool hidden = l + 1 < net.layers;
-        const int64_t gf = group_floats(win);
-        cfloat *wl = (cfloat *)(net.w + net.off[l]);
-        float y[kW];
-#pragma unroll
-        for (int g = 0; g < kW / 4; ++g) {
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (4 * g < wout) {                                              // wave-uniform
-                cfloat *blk = wl + g * gf;
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) acc[jj] = blk[jj];
-#pragma unroll
-                for (int c = 0; c < kW / 8; ++c) {
-                    if (c < nch) {                                           // wave-uniform
-                        cfloat *ch = blk + 4 + 32 * c;
-#pragma unroll
-                        for (int ii = 0; ii < 8; ++ii) {
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) acc[jj] = __builtin_fmaf(ch[jj * 8 + ii], x[8 * c + ii], acc[jj]);
-                        }
-                    }
-                }
-                if (hidden) {
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) acc[jj] = acc[jj] > 0.0f ? acc[jj] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) y[4 * g + jj] = acc[jj];
-        }
-#pragma unroll
-        for (int i = 0; i < kW; ++i) x[i] = y[i];
-    }
-}
-
-// the network input of lane i: ring slots oldest first, O values each (O compile-time, so x's indices are)
-template <int O>
-__device__ __forceinline__ void load_input(const ActorHist &hs, int32_t newest, int64_t i, float (&x)[kW]) {
-#pragma unroll
-    for (int s = 0; s < kW / O; ++s) {
-        int32_t row = 0;
-        if (s < hs.history) {                                                // wave-uniform
-            row = newest + 1 + s;
-            row = row >= hs.history ? row - hs.history : row;
-            row = row >= hs.history ? row - hs.history : row;
-        }
-#pragma unroll
-        for (int k = 0; k < O; ++k) x[s * O + k] = s < hs.history ? hs.hist[((int64_t)row * O + k) * hs.stride + i] : 0.0f;
-    }
-#pragma unroll
-    for (int i2 = (kW / O) * O; i2 < kW; ++i2) x[i2] = 0.0f;
-}
 
 // first index of the largest logit (moves only on a strictly greater value)
 __device__ __forceinline__ int32_t argmax_logits(const float (&x)[kW], int32_t action_n) {
@@ -157,32 +75,6 @@ __global__ __launch_bounds__(256) void actor_act_kernel(const ActorNet net, cons
     }
     const int32_t greedy = argmax_logits(x, net.action_n);
     actions[i] = compose_one(greedy, net.action_n, coin_threshold(aa.epsilon), aa.seed, aa.lane_offset + (uint64_t)i, aa.tick);
-}
-
-// push (restart = done bytes; lanes without one write the new slot only) or fill (restart = mask, NULL: every lane; lanes without one
-// are not touched)
-template <class R, int O>
-__global__ __launch_bounds__(256) void actor_push_kernel(const ActorHist hs, const R *__restrict__ obs, int64_t obs_stride,
-                                                         const uint8_t *__restrict__ restart, int32_t push) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= hs.n) return;
-    const bool all = restart ? restart[i] != 0 : !push;
-    if (!push && !all) return;
-    // the observation is loaded once, before any store (the history is not declared apart from it, so a load after a store of the
-    // ring would be issued again behind that store)
-    float v[O];
-#pragma unroll
-    for (int k = 0; k < O; ++k) v[k] = (float)obs[k * obs_stride + i];
-    float *__restrict__ h = hs.hist + i;
-    if (!all) {                                       // the common case: one slot
-#pragma unroll
-        for (int k = 0; k < O; ++k) h[((int64_t)hs.slot * O + k) * hs.stride] = v[k];
-        return;
-    }
-    for (int sl = 0; sl < hs.history; ++sl) {
-#pragma unroll
-        for (int k = 0; k < O; ++k) h[((int64_t)sl * O + k) * hs.stride] = v[k];
-    }
 }
 
 // flat torch layout (per layer W [wout][win] row-major, then b [wout]) -> the packed block actor_forward reads
@@ -237,31 +129,15 @@ struct ActorHook {
         act[0] = compose_one(argmax_logits(x, net.action_n), net.action_n, explore_at_or_below, ro.action_seed, lane_offset + (uint64_t)i, ro.action_tick0 + (uint64_t)t);
     }
 
-    // gymnet_vecenv_actor_push_device, as actor_push_kernel does it: the new slot only in the common case, every slot for a lane whose
-    // done byte is set
+    // gymnet_vecenv_actor_push_device (actor_net.hpp)
     __device__ __forceinline__ void after(int64_t, int64_t i, const uint8_t (&done)[1], const float (&s)[S][1], const float (&o)[O][1]) {
-        newest = newest + 1 == hs.history ? 0 : newest + 1;
-        float v[O];
-#pragma unroll
-        for (int k = 0; k < O; ++k) v[k] = Env::OBS_ALIASES_STATE ? s[k < S ? k : 0][0] : o[k][0];
-        float *__restrict__ h = hs.hist + i;
-        if (done[0] == 0) {
-#pragma unroll
-            for (int k = 0; k < O; ++k) h[((int64_t)newest * O + k) * hs.stride] = v[k];
-            return;
-        }
-        for (int sl = 0; sl < hs.history; ++sl) {
-#pragma unroll
-            for (int k = 0; k < O; ++k) h[((int64_t)sl * O + k) * hs.stride] = v[k];
-        }
+        hook_push<Env>(hs, newest, i, done, s, o);
     }
 };
 
 // rollout_kernel's prologue (step_kernels.hpp) with one lane per thread, then rollout_body with the hook above: bit-identical to
-// steps x (act, step, push).  RECORDS: the rollout keeps compact episode records, with the overflow segment.
-// kActorMinBlocks: the lean forms fit three waves per SIMD (three workgroups of four waves per CU, 168 VGPRs) and are held to it — one
-// register more would cost a third of their occupancy; the bookkeeping forms (181-207 VGPRs, two waves) get no cap: 1 is the default.
-template <bool EXTRAS> constexpr int kActorMinBlocks = EXTRAS ? 1 : 3;
+// steps x (act, step, push).  RECORDS: the rollout keeps compact episode records, with the overflow segment.  (The prologue is written
+// out here and in actor_box_rollout_kernel: moved into a helper it changes the instruction streams of all 18 forms.)
 template <class Env, bool AUTORESET, bool EXTRAS, bool RECORDS>
 __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_rollout_kernel(const StepArgs a, const RolloutArgs ro, const ActorNet net, const ActorHist hs) {
     constexpr bool RESETF = Env::OBS_ALIASES_STATE && AUTORESET;         // the wave-compacted reset where the env has it
@@ -305,8 +181,6 @@ static hipError_t launch_actor_rollout_env(bool autoreset, bool extras, bool rec
     return hipGetLastError();
 }
 
-static inline dim3 lane_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 namespace {
 
 // floats of the packed block for widths[0 .. layers]; off[l] = where layer l starts
@@ -328,6 +202,9 @@ template <class R>
 hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st) {
     switch (hs.obs_dim) {
         case 2: hipLaunchKernelGGL((actor_push_kernel<R, 2>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
+        case 3:                                       // Pendulum, float32 only: the kernel is actor_box.hip's
+            if constexpr (sizeof(R) == 4) return launch_actor_box_push3(hs, obs, obs_stride, restart, push, st);
+            else return hipErrorInvalidValue;
         case 4: hipLaunchKernelGGL((actor_push_kernel<R, 4>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
         case 6: hipLaunchKernelGGL((actor_push_kernel<R, 6>), lane_grid(hs.n), dim3(256), 0, st, hs, obs, obs_stride, restart, (int32_t)push); break;
         default: return hipErrorInvalidValue;
@@ -357,20 +234,9 @@ hipError_t launch_actor_act(const ActorNet &net, const ActorHist &hs, int32_t *a
 
 }  // namespace
 
-// the configured actor: hist.slot is the ring slot of the newest observation; last: the handle's step counters at the last config, reset,
-// push or actor rollout, so act can tell that the history is current and push that exactly one vector step ran in between
-struct Actor { DeviceAllocs mem; ActorNet net{}; ActorHist hist{}; int64_t count = 0, packed = 0; StepMark last; };
-
 int release_actor(gymnet_vecenv *h) { return release_attachment(h, h->actor); }
 
 namespace {
-
-int need_actor(gymnet_vecenv *h) {
-    return h->actor ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no actor configured (gymnet_vecenv_actor_config)");
-}
-
-// the history is current: no vector step since the last actor config, reset, push or actor rollout
-bool actor_current(const gymnet_vecenv *h) { return since(h, h->actor->last) == StepMark{0, 0}; }
 
 int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
     HIP_TRY(h, launch_actor_push(h->f64, h->actor->hist, h->d_obs, h->ostride, d_mask, false, h->stream));
@@ -386,7 +252,7 @@ int actor_rollout_check(gymnet_vecenv *h) {
     return GYMNET_OK;
 }
 
-// float32 CartPole / MountainCar / Acrobot
+// float32 CartPole / MountainCar / Acrobot here, Pendulum / MountainCarContinuous in actor_box.hip
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
@@ -394,6 +260,7 @@ hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &
         case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
         case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
         case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
+        case GYMNET_ENV_PENDULUM: case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS: return actor_box_rollout_launch(h, records, a, r);
         default: return hipErrorInvalidValue;
     }
 }
@@ -405,35 +272,35 @@ void actor_rollout_done(gymnet_vecenv *h, int64_t steps) {
     h->actor->last = mark(h);
 }
 
-}  // namespace gymnet
-
-using namespace gymnet;
-
-extern "C" {
-
-int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
-                               int64_t count) {
-    return guarded([&]() -> int {
-    ENTER(h);
+// gymnet_vecenv_actor_config (box = false) and gymnet_vecenv_actor_box_config (box = true) behind ENTER: the same network, history and
+// checks; the kind must be the env's, and the last width is the Discrete space's n or the Box space's one dimension
+int actor_configure(gymnet_vecenv *h, bool box, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count) {
     if (num_layers == 0) return release_actor(h);
     const EnvDesc &d = *h->desc;
-    if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions; %s has a Box action space", d.name);
+    if (d.box_action && !box)
+        return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions; %s has a Box action space (gymnet_vecenv_actor_box_config)", d.name);
+    if (!d.box_action && box)
+        return fail(h, GYMNET_ERR_UNSUPPORTED, "the Box actor chooses Box actions; %s has a Discrete action space (gymnet_vecenv_actor_config)", d.name);
+    if (box && h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the Box actor serves float32 handles");
+    const int32_t last = box ? 1 : d.action_n;
     if (num_layers < 1 || num_layers > kActorMaxLayers) return fail(h, GYMNET_ERR_INVALID_ARG, "num_layers %d not in [0, %d]", num_layers, kActorMaxLayers);
     if (!widths || !weights) return fail(h, GYMNET_ERR_INVALID_ARG, "widths / weights is null");
     if (history < 1 || (int64_t)history * d.obs_dim > kActorMaxWidth)
         return fail(h, GYMNET_ERR_INVALID_ARG, "history %d: history * obs_dim must be in [1, %d]", history, kActorMaxWidth);
-    if (d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
+    if (!box && d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
     int64_t params = 0;
     for (int l = 0; l <= num_layers; ++l)
         if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
     for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
     if (widths[0] != history * d.obs_dim) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], history * d.obs_dim);
-    if (widths[num_layers] != d.action_n) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != action_n = %d", num_layers, widths[num_layers], d.action_n);
+    if (widths[num_layers] != last)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != %s = %d", num_layers, widths[num_layers], box ? "the action dimension" : "action_n", last);
     if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
     if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
     std::unique_ptr<Actor> fresh(new Actor);
+    fresh->box = box;
     ActorNet &net = fresh->net;
-    net.layers = num_layers; net.action_n = d.action_n;
+    net.layers = num_layers; net.action_n = last;
     for (int l = 0; l < num_layers; ++l) { net.win[l] = widths[l]; net.wout[l] = widths[l + 1]; }
     fresh->count = params;
     fresh->packed = actor_packed_floats(widths, num_layers, net.off);
@@ -452,6 +319,19 @@ int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_la
     HIP_TRY(h, launch_actor_pack(net, flat, packed, h->actor->packed, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));     // the caller's host weights may go away when we return
     return actor_refill(h, nullptr);
+}
+
+}  // namespace gymnet
+
+using namespace gymnet;
+
+extern "C" {
+
+int gymnet_vecenv_actor_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
+                               int64_t count) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    return actor_configure(h, false, history, num_layers, widths, weights, count);
     });
 }
 
@@ -485,7 +365,7 @@ int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
                     "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)ac.last.tick,
                     (unsigned long long)h->tick, (unsigned long long)since(h, ac.last).launches);
     ActorHist hs = ac.hist;
-    hs.slot = hs.slot + 1 == hs.history ? 0 : hs.slot + 1;
+    hs.slot = ring_next(hs.slot, hs.history);
     HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));
     ac.hist = hs;
     ac.last = mark(h);
@@ -497,6 +377,7 @@ int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *
     return guarded([&]() -> int {
     ENTER(h);
     ST_TRY(need_actor(h));
+    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "this handle's actor chooses Box actions: gymnet_vecenv_actor_box_act_device");
     if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
     if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
     if (!actor_current(h))

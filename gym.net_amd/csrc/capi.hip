@@ -1236,7 +1236,6 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
     }
     if (actor) {
-        if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "the actor chooses Discrete actions");
         if (h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout runs float32 handles (float64: act / step / push)");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
         ST_TRY(actor_rollout_check(h));

@@ -300,7 +300,7 @@ class VectorEnv:
                     over d_actions as the policy's actions, TrainingPlaySession.cs:46-52) or "actor" (the handle's Actor chooses
                     step t's action as Act(epsilon, action_seed, action_tick0 + t) would, and keeps its history current; d_actions
                     may be None)
-          rec_actions  [T][N] device buffer for the actions taken
+          rec_actions  [T][N] device buffer for the actions taken (int32; float32 on a Box-action env)
           episodes  dict(step=, lane=, ret=, length=, capacity=, count=): device arrays for the compact records of the episodes
                     that end during the rollout (any array may be omitted; count: uint32[2] = records written, episodes ended);
                     no_overflow=True selects the 8 % faster kernel variant that may drop records of very unevenly finishing lanes
@@ -396,8 +396,9 @@ class VectorEnv:
     def Actor(self, net, history=4):
         """A fully connected ReLU network that chooses every lane's action on the device (gymnet_vecenv_actor_config): the trainer's
         ComposeAction -> Trainer.Predict -> argmax (BasePlaySession.cs:78-81) from the last `history` observations of each lane.  net is
-        a list of (W, b) pairs (W [out][in], torch's nn.Linear layout) or a torch nn.Sequential of Linear / ReLU layers.  Replaces
-        any actor this handle had."""
+        a list of (W, b) pairs (W [out][in], torch's nn.Linear layout) or a torch nn.Sequential of Linear / ReLU layers.  On a Box-action
+        env (Pendulum, MountainCarContinuous) it is a Box actor (gymnet_vecenv_actor_box_config): the last layer is one wide and its
+        output, clamped to the action bounds, is the action.  Replaces any actor this handle had."""
         return Actor(self, net, history)
 
     def PackObsDevice(self, d_obs_rowmajor):
@@ -813,9 +814,12 @@ def actor_layers(net):
     return out
 
 
-def actor_pack(net):
-    """(widths int32 [L + 1], weights float32 [count]) in gymnet_vecenv_actor_config's layout: per layer W row-major, then b."""
+def actor_pack(net, box=False):
+    """(widths int32 [L + 1], weights float32 [count]) in gymnet_vecenv_actor_config's layout: per layer W row-major, then b.  box: the
+    network of a Box actor (gymnet_vecenv_actor_box_config), whose last layer must be one wide."""
     layers = actor_layers(net)
+    if box and layers[-1][0].shape[0] != 1:
+        raise ValueError(f"a Box actor's last layer gives the one action value; this one is {layers[-1][0].shape[0]} wide")
     widths = [layers[0][0].shape[1]]
     for k, (w, b) in enumerate(layers):
         if w.shape[1] != widths[-1]:
@@ -831,13 +835,15 @@ class Actor:
 
     def __init__(self, env, net, history):
         history = int(history)
-        widths, flat = actor_pack(net)
+        self.IsBox = isinstance(env.ActionSpace, Box)
+        widths, flat = actor_pack(net, box=self.IsBox)
         if history < 1:
             raise ValueError("history must be >= 1")
         if widths[0] != history * env.ObsDim:
             raise ValueError(f"the first layer takes {widths[0]} inputs; history * obs_dim = {history * env.ObsDim}")
         self._env, self._lib, self._h = env, env._lib, env._h
-        capi.check(self._lib.gymnet_vecenv_actor_config(self._h, history, len(widths) - 1, _host(widths), _host(flat), flat.size))
+        config = self._lib.gymnet_vecenv_actor_box_config if self.IsBox else self._lib.gymnet_vecenv_actor_config
+        capi.check(config(self._h, history, len(widths) - 1, _host(widths), _host(flat), flat.size))
         prev = getattr(env, "_actor", None)
         if prev is not None and prev is not self:
             prev._h = None                      # the handle holds one actor: the previous one is gone
@@ -853,13 +859,18 @@ class Actor:
     def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None):
         """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
-        compose it.  logits: an optional device float32 [N, action_n]."""
+        compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
+        float32 [N] — the network's one output clamped to the action bounds, or ActionSpace.Sample() as SampleActionsDevice(seed=seed,
+        tick=tick) draws it where the lane explores — and logits takes the [N, 1] unclamped outputs."""
         if out is None:
-            import torch
-            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.int32, device=f"cuda:{self._env.Device}")
-        capi.check(self._lib.gymnet_vecenv_actor_act_device(self._handle(), _ptr(out), _ptr(logits), float(epsilon),
-                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+            out = self._actions()
+        act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
+        capi.check(act(self._handle(), _ptr(out), _ptr(logits), float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
         return out
+
+    def _actions(self):
+        import torch
+        return torch.empty(self._env.NumberOfEnvironments, dtype=torch.float32 if self.IsBox else torch.int32, device=f"cuda:{self._env.Device}")
 
     def Push(self, done=None):
         """Once after each single vector step: lanes whose done byte is set (device bytes; None: the handle's own) refill every slot with
@@ -905,8 +916,7 @@ class Actor:
     def Step(self, epsilon=0.0, seed=0, tick=0):
         """Act(epsilon, seed, tick), StepDevice, Push(): one closed-loop vector step; returns the device actions taken."""
         if self._out is None:
-            import torch
-            self._out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.int32, device=f"cuda:{self._env.Device}")
+            self._out = self._actions()
         self.Act(epsilon, seed, tick, out=self._out)
         self._env.StepDevice(self._out)
         self.Push()
@@ -915,7 +925,7 @@ class Actor:
     def Close(self):
         """Releases the actor."""
         if self._h is not None and self._env._h:
-            capi.check(self._lib.gymnet_vecenv_actor_config(self._h, 0, 0, None, None, 0))
+            capi.check(self._lib.gymnet_vecenv_actor_config(self._h, 0, 0, None, None, 0))      # (releases either kind)
             self._env._actor = None
         self._h = None
 

@@ -324,9 +324,11 @@ int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, 
 /* GYMNET_ACTIONS_ACTOR (additive in ABI 6): the handle's actor chooses step t's action as gymnet_vecenv_actor_act_device(epsilon,
  * action_seed, action_tick0 + t) would, from the history the kernel keeps current (d_actions is ignored): bit-identical to `steps` x
  * (actor_act_device, step_device, actor_push_device), the final history included.  Needs a configured actor whose history is current;
- * float32 CartPole / MountainCar / Acrobot handles (GYMNET_ERR_UNSUPPORTED for float64 handles and Box envs).  Every flag combination of
- * the other sources is accepted; GYMNET_RECORDS_NO_OVERFLOW is accepted and served by the variant with the overflow segment (nothing is
- * dropped below ep_capacity). */
+ * float32 handles (GYMNET_ERR_UNSUPPORTED for float64 handles).  On a Box-action handle (Pendulum, MountainCarContinuous) the actor is the
+ * Box actor of gymnet_vecenv_actor_box_config, step t's action is what gymnet_vecenv_actor_box_act_device(epsilon, action_seed,
+ * action_tick0 + t) writes, epsilon means that call's rule and d_rec_actions is float32 [T][N]; without a Box actor the call fails as it
+ * does without any actor.  Every flag combination of the other sources is accepted; GYMNET_RECORDS_NO_OVERFLOW is accepted and served
+ * by the variant with the overflow segment (nothing is dropped below ep_capacity). */
 typedef enum gymnet_action_source { GYMNET_ACTIONS_RING = 0, GYMNET_ACTIONS_SAMPLE = 1, GYMNET_ACTIONS_EPSILON_GREEDY = 2,
                                     GYMNET_ACTIONS_ACTOR = 3 } gymnet_action_source;
 typedef struct gymnet_rollout_spec {
@@ -580,7 +582,8 @@ int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_
  *   but are not step launches, so a push after them is refused: drive an actor there with gymnet_vecenv_step_device (or the fused
  *   actor rollout).
  * Envs: Discrete-action envs (CartPole, MountainCar, Acrobot) on float32 handles, and float64 CartPole handles for config / reset /
- *   push / act; Box-action envs: GYMNET_ERR_UNSUPPORTED.  num_layers 0 releases the actor (the other arguments are not looked at).
+ *   push / act; Box-action envs: GYMNET_ERR_UNSUPPORTED from actor_config (their actor is gymnet_vecenv_actor_box_config, below; load,
+ *   reset, push and view serve both kinds).  num_layers 0 releases the actor (the other arguments are not looked at).
  *   Every call but config is ordered on the handle's stream and does not block; none changes state, observations, tick, counters or
  *   the done bytes.  The actor is not part of a checkpoint.
  * Errors (nothing written): GYMNET_ERR_INVALID_ARG for widths, count, history or epsilon outside the ranges above, null pointers, calls
@@ -592,6 +595,28 @@ int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask);
 int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done);
 int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick);
 int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot);
+/* The Box actor (additive in ABI 6): the same actor on a Box action space — Pendulum-v1 (obs_dim 3, bounds -2 .. 2) and
+ * MountainCarContinuous-v0 (obs_dim 2, bounds -1 .. 1), float32 handles (neither env has a float64 mode).
+ * Network: as above — L in [1, 4] layers, every width in [1, 64], at most 8192 parameters, torch's nn.Linear layout, ReLU between the
+ *   layers, the same fmaf chain in ascending input order — with w_0 = S * obs_dim <= 64 (so S <= 21 on Pendulum, <= 32 on
+ *   MountainCarContinuous) and w_L = the action dimension = 1.  Call the one output `raw`.
+ * Greedy action: raw clamped to the env's bounds in the form the envs themselves use, raw < low ? low : (raw > high ? high : raw), low and
+ *   high from gymnet_env_info (action_low / action_high); a NaN passes through it, as it does through Pendulum's own clamp.
+ * Exploration (TrainingPlaySession.ComposeAction, TrainingPlaySession.cs:46-52, carried over to a Box space): let b be word B of the
+ *   aux stream for (seed, global lane, tick).  If b <= coin_threshold(epsilon) — u01_24(b) <= epsilon — the action is ActionSpace.Sample()
+ *   = low + (high - low) * u01_24(word A of the action stream): the value gymnet_vecenv_sample_actions_device writes for the same
+ *   (seed, lane, tick).  Otherwise it is the greedy action.
+ * Out of scope: Gaussian action noise, tanh (or any other squashing) heads, and action dimensions above 1.
+ * box_config: the arguments and checks of actor_config, with widths[num_layers] == 1; GYMNET_ERR_UNSUPPORTED on a Discrete-action env;
+ *   num_layers 0 releases the actor.  The handle still owns at most one actor of either kind: configuring one replaces the other
+ *   (everything is allocated before the old actor is released).
+ * box_act_device: d_actions [num_envs] float32; d_raw [num_envs] float32 or NULL receives the unclamped output (the counterpart of
+ *   d_logits).  The epsilon, null-pointer and staleness checks of actor_act_device.  Each act call refuses the other kind of actor with
+ *   GYMNET_ERR_INVALID_ARG (nothing written).
+ * History, staleness, load_device, reset_device, push_device and view are the rules above, shared by both kinds. */
+int gymnet_vecenv_actor_box_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
+                                   int64_t count);
+int gymnet_vecenv_actor_box_act_device(gymnet_vecenv *h, float *d_actions, float *d_raw, float epsilon, uint64_t seed, uint64_t tick);
 
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */

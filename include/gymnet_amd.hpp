@@ -357,6 +357,16 @@ public:
     void ActorAct(int32_t *d_actions, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_logits = nullptr) {
         check(gymnet_vecenv_actor_act_device(h_, d_actions, d_logits, epsilon, seed, tick));
     }
+    // The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous; its one output, clamped to the
+    // env's bounds, is the action.  Empty widths release the actor.  LoadActorWeights / ResetActor / PushActor serve both kinds.
+    void ConfigureBoxActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
+        if (widths.empty()) { check(gymnet_vecenv_actor_box_config(h_, 0, 0, nullptr, nullptr, 0)); return; }
+        check(gymnet_vecenv_actor_box_config(h_, history, (int32_t)widths.size() - 1, widths.data(), weights.data(), (int64_t)weights.size()));
+    }
+    // d_actions float32 [N]; d_raw float32 [N] or null: the unclamped outputs
+    void BoxActorAct(float *d_actions, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_raw = nullptr) {
+        check(gymnet_vecenv_actor_box_act_device(h_, d_actions, d_raw, epsilon, seed, tick));
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
