@@ -316,11 +316,19 @@ __global__ __launch_bounds__(256) void compose_discrete_kernel(const int32_t *__
 
 // Box.Sample() of one element (Box.cs:69-90): the reference's four regimes, selected by which bounds are finite.  wa = the
 // element's word A; the unbounded regime alone needs a second uniform — word B, fetched through `wb()` only there.
+// Bounded regime: low + (high - low) * u wherever the width is a finite float.  A Box as wide as CartPole's own ObservationSpace
+// (velocities in [-float.MaxValue, float.MaxValue], CartPoleEnv.cs:46-48) overflows the width to +inf — every draw +inf, or NaN at
+// u == 0 — so such bounds take the convex form low * (1 - u) + high * u: 1 - u is exact for a 24-bit u, the two products have
+// opposite signs (a width can only overflow when low < 0 < high) and each lies between 0 and its bound, so the sum is finite and
+// inside [low, high]; u == 0 gives exactly low.
 template <class AuxWord>
 __device__ __forceinline__ float box_sample_value(float low, float high, uint32_t wa, AuxWord wb) {
     const bool blo = low > -INFINITY, bhi = high < INFINITY;     // Box.CheckBounded (Box.cs:53-58)
     const float u = u01_24(wa);
-    if (blo && bhi) return low + (high - low) * u;                // Box.cs:85 uniform(low, high)
+    if (blo && bhi) {                                             // Box.cs:85 uniform(low, high)
+        const float width = high - low;
+        return __builtin_isfinite(width) ? low + width * u : low * (1.0f - u) + high * u;
+    }
     if (blo) return -logf(1.0f - u) + low;                        // Box.cs:83 exponential(1) + low
     if (bhi) return -logf(1.0f - u) + high;                       // Box.cs:84 exponential(1) + high (sic)
     const float u1 = (float)((wa >> 8) + 1u) * (1.0f / 16777216.0f);   // (0, 1]

@@ -668,7 +668,8 @@ int gymnet_sample_discrete_masked_device(int device, void *stream, int32_t *d_ou
                                          const uint8_t *d_mask, int64_t mask_stride, uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* Box.Sample() (Box.cs:69-90), the reference's four regimes per element: bounded -> uniform(low, high);
  * low only -> low + Exp(1); high only -> high + Exp(1) (sic, Box.cs:84); unbounded -> Normal(0.5, 1) (sic, Box.cs:82).
- * low = -INFINITY / high = +INFINITY select the regime. */
+ * low = -INFINITY / high = +INFINITY select the regime.  The bounded draw is low + (high - low) * u in float32; where high - low
+ * overflows float32 (bounds as wide as CartPole's +-float.MaxValue velocities) it is low * (1 - u) + high * u: finite, inside the bounds. */
 int gymnet_sample_box_device(int device, void *stream, float *d_out, int64_t count, float low, float high,
                              uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* ABI 3.  Box.Sample() for a Box built from Low / High ARRAYS (Box.cs:25-51: `new Box(NDArray low, NDArray high)`), e.g. an

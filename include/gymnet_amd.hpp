@@ -100,8 +100,12 @@ public:
     std::vector<float> Sample() {                                               // Box.cs:72-93, the reference's four regimes
         std::vector<float> s(Low.size());
         for (size_t i = 0; i < s.size(); ++i) {
-            if (BoundedLow[i] && BoundedHigh[i]) s[i] = std::uniform_real_distribution<float>(Low[i], High[i])(rng_);
-            else if (BoundedLow[i]) s[i] = std::exponential_distribution<float>(1.0f)(rng_) + Low[i];
+            if (BoundedLow[i] && BoundedHigh[i]) {
+                // High - Low overflows float for bounds as wide as CartPole's +-float.MaxValue velocities (CartPoleEnv.cs:46-48), and
+                // uniform_real_distribution then returns inf / NaN: draw those as Low * (1 - u) + High * u, which cannot overflow
+                if (std::isfinite(High[i] - Low[i])) s[i] = std::uniform_real_distribution<float>(Low[i], High[i])(rng_);
+                else { const float u = std::uniform_real_distribution<float>(0.0f, 1.0f)(rng_); s[i] = Low[i] * (1.0f - u) + High[i] * u; }
+            } else if (BoundedLow[i]) s[i] = std::exponential_distribution<float>(1.0f)(rng_) + Low[i];
             else if (BoundedHigh[i]) s[i] = std::exponential_distribution<float>(1.0f)(rng_) + High[i];   // sic, Box.cs:84
             else s[i] = std::normal_distribution<float>(0.5f, 1.0f)(rng_);                                // sic, Box.cs:82
         }

@@ -497,11 +497,16 @@ void ref_compose_discrete_batch(uint64_t seed, uint64_t lane0, uint64_t tick, in
 }
 
 /* Box.Sample() bounded regime — src/Gym/Spaces/Box.cs:69-90: uniform(low, high). Engine
- * semantics (binary32): low + (high-low)*u with u = 24-bit uniform from word A. */
+ * semantics (binary32): low + (high-low)*u with u = 24-bit uniform from word A; where high-low overflows binary32 (bounds as wide as
+ * CartPole's +-float.MaxValue velocity components) the convex form low*(1-u) + high*u, which cannot overflow (csrc/kernels.hip
+ * box_sample_value). */
 void ref_box_uniform_sample_batch(uint64_t seed, uint64_t lane0, uint64_t tick, float low, float high,
                                   float *out, int64_t count) {
-    for (int64_t i = 0; i < count; ++i)
-        out[i] = low + (high - low) * u01_24(ref_action_word(seed, lane0 + (uint64_t)i, tick));
+    const float width = high - low;
+    for (int64_t i = 0; i < count; ++i) {
+        const float u = u01_24(ref_action_word(seed, lane0 + (uint64_t)i, tick));
+        out[i] = isfinite(width) ? low + width * u : low * (1.0f - u) + high * u;
+    }
 }
 
 /* ------------------------------------------------------------------------------------------

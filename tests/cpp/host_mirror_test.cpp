@@ -41,6 +41,16 @@ static void cpu_tests() {
         Box lo(std::vector<float>{2.0f, -inf}, std::vector<float>{inf, 7.0f}, 1);
         for (int i = 0; i < 200; ++i) { auto s = lo.Sample(); CHECK(s[0] >= 2.0f && s[1] >= 7.0f, "one-sided regimes as the reference writes them (Box.cs:83-84)"); }
         CHECK(lo.Contains({3.0f, 1.0f}) && !lo.Contains({1.0f, 1.0f}), "Box.Contains");
+        // CartPole's own ObservationSpace (CartPoleEnv.cs:46-48): the velocity bounds are +-float.MaxValue, whose width overflows float
+        const float fmax = std::numeric_limits<float>::max();
+        Box cart(std::vector<float>{-4.8f, -fmax, -0.418f, -fmax}, std::vector<float>{4.8f, fmax, 0.418f, fmax}, 2);
+        for (int i = 0; i < 200; ++i) {
+            auto s = cart.Sample();
+            bool finite = true;
+            for (float v : s) finite = finite && std::isfinite(v);
+            CHECK(finite, "Box.Sample() is finite for float.MaxValue bounds");
+            CHECK(cart.Contains(s), "Box.Sample() lies inside float.MaxValue bounds");
+        }
     }
     {   // Discrete.Contains (Discrete.cs:38-40)
         gymnet::Discrete d(2, 5);
