@@ -149,6 +149,9 @@ PROTOTYPES = {
     "gymnet_vecenv_rollout_device": (C.c_int, [_H, _P, C.c_int64, C.c_int64, C.c_int64]),
     "gymnet_vecenv_rollout_fused_device": (C.c_int, [_H, _P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(RolloutBuffers)]),
     "gymnet_vecenv_rollout_fused_ex_device": (C.c_int, [_H, C.POINTER(RolloutSpec)]),
+    "gymnet_vecenv_step_repeat_device": (C.c_int, [_H, _P, C.c_int32]),
+    "gymnet_vecenv_step_repeat": (C.c_int, [_H, _P, C.c_int32, _P, _P, _P]),
+    "gymnet_vecenv_rollout_repeat_device": (C.c_int, [_H, C.POINTER(RolloutSpec), C.c_int32]),
     "gymnet_vecenv_pack_obs_device": (C.c_int, [_H, _P]),
     "gymnet_vecenv_sync": (C.c_int, [_H]),
     "gymnet_vecenv_device_view": (C.c_int, [_H, C.POINTER(DeviceView)]),

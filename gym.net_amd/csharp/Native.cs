@@ -139,6 +139,10 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_device(IntPtr h, IntPtr d_actions, long steps, long action_stride, long ring, ref GymnetRolloutBuffers rec);
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_device(IntPtr h, IntPtr d_actions, long steps, long action_stride, long ring, IntPtr rec_null);   // rec = NULL: record nothing
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_ex_device(IntPtr h, ref GymnetRolloutSpec spec);
+        // frame skip: `repeat` skipped frames per decision, in [0, 255]
+        [DllImport(Lib)] public static extern int gymnet_vecenv_step_repeat_device(IntPtr h, IntPtr d_actions, int repeat);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_step_repeat(IntPtr h, void* actions, int repeat, void* obs_out, float* reward_out, byte* done_out);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_repeat_device(IntPtr h, ref GymnetRolloutSpec spec, int repeat);
         [DllImport(Lib)] public static extern int gymnet_vecenv_pack_obs_device(IntPtr h, IntPtr d_obs_rowmajor);
         [DllImport(Lib)] public static extern int gymnet_vecenv_sync(IntPtr h);
         [DllImport(Lib)] public static extern int gymnet_vecenv_device_view(IntPtr h, out GymnetDeviceView view);

@@ -310,6 +310,21 @@ namespace Gym.Envs.Amd {
             Native.Check(Native.gymnet_vecenv_rollout_fused_ex_device(_h, ref spec));
         }
 
+        /// Frame skip (IGameConfiguration.SkippedFrames, BasePlaySession.cs:37-56): one DECISION, dActions (device, int32 / float32 [N])
+        /// held for repeat + 1 env steps inside one launch.  A lane that finishes inside the decision keeps that done byte, is reset
+        /// there on an AutoReset handle and idles for the rest; the reward is the sum of the sub-step rewards taken.  repeat in [0, 255].
+        public void StepRepeatDevice(IntPtr dActions, int repeat) => Native.Check(Native.gymnet_vecenv_step_repeat_device(_h, dActions, repeat));
+        /// The same over the pinned buffers: reads HostBuffers().Actions, fills Obs / Reward / Done.  Blocks until they are written.
+        public void StepRepeatPinned(int repeat) {
+            var b = HostBuffers();
+            Native.Check(Native.gymnet_vecenv_step_repeat(_h, (void*) b.Actions, repeat, (void*) b.Obs, (float*) b.Reward, (byte*) b.Done));
+        }
+        /// The fused form: spec.steps DECISIONS of repeat + 1 env steps each; the rec_* buffers and the records' step index are per decision.
+        public void RolloutRepeat(GymnetRolloutSpec spec, int repeat) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_repeat_device(_h, ref spec, repeat));
+        }
+
         /// ABI 4: any per-lane array the handle keeps, by id — with GetState / the tick / the seed a complete checkpoint of every
         /// configuration (episode return / length, done flags, per-lane Philox keys, ...).  T must be the array's element type.
         public T[] GetArray<T>(GymnetArrayId which, int count) where T : unmanaged {

@@ -363,7 +363,7 @@ int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
     if (!(since(h, ac.last) == StepMark{1, 1}))
         return fail(h, GYMNET_ERR_INVALID_ARG, "an actor push needs exactly one vector step since the last actor config, reset or push (tick %llu -> %llu, "
                     "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)ac.last.tick,
-                    (unsigned long long)h->tick, (unsigned long long)since(h, ac.last).launches);
+                    (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)since(h, ac.last).launches);   // (both on the decision clock: StepMark)
     ActorHist hs = ac.hist;
     hs.slot = ring_next(hs.slot, hs.history);
     HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));

@@ -1168,8 +1168,9 @@ int ensure_episode_segments(gymnet_vecenv *h, int64_t capacity) {
     return GYMNET_OK;
 }
 
+// held: frame skip — sp.steps decisions of held + 1 sub-steps each (action_repeat.hip); 0: the fused rollout
 template <class R>
-int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchCfg cfg, bool episodes) {
+int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchCfg cfg, bool episodes, int32_t held = 0) {
     const StepArgsT<R> a = make_step_args<R>(h, sp.d_actions);
     RolloutArgsT<R> r{};
     r.steps = sp.steps; r.action_stride = sp.action_stride; r.ring = sp.ring;
@@ -1189,7 +1190,9 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
         // the kShards + 1 counters, zeroed on the stream by a kernel of our own
         HIP_TRY(h, launch_fill_i32(reinterpret_cast<int32_t *>(r.ep_count), 0, (int64_t)(kShards + 1) * kCountStride, h->stream));
     }
-    if constexpr (sizeof(R) == 4) {
+    if (held > 0) {
+        HIP_TRY(h, repeat_rollout_launch(h, a, r, held + 1));
+    } else if constexpr (sizeof(R) == 4) {
         if (sp.action_source == GYMNET_ACTIONS_ACTOR) {
             HIP_TRY(h, actor_rollout_launch(h, episodes, a, r));
         } else {
@@ -1211,13 +1214,10 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
     return GYMNET_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec) {
-    return guarded([&]() -> int {
-    ENTER(h);
+// gymnet_vecenv_rollout_fused_ex_device on a handle the caller has ENTERed.  held > 0: gymnet_vecenv_rollout_repeat_device — the same
+// checks, then spec.steps decisions of held + 1 sub-steps each.  validated: the caller has run VALIDATE_ACTIONS over the one slice read
+// (gymnet_vecenv_step_repeat_device).
+int rollout_fused_entered(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t held, bool validated) {
     if (!spec) return fail(h, GYMNET_ERR_INVALID_ARG, "spec is null");
     if (spec->struct_size != sizeof(gymnet_rollout_spec))
         return fail(h, GYMNET_ERR_INVALID_ARG, "spec.struct_size %u != %zu (ABI mismatch)", spec->struct_size, sizeof(gymnet_rollout_spec));
@@ -1235,12 +1235,17 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
         if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "epsilon-greedy composition is defined for Discrete action spaces");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
     }
+    if (actor && held > 0)
+        return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout has no frame skip: run the unfused loop, one decision at a time "
+                    "(actor_act_device, step_repeat_device, actor_push_device)");
+    if (held > 0 && sp.steps * ((int64_t)held + 1) > INT32_MAX)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "steps * (repeat + 1) must fit an int32");
     if (actor) {
         if (h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout runs float32 handles (float64: act / step / push)");
         if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
         ST_TRY(actor_rollout_check(h));
     }
-    if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && ring_read)
+    if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && ring_read && !validated)
         return fail(h, GYMNET_ERR_UNSUPPORTED, "VALIDATE_ACTIONS is per step; use gymnet_vecenv_rollout_device (sampled actions are valid by construction)");
     const bool episodes = sp.d_ep_lane || sp.d_ep_step || sp.d_ep_return || sp.d_ep_length || sp.d_ep_count;
     if (episodes) {
@@ -1272,14 +1277,73 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
         else if (!streams_fit(w)) cfg.vec = 1;
     }
     if (episodes) ST_TRY(ensure_episode_segments(h, sp.ep_capacity));
-    ST_TRY(h->f64 ? rollout_fused_typed<double>(h, sp, cfg, episodes) : rollout_fused_typed<float>(h, sp, cfg, episodes));
+    ST_TRY(h->f64 ? rollout_fused_typed<double>(h, sp, cfg, episodes, held) : rollout_fused_typed<float>(h, sp, cfg, episodes, held));
     swap_buffers(h);                     // DOUBLE_BUFFER: the launch read one buffer and wrote the other, once
-    h->tick += (uint64_t)sp.steps;
+    const uint64_t ticks = (uint64_t)sp.steps * ((uint64_t)held + 1);       // a sub-step is an engine tick
+    h->tick += ticks;
+    h->held_ticks += ticks - (uint64_t)sp.steps;
     h->tslot ^= 1;                       // one launch: it read one half of d_tick2 and wrote the other
     h->step_launches += 1;
-    h->lane_steps += (uint64_t)sp.steps * (uint64_t)h->n;
+    h->lane_steps += ticks * (uint64_t)h->n;      // slots: the host does not know which sub-steps found their lane idle
     if (actor) actor_rollout_done(h, sp.steps);
     return GYMNET_OK;
+}
+
+bool repeat_in_range(gymnet_vecenv *h, int32_t repeat) {
+    if (repeat >= 0 && repeat <= 255) return true;
+    fail(h, GYMNET_ERR_INVALID_ARG, "repeat must be in [0, 255] (skipped frames per decision), got %d", repeat);
+    return false;
+}
+
+// one decision: d_actions held for repeat + 1 env steps (repeat > 0; VALIDATE_ACTIONS has been applied by the caller)
+int launch_one_decision(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
+    gymnet_rollout_spec spec{};
+    spec.struct_size = sizeof spec;
+    spec.action_source = GYMNET_ACTIONS_RING;
+    spec.d_actions = d_actions; spec.steps = 1; spec.action_stride = 0; spec.ring = 1;
+    return rollout_fused_entered(h, &spec, repeat, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    return rollout_fused_entered(h, spec, 0, false);
+    });
+}
+
+int gymnet_vecenv_rollout_repeat_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t repeat) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    return rollout_fused_entered(h, spec, repeat, false);
+    });
+}
+
+int gymnet_vecenv_step_repeat_device(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (repeat == 0 && h->lcfg.vec > 1 && !aligned_to(d_actions, 4 * h->lcfg.vec))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions must be %d-byte aligned", 4 * h->lcfg.vec);
+    ST_TRY(validate_staged_actions(h, d_actions));
+    return repeat == 0 ? launch_one_step(h, d_actions) : launch_one_decision(h, d_actions, repeat);
+    });
+}
+
+int gymnet_vecenv_step_repeat(gymnet_vecenv *h, const void *actions, int32_t repeat, void *obs_out, float *reward_out, uint8_t *done_out) {
+    return guarded([&]() -> int {
+    ENTER(h);                            // (not served by the resident kernel: a resident handle leaves residency first)
+    if (h->async_pending) return fail(h, GYMNET_ERR_ALREADY_STEPPING, "already running an async step");
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    const void *d_act = nullptr;
+    ST_TRY(stage_host_actions(h, actions, &d_act, true));
+    ST_TRY(repeat == 0 ? launch_one_step(h, d_act) : launch_one_decision(h, d_act, repeat));
+    return copy_out(h, obs_out, reward_out, done_out);
     });
 }
 

@@ -564,7 +564,7 @@ int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, co
     if (!(since(h, em.last) == StepMark{1, 1}))
         return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
                     "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device", (unsigned long long)em.last.tick,
-                    (unsigned long long)h->tick, (unsigned long long)since(h, em.last).launches);
+                    (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)since(h, em.last).launches);   // (both on the decision clock: StepMark)
     MemPushArgs p{};
     p.obs = h->d_obs; p.obs_stride = h->ostride;
     p.actions = d_actions; p.reward = h->d_reward; p.done = d_done ? d_done : h->d_done;

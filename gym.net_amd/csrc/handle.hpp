@@ -118,6 +118,7 @@ struct gymnet_vecenv {
     gymnet::EpisodeMemory *memory = nullptr;
     gymnet::Actor *actor = nullptr;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
+    uint64_t held_ticks = 0;       // engine ticks that repeated a decision's action (frame skip: R - 1 per decision), see StepMark
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;
     bool async_pending = false;
@@ -238,11 +239,13 @@ int release_attachment(gymnet_vecenv *h, A *&slot) {
 int release_render(gymnet_vecenv *h), release_stack(gymnet_vecenv *h);      // render.hip, pixel_stack.hip
 int release_memory(gymnet_vecenv *h), release_actor(gymnet_vecenv *h);      // episode_memory.hip, actor.hip
 
-// Where the handle's step counters stood at an attachment's last config / reset / push: "exactly one vector step since" is
-// since(h, m) == {1, 1}, "none" is {0, 0}.
+// Where the handle's step counters stood at an attachment's last config / reset / push: "exactly one decision since" is
+// since(h, m) == {1, 1}, "none" is {0, 0}.  A decision is one vector step, or one action held for R sub-steps in one launch
+// (action_repeat.hip): the tick counts DECISION ticks here — engine ticks less h->held_ticks, the R - 1 ticks per decision a frame-skip
+// launch holds its action for — so a fused rollout of R steps still reads {R, 1} and T > 1 held decisions read {T, 1}.
 struct StepMark { uint64_t tick = 0, launches = 0; };
-inline StepMark mark(const gymnet_vecenv *h) { return {h->tick, h->step_launches}; }
-inline StepMark since(const gymnet_vecenv *h, StepMark m) { return {h->tick - m.tick, h->step_launches - m.launches}; }
+inline StepMark mark(const gymnet_vecenv *h) { return {h->tick - h->held_ticks, h->step_launches}; }
+inline StepMark since(const gymnet_vecenv *h, StepMark m) { return {h->tick - h->held_ticks - m.tick, h->step_launches - m.launches}; }
 inline bool operator==(StepMark a, StepMark b) { return a.tick == b.tick && a.launches == b.launches; }
 
 // the handle's launcher table, for code typed by its state scalar R
@@ -278,5 +281,8 @@ int resident_stop(gymnet_vecenv *h);                                 // tells a 
 int actor_rollout_check(gymnet_vecenv *h);
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
+// the fused rollout with frame skip (action_repeat.hip): r.steps decisions of R sub-steps each under one action, one launch
+hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs &a, const RolloutArgs &r, int32_t R);
+hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const RolloutArgs64 &r, int32_t R);
 
 }  // namespace gymnet

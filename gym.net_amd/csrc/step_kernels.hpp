@@ -1047,10 +1047,24 @@ struct EpisodeStage { int32_t t[kStageRecords], lane[kStageRecords]; float ret[k
 //           Its actions are recorded on every handle, like sampled ones.  Both calls are compiled out for NoHook.
 struct NoHook { static constexpr bool CHOOSES = false; };
 
-template <class Env, int VEC, bool AUTORESET, bool GUARD, bool EXTRAS, bool SAMPLE, int RESETF = 0, int RECORDS = 0, class Hook = NoHook>
+//   Rep     frame skip (action_repeat.hip; the contract is gymnet_vecenv_rollout_repeat_device in include/gymnet_amd.h).  NoRepeat: every
+//           trip of the loop is one step, as described above.  HeldAction{R}: a trip is a DECISION — ro.steps counts decisions, t is the
+//           decision's index in everything that carries one (ring slice, action tick, rec_* row, episode record, "the last step" of the
+//           done list) — and the part of the body from the `substep` label to the fused reset runs R times under the trip's action, sub-step
+//           `sub` at engine tick tick0 + t * R + sub.  The env step, the bookkeeping, the record staging, the fused reset and the
+//           write-back are the ones below for both; what the switch adds is a live flag per sub-lane (set at sub-step 0, cleared when the
+//           lane's done byte comes out non-zero: an idle lane takes no step, earns nothing, keeps its state), the decision's reward (the
+//           first sub-step's reward itself, then += in sub-step order) and done byte, and the way back to `substep` past the rec_* stores.
+//           All of it is `if constexpr (Rep::ON)`, and the NoRepeat text is otherwise untouched — even a renamed loop index moves registers
+//           in a third of the existing rollout kernels (tools/isa_diff.py) — which is why the inner loop is a label and not a `for`.
+struct NoRepeat { static constexpr bool ON = false; };
+struct HeldAction { static constexpr bool ON = true; int32_t R; };
+
+template <class Env, int VEC, bool AUTORESET, bool GUARD, bool EXTRAS, bool SAMPLE, int RESETF = 0, int RECORDS = 0, class Hook = NoHook, class Rep = NoRepeat>
 __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real> &a, const RolloutArgsT<typename Env::Real> &ro,
                                              const int64_t i0, const uint64_t tick0, ResetScratch<Env> *sc = nullptr, EpisodeStage *stage = nullptr,
-                                             Hook hook = Hook{}) {
+                                             Hook hook = Hook{}, Rep rep = Rep{}) {
+    static_assert(!Rep::ON || (!Hook::CHOOSES && !(Env::PACKED2 && VEC == 2)), "frame skip: ring / sampled actions, unpacked sub-lanes");
     constexpr int S = Env::S, O = Env::O;
     using Act = typename Env::Action;
     using Real = typename Env::Real;
@@ -1142,6 +1156,13 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
         }
     };
 
+    // Rep::ON: the sub-step inside the trip, and the decision's accumulators
+    int32_t sub = 0;
+    bool closes = true;                // this sub-step is the decision's last
+    bool live[VEC];
+    float dec_reward[VEC];
+    uint8_t dec_done[VEC];
+
     for (int64_t t = 0; t < ro.steps; ++t) {
         int64_t nslice = slice + 1;
         if (nslice == ro.ring) nslice = 0;
@@ -1160,6 +1181,12 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
         } else {
             if (t + 1 < ro.steps) load_action(nslice, act_next);        // in flight during this step's math
         }
+        if constexpr (Rep::ON) {
+            sub = 0;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) live[j] = true;
+        }
+    substep:                               // (Rep::ON comes back here for the decision's next sub-step)
         uint32_t pending = 0;
         bool after[VEC];
 #pragma unroll
@@ -1172,6 +1199,9 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
             auto all_sublanes = [&](auto small_tag) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
+                    if constexpr (Rep::ON) {
+                        if (!live[j]) { done[j] = 0; reward[j] = 0.0f; continue; }     // idle: no step, no reward, the state stays
+                    }
                     Real sj[S], oj[O];
                     float rw;
                     bool dn;
@@ -1212,6 +1242,9 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
             for (int j = 0; j < VEC; ++j) {
                 const bool in_range = !GUARD || i0 + j < n;
                 fin_ret[j] = 0.0f; fin_len[j] = 0;
+                if constexpr (Rep::ON) {
+                    if (!live[j]) { finished[j] = false; continue; }                   // idle: the episode counters stand still
+                }
                 if (stats) {
                     ep_ret[j] += reward[j];
                     ep_len[j] += 1;
@@ -1267,6 +1300,18 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
             if (a.done_list && t + 1 == ro.steps) append_done_records<Env, VEC>(a, finished, i0, s, o, fin_ret, fin_len, stats);
         }
         if constexpr (!AUTORESET && Env::HAS_SBD) count_after_done<VEC>(a, after);
+        if constexpr (Rep::ON) {
+            closes = sub + 1 == rep.R;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                // (an idle sub-lane arrives with reward 0 and done 0 and adds neither)
+                if (sub == 0) { dec_reward[j] = reward[j]; dec_done[j] = done[j]; }
+                else if (live[j]) { dec_reward[j] += reward[j]; dec_done[j] = done[j]; }
+                live[j] = live[j] && done[j] == 0;
+                if (closes) { reward[j] = dec_reward[j]; done[j] = dec_done[j]; }      // what the rec_* rows and d_reward / d_done receive
+            }
+            if (!closes) goto scalars_recorded;
+        }
         if (ro.rec_reward) store_f32<VEC, true, GUARD>(ro.rec_reward + t * n, i0, n, reward);
         if (ro.rec_done) store_u8<VEC, true, GUARD>(ro.rec_done + t * n, i0, n, done);
         if constexpr (EXTRAS || SAMPLE || Hook::CHOOSES) {
@@ -1275,7 +1320,14 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
                 else store_i32<VEC, true, GUARD>(static_cast<int32_t *>(ro.rec_action) + t * n, i0, n, act);
             }
         }
-        if constexpr (AUTORESET && RESETF == 1) reset_pending_wave<Env, VEC, EXTRAS>(pending, s, a, i0, n, tick0 + (uint64_t)t, sc);
+    scalars_recorded:
+        if constexpr (Rep::ON) {           // the reset draw of the SUB-STEP's tick: the one a single step at that tick makes
+            const uint64_t tick = tick0 + (uint64_t)t * (uint64_t)rep.R + (uint64_t)sub;
+            if constexpr (AUTORESET && RESETF == 1) reset_pending_wave<Env, VEC, EXTRAS>(pending, s, a, i0, n, tick, sc);
+            else if constexpr (AUTORESET) reset_pending<Env, VEC, EXTRAS>(pending, s, o, a, i0, n, tick);
+            if (!closes) { ++sub; goto substep; }
+        }
+        else if constexpr (AUTORESET && RESETF == 1) reset_pending_wave<Env, VEC, EXTRAS>(pending, s, a, i0, n, tick0 + (uint64_t)t, sc);
         else if constexpr (AUTORESET) reset_pending<Env, VEC, EXTRAS>(pending, s, o, a, i0, n, tick0 + (uint64_t)t);
         if (ro.rec_obs) {
 #pragma unroll

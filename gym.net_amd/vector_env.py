@@ -41,6 +41,13 @@ def _host(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _repeat(repeat):
+    """`repeat` skipped frames per decision as the native calls take it: an int in [0, 255], refused here before any native call"""
+    if isinstance(repeat, (bool, np.bool_)) or not isinstance(repeat, (int, np.integer)) or not 0 <= int(repeat) <= 255:
+        raise ValueError(f"repeat must be an int in [0, 255] (skipped frames per decision), got {repeat!r}")
+    return int(repeat)
+
+
 class BatchStep:
     """What `Step[]` (IVecEnv.cs:15) becomes at 2^20 lanes: three arrays.  Indexing / iterating yields the
     reference's per-env Step records (Step.cs:7-20), materialised lazily."""
@@ -222,6 +229,16 @@ class VectorEnv:
             capi.check(self._lib.gymnet_vecenv_step(self._h, _host(a), _host(obs), _host(rew), _host(done)))
         return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
 
+    def StepRepeat(self, action, repeat):
+        """Frame skip at the host boundary (gymnet_vecenv_step_repeat): one action per lane, held for repeat + 1 env steps in one launch.
+        The BatchStep carries the decision's observation (post-reset where a lane finished), its summed reward and its done byte; a
+        lane that finishes inside the decision stops there (see StepRepeatDevice).  repeat = 0 is Step(action) with an array."""
+        repeat = _repeat(repeat)
+        obs, rew, done = self._outs()
+        a = self._actions(action)
+        capi.check(self._lib.gymnet_vecenv_step_repeat(self._h, _host(a), repeat, _host(obs), _host(rew), _host(done)))
+        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+
     def HostBuffers(self):
         """(actions, obs, reward, done): numpy views over the library's page-locked, device-mapped host buffers
         (gymnet_vecenv_host_buffers).  Passing them to StepInto / ResetInto runs the host boundary without staging copies."""
@@ -287,11 +304,19 @@ class VectorEnv:
     def StepDevice(self, d_actions):
         capi.check(self._lib.gymnet_vecenv_step_device(self._h, _ptr(d_actions)))
 
+    def StepRepeatDevice(self, d_actions, repeat):
+        """One DECISION (gymnet_vecenv_step_repeat_device): d_actions held for R = repeat + 1 env steps inside one launch — the
+        reference's SkippedFrames (BasePlaySession.cs:37-56).  A lane whose done byte comes out non-zero at a sub-step keeps that byte,
+        is reset there on an auto_reset handle, and idles for the rest of the decision; the reward is the sum of the sub-step rewards
+        taken; the tick advances by R.  repeat = 0 is StepDevice."""
+        repeat = _repeat(repeat)
+        capi.check(self._lib.gymnet_vecenv_step_repeat_device(self._h, _ptr(d_actions), repeat))
+
     def RolloutDevice(self, d_actions, steps, action_stride, ring):
         capi.check(self._lib.gymnet_vecenv_rollout_device(self._h, _ptr(d_actions), int(steps), int(action_stride), int(ring)))
 
     def RolloutFusedDevice(self, d_actions, steps, action_stride=0, ring=1, rec_obs=None, rec_reward=None, rec_done=None, actions="ring",
-                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None):
+                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0):
         """`steps` vector steps in ONE kernel launch (state stays in registers); optional device-side rollout
         buffers rec_obs [T][D][N] (of the handle's dtype: float64 for a float64 handle), rec_reward [T][N], rec_done [T][N]
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
@@ -305,7 +330,10 @@ class VectorEnv:
                     that end during the rollout (any array may be omitted; count: uint32[2] = records written, episodes ended);
                     no_overflow=True selects the 8 % faster kernel variant that may drop records of very unevenly finishing lanes
                     below `capacity` (GYMNET_RECORDS_NO_OVERFLOW; count[1] > count[0] says so);
-                    needs a bookkeeping handle (BasePlaySession.cs:58-69)."""
+                    needs a bookkeeping handle (BasePlaySession.cs:58-69).
+          repeat    frame skip (gymnet_vecenv_rollout_repeat_device): `steps` counts DECISIONS, each action is held for repeat + 1 env
+                    steps, the rec_* buffers and the records' step index are per decision ("actor" needs repeat = 0)."""
+        repeat = _repeat(repeat)
         src = {"ring": capi.ACTIONS_RING, "sample": capi.ACTIONS_SAMPLE, "epsilon_greedy": capi.ACTIONS_EPSILON_GREEDY,
                "actor": capi.ACTIONS_ACTOR}[actions]
         ep = episodes or {}
@@ -318,7 +346,10 @@ class VectorEnv:
                                 d_rec_obs=_ptr(rec_obs), d_rec_reward=_ptr(rec_reward), d_rec_done=_ptr(rec_done), d_rec_actions=_ptr(rec_actions),
                                 d_ep_step=_ptr(ep.get("step")), d_ep_lane=_ptr(ep.get("lane")), d_ep_return=_ptr(ep.get("ret")),
                                 d_ep_length=_ptr(ep.get("length")), ep_capacity=int(ep.get("capacity", 0)), d_ep_count=_ptr(ep.get("count")))
-        capi.check(self._lib.gymnet_vecenv_rollout_fused_ex_device(self._h, C.byref(spec)))
+        if repeat:
+            capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
+        else:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_ex_device(self._h, C.byref(spec)))
 
     def SampleActionsDevice(self, d_actions, seed=0, tick=0):
         capi.check(self._lib.gymnet_vecenv_sample_actions_device(self._h, _ptr(d_actions), int(seed), int(tick)))
@@ -665,9 +696,14 @@ class PixelFrameStack:
         the current frame, the others shift by one and take it as the newest."""
         capi.check(self._lib.gymnet_vecenv_pixel_stack_push_device(self._handle(), _ptr(done)))
 
-    def Step(self, d_actions):
-        """StepDevice(d_actions) followed by Push()."""
-        self._env.StepDevice(d_actions)
+    def Step(self, d_actions, repeat=0):
+        """StepDevice(d_actions) — with repeat > 0 StepRepeatDevice(d_actions, repeat): one decision, the action held for repeat + 1
+        env steps — followed by Push().  A lane that finished anywhere inside the decision restarts its stack."""
+        repeat = _repeat(repeat)
+        if repeat:
+            self._env.StepRepeatDevice(d_actions, repeat)
+        else:
+            self._env.StepDevice(d_actions)
         self.Push()
 
     def Read(self, lanes=None):
@@ -711,9 +747,14 @@ class EpisodeMemory:
         (None: the handle's own)."""
         capi.check(self._lib.gymnet_vecenv_memory_push_device(self._handle(), _ptr(actions), _ptr(done)))
 
-    def Step(self, actions):
-        """StepDevice(actions) followed by Push(actions)."""
-        self._env.StepDevice(actions)
+    def Step(self, actions, repeat=0):
+        """StepDevice(actions) — with repeat > 0 StepRepeatDevice(actions, repeat): one decision — followed by Push(actions).  The row of
+        a decision is (observation when the action was chosen, action, summed reward, done byte)."""
+        repeat = _repeat(repeat)
+        if repeat:
+            self._env.StepRepeatDevice(actions, repeat)
+        else:
+            self._env.StepDevice(actions)
         self.Push(actions)
 
     def Reset(self, mask=None, clear=False):
@@ -913,12 +954,17 @@ class Actor:
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
 
-    def Step(self, epsilon=0.0, seed=0, tick=0):
-        """Act(epsilon, seed, tick), StepDevice, Push(): one closed-loop vector step; returns the device actions taken."""
+    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0):
+        """Act(epsilon, seed, tick), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —, Push(): one
+        closed-loop decision; returns the device actions taken."""
+        repeat = _repeat(repeat)
         if self._out is None:
             self._out = self._actions()
         self.Act(epsilon, seed, tick, out=self._out)
-        self._env.StepDevice(self._out)
+        if repeat:
+            self._env.StepRepeatDevice(self._out, repeat)
+        else:
+            self._env.StepDevice(self._out)
         self.Push()
         return self._out
 

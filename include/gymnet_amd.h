@@ -363,6 +363,40 @@ typedef struct gymnet_rollout_spec {
                                     for GYMNET_RECORDS_NO_OVERFLOW, round 5's behaviour.) */
 } gymnet_rollout_spec;
 int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec);
+/* ---- Frame skip: a decision's action held for several env steps inside ONE launch (the reference's IGameConfiguration.SkippedFrames,
+ * BasePlaySession.cs:37-56) ----------------------------------------------------------------------------------------------------------
+ * `repeat` = k >= 0 skipped frames; R = k + 1 sub-steps per DECISION.  repeat must lie in [0, 255] (else GYMNET_ERR_INVALID_ARG).  For a
+ * launch of T decisions that starts at engine tick tick0, decision d, sub-step r:
+ *   - the sub-step's engine tick is tick0 + d * R + r; the launch advances the handle's tick by T * R;
+ *   - the action of decision d is chosen once and held for its R sub-steps: ring slice d % ring, or with sampled / epsilon-greedy actions the
+ *     draw at action tick action_tick0 + d;
+ *   - every lane takes sub-step 0 exactly as the one-step call would at that tick — without GYMNET_FLAG_AUTORESET including the
+ *     steps_beyond_done rule and the stepped-after-done counter of a lane that was already done: every lane is LIVE at sub-step 0;
+ *   - a live lane advances as the one-step kernel does at that tick (physics, episode return += reward, episode length += 1, truncation at
+ *     max_episode_steps: the episode length counts env steps, not decisions);
+ *   - when a live lane's done byte comes out non-zero at sub-step r, that byte is the decision's done byte; the terminal observation, the
+ *     finished-episode views, the done list and the records are written as the one-step kernel writes them (a compact record of the fused
+ *     form carries the DECISION index d as its step index); with AUTORESET the lane is re-drawn with the reset draw of tick
+ *     tick0 + d * R + r, the draw a single step at that tick makes; and the lane is IDLE for sub-steps r + 1 .. R - 1: no step, no reward,
+ *     no change of episode length or state.  At the next decision it sits on the first observation of its new episode (the reference starts
+ *     an episode with a decision) — without AUTORESET on its terminal state, steps_beyond_done as the one step left it;
+ *   - the decision's reward is the float32 sum of the sub-step rewards taken, added in sub-step order STARTING FROM THE FIRST SUB-STEP'S
+ *     REWARD ITSELF (not from 0.0f: a -0.0f reward survives, and repeat = 0 is bit-identical to the one-step call);
+ *   - afterwards d_obs / d_reward / d_done hold the last decision's observation (post-reset where a reset happened), summed reward and
+ *     done byte; the d_rec_* arrays of a spec are per decision: [T][...][num_envs];
+ *   - gymnet_counters.lane_steps grows by T * R * num_envs: it counts SLOTS — which sub-steps found their lane idle is not known to the host.
+ * float32 and float64 handles, every env, every flag combination the fused rollout accepts.  repeat = 0 gives, bit for bit, what
+ * step_device / step / rollout_fused_ex_device give (the calls forward).
+ *
+ * step_repeat_device: ONE decision with d_actions [num_envs]; validates like step_device on a VALIDATE_ACTIONS handle.  step_repeat: the
+ * host-boundary form — stages the actions, runs one decision, copies out like gymnet_vecenv_step (it is not served by the resident kernel:
+ * a GYMNET_FLAG_RESIDENT handle leaves residency first).  rollout_repeat_device: the fused form over an existing spec, spec.steps = the
+ * number of decisions T (T * R must fit an int32); RING, SAMPLE and EPSILON_GREEDY with every check of rollout_fused_ex_device;
+ * GYMNET_ACTIONS_ACTOR with repeat > 0 is GYMNET_ERR_UNSUPPORTED (run the unfused loop: act, step_repeat_device, push).
+ * One decision — of any repeat — counts as one step for the attachments below: a pixel-stack, memory or actor push is accepted after it. */
+int gymnet_vecenv_step_repeat_device(gymnet_vecenv *h, const void *d_actions, int32_t repeat);
+int gymnet_vecenv_step_repeat(gymnet_vecenv *h, const void *actions, int32_t repeat, void *obs_out, float *reward_out, uint8_t *done_out);
+int gymnet_vecenv_rollout_repeat_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t repeat);
 /* Pack the SoA observations into row-major [num_envs, obs_dim] on the device (the NDArray layout; float32, or float64 for a
  * GYMNET_FLAG_F64 handle). */
 int gymnet_vecenv_pack_obs_device(gymnet_vecenv *h, void *d_obs_rowmajor);

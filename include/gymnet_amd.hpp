@@ -286,6 +286,18 @@ public:
     // device-resident path
     void ResetDevice() { check(gymnet_vecenv_reset_device(h_)); }
     void StepDevice(const void *d_actions) { check(gymnet_vecenv_step_device(h_, d_actions)); }
+    // Frame skip (gymnet_vecenv_step_repeat_device): one DECISION — d_actions held for repeat + 1 env steps in one launch; a lane that
+    // finishes inside it keeps that done byte and idles for the rest; the reward is the sum of the sub-steps taken.  repeat in [0, 255].
+    void StepRepeatDevice(const void *d_actions, int32_t repeat) { check(gymnet_vecenv_step_repeat_device(h_, d_actions, repeat)); }
+    /// the host-boundary form with caller-owned buffers, as StepInto
+    void StepRepeatInto(const void *actions, int32_t repeat, void *obs_out, float *reward_out, uint8_t *done_out) {
+        check(gymnet_vecenv_step_repeat(h_, actions, repeat, obs_out, reward_out, done_out));
+    }
+    /// the fused form: spec.steps DECISIONS of repeat + 1 env steps each, rec_* buffers and record indices per decision
+    void RolloutRepeatDevice(gymnet_rollout_spec spec, int32_t repeat) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_repeat_device(h_, &spec, repeat));
+    }
     void RolloutDevice(const void *d_actions, int64_t steps, int64_t stride, int64_t ring) { check(gymnet_vecenv_rollout_device(h_, d_actions, steps, stride, ring)); }
     void Sync() { check(gymnet_vecenv_sync(h_)); }
     gymnet_device_view DeviceView() const { gymnet_device_view v{}; check(gymnet_vecenv_device_view(h_, &v)); return v; }

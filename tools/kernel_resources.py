@@ -3,7 +3,8 @@
 VGPRs -> waves per SIMD (512 / VGPRs, at most 8), scratch bytes (spills), static LDS bytes.  Round 5 found two slowdowns that only this view
 explains — a float32 bookkeeping rollout that allocated 131-152 VGPRs (three waves per SIMD where 2^20 lanes need four) and a float64
 four-pair kernel that must stay at two waves per SIMD because it spills when capped for three (profiles/occupancy_hints_r05.txt).
-    python tools/kernel_resources.py [env ...]        env: the env_<env>.hip units of gym.net_amd/build.py's SOURCES (default: all)
+    python tools/kernel_resources.py [env ...]        env: the env_<env>.hip units of gym.net_amd/build.py's SOURCES (default: all),
+                                                      or any unit of SOURCES by file name (action_repeat.hip)
 Prints one line per kernel; tests/test_kernel_resources.py asserts the invariants the launch policy relies on."""
 import os
 import re
@@ -36,8 +37,9 @@ ENVS = tuple(e for e in CLI_ENVS if e != "mountaincar_continuous")
 
 
 def assembly(env, outdir):
-    out = os.path.join(outdir, env + ".s")
-    r = subprocess.run([HIPCC] + FLAGS + [os.path.join(CSRC, f"env_{env}.hip"), "-o", out], capture_output=True, text=True)
+    unit = env if env.endswith(".hip") else f"env_{env}.hip"
+    out = os.path.join(outdir, os.path.splitext(unit)[0] + ".s")
+    r = subprocess.run([HIPCC] + FLAGS + [os.path.join(CSRC, unit), "-o", out], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-2000:])
     return out
@@ -77,7 +79,8 @@ def collect(envs=ENVS):
 if __name__ == "__main__":
     envs = tuple(sys.argv[1:]) or CLI_ENVS
     res = collect(envs)
-    print(f"# hipcc {' '.join(FLAGS)}  (gym.net_amd/csrc/env_*.hip)   waves per SIMD = min(8, 512 // VGPRs)")
+    units = " ".join(e if e.endswith(".hip") else f"env_{e}.hip" for e in envs)
+    print(f"# hipcc {' '.join(FLAGS)}  (gym.net_amd/csrc/: {units})   waves per SIMD = min(8, 512 // VGPRs)")
     print(f"{'kernel':72s} {'VGPRs':>6s} {'waves/SIMD':>10s} {'scratch B':>10s} {'LDS B':>7s}")
     for k in sorted(res):
         v = res[k]
