@@ -51,6 +51,8 @@ PIXELS_RGB8, PIXELS_GRAY8 = 1, 2     # gymnet_vecenv_render(_device) formats
 RENDER_WIDTH, RENDER_HEIGHT = 600, 400
 STACK_GRAY8, STACK_BINARY8, STACK_BINARY_F32 = 2, 3, 4     # gymnet_vecenv_pixel_stack_config formats
 MEMORY_PARAMS = 0            # gymnet_vecenv_memory_dataset_device format (the others are the STACK_* formats)
+BOX_HEAD_CLAMP, BOX_HEAD_TANH = 0, 1                 # gymnet_vecenv_actor_box_set_policy: gymnet_box_head
+BOX_EXPLORE_SAMPLE, BOX_EXPLORE_GAUSSIAN = 0, 1      # ... and gymnet_box_explore
 
 
 class Config(C.Structure):
@@ -194,6 +196,8 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "gymnet_vecenv_actor_box_config": (C.c_int, [_H, C.c_int32, C.c_int32, _P, _P, C.c_int64]),
     "gymnet_vecenv_actor_box_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
+    "gymnet_vecenv_actor_box_set_policy": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_float]),
+    "gymnet_vecenv_actor_box_get_policy": (C.c_int, [_H, _P, _P, _P]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

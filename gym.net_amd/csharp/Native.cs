@@ -25,6 +25,9 @@ namespace Gym.Envs.Amd {
     }
 
     public enum GymnetDtype { F32 = 0, F64 = 1 }
+    // gymnet_vecenv_actor_box_set_policy: a Box actor's head and what its exploring lanes take
+    public enum GymnetBoxHead { Clamp = 0, Tanh = 1 }
+    public enum GymnetBoxExplore { Sample = 0, Gaussian = 1 }
 
     public enum GymnetPixelFormat { Rgb8 = 1, Gray8 = 2 }     // gymnet_vecenv_render(_device): 3 bytes per pixel / 1 byte (BT.709 luma)
 
@@ -193,6 +196,8 @@ namespace Gym.Envs.Amd {
         // the Box actor (Pendulum, MountainCarContinuous): the last layer's one output, clamped to the env's bounds, is the action
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, float epsilon, ulong seed, ulong tick);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_set_policy(IntPtr h, int head, int explore, float sigma);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_get_policy(IntPtr h, int* head, int* explore, float* sigma);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

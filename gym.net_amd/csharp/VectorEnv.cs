@@ -302,6 +302,15 @@ namespace Gym.Envs.Amd {
         /// epsilon (TrainingPlaySession.cs:46-52 on a Box space); dRaw float [N] or IntPtr.Zero receives the unclamped outputs.
         public void BoxActorAct(IntPtr dActions, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dRaw = default) =>
             Native.Check(Native.gymnet_vecenv_actor_box_act_device(_h, dActions, dRaw, epsilon, seed, tick));
+        /// A Box actor's policy (gymnet_vecenv_actor_box_set_policy): a tanh head and / or Gaussian noise of scale sigma around the greedy
+        /// action on the lanes that explore; BoxActorAct and the fused actor rollout read it.  A new actor has (Clamp, Sample, 0).
+        public void SetBoxActorPolicy(GymnetBoxHead head, GymnetBoxExplore explore, float sigma = 0f) =>
+            Native.Check(Native.gymnet_vecenv_actor_box_set_policy(_h, (int) head, (int) explore, sigma));
+        public void GetBoxActorPolicy(out GymnetBoxHead head, out GymnetBoxExplore explore, out float sigma) {
+            int hd, ex; float sg;
+            Native.Check(Native.gymnet_vecenv_actor_box_get_policy(_h, &hd, &ex, &sg));
+            head = (GymnetBoxHead) hd; explore = (GymnetBoxExplore) ex; sigma = sg;
+        }
 
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));

@@ -3,7 +3,9 @@
 // form the envs use (a NaN passes), is the greedy action, and exploration is TrainingPlaySession.ComposeAction (TrainingPlaySession.cs:
 // 46-52) carried over to a Box space: where word B of the aux stream is at or below coin_threshold(epsilon) the action is
 // ActionSpace.Sample() = low + (high - low) * u01_24(word A of the action stream), the value gymnet_vecenv_sample_actions_device writes
-// for the same (seed, global lane, tick).  The contract is gymnet_vecenv_actor_box_config in include/gymnet_amd.h.
+// for the same (seed, global lane, tick).  The contract is gymnet_vecenv_actor_box_config in include/gymnet_amd.h.  That is the default
+// policy; under any other (gymnet_vecenv_actor_box_set_policy: tanh head, Gaussian noise) the two host entry points below hand over to
+// actor_box_policy.hip, and this unit's kernels stay what they were.
 //
 // Fused rollout (actor_box_rollout_kernel): step_kernels.hpp's rollout_body, one lane per thread, with a hook whose choose() is the act
 // kernel's body and whose after() is the shared push: bit-identical to steps x (box_act, step, push).  Pendulum's observation has three
@@ -131,6 +133,7 @@ static hipError_t launch_actor_box_rollout_env(bool autoreset, bool extras, bool
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
+    if (!ac.default_policy()) return actor_box_policy_rollout_launch(h, records, a, r);
     switch (h->cfg.env_id) {
         case GYMNET_ENV_PENDULUM: return launch_actor_box_rollout_env<Pendulum>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
         case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS:
@@ -184,7 +187,13 @@ int gymnet_vecenv_actor_box_act_device(gymnet_vecenv *h, float *d_actions, float
         return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
     ActorAct aa{};
     aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
-    HIP_TRY(h, launch_actor_box_act(h->actor->net, h->actor->hist, d_actions, d_raw, h->desc->action_low, h->desc->action_high, aa, h->stream));
+    const Actor &ac = *h->actor;
+    if (!ac.default_policy()) {
+        HIP_TRY(h, actor_box_policy_act_launch(ac.net, ac.hist, d_actions, d_raw, h->desc->action_low, h->desc->action_high, aa,
+                                               BoxPolicy{ac.head, ac.explore, ac.sigma}, h->stream));
+        return GYMNET_OK;
+    }
+    HIP_TRY(h, launch_actor_box_act(ac.net, ac.hist, d_actions, d_raw, h->desc->action_low, h->desc->action_high, aa, h->stream));
     return GYMNET_OK;
     });
 }

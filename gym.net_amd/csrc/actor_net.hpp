@@ -1,7 +1,7 @@
 // actor_net.hpp — what the two actor units share: the network and the per-lane observation history as the kernels see them, the forward
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), and the handle's Actor attachment
 // with the calls one unit makes into the other.  actor.hip serves the Discrete envs (argmax head) and owns the attachment; actor_box.hip
-// serves the Box envs (clamp head).  Internal to the library.
+// serves the Box envs (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise).  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -150,7 +150,15 @@ static inline dim3 lane_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256
 // the configured actor: hist.slot is the ring slot of the newest observation; last: the handle's step counters at the last config, reset,
 // push or actor rollout, so act can tell that the history is current and push that exactly one vector step ran in between.  box: the
 // handle's env has a Box action space and the last layer's one value is the action (actor_box.hip); else its values are logits
-struct Actor { DeviceAllocs mem; ActorNet net{}; ActorHist hist{}; int64_t count = 0, packed = 0; StepMark last; bool box = false; };
+struct Actor {
+    DeviceAllocs mem; ActorNet net{}; ActorHist hist{}; int64_t count = 0, packed = 0; StepMark last; bool box = false;
+    // a Box actor's policy (gymnet_vecenv_actor_box_set_policy): a fresh actor has the default, which the kernels of actor_box.hip serve;
+    // any other runs through actor_box_policy.hip
+    int32_t head = GYMNET_BOX_HEAD_CLAMP, explore = GYMNET_BOX_EXPLORE_SAMPLE; float sigma = 0.0f;
+    bool default_policy() const { return head == GYMNET_BOX_HEAD_CLAMP && explore == GYMNET_BOX_EXPLORE_SAMPLE; }
+};
+// what the kernels of actor_box_policy.hip take of it, as a kernel argument
+struct BoxPolicy { int32_t head, explore; float sigma; };
 
 // the message names the config call that serves the handle's env
 inline int need_actor(gymnet_vecenv *h) {
@@ -166,5 +174,9 @@ int actor_configure(gymnet_vecenv *h, bool box, int32_t history, int32_t num_lay
 // actor_box.hip: the push / fill of a three-row observation (Pendulum), and the fused rollout of a Box handle
 hipError_t launch_actor_box_push3(const ActorHist &hs, const float *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st);
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+// actor_box_policy.hip: act and the fused rollout of a Box handle whose policy is not the default
+hipError_t actor_box_policy_act_launch(const ActorNet &net, const ActorHist &hs, float *actions, float *raw, float low, float high, const ActorAct &aa,
+                                       const BoxPolicy &pol, hipStream_t st);
+hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 
 }  // namespace gymnet

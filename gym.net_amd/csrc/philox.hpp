@@ -65,6 +65,10 @@ __host__ __device__ __forceinline__ PhiloxWords lane_words(uint64_t seed, uint64
 // Box.cs:82's normal) and is only drawn by them.  A thread that owns four aligned lanes (the dwordx4 forms) pays one call per step
 // instead of four; v1 drew a whole call per lane (counter (L, t)) and used words 0 and 1 of it.
 constexpr uint64_t kStreamReset = 0ull, kStreamAction = 0x9E3779B97F4A7C15ull, kStreamAux = 0xD6E8FEB86659FD93ull;
+// NOISE STREAM (additive in ABI 6): the second uniform of a Box actor's Gaussian exploration noise (actor_box_policy.hip),
+//     word N of global lane L at tick t = word (L & 3) of Philox(key = seed ^ kStreamNoise, counter = (L >> 2, t))
+// Word B cannot serve there: on an exploring lane it is at or below the coin's threshold by construction.
+constexpr uint64_t kStreamNoise = 0xA0761D6478BD642Full;
 template <bool UNIFORM_KEY = false>
 __host__ __device__ __forceinline__ PhiloxWords stream_words(uint64_t stream, uint64_t seed, uint64_t lane, uint64_t tick) {
     return lane_words<UNIFORM_KEY>(seed ^ stream, lane, tick);
@@ -89,6 +93,10 @@ __host__ __device__ __forceinline__ uint32_t action_word(uint64_t seed, uint64_t
 template <bool UNIFORM_KEY = false>
 __host__ __device__ __forceinline__ uint32_t aux_word(uint64_t seed, uint64_t lane, uint64_t tick) {
     return word_of(aux_group_words<UNIFORM_KEY>(seed, lane >> 2, tick), (uint32_t)lane & 3u);
+}
+template <bool UNIFORM_KEY = false>
+__host__ __device__ __forceinline__ uint32_t noise_word(uint64_t seed, uint64_t lane, uint64_t tick) {
+    return word_of(stream_words<UNIFORM_KEY>(kStreamNoise, seed, lane >> 2, tick), (uint32_t)lane & 3u);
 }
 
 // 24-bit uniform in [0,1): exactly representable in binary32

@@ -902,12 +902,42 @@ class Actor:
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
         compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
         float32 [N] — the network's one output clamped to the action bounds, or ActionSpace.Sample() as SampleActionsDevice(seed=seed,
-        tick=tick) draws it where the lane explores — and logits takes the [N, 1] unclamped outputs."""
+        tick=tick) draws it where the lane explores — and logits takes the [N, 1] unclamped outputs.  That is the default policy;
+        SetPolicy changes the head and what an exploring lane takes."""
         if out is None:
             out = self._actions()
         act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
         capi.check(act(self._handle(), _ptr(out), _ptr(logits), float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
         return out
+
+    _HEADS = {"clamp": capi.BOX_HEAD_CLAMP, "tanh": capi.BOX_HEAD_TANH}
+    _EXPLORES = {"sample": capi.BOX_EXPLORE_SAMPLE, "gaussian": capi.BOX_EXPLORE_GAUSSIAN}
+
+    def SetPolicy(self, head="clamp", explore="sample", sigma=0.0):
+        """A Box actor's policy (gymnet_vecenv_actor_box_set_policy), read by Act, Step and RolloutFusedDevice(actions="actor") from the
+        next call on.  head: "clamp" (the network's output clamped to the bounds) or "tanh" (mid + half * tanh(output)).  explore: what
+        a lane whose coin says "explore" takes: "sample" (ActionSpace.Sample()) or "gaussian" (the greedy action plus sigma * a standard
+        normal draw, clamped to the bounds).  A new actor has ("clamp", "sample", 0.0); Load, Push and Reset keep the policy."""
+        if not self.IsBox:
+            raise ValueError("a policy belongs to a Box actor; this one chooses Discrete actions")
+        if head not in self._HEADS:
+            raise ValueError(f"head must be one of {sorted(self._HEADS)}, got {head!r}")
+        if explore not in self._EXPLORES:
+            raise ValueError(f"explore must be one of {sorted(self._EXPLORES)}, got {explore!r}")
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma >= 0.0):
+            raise ValueError("sigma must be finite and >= 0")
+        capi.check(self._lib.gymnet_vecenv_actor_box_set_policy(self._handle(), self._HEADS[head], self._EXPLORES[explore], sigma))
+
+    @property
+    def Policy(self):
+        """(head, explore, sigma) as SetPolicy takes them, read from the library (gymnet_vecenv_actor_box_get_policy)."""
+        if not self.IsBox:
+            raise ValueError("a policy belongs to a Box actor; this one chooses Discrete actions")
+        head, explore, sigma = C.c_int32(), C.c_int32(), C.c_float()
+        capi.check(self._lib.gymnet_vecenv_actor_box_get_policy(self._handle(), C.byref(head), C.byref(explore), C.byref(sigma)))
+        heads, explores = {v: k for k, v in self._HEADS.items()}, {v: k for k, v in self._EXPLORES.items()}
+        return heads[head.value], explores[explore.value], float(sigma.value)
 
     def _actions(self):
         import torch

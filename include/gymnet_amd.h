@@ -640,7 +640,8 @@ int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_
  *   aux stream for (seed, global lane, tick).  If b <= coin_threshold(epsilon) — u01_24(b) <= epsilon — the action is ActionSpace.Sample()
  *   = low + (high - low) * u01_24(word A of the action stream): the value gymnet_vecenv_sample_actions_device writes for the same
  *   (seed, lane, tick).  Otherwise it is the greedy action.
- * Out of scope: Gaussian action noise, tanh (or any other squashing) heads, and action dimensions above 1.
+ *   That is the default policy; gymnet_vecenv_actor_box_set_policy (below) offers a tanh head and Gaussian noise around the greedy action.
+ * Out of scope: action dimensions above 1.
  * box_config: the arguments and checks of actor_config, with widths[num_layers] == 1; GYMNET_ERR_UNSUPPORTED on a Discrete-action env;
  *   num_layers 0 releases the actor.  The handle still owns at most one actor of either kind: configuring one replaces the other
  *   (everything is allocated before the old actor is released).
@@ -651,6 +652,30 @@ int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_
 int gymnet_vecenv_actor_box_config(gymnet_vecenv *h, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights,
                                    int64_t count);
 int gymnet_vecenv_actor_box_act_device(gymnet_vecenv *h, float *d_actions, float *d_raw, float epsilon, uint64_t seed, uint64_t tick);
+/* A Box actor's policy (additive in ABI 6): (head, explore, sigma), read by box_act_device and by the fused rollout with
+ * GYMNET_ACTIONS_ACTOR, which stays bit-identical to steps x (box_act_device, step_device, actor_push_device) under every policy.
+ * head:    CLAMP (default): greedy = raw < low ? low : (raw > high ? high : raw).  TANH: greedy = mid + half * tanh(raw) in float32,
+ *   mid = 0.5f * (low + high), half = 0.5f * (high - low) (0 and 2 on Pendulum, 0 and 1 on MountainCarContinuous, exactly), the product
+ *   and the sum rounded on their own.  A NaN passes either head.  d_raw receives raw, unchanged, whatever the head.
+ * explore: the coin is unchanged — a lane explores if and only if word B of the aux stream is <= coin_threshold(epsilon).
+ *   SAMPLE (default): an exploring lane takes ActionSpace.Sample() = low + (high - low) * u01_24(word A), whatever the head.
+ *   GAUSSIAN: an exploring lane takes clamp(greedy + sigma * z, low, high), z = sqrt(-2 ln u1) * cos(2 pi u2), with
+ *   u1 = ((A >> 8) + 1) * 2^-24 from the lane's word A of the action stream (the u1 of the Box sampler's unbounded regime) and
+ *   u2 = u01_24(N), N the lane's word of the noise stream: word (L & 3) of Philox(key = seed ^ 0xA0761D6478BD642F, counter = (L >> 2,
+ *   tick)) for global lane L, laid out like words A and B.  (Word B is not u2: on an exploring lane it is small by construction.)
+ *   A lane that does not explore takes greedy.
+ * Exact: raw, which lanes explore, the words, and under sigma == 0 the value (clamp(greedy + 0 * z) == greedy).  Toleranced against
+ *   float64: z within 1e-5 (|z| <= 5.77); the tanh greedy within half * 5 * 2^-24 plus one spacing of float32(max(|low|, |high|)); a
+ *   Gaussian action within that, plus sigma * 1e-5, plus one spacing of float32(|greedy| + sigma * |z|).
+ * set_policy: stored on the actor and read at the next act / actor rollout launch, so ordered on the handle's stream like the other
+ *   actor calls; changes no history and no staleness state.  sigma is stored whatever explore is.  box_config leaves the policy at
+ *   (CLAMP, SAMPLE, 0) — also a re-config; load_device, push_device and reset_device keep it.  GYMNET_ERR_INVALID_ARG, nothing changed:
+ *   no actor, a Discrete actor, an unknown enum value, sigma not finite or below 0.
+ * get_policy: any out pointer may be NULL; the same refusals for a handle without a Box actor. */
+typedef enum gymnet_box_head    { GYMNET_BOX_HEAD_CLAMP = 0,     GYMNET_BOX_HEAD_TANH = 1 }        gymnet_box_head;
+typedef enum gymnet_box_explore { GYMNET_BOX_EXPLORE_SAMPLE = 0, GYMNET_BOX_EXPLORE_GAUSSIAN = 1 } gymnet_box_explore;
+int gymnet_vecenv_actor_box_set_policy(gymnet_vecenv *h, int32_t head, int32_t explore, float sigma);
+int gymnet_vecenv_actor_box_get_policy(gymnet_vecenv *h, int32_t *head, int32_t *explore, float *sigma);
 
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */

@@ -383,6 +383,16 @@ public:
     void BoxActorAct(float *d_actions, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_raw = nullptr) {
         check(gymnet_vecenv_actor_box_act_device(h_, d_actions, d_raw, epsilon, seed, tick));
     }
+    // A Box actor's policy (gymnet_vecenv_actor_box_set_policy): a tanh head and / or Gaussian noise of scale sigma around the greedy action
+    // on the lanes that explore; BoxActorAct and the fused actor rollout read it.  A new actor has (CLAMP, SAMPLE, 0).
+    void SetBoxActorPolicy(gymnet_box_head head, gymnet_box_explore explore, float sigma = 0.0f) {
+        check(gymnet_vecenv_actor_box_set_policy(h_, (int32_t)head, (int32_t)explore, sigma));
+    }
+    void GetBoxActorPolicy(gymnet_box_head &head, gymnet_box_explore &explore, float &sigma) const {
+        int32_t hd = 0, ex = 0;
+        check(gymnet_vecenv_actor_box_get_policy(h_, &hd, &ex, &sigma));
+        head = (gymnet_box_head)hd; explore = (gymnet_box_explore)ex;
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
