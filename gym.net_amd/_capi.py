@@ -181,8 +181,10 @@ PROTOTYPES = {
     "gymnet_vecenv_pixel_stack_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gymnet_vecenv_pixel_stack_read": (C.c_int, [_H, _P, C.c_int64, C.c_int64]),
     "gymnet_vecenv_memory_config": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "gymnet_vecenv_memory_config_rollout": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gymnet_vecenv_memory_reset_device": (C.c_int, [_H, _P, C.c_int32]),
     "gymnet_vecenv_memory_push_device": (C.c_int, [_H, _P, _P]),
+    "gymnet_vecenv_memory_push_rollout_device": (C.c_int, [_H, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "gymnet_vecenv_memory_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gymnet_vecenv_memory_episodes": (C.c_int, [_H, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "gymnet_vecenv_memory_dataset_size": (C.c_int, [_H, C.POINTER(C.c_int64)]),

@@ -177,8 +177,11 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_pixel_stack_read(IntPtr h, void* out_stacks, long first_lane, long count);
         // episode memory: the best `capacity` episodes by (return, end tick, lane) and the dataset built from them
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_config(IntPtr h, int capacity, int max_length, int history);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_config_rollout(IntPtr h, int capacity, int max_length, int history, int rollout_chunk);
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_reset_device(IntPtr h, IntPtr d_mask, int clear_pool);
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_push_device(IntPtr h, IntPtr d_actions, IntPtr d_done);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_memory_push_rollout_device(IntPtr h, long steps, IntPtr d_rec_obs, IntPtr d_actions,
+            long action_stride, long ring, IntPtr d_rec_reward, IntPtr d_rec_done);
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_stats(IntPtr h, out long kept, out long ended, out long admitted, out long too_long);
         [DllImport(Lib)] public static extern int gymnet_vecenv_memory_episodes(IntPtr h, float* ret, int* len, ulong* end_tick, int* lane, long capacity,
                                                                                out long count);

@@ -234,6 +234,17 @@ namespace Gym.Envs.Amd {
         public void ConfigureEpisodeMemory(int capacity = 100, int maxLength = 0, int history = 4) =>
             Native.Check(Native.gymnet_vecenv_memory_config(_h, capacity, maxLength, history));
 
+        /// ConfigureEpisodeMemory sized for PushMemoryRollout passes of rolloutChunk (1 .. 64) steps: rolloutChunk - 1 more staging slots and
+        /// candidate segments.
+        public void ConfigureEpisodeMemoryRollout(int capacity = 100, int maxLength = 0, int history = 4, int rolloutChunk = 16) =>
+            Native.Check(Native.gymnet_vecenv_memory_config_rollout(_h, capacity, maxLength, history, rolloutChunk));
+
+        /// Once after ONE launch of `steps` steps (any fused rollout, or a single StepDevice with steps = 1): the rows it recorded — dRecObs
+        /// [steps][obs_dim][N], dRecReward and dRecDone [steps][N] — and its actions, step t's at row (t % ring) * actionStride of dActions
+        /// (a [steps][N] record: actionStride = N, ring = steps).  The memory ends as `steps` x (StepDevice, PushEpisodeMemory) would have left it.
+        public void PushMemoryRollout(long steps, IntPtr dRecObs, IntPtr dActions, long actionStride, long ring, IntPtr dRecReward, IntPtr dRecDone) =>
+            Native.Check(Native.gymnet_vecenv_memory_push_rollout_device(_h, steps, dRecObs, dActions, actionStride, ring, dRecReward, dRecDone));
+
         /// Once after each single StepDevice: dActions are the device actions that step took; dDone IntPtr.Zero = the handle's own done bytes.
         public void PushEpisodeMemory(IntPtr dActions, IntPtr dDone = default) =>
             Native.Check(Native.gymnet_vecenv_memory_push_device(_h, dActions, dDone));

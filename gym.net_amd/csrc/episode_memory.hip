@@ -19,6 +19,14 @@
 // params rows (one thread per row) or frames re-rendered from the stored observations with cartpole_raster.hpp (one wave per 1024
 // pixels of one frame, as the pixel stack draws them).
 //
+// Rollout ingest (gymnet_vecenv_memory_push_rollout_device): the T recorded rows of one fused rollout go in as T pushes would, C steps
+// per pass.  The ring then has L + C slots (ring_slots): an episode that ends at push pos still occupies pos - len + 1 .. pos, the pass
+// writes at most slot pos + C, so nothing a merge of the pass needs is overwritten before it runs.  The scan kernel is the push kernel
+// looped over the pass's steps with the lane's length and return in registers; step j's candidates go to segment j of the candidate list
+// (its own counter), filtered against the pool as it stood before the pass — a threshold that is up to C steps stale only lets more
+// candidates through.  The merge kernel then runs the merge once per segment in step order, so the kept set and `admitted` are those of
+// T single pushes.
+//
 // The host side follows the kernels: gymnet_vecenv_memory_* and the handle's EpisodeMemory attachment.
 #include <algorithm>
 #include <type_traits>
@@ -34,24 +42,25 @@ namespace {
 struct MemEntry { float ret; int32_t len; uint64_t tick; int32_t lane, block; };
 struct MemCand { float ret; int32_t len, lane, pad; };      // an episode that passed the push's admission filter
 struct MemCtl {
-    uint32_t cand_count;       // candidates of the most recent push (the merge consumes them and zeroes this)
+    uint32_t cand_count;       // candidates of the most recent push (the merge consumes them and zeroes this); segment 0's of an ingest pass
     int32_t kept;              // pool entries [0, kept) are live
     int32_t full;              // kept == capacity: the push admits an ended episode only when ret >= thr
     float thr;                 // the lowest kept return (valid when full)
     uint64_t admitted;         // episodes the merges put into the pool
     uint64_t rows;             // dataset rows of the most recent dataset build
-};
+};                             // (the counters of candidate segments 1 .. C - 1 follow it in memory: seg_counter)
 struct MemoryArgs {
     int64_t n;
     int32_t obs_dim, esz;                      // observation values per step and their size (4 float, 8 double)
     int32_t max_len, capacity;                 // L and K
-    // staging ring [L + 1 slots]: slot s at ring + s * slot_bytes holds obs [obs_dim][n] (esz each), action [n] (4 B), reward [n] (4 B)
+    int32_t ring_slots, chunk;                 // L + C staging slots; C = steps per ingest pass (1: memory_config)
+    // staging ring [L + C slots]: slot s at ring + s * slot_bytes holds obs [obs_dim][n] (esz each), action [n] (4 B), reward [n] (4 B)
     uint8_t *ring; int64_t slot_bytes;
     // pool: block b at pool + b * max_len * row_bytes, row p = obs [obs_dim] (esz each), action (4 B), reward (4 B)
     uint8_t *pool; int64_t row_bytes;
     int32_t *lane_len;                         // steps of the lane's open episode (-1: the lane is closed)
     float *lane_ret;                           // float32 sum of its rewards in step order
-    MemCand *cand;                             // [n]
+    MemCand *cand;                             // [C segments][n]
     MemCtl *ctl;
     MemEntry *meta, *meta_tmp;                 // [capacity] each: live entries, then free blocks
     int32_t *scratch;                          // [capacity]: free blocks during a merge, the descending key order during a dataset build
@@ -62,8 +71,17 @@ struct MemoryArgs {
 struct MemPushArgs {
     const void *obs; int64_t obs_stride;       // the CURRENT observation buffer (after the step)
     const void *actions; const float *reward; const uint8_t *done;
-    int64_t slot;                              // ring slot of this step (pos % (L + 1)); the next step's is (pos + 1) % (L + 1)
+    int64_t slot;                              // ring slot of this step (pos % ring_slots); the next step's is (pos + 1) % ring_slots
     uint64_t end_tick;                         // engine tick after the step: the key of the episodes that end in it
+    int32_t autoreset;
+};
+// one ingest pass: steps t0 .. t0 + count - 1 of the buffers a rollout launch recorded
+struct MemRolloutArgs {
+    const void *rec_obs;                       // [steps][obs_dim][n]
+    const uint32_t *actions; int64_t action_stride, ring;      // step t's actions: row (t % ring) * action_stride
+    const float *rec_reward; const uint8_t *rec_done;          // [steps][n] each
+    int64_t t0; int32_t count;                 // count <= chunk
+    int64_t slot;                              // ring slot of step t0
     int32_t autoreset;
 };
 // format 0 = params rows, else GYMNET_STACK_* frames drawn as the pixel stack draws them (geo: their sample positions)
@@ -130,6 +148,12 @@ __global__ __launch_bounds__(256) void memory_init_kernel(MemoryArgs m) {
     if (i < m.capacity) m.meta[i] = MemEntry{0.0f, 0, 0ull, -1, (int32_t)i};
     if (i < 2 * (int64_t)m.push_blocks) m.partials[i] = 0ull;
     if (i == 0) *m.ctl = MemCtl{};
+    if (i < m.chunk - 1) reinterpret_cast<uint32_t *>(m.ctl + 1)[i] = 0u;
+}
+
+// the candidate counter of segment s of an ingest pass (segment 0's is the single push's)
+__device__ __forceinline__ uint32_t *seg_counter(const MemoryArgs &m, int s) {
+    return s == 0 ? &m.ctl->cand_count : reinterpret_cast<uint32_t *>(m.ctl + 1) + (s - 1);
 }
 
 template <class R>
@@ -168,7 +192,7 @@ __global__ __launch_bounds__(kPushBlock) void memory_push_kernel(MemoryArgs m, M
             cand = !too_long && (!m.ctl->full || ret >= m.ctl->thr);
         }
         if (!done || p.autoreset) {                       // the next step's o_p, or the auto-reset episode's o_0
-            const int64_t nxt = p.slot == m.max_len ? 0 : p.slot + 1;
+            const int64_t nxt = p.slot + 1 == m.ring_slots ? 0 : p.slot + 1;
             R *o = reinterpret_cast<R *>(m.ring + nxt * m.slot_bytes);
             const R *src = static_cast<const R *>(p.obs);
             for (int d = 0; d < m.obs_dim; ++d) o[(int64_t)d * m.n + k] = src[(int64_t)d * p.obs_stride + k];
@@ -197,23 +221,32 @@ __global__ __launch_bounds__(kPushBlock) void memory_push_kernel(MemoryArgs m, M
     }
 }
 
-__device__ __forceinline__ Key entry_key(const MemoryArgs &m, int64_t i, int32_t kept, uint64_t end_tick) {
+__device__ __forceinline__ Key entry_key(const MemoryArgs &m, const MemCand *cand, int64_t i, int32_t kept, uint64_t end_tick) {
     if (i < kept) { const MemEntry e = m.meta[i]; return make_key(e.ret, e.tick, e.lane); }
-    const MemCand c = m.cand[i - kept];
+    const MemCand c = cand[i - kept];
     return make_key(c.ret, end_tick, c.lane);
 }
 
-template <int ESZ>
-__global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m, int64_t slot, uint64_t end_tick) {
+// one merge by one workgroup of kMergeBlock: the candidates cand[0, *count) of the step staged in `slot`, whose episodes end at end_tick.
+// REFILTER (the rollout ingest, whose scan filtered against the pool as it stood before the pass): a candidate counts only if it also
+// passes the single push's filter against the pool as it stands now, so the merge sees exactly the candidates a single push would have
+// made — also for a return that compares false with everything (NaN) when the pool filled earlier in the pass.
+template <int ESZ, bool REFILTER>
+__device__ __forceinline__ void merge_body(const MemoryArgs &m, const MemCand *cand, uint32_t *count, int64_t slot, uint64_t end_tick) {
     using W = typename std::conditional<ESZ == 8, uint64_t, uint32_t>::type;
     __shared__ uint32_t hist[256];
     __shared__ uint32_t tau[4];
     __shared__ uint32_t need_s, min_bits;
     __shared__ int32_t n_keep, n_free, n_win;
-    const uint32_t cands = m.ctl->cand_count;
+    const uint32_t cands = *count;
     if (cands == 0) return;
     const int32_t kept = m.ctl->kept, cap = m.capacity;
+    const int32_t full_now = REFILTER ? m.ctl->full : 0;
+    const float thr_now = REFILTER ? m.ctl->thr : 0.0f;
+    auto counts = [&](const MemCand &c) { return !REFILTER || !full_now || c.ret >= thr_now; };
     const int64_t total = (int64_t)kept + cands;
+    // (REFILTER: total counts every candidate, so with a full pool the caller must have found one that counts — memory_merge_rollout_kernel's
+    // pre-check — or the selection would look for a key that is not there)
     const bool select = total > cap;
     const int tid = threadIdx.x;
     if (tid < 4) tau[tid] = 0u;
@@ -226,7 +259,8 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m,
             __syncthreads();
             const uint32_t t[4] = {tau[0], tau[1], tau[2], tau[3]};
             for (int64_t i = tid; i < total; i += kMergeBlock) {
-                const Key k = entry_key(m, i, kept, end_tick);
+                if (REFILTER && i >= kept && !counts(cand[i - kept])) continue;
+                const Key k = entry_key(m, cand, i, kept, end_tick);
                 if (prefix_match(k, t, d)) atomicAdd(&hist[digit(k, d)], 1u);
             }
             __syncthreads();
@@ -255,8 +289,8 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m,
     __syncthreads();
     const int32_t keep = n_keep;
     for (int64_t j = tid; j < cands; j += kMergeBlock) {
-        const MemCand c = m.cand[j];
-        if (!select || !key_less(make_key(c.ret, end_tick, c.lane), t)) {
+        const MemCand c = cand[j];
+        if (counts(c) && (!select || !key_less(make_key(c.ret, end_tick, c.lane), t))) {
             const int32_t s = atomicAdd(&n_win, 1);
             if (keep + s < cap) m.meta_tmp[keep + s] = MemEntry{c.ret, c.len, end_tick, c.lane, m.scratch[s]};
         }
@@ -280,7 +314,7 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m,
         uint8_t *blk = m.pool + (int64_t)e.block * m.max_len * m.row_bytes;
         for (int q = lid; q < e.len; q += 64) {
             int64_t s = slot - e.len + 1 + q;
-            if (s < 0) s += m.max_len + 1;
+            if (s < 0) s += m.ring_slots;
             const uint8_t *src = m.ring + s * m.slot_bytes;
             uint8_t *row = blk + (int64_t)q * m.row_bytes;
             for (int d = 0; d < m.obs_dim; ++d)
@@ -295,7 +329,145 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m,
         m.ctl->full = live == cap ? 1 : 0;
         m.ctl->thr = bits_ret(min_bits);
         m.ctl->admitted += (uint64_t)win;
-        m.ctl->cand_count = 0u;
+        *count = 0u;
+    }
+}
+
+template <int ESZ>
+__global__ __launch_bounds__(kMergeBlock) void memory_merge_kernel(MemoryArgs m, int64_t slot, uint64_t end_tick) {
+    merge_body<ESZ, false>(m, m.cand, &m.ctl->cand_count, slot, end_tick);
+}
+
+// The push kernel over the `count` steps of one ingest pass, reading the recorded rows instead of the handle's live arrays.  Step j's
+// candidates go to segment j; the pool's full / thr are read once, as they stood before the pass.  The rows of step j + 1 are loaded
+// into a second register set before step j's stores are issued.  (As compiled, the wait ahead of those stores covers the new loads too:
+// they overlap the step's arithmetic, not its stores — docs/ledger.md §24.)
+constexpr int kMemMaxObs = 8;      // observation values per step held in registers
+static_assert(kMemMaxObs >= (int)(sizeof(EnvDesc::obs_low) / sizeof(float)), "the scan kernel holds every observation value an env can have");
+
+template <class R>
+__global__ __launch_bounds__(kPushBlock) void memory_scan_rollout_kernel(MemoryArgs m, MemRolloutArgs p) {
+    __shared__ uint32_t cnt[2];
+    if (threadIdx.x == 0) { cnt[0] = 0u; cnt[1] = 0u; }
+    __syncthreads();
+    const int64_t k = (int64_t)blockIdx.x * kPushBlock + threadIdx.x;
+    const bool valid = k < m.n;
+    const int lid = threadIdx.x & 63;
+    const int D = m.obs_dim;
+    const int64_t n = m.n, obs_bytes = (int64_t)D * n * (int64_t)sizeof(R);
+    const R *rec_obs = static_cast<const R *>(p.rec_obs);
+    const int32_t full = m.ctl->full;
+    const float thr = m.ctl->thr;
+    int32_t len = -1;
+    float ret = 0.0f;
+    if (valid) { len = m.lane_len[k]; ret = m.lane_ret[k]; }
+    uint32_t ended_n = 0u, too_long_n = 0u;      // wave-uniform: episodes this wave ended in the pass
+    // the rows of one step
+    uint32_t a = 0u, a_nx = 0u;
+    float r = 0.0f, r_nx = 0.0f;
+    uint8_t dn = 0, dn_nx = 0;
+    R o[kMemMaxObs], o_nx[kMemMaxObs];
+#pragma unroll
+    for (int d = 0; d < kMemMaxObs; ++d) { o[d] = R(0); o_nx[d] = R(0); }
+    int64_t ring_i = p.t0 % p.ring;              // the action row of the next step to load
+    auto load = [&](int64_t t, uint32_t &aa, float &rr, uint8_t &dd, R (&oo)[kMemMaxObs]) {
+        const int64_t arow = ring_i * p.action_stride;
+        ring_i = ring_i + 1 == p.ring ? 0 : ring_i + 1;
+        if (!valid) return;
+        aa = p.actions[arow + k];
+        rr = p.rec_reward[t * n + k];
+        dd = p.rec_done[t * n + k];
+        const R *row = rec_obs + t * D * n + k;
+#pragma unroll
+        for (int d = 0; d < kMemMaxObs; ++d)
+            if (d < D) oo[d] = row[(int64_t)d * n];
+    };
+    load(p.t0, a, r, dn, o);
+    int64_t slot = p.slot;
+    for (int j = 0; j < p.count; ++j) {
+        if (j + 1 < p.count) load(p.t0 + j + 1, a_nx, r_nx, dn_nx, o_nx);
+        const int64_t nxt = slot + 1 == m.ring_slots ? 0 : slot + 1;
+        bool ended = false, too_long = false, cand = false;
+        float ep_ret = 0.0f;
+        int32_t ep_len = 0;
+        if (len >= 0) {
+            uint8_t *sp = m.ring + slot * m.slot_bytes;
+            const bool done = dn != 0;
+            reinterpret_cast<uint32_t *>(sp + obs_bytes)[k] = a;
+            reinterpret_cast<float *>(sp + obs_bytes + 4 * n)[k] = r;
+            ret += r;
+            len += 1;
+            if (done) {
+                ended = true;
+                too_long = len > m.max_len;
+                cand = !too_long && (!full || ret >= thr);
+                ep_ret = ret; ep_len = len;
+            }
+            if (!done || p.autoreset) {
+                R *on = reinterpret_cast<R *>(m.ring + nxt * m.slot_bytes);
+#pragma unroll
+                for (int d = 0; d < kMemMaxObs; ++d)
+                    if (d < D) on[(int64_t)d * n + k] = o[d];
+            }
+            if (done) { len = p.autoreset ? 0 : -1; ret = 0.0f; }
+        }
+        const uint64_t cm = __ballot(cand);
+        if (cm) {
+            const int leader = __ffsll((unsigned long long)cm) - 1;
+            uint32_t base = 0;
+            if (lid == leader) base = atomicAdd(seg_counter(m, j), (uint32_t)__popcll(cm));
+            base = __shfl(base, leader);
+            if (cand) m.cand[(int64_t)j * n + base + wave_rank(cm)] = MemCand{ep_ret, ep_len, (int32_t)k, 0};
+        }
+        ended_n += (uint32_t)__popcll(__ballot(ended));
+        too_long_n += (uint32_t)__popcll(__ballot(too_long));
+        slot = nxt;
+        a = a_nx; r = r_nx; dn = dn_nx;
+#pragma unroll
+        for (int d = 0; d < kMemMaxObs; ++d) o[d] = o_nx[d];
+    }
+    if (valid) { m.lane_len[k] = len; m.lane_ret[k] = ret; }
+    if (lid == 0 && ended_n) {
+        atomicAdd(&cnt[0], ended_n);
+        if (too_long_n) atomicAdd(&cnt[1], too_long_n);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt[0]) {
+        m.partials[2 * blockIdx.x] += cnt[0];
+        m.partials[2 * blockIdx.x + 1] += cnt[1];
+    }
+}
+
+// `count` merges in step order: segment j holds the candidates of the step staged in slot + j, whose episodes end at end_tick + j * dtick.
+// The scan filtered them against the pool as it stood before the pass; a segment none of whose candidates passes the single push's
+// filter against the pool as it stands NOW (full, and every return below the lowest kept) cannot change the pool and is dropped
+// without a selection.
+template <int ESZ>
+__global__ __launch_bounds__(kMergeBlock) void memory_merge_rollout_kernel(MemoryArgs m, int64_t slot, uint64_t end_tick, uint64_t dtick,
+                                                                            int32_t count) {
+    __shared__ uint32_t pass;
+    for (int j = 0; j < count; ++j) {
+        uint32_t *counter = seg_counter(m, j);
+        const uint32_t cands = *counter;         // (uniform: only this segment's turn zeroes it, behind a barrier)
+        if (cands != 0u) {
+            const MemCand *cand = m.cand + (int64_t)j * m.n;
+            if (threadIdx.x == 0) pass = 0u;
+            __syncthreads();
+            const int32_t full = m.ctl->full;
+            const float thr = m.ctl->thr;
+            bool any = false;
+            for (uint32_t i = threadIdx.x; i < cands; i += kMergeBlock) any |= !full || cand[i].ret >= thr;
+            if (any) pass = 1u;
+            __syncthreads();
+            if (pass) {
+                int64_t s = slot + j;
+                if (s >= m.ring_slots) s -= m.ring_slots;
+                merge_body<ESZ, true>(m, cand, counter, s, end_tick + (uint64_t)j * dtick);
+            } else if (threadIdx.x == 0) {
+                *counter = 0u;
+            }
+        }
+        __syncthreads();                         // the next merge reads the pool and the control block this one wrote
     }
 }
 
@@ -460,15 +632,32 @@ hipError_t launch_memory_push(bool f64, const MemoryArgs &m, const MemPushArgs &
     return hipGetLastError();
 }
 
+// one ingest pass: the scan over p.count steps, then their merges; dtick = engine ticks per step
+hipError_t launch_memory_push_rollout(bool f64, const MemoryArgs &m, const MemRolloutArgs &p, uint64_t end_tick, uint64_t dtick, hipStream_t st) {
+    if (f64) {
+        hipLaunchKernelGGL(memory_scan_rollout_kernel<double>, dim3(m.push_blocks), dim3(kPushBlock), 0, st, m, p);
+        hipLaunchKernelGGL(memory_merge_rollout_kernel<8>, dim3(1), dim3(kMergeBlock), 0, st, m, p.slot, end_tick, dtick, p.count);
+    } else {
+        hipLaunchKernelGGL(memory_scan_rollout_kernel<float>, dim3(m.push_blocks), dim3(kPushBlock), 0, st, m, p);
+        hipLaunchKernelGGL(memory_merge_rollout_kernel<4>, dim3(1), dim3(kMergeBlock), 0, st, m, p.slot, end_tick, dtick, p.count);
+    }
+    return hipGetLastError();
+}
+
 constexpr int32_t kMemoryMaxCapacity = 65536;
 constexpr int32_t kMemoryMaxHistory = 64;
 constexpr int32_t kMemoryMaxLength = 1 << 24;
+constexpr int32_t kMemoryMaxChunk = 64;
 
 }  // namespace
 
-// the configured memory: pos counts its pushes (the ring slot of the next step is pos % (max_len + 1)); last: the handle's step counters
-// at its last config, reset or push, so a push can tell that exactly one vector step ran in between
-struct EpisodeMemory { DeviceAllocs mem; MemoryArgs args{}; int32_t history = 0; uint64_t pos = 0; StepMark last; };
+// the configured memory: pos counts its pushes (the ring slot of the next step is pos % ring_slots); last: the handle's step counters
+// at its last config, reset or push, so a push can tell that exactly one vector step ran in between; last_tick: the engine tick then
+// (an ingest reads the launch's ticks per decision off it)
+struct EpisodeMemory {
+    DeviceAllocs mem; MemoryArgs args{}; int32_t history = 0; uint64_t pos = 0; StepMark last; uint64_t last_tick = 0;
+    void mark_now(const gymnet_vecenv *h) { last = mark(h); last_tick = h->tick; }
+};
 
 int release_memory(gymnet_vecenv *h) { return release_attachment(h, h->memory); }
 
@@ -478,7 +667,7 @@ int need_memory(gymnet_vecenv *h) {
     return h->memory ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no episode memory configured (gymnet_vecenv_memory_config)");
 }
 
-int64_t ring_slot(const EpisodeMemory &em) { return (int64_t)(em.pos % (uint64_t)(em.args.max_len + 1)); }
+int64_t ring_slot(const EpisodeMemory &em) { return (int64_t)(em.pos % (uint64_t)em.args.ring_slots); }
 
 // the kept entries [0, kept) and the control block, read back after the stream has drained
 int read_pool(gymnet_vecenv *h, MemCtl *ctl, std::vector<MemEntry> *meta) {
@@ -489,6 +678,59 @@ int read_pool(gymnet_vecenv *h, MemCtl *ctl, std::vector<MemEntry> *meta) {
         meta->resize((size_t)ctl->kept);
         if (ctl->kept > 0) HIP_TRY(h, hipMemcpy(meta->data(), m.meta, sizeof(MemEntry) * (size_t)ctl->kept, hipMemcpyDeviceToHost));
     }
+    return GYMNET_OK;
+}
+
+// a push of `asked` steps is accepted after exactly one step launch of that many decisions
+int check_push_follows(gymnet_vecenv *h, const EpisodeMemory &em, int64_t asked) {
+    const StepMark s = since(h, em.last);
+    if (asked >= 1 && s == StepMark{(uint64_t)asked, 1}) return GYMNET_OK;
+    return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
+                "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device [%llu step(s) seen, %lld asked: a "
+                "launch of several steps goes in through gymnet_vecenv_memory_push_rollout_device]", (unsigned long long)em.last.tick,
+                (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)s.launches, (unsigned long long)s.tick,
+                (long long)asked);   // (both on the decision clock: StepMark)
+}
+
+// gymnet_vecenv_memory_config (chunk 1) and gymnet_vecenv_memory_config_rollout, on a handle the caller has ENTERed
+int memory_configure(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history, int32_t chunk) {
+    if (capacity == 0) return release_memory(h);
+    if (capacity < 0 || capacity > kMemoryMaxCapacity)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %d not in [0, %d]", capacity, kMemoryMaxCapacity);
+    if (history < 1 || history > kMemoryMaxHistory) return fail(h, GYMNET_ERR_INVALID_ARG, "history %d not in [1, %d]", history, kMemoryMaxHistory);
+    const int32_t len = max_length == 0 ? h->cfg.max_episode_steps : max_length;
+    if (max_length < 0 || len < 1 || len > kMemoryMaxLength)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "max_length %d not in [1, %d] (0 = max_episode_steps, which is %d)", max_length, kMemoryMaxLength,
+                    h->cfg.max_episode_steps);
+    const int obs_dim = h->desc->obs_dim;
+    const int64_t row = (int64_t)obs_dim * (int64_t)h->esz + 8;
+    const double ring_d = (double)(len + chunk) * (double)h->n * (double)row, pool_d = (double)capacity * (double)len * (double)row;
+    if (ring_d > 9.0e18 || pool_d > 9.0e18) return fail(h, GYMNET_ERR_INVALID_ARG, "episode memory of %.3g bytes overflows", ring_d + pool_d);
+    std::unique_ptr<EpisodeMemory> fresh(new EpisodeMemory);
+    MemoryArgs &m = fresh->args;
+    m.n = h->n; m.obs_dim = obs_dim; m.esz = (int32_t)h->esz;
+    m.max_len = len; m.capacity = capacity;
+    m.ring_slots = len + chunk; m.chunk = chunk;
+    m.slot_bytes = h->n * row; m.row_bytes = row;
+    m.push_blocks = (int32_t)((h->n + kPushBlock - 1) / kPushBlock);
+    // every region (ring, pool, per-lane state, candidates, control, pool entries, scratch, row offsets, counters) or none
+    bool ok = true;
+    auto take = [&](auto *&p, int64_t bytes) {
+        using P = std::remove_reference_t<decltype(p)>;
+        ok = ok && (p = static_cast<P>(fresh->mem.take((size_t)bytes))) != nullptr;
+    };
+    take(m.ring, (int64_t)m.ring_slots * m.slot_bytes); take(m.pool, (int64_t)capacity * len * row);
+    take(m.lane_len, 4 * h->n); take(m.lane_ret, 4 * h->n); take(m.cand, (int64_t)sizeof(MemCand) * h->n * chunk);
+    take(m.ctl, sizeof(MemCtl) + 4 * (int64_t)(chunk - 1)); take(m.meta, (int64_t)sizeof(MemEntry) * capacity);
+    take(m.meta_tmp, (int64_t)sizeof(MemEntry) * capacity); take(m.scratch, 4 * (int64_t)capacity);
+    take(m.row_off, 8 * ((int64_t)capacity + 1)); take(m.partials, 16 * (int64_t)m.push_blocks);
+    if (!ok) return fail(h, GYMNET_ERR_OOM, "hipMalloc of the episode memory (%.3g bytes) failed", ring_d + pool_d);
+    fresh->history = history;
+    fresh->mark_now(h);
+    ST_TRY(release_memory(h));
+    h->memory = fresh.release();
+    HIP_TRY(h, launch_memory_init(m, h->stream));
+    HIP_TRY(h, launch_memory_open(h->f64, m, h->d_obs, h->ostride, nullptr, 0, h->stream));
     return GYMNET_OK;
 }
 
@@ -503,43 +745,16 @@ extern "C" {
 int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history) {
     return guarded([&]() -> int {
     ENTER(h);
-    if (capacity == 0) return release_memory(h);
-    if (capacity < 0 || capacity > kMemoryMaxCapacity)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "capacity %d not in [0, %d]", capacity, kMemoryMaxCapacity);
-    if (history < 1 || history > kMemoryMaxHistory) return fail(h, GYMNET_ERR_INVALID_ARG, "history %d not in [1, %d]", history, kMemoryMaxHistory);
-    const int32_t len = max_length == 0 ? h->cfg.max_episode_steps : max_length;
-    if (max_length < 0 || len < 1 || len > kMemoryMaxLength)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "max_length %d not in [1, %d] (0 = max_episode_steps, which is %d)", max_length, kMemoryMaxLength,
-                    h->cfg.max_episode_steps);
-    const int obs_dim = h->desc->obs_dim;
-    const int64_t row = (int64_t)obs_dim * (int64_t)h->esz + 8;
-    const double ring_d = (double)(len + 1) * (double)h->n * (double)row, pool_d = (double)capacity * (double)len * (double)row;
-    if (ring_d > 9.0e18 || pool_d > 9.0e18) return fail(h, GYMNET_ERR_INVALID_ARG, "episode memory of %.3g bytes overflows", ring_d + pool_d);
-    std::unique_ptr<EpisodeMemory> fresh(new EpisodeMemory);
-    MemoryArgs &m = fresh->args;
-    m.n = h->n; m.obs_dim = obs_dim; m.esz = (int32_t)h->esz;
-    m.max_len = len; m.capacity = capacity;
-    m.slot_bytes = h->n * row; m.row_bytes = row;
-    m.push_blocks = (int32_t)((h->n + kPushBlock - 1) / kPushBlock);
-    // every region (ring, pool, per-lane state, candidates, control, pool entries, scratch, row offsets, counters) or none
-    bool ok = true;
-    auto take = [&](auto *&p, int64_t bytes) {
-        using P = std::remove_reference_t<decltype(p)>;
-        ok = ok && (p = static_cast<P>(fresh->mem.take((size_t)bytes))) != nullptr;
-    };
-    take(m.ring, (int64_t)(len + 1) * m.slot_bytes); take(m.pool, (int64_t)capacity * len * row);
-    take(m.lane_len, 4 * h->n); take(m.lane_ret, 4 * h->n); take(m.cand, (int64_t)sizeof(MemCand) * h->n);
-    take(m.ctl, sizeof(MemCtl)); take(m.meta, (int64_t)sizeof(MemEntry) * capacity);
-    take(m.meta_tmp, (int64_t)sizeof(MemEntry) * capacity); take(m.scratch, 4 * (int64_t)capacity);
-    take(m.row_off, 8 * ((int64_t)capacity + 1)); take(m.partials, 16 * (int64_t)m.push_blocks);
-    if (!ok) return fail(h, GYMNET_ERR_OOM, "hipMalloc of the episode memory (%.3g bytes) failed", ring_d + pool_d);
-    fresh->history = history;
-    fresh->last = mark(h);
-    ST_TRY(release_memory(h));
-    h->memory = fresh.release();
-    HIP_TRY(h, launch_memory_init(m, h->stream));
-    HIP_TRY(h, launch_memory_open(h->f64, m, h->d_obs, h->ostride, nullptr, 0, h->stream));
-    return GYMNET_OK;
+    return memory_configure(h, capacity, max_length, history, 1);
+    });
+}
+
+int gymnet_vecenv_memory_config_rollout(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history, int32_t rollout_chunk) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (rollout_chunk < 1 || rollout_chunk > kMemoryMaxChunk)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "rollout_chunk %d not in [1, %d]", rollout_chunk, kMemoryMaxChunk);
+    return memory_configure(h, capacity, max_length, history, rollout_chunk);
     });
 }
 
@@ -550,7 +765,7 @@ int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, i
     EpisodeMemory &em = *h->memory;
     if (clear_pool) HIP_TRY(h, launch_memory_init(em.args, h->stream));
     HIP_TRY(h, launch_memory_open(h->f64, em.args, h->d_obs, h->ostride, d_mask, ring_slot(em), h->stream));
-    em.last = mark(h);
+    em.mark_now(h);
     return GYMNET_OK;
     });
 }
@@ -561,10 +776,7 @@ int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, co
     ST_TRY(need_memory(h));
     EpisodeMemory &em = *h->memory;
     if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (!(since(h, em.last) == StepMark{1, 1}))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
-                    "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device", (unsigned long long)em.last.tick,
-                    (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)since(h, em.last).launches);   // (both on the decision clock: StepMark)
+    ST_TRY(check_push_follows(h, em, 1));
     MemPushArgs p{};
     p.obs = h->d_obs; p.obs_stride = h->ostride;
     p.actions = d_actions; p.reward = h->d_reward; p.done = d_done ? d_done : h->d_done;
@@ -573,7 +785,39 @@ int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, co
     p.autoreset = h->autoreset ? 1 : 0;
     HIP_TRY(h, launch_memory_push(h->f64, em.args, p, h->stream));
     em.pos += 1;
-    em.last = mark(h);
+    em.mark_now(h);
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_memory_push_rollout_device(gymnet_vecenv *h, int64_t steps, const void *d_rec_obs, const void *d_actions,
+                                             int64_t action_stride, int64_t ring, const float *d_rec_reward, const uint8_t *d_rec_done) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_memory(h));
+    EpisodeMemory &em = *h->memory;
+    if (!d_rec_obs || !d_actions || !d_rec_reward || !d_rec_done)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_obs, d_actions, d_rec_reward or d_rec_done is null");
+    if (steps < 1 || ring < 1 || action_stride < 0)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride (%lld, %lld, %lld)", (long long)steps, (long long)ring, (long long)action_stride);
+    ST_TRY(check_push_follows(h, em, steps));
+    // the launch's engine ticks per decision (frame skip: R sub-steps each): row t ends at tick_before + (t + 1) * R
+    const uint64_t ticks = h->tick - em.last_tick;
+    if (ticks < (uint64_t)steps || ticks % (uint64_t)steps != 0)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the tick moved by %llu over %lld steps: not one launch's", (unsigned long long)ticks, (long long)steps);
+    const uint64_t dtick = ticks / (uint64_t)steps;
+    MemRolloutArgs p{};
+    p.rec_obs = d_rec_obs; p.actions = static_cast<const uint32_t *>(d_actions); p.action_stride = action_stride; p.ring = ring;
+    p.rec_reward = d_rec_reward; p.rec_done = d_rec_done;
+    p.autoreset = h->autoreset ? 1 : 0;
+    for (int64_t t0 = 0; t0 < steps; t0 += em.args.chunk) {
+        p.t0 = t0;
+        p.count = (int32_t)std::min<int64_t>(em.args.chunk, steps - t0);
+        p.slot = ring_slot(em);
+        HIP_TRY(h, launch_memory_push_rollout(h->f64, em.args, p, em.last_tick + (uint64_t)(t0 + 1) * dtick, dtick, h->stream));
+        em.pos += (uint64_t)p.count;
+    }
+    em.mark_now(h);
     return GYMNET_OK;
     });
 }

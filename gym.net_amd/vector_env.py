@@ -48,6 +48,13 @@ def _repeat(repeat):
     return int(repeat)
 
 
+def _count(value, name, low, high=None):
+    """an int argument in [low, high] as the native calls take it, refused here before any native call"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < low or (high is not None and int(value) > high):
+        raise ValueError(f"{name} must be an int {'>= %d' % low if high is None else 'in [%d, %d]' % (low, high)}, got {value!r}")
+    return int(value)
+
+
 class BatchStep:
     """What `Step[]` (IVecEnv.cs:15) becomes at 2^20 lanes: three arrays.  Indexing / iterating yields the
     reference's per-env Step records (Step.cs:7-20), materialised lazily."""
@@ -417,12 +424,14 @@ class VectorEnv:
         dtype is adopted with lane_stride = its stride(0).  Replaces any stack this handle had.  CartPole only."""
         return PixelFrameStack(self, depth, size, crop, format, out)
 
-    def EpisodeMemory(self, capacity=100, max_length=0, history=4):
+    def EpisodeMemory(self, capacity=100, max_length=0, history=4, rollout_chunk=0):
         """The trainer's episode memory on the device (gymnet_vecenv_memory_config): every step of each lane's open episode, the best
         `capacity` finished episodes by (return, end tick, lane) and the dataset built from them (ReplayMemory.cs:25-67,
         DataBuilder.cs:25-55).  max_length 0 = the handle's max_episode_steps; history = steps per dataset row (MemoryStates).
-        Replaces any memory this handle had."""
-        return EpisodeMemory(self, capacity, max_length, history)
+        rollout_chunk = C in [1, 64] (gymnet_vecenv_memory_config_rollout) sizes the memory for PushRollout / Rollout passes of C steps:
+        C - 1 more staging slots and candidate segments; 0 is the plain config, whose ingest runs one step per pass.  Replaces any memory
+        this handle had."""
+        return EpisodeMemory(self, capacity, max_length, history, rollout_chunk)
 
     def Actor(self, net, history=4):
         """A fully connected ReLU network that chooses every lane's action on the device (gymnet_vecenv_actor_config): the trainer's
@@ -728,14 +737,19 @@ class EpisodeMemory:
     _FORMATS = {"params": (capi.MEMORY_PARAMS, "float32"), "gray8": (capi.STACK_GRAY8, "uint8"), "binary8": (capi.STACK_BINARY8, "uint8"),
                 "binary_f32": (capi.STACK_BINARY_F32, "float32")}
 
-    def __init__(self, env, capacity, max_length, history):
+    def __init__(self, env, capacity, max_length, history, rollout_chunk=0):
+        rollout_chunk = _count(rollout_chunk, "rollout_chunk", 0, 64)
         self._env, self._lib, self._h = env, env._lib, env._h
-        capi.check(self._lib.gymnet_vecenv_memory_config(self._h, int(capacity), int(max_length), int(history)))
+        if rollout_chunk:
+            capi.check(self._lib.gymnet_vecenv_memory_config_rollout(self._h, int(capacity), int(max_length), int(history), rollout_chunk))
+        else:
+            capi.check(self._lib.gymnet_vecenv_memory_config(self._h, int(capacity), int(max_length), int(history)))
         prev = getattr(env, "_episode_memory", None)
         if prev is not None:
             prev._h = None                      # the handle holds one memory: the previous one is gone
         env._episode_memory = self
-        self.Capacity, self.History = int(capacity), int(history)
+        self.Capacity, self.History, self.RolloutChunk = int(capacity), int(history), rollout_chunk
+        self._rec = None
 
     def _handle(self):
         if self._h is None or not self._env._h:
@@ -756,6 +770,50 @@ class EpisodeMemory:
         else:
             self._env.StepDevice(actions)
         self.Push(actions)
+
+    def PushRollout(self, steps, rec_obs, actions, rec_reward, rec_done, action_stride=None, ring=None):
+        """Once after ONE launch of `steps` steps (RolloutFusedDevice with any action source or repeat; StepDevice with steps = 1): the
+        rows that launch recorded — rec_obs [T][D][N], rec_reward [T][N], rec_done [T][N] — and its actions, step t's at row
+        (t % ring) * action_stride of `actions` (defaults: N and steps, a [T][N] rec_actions; a ring rollout passes its own ring, stride
+        and ring length).  The memory ends as `steps` x (StepDevice, Push) would have left it, bit for bit
+        (gymnet_vecenv_memory_push_rollout_device)."""
+        steps = _count(steps, "steps", 1)
+        stride = self._env.NumberOfEnvironments if action_stride is None else _count(action_stride, "action_stride", 0)
+        ring = steps if ring is None else _count(ring, "ring", 1)
+        capi.check(self._lib.gymnet_vecenv_memory_push_rollout_device(self._handle(), steps, _ptr(rec_obs), _ptr(actions), stride, ring,
+                                                                      _ptr(rec_reward), _ptr(rec_done)))
+
+    def Rollout(self, steps, d_actions=None, **rollout_kwargs):
+        """RolloutFusedDevice(d_actions, steps, **rollout_kwargs) recording every stream into buffers this memory keeps (and reuses while
+        `steps` stays), then PushRollout of them: one rollout launch plus two small launches per rollout_chunk steps.  Returns the
+        actions taken: the recorded int32 (Box: float32) torch tensor [steps, N], which the next Rollout overwrites — or, with
+        actions="ring", d_actions itself (a ring rollout's actions are its ring)."""
+        import torch
+        steps = _count(steps, "steps", 1)
+        env = self._env
+        self._handle()
+        taken = set(rollout_kwargs) & {"rec_obs", "rec_reward", "rec_done", "rec_actions"}
+        if taken:
+            raise TypeError(f"Rollout records into its own buffers: {sorted(taken)}")
+        if env.Device is None:
+            raise ValueError("this handle's device is not known")
+        n, box = env.NumberOfEnvironments, isinstance(env.ActionSpace, Box)
+        if self._rec is None or self._rec[0].shape[0] != steps:
+            dev = f"cuda:{env.Device}"
+            self._rec = (torch.empty((steps, env.ObsDim, n), dtype=getattr(torch, env._dtype.name), device=dev),
+                         torch.empty((steps, n), dtype=torch.float32, device=dev), torch.empty((steps, n), dtype=torch.uint8, device=dev),
+                         torch.empty((steps, n), dtype=torch.float32 if box else torch.int32, device=dev))
+        obs, rew, done, act = self._rec
+        if rollout_kwargs.get("actions", "ring") == "ring":       # a ring rollout's actions ARE its ring: nothing to record
+            if d_actions is None:              # (checked before the launch: a refused ingest after it would leave the memory behind)
+                raise ValueError("a ring rollout needs d_actions")
+            env.RolloutFusedDevice(d_actions, steps, rec_obs=obs, rec_reward=rew, rec_done=done, **rollout_kwargs)
+            self.PushRollout(steps, obs, d_actions, rew, done, action_stride=rollout_kwargs.get("action_stride", 0),
+                             ring=rollout_kwargs.get("ring", 1))
+            return d_actions
+        env.RolloutFusedDevice(d_actions, steps, rec_obs=obs, rec_reward=rew, rec_done=done, rec_actions=act, **rollout_kwargs)
+        self.PushRollout(steps, obs, act, rew, done)
+        return act
 
     def Reset(self, mask=None, clear=False):
         """Lanes whose device mask byte is set (None: every lane) open a new episode from their current observation (after

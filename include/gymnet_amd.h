@@ -550,16 +550,29 @@ int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_la
  *   GYMNET_STACK_GRAY8 / _BINARY8 / _BINARY_F32 (CartPole only): x = [S][out_h][out_w] bytes (floats for BINARY_F32): the frames a
  *     pixel stack of the same format, crop, size and depth S held when the action was chosen, re-rendered from the stored observations.
  * Memory: (L + 1) * num_envs * row + K * L * row bytes, row = obs_dim * (4, or 8 for GYMNET_FLAG_F64) + 8, plus about 40 bytes per lane
- *   and 60 per kept episode: 12.6 GB for 2^20 CartPole float32 lanes with L = 500.
+ *   and 60 per kept episode: 12.6 GB for 2^20 CartPole float32 lanes with L = 500.  config_rollout with rollout_chunk = C adds C - 1 more
+ *   staging slots of num_envs * row bytes and (C - 1) * num_envs * 16 bytes of candidates: 0.63 GB more at 2^20 CartPole lanes, C = 16.
  * config: capacity 0 releases the memory (the other arguments are then not looked at); else K in [1, 65536], history in [1, 64],
  *   max_length in [1, 2^24] or 0 for the handle's max_episode_steps (which must then be > 0).  Replaces any memory the handle had,
  *   with an empty pool, and opens every lane from its current observation.
+ * config_rollout: config, plus rollout_chunk = C in [1, 64]: the number of consecutive steps one pass of push_rollout_device handles (a
+ *   staging ring of L + C slots instead of L + 1, C candidate segments).  C = 1 is config.  Every other call treats the two alike.
  * reset_device: lanes with d_mask[lane] != 0 (NULL: every lane) abandon their partial episode and open one from their current
  *   observation (call it after gymnet_vecenv_reset(_device) / _reset_where(_device)); clear_pool != 0 also empties the pool and zeroes
  *   the counters.
  * push_device: once after each single vector step; d_actions are the actions that step took (device, [num_envs] of 4 bytes), d_done
  *   NULL means the handle's own done bytes.  Refused unless exactly one vector step ran since the last config, memory reset or push
  *   (a missed push, a multi-step rollout, or a reset of the handle without a memory reset in between).
+ * push_rollout_device: the `steps` recorded rows of ONE step launch, ingested as `steps` single pushes would have been.  Accepted only when
+ *   exactly one step launch of `steps` decisions ran since the last config, memory reset or push: any fused rollout
+ *   (gymnet_vecenv_rollout_fused_device / _fused_ex_device / _rollout_repeat_device, every action source), or a single step with steps = 1.
+ *   The buffers are what that launch wrote: d_rec_obs [steps][obs_dim][num_envs] in the handle's scalar, d_rec_reward and d_rec_done
+ *   [steps][num_envs]; step t's actions are the num_envs 4-byte words at d_actions + (t % ring) * action_stride elements, as in
+ *   gymnet_rollout_spec — a ring rollout passes its own ring, a sampled, epsilon-greedy or actor rollout its d_rec_actions with
+ *   action_stride = num_envs, ring = steps.  Afterwards every observable of the memory (stats, episodes, dataset_size, dataset_device in
+ *   every format, and every later push, ingest, reset and dataset) is bit for bit what step + push_device, `steps` times, would have left.
+ *   Row t's episodes end at engine tick tick_before + (t + 1) * R, R = the launch's ticks per decision (frame skip).  The steps go in
+ *   rollout_chunk at a time, two launches per pass; a memory from the plain config ingests with C = 1.
  * stats: kept episodes, episodes ended, episodes admitted into the kept set, episodes too long (any pointer may be NULL).  Blocks.
  * episodes: the kept episodes in descending key order, at most `capacity` of them (any array may be NULL); *count = how many are kept.
  *   Blocks.
@@ -570,13 +583,17 @@ int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_la
  * Everything but stats, episodes and dataset_size is ordered on the handle's stream and does not block; none of the calls changes state,
  *   observations, tick, counters, the Philox stream or the done bytes.  The memory is not part of a checkpoint.
  * Errors (nothing written): GYMNET_ERR_INVALID_ARG for arguments outside the ranges above, calls before a memory is configured, a null
- *   d_actions or a refused push, an unknown dataset format, a d_onehot on a Box env, a BINARY_F32 d_x that is not 4-byte aligned, a
+ *   d_actions or a refused push (push_rollout_device: any null pointer, steps < 1, ring < 1, action_stride < 0, or a step count that is
+ *   not the one launch's since the last memory event), an unknown dataset format, a d_onehot on a Box env, a BINARY_F32 d_x that is not 4-byte aligned, a
  *   negative capacity; GYMNET_ERR_UNSUPPORTED for a pixel dataset on an env other than CartPole; GYMNET_ERR_OOM when the memory cannot
  *   be allocated (the previous memory stays). */
 enum { GYMNET_MEMORY_PARAMS = 0 };
 int gymnet_vecenv_memory_config(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history);
+int gymnet_vecenv_memory_config_rollout(gymnet_vecenv *h, int32_t capacity, int32_t max_length, int32_t history, int32_t rollout_chunk);
 int gymnet_vecenv_memory_reset_device(gymnet_vecenv *h, const uint8_t *d_mask, int32_t clear_pool);
 int gymnet_vecenv_memory_push_device(gymnet_vecenv *h, const void *d_actions, const uint8_t *d_done);
+int gymnet_vecenv_memory_push_rollout_device(gymnet_vecenv *h, int64_t steps, const void *d_rec_obs, const void *d_actions,
+                                             int64_t action_stride, int64_t ring, const float *d_rec_reward, const uint8_t *d_rec_done);
 int gymnet_vecenv_memory_stats(gymnet_vecenv *h, int64_t *kept, int64_t *ended, int64_t *admitted, int64_t *too_long);
 int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, uint64_t *end_tick, int32_t *lane, int64_t capacity,
                                   int64_t *count);

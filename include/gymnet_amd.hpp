@@ -328,6 +328,20 @@ public:
     void ConfigureEpisodeMemory(int32_t capacity = 100, int32_t max_length = 0, int32_t history = 4) {
         check(gymnet_vecenv_memory_config(h_, capacity, max_length, history));
     }
+    /// ConfigureEpisodeMemory sized for PushMemoryRollout passes of rollout_chunk (1 .. 64) steps: rollout_chunk - 1 more staging slots and
+    /// candidate segments
+    void ConfigureEpisodeMemoryRollout(int32_t capacity = 100, int32_t max_length = 0, int32_t history = 4, int32_t rollout_chunk = 16) {
+        check(gymnet_vecenv_memory_config_rollout(h_, capacity, max_length, history, rollout_chunk));
+    }
+    /// once after ONE launch of `steps` steps (any fused rollout, or a single StepDevice with steps = 1): the rows it recorded — d_rec_obs
+    /// [steps][obs_dim][N], d_rec_reward and d_rec_done [steps][N] — and its actions, step t's at row (t % ring) * action_stride of d_actions
+    /// (-1: a [steps][N] record, action_stride = N and ring = steps).  The memory ends as `steps` x (StepDevice, PushEpisodeMemory) would
+    /// have left it
+    void PushMemoryRollout(int64_t steps, const void *d_rec_obs, const void *d_actions, const float *d_rec_reward, const uint8_t *d_rec_done,
+                           int64_t action_stride = -1, int64_t ring = -1) {
+        check(gymnet_vecenv_memory_push_rollout_device(h_, steps, d_rec_obs, d_actions, action_stride < 0 ? n_ : action_stride,
+                                                       ring < 0 ? steps : ring, d_rec_reward, d_rec_done));
+    }
     void PushEpisodeMemory(const void *d_actions, const uint8_t *d_done = nullptr) { check(gymnet_vecenv_memory_push_device(h_, d_actions, d_done)); }
     void ResetEpisodeMemory(const uint8_t *d_mask = nullptr, bool clear_pool = false) {
         check(gymnet_vecenv_memory_reset_device(h_, d_mask, clear_pool ? 1 : 0));

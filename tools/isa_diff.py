@@ -30,7 +30,7 @@ def kernels(paths):
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     res = {}
     for m, d in zip(names, dem):
-        d = re.sub(r"\(.*\)$", "", d.replace("void ", "", 1)).strip()
+        d = re.sub(r"\(.*\)$", "", d.replace("(anonymous namespace)::", "").replace("void ", "", 1)).strip()
         res[d] = out[m]
     return res
 

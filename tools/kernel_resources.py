@@ -61,7 +61,7 @@ def kernels(path):
                 meta[m.group(1)] = int(m.group(2))
         if "NumVgprs" not in meta:
             continue
-        name = re.sub(r"\(.*\)$", "", dem[idx].replace("gymnet::", "").replace("void ", "")).replace(", ", ",")
+        name = re.sub(r"\(.*\)$", "", dem[idx].replace("(anonymous namespace)::", "").replace("gymnet::", "").replace("void ", "")).replace(", ", ",")
         out[name] = {"vgpr": meta["NumVgprs"], "occupancy": meta.get("Occupancy", -1), "scratch": meta.get("ScratchSize", 0), "lds": meta.get("LDSByteSize", 0)}
     return out
 
