@@ -207,6 +207,7 @@ struct CartPole {
     template <bool SMALL_ANGLE = false, bool AUTORESET = false>
     __device__ __forceinline__ static void step(float (&s)[S], Action a, float &reward, bool &done) {
         const float x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+        const float s_in[S] = {x, x_dot, theta, theta_dot};
         const float force = (a == 1) ? force_mag : -force_mag;                                   // :146
         float sintheta, costheta;
         if constexpr (SMALL_ANGLE) sincos_tiny(theta, sintheta, costheta);
@@ -229,10 +230,20 @@ struct CartPole {
         // so fma(tau, x_dot, x) IS the reference's x + tau * x_dot; |v| > thr is the four strict comparisons, false for NaN).
         // Comparing the rounded binary32 values instead flips the flag for inputs within ~2 float32 ulps of a threshold
         // (22 of the 200 such vectors in tests/golden/cartpole_reference_text.npz).  4 conversions + 2 v_fma_f64 + 2 v_cmp.
-        const double vx = __builtin_fma((double)tau, (double)x_dot, (double)x);
-        const double vtheta = __builtin_fma((double)tau, (double)theta_dot, (double)theta);
-        done = __builtin_fabs(vx) > (double)x_threshold || __builtin_fabs(vtheta) > (double)theta_threshold;
+        bool term[DONE_TERMS];
+        done_terms_of_inputs(s_in, term);
+        done = term[0] || term[1];
         reward = 1.0f;   // the steps_beyond_done rule (:168-183) is applied by the kernel, which owns sbd
+    }
+
+    // the done flag of the step that STARTS from state s, as the compares it is the OR of (the comment in step(): two binary64 sums of
+    // the step's inputs against their thresholds)
+    static constexpr int DONE_TERMS = 2;
+    __device__ __forceinline__ static void done_terms_of_inputs(const float (&s)[S], bool (&term)[DONE_TERMS]) {
+        const double vx = __builtin_fma((double)tau, (double)s[1], (double)s[0]);
+        const double vtheta = __builtin_fma((double)tau, (double)s[3], (double)s[2]);
+        term[0] = __builtin_fabs(vx) > (double)x_threshold;
+        term[1] = __builtin_fabs(vtheta) > (double)theta_threshold;
     }
 
     // :63-67 — state = uniform(-0.05, 0.05, 4) as low + (high-low)*u

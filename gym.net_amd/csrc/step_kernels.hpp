@@ -148,6 +148,59 @@ __device__ __forceinline__ void advance_all(typename Env::Real (&s)[Env::S][VEC]
     }
 }
 
+// advance_all() for the unguarded body of an env with a small-angle path whose done flag is a function of the step's INPUTS
+// (Env::done_terms_of_inputs: CartPole).  The flags are decided once, after the two trigonometry paths have joined, from the values the step
+// started with.  Decided inside the paths they cross the join as 0/1 bytes in vector registers and every later use — the reset's ballots
+// first of all — has to turn them back into wave masks; decided behind the join they are the compares' own masks.  Same expression on
+// the same inputs: the same flags.  `dmask` receives each sub-lane's flag as the wave's ballot, taken term by term — the flag is an OR of
+// compares, a ballot of ONE compare is that compare's result register, and the OR is scalar; the ballot of the OR-ed flag would cost a
+// select and a second compare in vector registers.
+template <class Env, class = void> struct has_done_of_inputs : std::false_type {};
+template <class Env> struct has_done_of_inputs<Env, std::void_t<decltype(&Env::done_terms_of_inputs)>> : std::true_type {};
+
+template <class Env, int VEC, bool AUTORESET>
+__device__ __forceinline__ void advance_all_late_done(typename Env::Real (&s)[Env::S][VEC], typename Env::Action (&act)[VEC], float (&rw)[VEC],
+                                                      bool (&dn)[VEC], uint64_t (&dmask)[VEC]) {
+    constexpr int S = Env::S, O = Env::O;
+    using Real = typename Env::Real;
+    static_assert(Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && has_done_of_inputs<Env>::value, "see above");
+    static_assert(AUTORESET || !Env::HAS_SBD, "the steps_beyond_done rule reads the flag inside the step");
+    Real was[S][VEC];
+#pragma unroll
+    for (int k = 0; k < S; ++k)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) was[k][j] = s[k][j];
+    auto all_sublanes = [&](auto small_tag) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            Real sj[S], oj[O];
+            int32_t sbd_unused = 0;
+            bool after_unused = false;
+#pragma unroll
+            for (int k = 0; k < S; ++k) sj[k] = s[k][j];
+            advance_sublane<Env, AUTORESET, decltype(small_tag)::value>(sj, act[j], sbd_unused, rw[j], dn[j], after_unused, true, oj);
+#pragma unroll
+            for (int k = 0; k < S; ++k) s[k][j] = sj[k];
+        }
+    };
+    if (wave_angles_small<Env, VEC>(s)) all_sublanes(std::true_type{});
+    else all_sublanes(std::false_type{});
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        Real wj[S];
+#pragma unroll
+        for (int k = 0; k < S; ++k) wj[k] = was[k][j];
+        bool term[Env::DONE_TERMS];
+        Env::done_terms_of_inputs(wj, term);
+        bool any = false;
+        uint64_t m = 0;
+#pragma unroll
+        for (int q = 0; q < Env::DONE_TERMS; ++q) { any = any || term[q]; m |= __builtin_amdgcn_ballot_w64(term[q]); }
+        dn[j] = any;
+        dmask[j] = m;
+    }
+}
+
 // Fused auto-reset of the sub-lanes flagged in `pending`.  ~4.5 % of CartPole lanes finish per step, so ~95 % of
 // 64-lane waves hold a finished lane in EVERY sub-lane position: a per-sub-lane `if (done) philox()` would make every
 // wave pay VEC Philox passes.  Instead each thread drains its finished sub-lanes one per loop trip; the trips a wave
@@ -321,6 +374,75 @@ __device__ __forceinline__ void reset_pending_wave(uint32_t pending, typename En
         }
         wave_lds_fence();
     }
+}
+
+// The compacted reset of a wave of a FULL workgroup (the unguarded body of the one-step kernels), one Philox call per reset.  The finished
+// flags come in as the bools the `done` compares produced, so their ballots ARE the compares' wave masks (no detour through packed
+// bytes), and the common case — all 64 lanes active, at most 64 finished slots in the wave: every wave of a full workgroup but a
+// statistical freak — is a single trip without the round loop of reset_pending_wave(): the slot scatter is predicated by the
+// finished masks alone, no `rank - base < A` compares, and a sub-lane's row comes back from index `rank & 63`.  Same slots, same
+// Philox counters, same conversions as reset_pending_wave(), which stays the fallback for everything else.
+//   fmask     the wave's ballot of fin[j], per sub-lane
+//   wave_i0   first lane index of this wave (wave-uniform; valid when lane 0 of the wave is active)
+template <class Env, int VEC, bool LANE_SEEDS>
+__device__ __forceinline__ void reset_finished_wave(const bool (&fin)[VEC], const uint64_t (&fmask)[VEC], typename Env::Real (&s)[Env::S][VEC], const StepArgsT<typename Env::Real> &a,
+                                                    int64_t i0, int64_t wave_i0, int64_t n, uint64_t tick, ResetScratch<Env> *sc) {
+    constexpr int S = Env::S;
+    using Real = typename Env::Real;
+    static_assert(Env::OBS_ALIASES_STATE && !has_split_reset<Env>(), "one-call resets that hand back the state only");
+    const uint32_t lane = lane_id();
+    uint32_t rank[VEC];
+    uint32_t total = 0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        const uint64_t m = fmask[j];
+        rank[j] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        total += (uint32_t)__popcll(m);
+    }
+    // wave-uniform; both are rare for the envs this serves (about one CartPole wave in twenty has nothing to reset): the round loop serves
+    // what the single trip does not
+    if (__builtin_expect(total == 0 || total > 64u || __ballot(1) != ~0ull, 0)) {
+        if (total != 0) {
+            uint32_t pending = 0;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) pending |= fin[j] ? (1u << j) : 0u;
+            reset_pending_wave<Env, VEC, LANE_SEEDS>(pending, s, a, i0, n, tick, sc);
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+        if (fin[j]) sc->slot[rank[j]] = lane * VEC + (uint32_t)j;
+    wave_lds_fence();
+    {
+        // every lane draws (kResetFullExec's reason: reset_pending_wave); the lanes without a slot redo slot 0's draw into a row nobody reads
+        const uint32_t sl = sc->slot[lane < total ? lane : 0u];
+        const int64_t gl = wave_i0 + (int64_t)sl;
+        Real sj[S];
+        bool drawn = false;
+        if constexpr (LANE_SEEDS) {
+            if (a.lane_seed) {                                 // kernel-uniform: per-lane keys are installed
+                draw_reset<Env, false>(sj, gl < n ? a.lane_seed[gl] : a.seed, a.lane_offset + (uint64_t)gl, tick);
+                drawn = true;
+            }
+        }
+        if (!drawn) draw_reset<Env, true>(sj, a.seed, a.lane_offset + (uint64_t)gl, tick);
+#pragma unroll
+        for (int k = 0; k < S; ++k) sc->draw[lane][k] = sj[k];
+    }
+    wave_lds_fence();
+    Real got[VEC][S];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) got[j][k] = sc->draw[rank[j] & 63u][k];
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) s[k][j] = fin[j] ? got[j][k] : s[k][j];
+    }
+    wave_lds_fence();
 }
 
 // wave64 compaction of the sub-lanes flagged in `finished`: rank of every flagged sub-lane inside the wave (ballot + mbcnt),
@@ -554,6 +676,70 @@ __device__ __forceinline__ void step_body(const StepArgsT<typename Env::Real> &a
     LaneInputs<Env, VEC> in;
     load_inputs<Env, VEC, AUTORESET, NT, GUARD>(a, i0, in);
     advance_and_store<Env, VEC, AUTORESET, EXTRAS, NT, GUARD, RESETF>(a, i0, tick, in, sc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The body of a FULL workgroup of the lean auto-reset kernels of an env with a late done flag (advance_all_late_done: CartPole) — at 2^20
+// lanes the headline kernel runs nothing else.  Three things set it apart from step_body<GUARD = false> (same loads, arithmetic, draws
+// and stores, bit for bit):
+//   * rows are addressed from scalar bases + one 32-bit offset per thread (lanes.hpp WgLanes);
+//   * the done flags are decided behind the join of the trigonometry paths and reach the reset as the compares' wave masks;
+//   * with RESETF == 1 the reset of a full wave with at most 64 finished slots is a single trip (reset_finished_wave).
+// Every other kernel variant and env keeps step_body: the bookkeeping variants, and the envs where this form measured no gain
+// (Pendulum) or a loss (MountainCar, ~1 %): docs/ledger.md §25.
+// ---------------------------------------------------------------------------------------------
+template <class Env, bool AUTORESET, bool EXTRAS>
+constexpr bool has_full_workgroup_body() {
+    return AUTORESET && !EXTRAS && Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && !has_split_reset<Env>() && has_done_of_inputs<Env>::value;
+}
+
+// the part of a row a full workgroup owns, as a scalar pointer: row base + the workgroup's first lane
+template <class T>
+__device__ __forceinline__ T *wg_row(T *row, const WgLanes &wg) { return wave_uniform(row + wg.first); }
+
+template <class Env, int VEC, int NT, int RESETF>
+__device__ __forceinline__ void step_body_wg(const StepArgsT<typename Env::Real> &a, const WgLanes wg, const uint64_t tick, ResetScratch<Env> *sc) {
+    constexpr int S = Env::S;
+    using Real = typename Env::Real;
+    constexpr bool NT_SL = (NT & 1) != 0, NT_SS = (NT & 2) != 0, NT_A = (NT & 4) != 0, NT_O = (NT & 8) != 0;
+    static_assert(!Env::BOX_ACTION && Env::OBS_ALIASES_STATE, "a discrete-action env whose observation is its state");
+    const int64_t i0 = wg.first + (int64_t)wg.local;
+
+    Real s[S][VEC];
+    typename Env::Action act[VEC];
+#pragma unroll
+    for (int k = 0; k < S; ++k) load_row_wg<Real, VEC, NT_SL>(wg_row(static_cast<const Real *>(a.state) + k * a.state_stride, wg), wg.local, s[k]);
+    load_row_wg<int32_t, VEC, NT_A>(wg_row(static_cast<const int32_t *>(a.action), wg), wg.local, act);
+
+    float reward[VEC];
+    bool finished[VEC];
+    uint64_t fmask[VEC];                 // the wave's ballot of finished[j]
+    advance_all_late_done<Env, VEC, true>(s, act, reward, finished, fmask);
+
+    // reward / done do not depend on the reset draw: get them on their way before the Philox rounds.  The done word comes straight from
+    // the compares' masks: one select of a constant per sub-lane.
+    {
+        const uint32_t local = reissued(wg.local);
+        store_row_wg<float, VEC, NT_O>(wg_row(a.reward, wg), local, reward);
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) w |= finished[j] ? (1u << (8 * j)) : 0u;
+        store_done_word_wg<VEC, NT_O>(wg_row(a.done, wg), local, w);
+    }
+
+    if constexpr (RESETF == 1) {
+        reset_finished_wave<Env, VEC, false>(finished, fmask, s, a, i0, wg.first + (int64_t)__builtin_amdgcn_readfirstlane(wg.local), a.n, tick, sc);
+    } else {
+        uint32_t pending = 0;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) pending |= finished[j] ? (1u << j) : 0u;
+        Real o_unused[Env::O][VEC];
+        reset_pending<Env, VEC, false>(pending, s, o_unused, a, i0, a.n, tick);
+    }
+
+    const uint32_t local = reissued(wg.local);
+#pragma unroll
+    for (int k = 0; k < S; ++k) store_row_wg<Real, VEC, NT_SS>(wg_row(a.state_out + k * a.state_stride, wg), local, s[k]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -947,7 +1133,8 @@ template <class Env, int VEC, bool AUTORESET, bool EXTRAS, int NT, int RESETF = 
 __global__ __launch_bounds__(256) void step_kernel(typename Env::Real *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2,
                                                    float *reward, int32_t block, int32_t parity, const StepArgsT<typename Env::Real> rest) {
     const StepArgsT<typename Env::Real> a = hot_step_args(state, action, n, state_stride, tick2, reward, parity, rest);
-    const int64_t i0 = ((int64_t)blockIdx.x * block + threadIdx.x) * VEC;
+    const WgLanes wg{(int64_t)blockIdx.x * block * VEC, (uint32_t)threadIdx.x * (uint32_t)VEC};
+    const int64_t i0 = wg.first + (int64_t)wg.local;
     ResetScratch<Env> *sc = nullptr;
     if constexpr (RESETF == 1) {
         __shared__ ResetScratch<Env> scratch[256 / 64];            // one table per wave of the workgroup
@@ -965,7 +1152,8 @@ __global__ __launch_bounds__(256) void step_kernel(typename Env::Real *state, co
     }
     // workgroup-uniform: every workgroup but (at most) the last runs the unguarded body
     if (((int64_t)blockIdx.x + 1) * block * VEC <= a.n) {
-        step_body<Env, VEC, AUTORESET, EXTRAS, NT, false, RESETF>(a, i0, tick, sc);
+        if constexpr (has_full_workgroup_body<Env, AUTORESET, EXTRAS>()) step_body_wg<Env, VEC, NT, RESETF>(a, wg, tick, sc);
+        else step_body<Env, VEC, AUTORESET, EXTRAS, NT, false, RESETF>(a, i0, tick, sc);
     } else {
         if (i0 >= a.n) return;
         step_body<Env, VEC, AUTORESET, EXTRAS, NT, true, RESETF>(a, i0, tick, sc);
