@@ -53,6 +53,7 @@ STACK_GRAY8, STACK_BINARY8, STACK_BINARY_F32 = 2, 3, 4     # gymnet_vecenv_pixel
 MEMORY_PARAMS = 0            # gymnet_vecenv_memory_dataset_device format (the others are the STACK_* formats)
 BOX_HEAD_CLAMP, BOX_HEAD_TANH = 0, 1                 # gymnet_vecenv_actor_box_set_policy: gymnet_box_head
 BOX_EXPLORE_SAMPLE, BOX_EXPLORE_GAUSSIAN = 0, 1      # ... and gymnet_box_explore
+ACTOR_EXPLORE_UNIFORM, ACTOR_EXPLORE_SOFTMAX = 0, 1  # gymnet_vecenv_actor_set_exploration: gymnet_actor_explore
 
 
 class Config(C.Structure):
@@ -196,6 +197,8 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_push_device": (C.c_int, [_H, _P]),
     "gymnet_vecenv_actor_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_actor_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "gymnet_vecenv_actor_set_exploration": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "gymnet_vecenv_actor_get_exploration": (C.c_int, [_H, _P, _P]),
     "gymnet_vecenv_actor_box_config": (C.c_int, [_H, C.c_int32, C.c_int32, _P, _P, C.c_int64]),
     "gymnet_vecenv_actor_box_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_actor_box_set_policy": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_float]),

@@ -28,6 +28,8 @@ namespace Gym.Envs.Amd {
     // gymnet_vecenv_actor_box_set_policy: a Box actor's head and what its exploring lanes take
     public enum GymnetBoxHead { Clamp = 0, Tanh = 1 }
     public enum GymnetBoxExplore { Sample = 0, Gaussian = 1 }
+    // gymnet_vecenv_actor_set_exploration: what a Discrete actor's exploring lanes take
+    public enum GymnetActorExplore { Uniform = 0, Softmax = 1 }
 
     public enum GymnetPixelFormat { Rgb8 = 1, Gray8 = 2 }     // gymnet_vecenv_render(_device): 3 bytes per pixel / 1 byte (BT.709 luma)
 
@@ -196,6 +198,8 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_push_device(IntPtr h, IntPtr d_done);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_view(IntPtr h, out IntPtr d_history, out long lane_stride, out int slot);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_set_exploration(IntPtr h, int explore, float temperature);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_get_exploration(IntPtr h, int* explore, float* temperature);
         // the Box actor (Pendulum, MountainCarContinuous): the last layer's one output, clamped to the env's bounds, is the action
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, float epsilon, ulong seed, ulong tick);

@@ -302,6 +302,15 @@ namespace Gym.Envs.Amd {
         /// (TrainingPlaySession.cs:46-52; epsilon 0 = TestingPlaySession); dLogits float [N][action_n] or IntPtr.Zero.
         public void ActorAct(IntPtr dActions, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dLogits = default) =>
             Native.Check(Native.gymnet_vecenv_actor_act_device(_h, dActions, dLogits, epsilon, seed, tick));
+        /// A Discrete actor's exploration setting (gymnet_vecenv_actor_set_exploration): under Softmax a lane that explores draws its action
+        /// from softmax(logits / temperature) instead of uniformly; ActorAct and the fused actor rollout read it.  A new actor has (Uniform, 1).
+        public void SetActorExploration(GymnetActorExplore explore, float temperature = 1f) =>
+            Native.Check(Native.gymnet_vecenv_actor_set_exploration(_h, (int) explore, temperature));
+        public void GetActorExploration(out GymnetActorExplore explore, out float temperature) {
+            int ex; float tp;
+            Native.Check(Native.gymnet_vecenv_actor_get_exploration(_h, &ex, &tp));
+            explore = (GymnetActorExplore) ex; temperature = tp;
+        }
         /// The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous with w_L = 1; its one output,
         /// clamped to the env's bounds, is the action.  No layers releases it.  LoadActorWeights / ResetActor / PushActor serve both kinds.
         public void ConfigureBoxActor(int history, int[] widths, float[] weights) {

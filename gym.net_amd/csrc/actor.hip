@@ -22,6 +22,8 @@
 //
 // What the Box actor (actor_box.hip: Pendulum, MountainCarContinuous) shares with this unit — the network and history structs, the forward
 // pass, load_input, the ring arithmetic, the push — is in actor_net.hpp; the Discrete head (argmax_logits, compose_one) stays here.
+// That head is the default exploration setting; under GYMNET_ACTOR_EXPLORE_SOFTMAX (gymnet_vecenv_actor_set_exploration) the two host entry
+// points that launch it hand over to actor_softmax.hip, and this unit's kernels stay what they were.
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, and the three calls the fused rollout
 // (capi.hip) makes when the actor chooses its actions.
@@ -256,6 +258,7 @@ int actor_rollout_check(gymnet_vecenv *h) {
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
+    if (!ac.box && !ac.default_exploration()) return actor_softmax_rollout_launch(h, records, a, r);
     switch (h->cfg.env_id) {
         case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
         case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
@@ -384,7 +387,12 @@ int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *
         return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
     ActorAct aa{};
     aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
-    HIP_TRY(h, launch_actor_act(h->actor->net, h->actor->hist, d_actions, d_logits, aa, h->stream));
+    const Actor &ac = *h->actor;
+    if (!ac.default_exploration()) {
+        HIP_TRY(h, actor_softmax_act_launch(ac.net, ac.hist, d_actions, d_logits, aa, ActorExplore{ac.discrete_explore, ac.inv_tau}, h->stream));
+        return GYMNET_OK;
+    }
+    HIP_TRY(h, launch_actor_act(ac.net, ac.hist, d_actions, d_logits, aa, h->stream));
     return GYMNET_OK;
     });
 }

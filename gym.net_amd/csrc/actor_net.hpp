@@ -1,7 +1,8 @@
 // actor_net.hpp — what the two actor units share: the network and the per-lane observation history as the kernels see them, the forward
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), and the handle's Actor attachment
 // with the calls one unit makes into the other.  actor.hip serves the Discrete envs (argmax head) and owns the attachment; actor_box.hip
-// serves the Box envs (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise).  Internal to the library.
+// serves the Box envs (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete
+// envs under an exploration setting other than the default (a draw from the softmax of the logits).  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -156,9 +157,15 @@ struct Actor {
     // any other runs through actor_box_policy.hip
     int32_t head = GYMNET_BOX_HEAD_CLAMP, explore = GYMNET_BOX_EXPLORE_SAMPLE; float sigma = 0.0f;
     bool default_policy() const { return head == GYMNET_BOX_HEAD_CLAMP && explore == GYMNET_BOX_EXPLORE_SAMPLE; }
+    // a Discrete actor's exploration setting (gymnet_vecenv_actor_set_exploration): a fresh actor has the default, which the kernels of
+    // actor.hip serve (UNIFORM at any temperature is that behaviour); SOFTMAX runs through actor_softmax.hip.  inv_tau = 1.0f / temperature
+    int32_t discrete_explore = GYMNET_ACTOR_EXPLORE_UNIFORM; float temperature = 1.0f, inv_tau = 1.0f;
+    bool default_exploration() const { return discrete_explore == GYMNET_ACTOR_EXPLORE_UNIFORM; }
 };
 // what the kernels of actor_box_policy.hip take of it, as a kernel argument
 struct BoxPolicy { int32_t head, explore; float sigma; };
+// ... and the kernels of actor_softmax.hip
+struct ActorExplore { int32_t explore; float inv_tau; };
 
 // the message names the config call that serves the handle's env
 inline int need_actor(gymnet_vecenv *h) {
@@ -178,5 +185,9 @@ hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepAr
 hipError_t actor_box_policy_act_launch(const ActorNet &net, const ActorHist &hs, float *actions, float *raw, float low, float high, const ActorAct &aa,
                                        const BoxPolicy &pol, hipStream_t st);
 hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+// actor_softmax.hip: act and the fused rollout of a Discrete handle whose exploration setting is not the default
+hipError_t actor_softmax_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, const ActorExplore &ex,
+                                    hipStream_t st);
+hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 
 }  // namespace gymnet

@@ -961,7 +961,8 @@ class Actor:
         compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
         float32 [N] — the network's one output clamped to the action bounds, or ActionSpace.Sample() as SampleActionsDevice(seed=seed,
         tick=tick) draws it where the lane explores — and logits takes the [N, 1] unclamped outputs.  That is the default policy;
-        SetPolicy changes the head and what an exploring lane takes."""
+        SetPolicy changes the head and what an exploring lane takes.  On a Discrete actor SetExploration("softmax", temperature) makes an
+        exploring lane draw from softmax(logits / temperature) instead."""
         if out is None:
             out = self._actions()
         act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
@@ -996,6 +997,35 @@ class Actor:
         capi.check(self._lib.gymnet_vecenv_actor_box_get_policy(self._handle(), C.byref(head), C.byref(explore), C.byref(sigma)))
         heads, explores = {v: k for k, v in self._HEADS.items()}, {v: k for k, v in self._EXPLORES.items()}
         return heads[head.value], explores[explore.value], float(sigma.value)
+
+    _EXPLORATIONS = {"uniform": capi.ACTOR_EXPLORE_UNIFORM, "softmax": capi.ACTOR_EXPLORE_SOFTMAX}
+
+    def SetExploration(self, explore="uniform", temperature=1.0):
+        """A Discrete actor's exploration setting (gymnet_vecenv_actor_set_exploration), read by Act, Step, RolloutFusedDevice(actions=
+        "actor") and EpisodeMemory.Rollout(actions="actor") from the next call on.  explore: what a lane whose coin says "explore" takes:
+        "uniform" (ActionSpace.Sample()) or "softmax" (a draw from softmax(logits / temperature): at epsilon = 1 every lane samples the
+        stochastic policy).  A new actor has ("uniform", 1.0); Load, Push and Reset keep the setting."""
+        if self.IsBox:
+            raise ValueError("an exploration setting belongs to a Discrete actor; this one chooses Box actions (SetPolicy)")
+        if not isinstance(explore, str) or explore not in self._EXPLORATIONS:
+            raise ValueError(f"explore must be one of {sorted(self._EXPLORATIONS)}, got {explore!r}")
+        if isinstance(temperature, (bool, np.bool_)):
+            raise ValueError("temperature must be a number, not a bool")
+        with np.errstate(over="ignore", divide="ignore"):
+            temperature = float(np.float32(temperature))
+            ok = np.isfinite(temperature) and temperature > 0.0 and np.isfinite(np.float32(1.0) / np.float32(temperature))
+        if not ok:
+            raise ValueError("temperature must be finite, > 0 and large enough for a finite float32 1 / temperature")
+        capi.check(self._lib.gymnet_vecenv_actor_set_exploration(self._handle(), self._EXPLORATIONS[explore], temperature))
+
+    @property
+    def Exploration(self):
+        """(explore, temperature) as SetExploration takes them, read from the library (gymnet_vecenv_actor_get_exploration)."""
+        if self.IsBox:
+            raise ValueError("an exploration setting belongs to a Discrete actor; this one chooses Box actions (Policy)")
+        explore, temperature = C.c_int32(), C.c_float()
+        capi.check(self._lib.gymnet_vecenv_actor_get_exploration(self._handle(), C.byref(explore), C.byref(temperature)))
+        return {v: k for k, v in self._EXPLORATIONS.items()}[explore.value], float(temperature.value)
 
     def _actions(self):
         import torch

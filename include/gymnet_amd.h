@@ -646,6 +646,39 @@ int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask);
 int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done);
 int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick);
 int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot);
+/* A Discrete actor's exploration setting (additive in ABI 6): (explore, temperature), read by act_device and by the fused rollout with
+ * GYMNET_ACTIONS_ACTOR, which stays bit-identical to steps x (act_device, step_device, actor_push_device) under every setting.
+ * The coin is unchanged — a lane explores if and only if word B of the aux stream is <= coin_threshold(epsilon) — and a lane that does
+ * not explore takes the greedy action (argmax).  What an exploring lane takes:
+ *   UNIFORM (default): ActionSpace.Sample() = umulhi(word A of the action stream, action_n), the behaviour described above, through the
+ *   same kernels, whatever the temperature.
+ *   SOFTMAX: a draw from softmax(logits / temperature), so at epsilon = 1 every lane samples the stochastic policy and at epsilon = 0
+ *   nothing changes.  The draw is specified in float32, every operation rounded on its own, in this order (A = action_n <= 8, l_k the
+ *   logits):
+ *     1. m = the greedy logit (the value the argmax settles on).
+ *     2. inv_tau = 1.0f / temperature, computed once on the host in float32.
+ *     3. e_k = exp_neg((l_k - m) * inv_tau) for ascending k — a difference, a product, then exp_neg: t = a * 1.44269504f; a t that is
+ *        not >= -125 (also a NaN) gives exactly +0.0f; otherwise n = rintf(t), f = t - n, p = the Horner chain of fmaf
+ *        ((((((c7 f + c6) f + c5) f + c4) f + c3) f + c2) f + c1) f + 1 with c_i = float32(ln2^i / i!), and the result is p with n added
+ *        to its exponent field as integer bits (csrc/exp_neg.hpp; not the device library's expf, whose bits a CPU cannot reproduce).
+ *     4. c_k = c_{k-1} + e_k in index order (c_{-1} = 0), S = c_{A-1}.
+ *     5. u = u01_24(word A), the lane's word of the action stream at (seed, global lane, tick) — the word UNIFORM feeds to umulhi.  (Word
+ *        B is not u: on an exploring lane it is small by construction.)
+ *     6. thr = u * S.
+ *     7. The action is the first k with thr < c_k; if there is none (thr rounded up to S, S = 0, NaN or infinite logits) it is the greedy
+ *        action.  So a chosen action has e_k > 0 or is the greedy one: an action whose weight underflowed to zero is never taken.
+ *   Word A is drawn only when some lane of the wave explores, as under UNIFORM.
+ * set_exploration: stored on the actor and read at the next act / actor rollout launch, so ordered on the handle's stream like the other
+ *   actor calls; changes no history and no staleness state.  temperature is stored whatever explore is.  actor_config leaves the setting
+ *   at (UNIFORM, 1.0) — also a re-config; load_device, push_device and reset_device keep it.  GYMNET_ERR_INVALID_ARG, nothing changed:
+ *   no actor, a Box actor, an unknown enum value, a temperature that is not finite, is <= 0, or is so small that 1.0f / temperature is
+ *   not finite.
+ * get_exploration: any out pointer may be NULL; the same refusals for a handle without a Discrete actor (outputs untouched).
+ * Out of scope: recording logits or log-probabilities inside the fused rollout (re-evaluate the recorded inputs; for one step act_device's
+ *   d_logits are the exact logits), a softmax for gymnet_vecenv_compose_actions_device, and the Box actor, whose policy is below. */
+typedef enum gymnet_actor_explore { GYMNET_ACTOR_EXPLORE_UNIFORM = 0, GYMNET_ACTOR_EXPLORE_SOFTMAX = 1 } gymnet_actor_explore;
+int gymnet_vecenv_actor_set_exploration(gymnet_vecenv *h, int32_t explore, float temperature);
+int gymnet_vecenv_actor_get_exploration(gymnet_vecenv *h, int32_t *explore, float *temperature);
 /* The Box actor (additive in ABI 6): the same actor on a Box action space — Pendulum-v1 (obs_dim 3, bounds -2 .. 2) and
  * MountainCarContinuous-v0 (obs_dim 2, bounds -1 .. 1), float32 handles (neither env has a float64 mode).
  * Network: as above — L in [1, 4] layers, every width in [1, 64], at most 8192 parameters, torch's nn.Linear layout, ReLU between the

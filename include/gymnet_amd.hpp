@@ -387,6 +387,16 @@ public:
     void ActorAct(int32_t *d_actions, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_logits = nullptr) {
         check(gymnet_vecenv_actor_act_device(h_, d_actions, d_logits, epsilon, seed, tick));
     }
+    // A Discrete actor's exploration setting (gymnet_vecenv_actor_set_exploration): under SOFTMAX a lane that explores draws its action from
+    // softmax(logits / temperature) instead of uniformly; ActorAct and the fused actor rollout read it.  A new actor has (UNIFORM, 1).
+    void SetActorExploration(gymnet_actor_explore explore, float temperature = 1.0f) {
+        check(gymnet_vecenv_actor_set_exploration(h_, (int32_t)explore, temperature));
+    }
+    void GetActorExploration(gymnet_actor_explore &explore, float &temperature) const {
+        int32_t ex = 0;
+        check(gymnet_vecenv_actor_get_exploration(h_, &ex, &temperature));
+        explore = (gymnet_actor_explore)ex;
+    }
     // The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous; its one output, clamped to the
     // env's bounds, is the action.  Empty widths release the actor.  LoadActorWeights / ResetActor / PushActor serve both kinds.
     void ConfigureBoxActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
