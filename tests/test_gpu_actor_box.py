@@ -73,6 +73,7 @@ def test_raw_and_actions_equal_the_twin(gpu_pkg, oracle, name, widths, S, n):
                 assert np.array_equal(x, x0)
             for eps in (0.0, 0.3, 1.0):
                 raw.fill_(-7.0)
+                torch.cuda.synchronize()                                     # the fill (torch's stream) ends before the handle's stream writes
                 got = actor.Act(eps, seed=77, tick=tick, logits=raw)
                 assert got.dtype == torch.float32 and tuple(got.shape) == (n,)
                 assert twin.same(host(raw), want_raw)

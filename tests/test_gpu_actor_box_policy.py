@@ -77,6 +77,7 @@ def test_act_equals_the_twin(gpu_pkg, name, head, explore, lane0):
         greedy = None
         for eps in (0.0, 0.3, 1.0):
             raw.fill_(-7.0)
+            torch.cuda.synchronize()                                         # the fill (torch's stream) ends before the handle's stream writes
             got = host(actor.Act(eps, seed=seed, tick=tick, logits=raw)).copy()
             assert got.dtype == np.float32 and got.shape == (N,)
             assert twin.same(host(raw), want_raw)                            # raw: the fmaf chain's bits, whatever the head

@@ -72,6 +72,7 @@ def test_act_equals_the_twin(gpu_pkg, name, lane0):
             assert actor.Exploration == ("softmax", tau)
             for eps in (0.0, 0.3, 1.0):
                 logits.fill_(-7.0)
+                torch.cuda.synchronize()                                     # the fill (torch's stream) ends before the handle's stream writes
                 got = host(actor.Act(eps, seed=seed, tick=tick, logits=logits)).copy()
                 assert got.dtype == np.int32 and got.shape == (N,)
                 assert twin.same(host(logits), want_logits)                  # the logits: the fmaf chain's bits

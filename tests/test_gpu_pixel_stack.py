@@ -72,6 +72,7 @@ def test_gray8_slots_equal_the_render_bitwise(gpu_pkg, dtype):
             frame = size[0] * size[1]
             stride = depth * frame + 5
             buf = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()                                      # torch's stream fills; the handle's does not wait for it
             assert _config(env, GRAY8, depth, crop, size, ext=buf.data_ptr() + 3, stride=stride) == 0
             env.Sync()
             b = buf.cpu().numpy()
@@ -323,6 +324,7 @@ def test_python_facade(gpu_pkg, fmt, dt):
             tensors.append(host)
             # a caller's tensor with padded lanes is adopted with its stride(0)
             big = torch.zeros((n, 4, 13, 21), dtype=getattr(torch, dt), device="cuda")
+            torch.cuda.synchronize()                               # the zeros are in place before the handle's stream writes
             st2 = env.PixelStack(depth=3, size=(21, 13), crop=(150, 100, 300, 250), format=fmt, out=big[:, :3])
             env.Sync()
             assert (big[:, 3] == 0).all() and np.array_equal(big[:, :3].cpu().numpy(), st2.Read())

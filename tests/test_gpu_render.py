@@ -61,8 +61,9 @@ def test_gray8_images_runner_layout(gpu_pkg):
         buf = np.full(n * stride + 64, 0xA5, np.uint8)
         assert _host_render(env, buf, GRAY8, 0, n, crop, size, stride, offset=800) == 0
         dev = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        env.RenderDevice(dev.data_ptr() + 800, "gray", crop=crop, size=size, lane_stride=stride)
         odd = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()                                          # torch's stream fills; the handle's does not wait for it
+        env.RenderDevice(dev.data_ptr() + 800, "gray", crop=crop, size=size, lane_stride=stride)
         env.RenderDevice(odd.data_ptr() + 801, "gray", crop=crop, size=size, lane_stride=stride)
         env.Sync()
         frames = env.RenderFrames(size, crop=crop)
@@ -162,6 +163,7 @@ def test_stream_ordering_double_buffer_and_auto_reset(gpu_pkg):
             env.SetState(s)
             acts = torch.from_numpy(rng.integers(0, 2, n).astype(np.int32)).cuda()
             out = torch.full((n * 800,), 0xA5, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()                                      # the sentinel is in place before the handle's stream starts
             for _ in range(3):
                 env.StepDevice(acts)                               # no synchronize in between: the render is ordered after the step
             env.RenderDevice(out, "gray", crop=crop, size=size)
