@@ -236,6 +236,45 @@ struct CartPole {
         reward = 1.0f;   // the steps_beyond_done rule (:168-183) is applied by the kernel, which owns sbd
     }
 
+    // step() cut where the action enters: step_pre() is everything the action has no part in — the trigonometry, the three action-free
+    // terms of :149-150 and the position updates, two thirds of the arithmetic — and step_post() the rest.  step_post(step_pre(s), a) is
+    // step(s, a) operation for operation: the same operands in the same association (`force + ((pml * theta_dot) * theta_dot) * sintheta`),
+    // div_tm in the same places, each operation rounded on its own.  A kernel whose action arrives later than its state rows (the one-step
+    // kernel's full-workgroup body, step_kernels.hpp) runs step_pre() while the action is still on its way.
+    struct Pre {
+        float x_dot, theta_dot;      // the velocities the step started with
+        float nx, ntheta;            // :154,156 — positions advance with the OLD velocities
+        float costheta;
+        float centrifugal;           // polemass_length * theta_dot * theta_dot * sintheta      (:149)
+        float gsin;                  // gravity * sintheta                                      (:150)
+        float divisor;               // length * (4/3 - masspole * costheta^2 / total_mass)     (:150)
+    };
+    template <bool SMALL_ANGLE = false>
+    __device__ __forceinline__ static void step_pre(const float (&s)[S], Pre &p) {
+        const float x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+        float sintheta, costheta;
+        if constexpr (SMALL_ANGLE) sincos_tiny(theta, sintheta, costheta);
+        else sincos_f32(theta, sintheta, costheta);                                              // :147-148
+        p.centrifugal = polemass_length * theta_dot * theta_dot * sintheta;
+        p.gsin = gravity * sintheta;
+        p.divisor = length * (4.0f / 3.0f - div_tm(masspole * costheta * costheta));
+        p.costheta = costheta;
+        p.nx = x + tau * x_dot;
+        p.ntheta = theta + tau * theta_dot;
+        p.x_dot = x_dot;
+        p.theta_dot = theta_dot;
+    }
+    // (`right`: the action is 1; a caller that has to keep the action's first read where it is makes the compare itself)
+    __device__ __forceinline__ static void step_post(const Pre &p, Action a, float (&s)[S], float &reward) { step_post(p, a == 1, s, reward); }
+    __device__ __forceinline__ static void step_post(const Pre &p, bool right, float (&s)[S], float &reward) {
+        const float force = right ? force_mag : -force_mag;                                      // :146
+        const float temp = div_tm(force + p.centrifugal);                                        // :149
+        const float thetaacc = (p.gsin - p.costheta * temp) / p.divisor;                         // :150
+        const float xacc = temp - div_tm(polemass_length * thetaacc * p.costheta);               // :151
+        s[0] = p.nx; s[1] = p.x_dot + tau * xacc; s[2] = p.ntheta; s[3] = p.theta_dot + tau * thetaacc;
+        reward = 1.0f;
+    }
+
     // the done flag of the step that STARTS from state s, as the compares it is the OR of (the comment in step(): two binary64 sums of
     // the step's inputs against their thresholds)
     static constexpr int DONE_TERMS = 2;

@@ -148,8 +148,8 @@ __device__ __forceinline__ void advance_all(typename Env::Real (&s)[Env::S][VEC]
     }
 }
 
-// advance_all() for the unguarded body of an env with a small-angle path whose done flag is a function of the step's INPUTS
-// (Env::done_terms_of_inputs: CartPole).  The flags are decided once, after the two trigonometry paths have joined, from the values the step
+// The step of the unguarded body of an env with a small-angle path whose done flag is a function of the step's INPUTS
+// (Env::done_terms_of_inputs: CartPole; pre_all_late_done() below).  The flags are decided once, after the two trigonometry paths have joined, from the values the step
 // started with.  Decided inside the paths they cross the join as 0/1 bytes in vector registers and every later use — the reset's ballots
 // first of all — has to turn them back into wave masks; decided behind the join they are the compares' own masks.  Same expression on
 // the same inputs: the same flags.  `dmask` receives each sub-lane's flag as the wave's ballot, taken term by term — the flag is an OR of
@@ -158,29 +158,26 @@ __device__ __forceinline__ void advance_all(typename Env::Real (&s)[Env::S][VEC]
 template <class Env, class = void> struct has_done_of_inputs : std::false_type {};
 template <class Env> struct has_done_of_inputs<Env, std::void_t<decltype(&Env::done_terms_of_inputs)>> : std::true_type {};
 
-template <class Env, int VEC, bool AUTORESET>
-__device__ __forceinline__ void advance_all_late_done(typename Env::Real (&s)[Env::S][VEC], typename Env::Action (&act)[VEC], float (&rw)[VEC],
-                                                      bool (&dn)[VEC], uint64_t (&dmask)[VEC]) {
-    constexpr int S = Env::S, O = Env::O;
+// The step itself comes in the two parts the env cuts it into where the action enters (Env::step_pre / step_post: envs.hpp).  The action is
+// the one input stream of a launch that no earlier launch has touched, so it is the last to arrive: everything that can be decided without it
+// — the action-free part of the dynamics, the flags, and with them the whole reset draw — runs in front of the wait for it.
+template <class Env, class = void> struct has_split_step : std::false_type {};
+template <class Env> struct has_split_step<Env, std::void_t<typename Env::Pre>> : std::true_type {};
+
+// the action-free part of the step of ALL VEC sub-lanes (the wave-uniform choice of the trigonometry path encloses nothing else), and the flags
+template <class Env, int VEC>
+__device__ __forceinline__ void pre_all_late_done(const typename Env::Real (&s)[Env::S][VEC], typename Env::Pre (&pre)[VEC], bool (&dn)[VEC],
+                                                  uint64_t (&dmask)[VEC]) {
+    constexpr int S = Env::S;
     using Real = typename Env::Real;
-    static_assert(Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && has_done_of_inputs<Env>::value, "see above");
-    static_assert(AUTORESET || !Env::HAS_SBD, "the steps_beyond_done rule reads the flag inside the step");
-    Real was[S][VEC];
-#pragma unroll
-    for (int k = 0; k < S; ++k)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) was[k][j] = s[k][j];
+    static_assert(Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && has_done_of_inputs<Env>::value && has_split_step<Env>::value, "see above");
     auto all_sublanes = [&](auto small_tag) {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            Real sj[S], oj[O];
-            int32_t sbd_unused = 0;
-            bool after_unused = false;
+            Real sj[S];
 #pragma unroll
             for (int k = 0; k < S; ++k) sj[k] = s[k][j];
-            advance_sublane<Env, AUTORESET, decltype(small_tag)::value>(sj, act[j], sbd_unused, rw[j], dn[j], after_unused, true, oj);
-#pragma unroll
-            for (int k = 0; k < S; ++k) s[k][j] = sj[k];
+            Env::template step_pre<decltype(small_tag)::value>(sj, pre[j]);
         }
     };
     if (wave_angles_small<Env, VEC>(s)) all_sublanes(std::true_type{});
@@ -189,7 +186,7 @@ __device__ __forceinline__ void advance_all_late_done(typename Env::Real (&s)[En
     for (int j = 0; j < VEC; ++j) {
         Real wj[S];
 #pragma unroll
-        for (int k = 0; k < S; ++k) wj[k] = was[k][j];
+        for (int k = 0; k < S; ++k) wj[k] = s[k][j];
         bool term[Env::DONE_TERMS];
         Env::done_terms_of_inputs(wj, term);
         bool any = false;
@@ -198,6 +195,29 @@ __device__ __forceinline__ void advance_all_late_done(typename Env::Real (&s)[En
         for (int q = 0; q < Env::DONE_TERMS; ++q) { any = any || term[q]; m |= __builtin_amdgcn_ballot_w64(term[q]); }
         dn[j] = any;
         dmask[j] = m;
+    }
+}
+
+// The wait for the action, and the rest of the step.  The compiler puts the wait in front of the first instruction that reads the action's
+// registers — the compare inside step_post() — and would let that compare drift forward to where the load was issued.  An empty asm (the
+// idiom of lanes.hpp reissued(): no instruction of its own) that reads what the front part produced last — a value of every sub-lane and the
+// flags' masks — hands out an opaque 1, and the action is compared with THAT: the compare stays behind the asm, which the compiler in turn
+// keeps behind every LDS access written before it.  The action's own registers are never an operand of the asm: as an in / out operand they
+// were copied first, and the copy was the read that drifted.
+template <class Env, int VEC>
+__device__ __forceinline__ void post_all(const typename Env::Pre (&pre)[VEC], const typename Env::Action (&act)[VEC], const uint64_t (&dmask)[VEC],
+                                         typename Env::Real (&s)[Env::S][VEC], float (&rw)[VEC]) {
+    constexpr int S = Env::S;
+    static_assert(std::is_same<typename Env::Action, int32_t>::value, "a discrete action");
+    int32_t one = 1;
+#pragma unroll
+    for (int jj = 0; jj < VEC; ++jj) asm volatile("" : "+s"(one) : "v"(pre[jj].divisor), "s"(dmask[jj]));
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        typename Env::Real sj[S];
+        Env::step_post(pre[j], act[j] == one, sj, rw[j]);
+#pragma unroll
+        for (int k = 0; k < S; ++k) s[k][j] = sj[k];
     }
 }
 
@@ -384,35 +404,39 @@ __device__ __forceinline__ void reset_pending_wave(uint32_t pending, typename En
 // Philox counters, same conversions as reset_pending_wave(), which stays the fallback for everything else.
 //   fmask     the wave's ballot of fin[j], per sub-lane
 //   wave_i0   first lane index of this wave (wave-uniform; valid when lane 0 of the wave is active)
+// It comes in two halves, because only the second touches the state: reset_finished_draw() — ranks, slot scatter, the Philox pass and the
+// drawn rows parked in the wave's table — needs nothing but the flags and may run before the step's own arithmetic is finished (step_body_wg
+// runs it in front of the wait for the action); reset_finished_take() hands the rows back to the finished sub-lanes, and reset_finished_rest() serves
+// the rare cases.
+template <int VEC>
+struct FinishedRanks {
+    uint32_t rank[VEC];             // a finished sub-lane's position among the wave's finished slots
+    uint32_t total;                 // how many the wave holds
+    bool single;                    // the common case (wave-uniform): the draw has been made and waits in the table
+};
+
 template <class Env, int VEC, bool LANE_SEEDS>
-__device__ __forceinline__ void reset_finished_wave(const bool (&fin)[VEC], const uint64_t (&fmask)[VEC], typename Env::Real (&s)[Env::S][VEC], const StepArgsT<typename Env::Real> &a,
-                                                    int64_t i0, int64_t wave_i0, int64_t n, uint64_t tick, ResetScratch<Env> *sc) {
+__device__ __forceinline__ void reset_finished_draw(const bool (&fin)[VEC], const uint64_t (&fmask)[VEC], const StepArgsT<typename Env::Real> &a,
+                                                    int64_t wave_i0, int64_t n, uint64_t tick, ResetScratch<Env> *sc, FinishedRanks<VEC> &fr) {
     constexpr int S = Env::S;
     using Real = typename Env::Real;
     static_assert(Env::OBS_ALIASES_STATE && !has_split_reset<Env>(), "one-call resets that hand back the state only");
     const uint32_t lane = lane_id();
-    uint32_t rank[VEC];
     uint32_t total = 0;
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
         const uint64_t m = fmask[j];
-        rank[j] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        fr.rank[j] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         total += (uint32_t)__popcll(m);
     }
+    fr.total = total;
     // wave-uniform; both are rare for the envs this serves (about one CartPole wave in twenty has nothing to reset): the round loop serves
     // what the single trip does not
-    if (__builtin_expect(total == 0 || total > 64u || __ballot(1) != ~0ull, 0)) {
-        if (total != 0) {
-            uint32_t pending = 0;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) pending |= fin[j] ? (1u << j) : 0u;
-            reset_pending_wave<Env, VEC, LANE_SEEDS>(pending, s, a, i0, n, tick, sc);
-        }
-        return;
-    }
+    fr.single = !__builtin_expect(total == 0 || total > 64u || __ballot(1) != ~0ull, 0);
+    if (!fr.single) return;
 #pragma unroll
     for (int j = 0; j < VEC; ++j)
-        if (fin[j]) sc->slot[rank[j]] = lane * VEC + (uint32_t)j;
+        if (fin[j]) sc->slot[fr.rank[j]] = lane * VEC + (uint32_t)j;
     wave_lds_fence();
     {
         // every lane draws (kResetFullExec's reason: reset_pending_wave); the lanes without a slot redo slot 0's draw into a row nobody reads
@@ -431,11 +455,19 @@ __device__ __forceinline__ void reset_finished_wave(const bool (&fin)[VEC], cons
         for (int k = 0; k < S; ++k) sc->draw[lane][k] = sj[k];
     }
     wave_lds_fence();
+}
+
+// the hand-back of the single trip (fr.single)
+template <class Env, int VEC>
+__device__ __forceinline__ void reset_finished_take(const bool (&fin)[VEC], const FinishedRanks<VEC> &fr, typename Env::Real (&s)[Env::S][VEC],
+                                                    ResetScratch<Env> *sc) {
+    constexpr int S = Env::S;
+    using Real = typename Env::Real;
     Real got[VEC][S];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
 #pragma unroll
-        for (int k = 0; k < S; ++k) got[j][k] = sc->draw[rank[j] & 63u][k];
+        for (int k = 0; k < S; ++k) got[j][k] = sc->draw[fr.rank[j] & 63u][k];
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
@@ -443,6 +475,17 @@ __device__ __forceinline__ void reset_finished_wave(const bool (&fin)[VEC], cons
         for (int k = 0; k < S; ++k) s[k][j] = fin[j] ? got[j][k] : s[k][j];
     }
     wave_lds_fence();
+}
+
+// what the single trip does not serve (!fr.single): nothing to reset, or the round loop
+template <class Env, int VEC, bool LANE_SEEDS>
+__device__ __forceinline__ void reset_finished_rest(const bool (&fin)[VEC], const FinishedRanks<VEC> &fr, typename Env::Real (&s)[Env::S][VEC],
+                                                    const StepArgsT<typename Env::Real> &a, int64_t i0, int64_t n, uint64_t tick, ResetScratch<Env> *sc) {
+    if (fr.total == 0) return;
+    uint32_t pending = 0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) pending |= fin[j] ? (1u << j) : 0u;
+    reset_pending_wave<Env, VEC, LANE_SEEDS>(pending, s, a, i0, n, tick, sc);
 }
 
 // wave64 compaction of the sub-lanes flagged in `finished`: rank of every flagged sub-lane inside the wave (ballot + mbcnt),
@@ -679,23 +722,32 @@ __device__ __forceinline__ void step_body(const StepArgsT<typename Env::Real> &a
 }
 
 // ---------------------------------------------------------------------------------------------
-// The body of a FULL workgroup of the lean auto-reset kernels of an env with a late done flag (advance_all_late_done: CartPole) — at 2^20
-// lanes the headline kernel runs nothing else.  Three things set it apart from step_body<GUARD = false> (same loads, arithmetic, draws
+// The body of a FULL workgroup of the lean auto-reset kernels of an env with a late done flag (pre_all_late_done: CartPole) — at 2^20
+// lanes the headline kernel runs nothing else.  Four things set it apart from step_body<GUARD = false> (same loads, arithmetic, draws
 // and stores, bit for bit):
 //   * rows are addressed from scalar bases + one 32-bit offset per thread (lanes.hpp WgLanes);
 //   * the done flags are decided behind the join of the trigonometry paths and reach the reset as the compares' wave masks;
-//   * with RESETF == 1 the reset of a full wave with at most 64 finished slots is a single trip (reset_finished_wave).
+//   * with RESETF == 1 the reset of a full wave with at most 64 finished slots is a single trip (reset_finished_draw / reset_finished_take);
+//   * the step is run in the env's two parts, and what the action has no part in — the front part, the flags, the reset's draw — in front of
+//     the wait for the action, the one stream of the launch that is not served from the Infinity Cache (docs/ledger.md §28).
 // Every other kernel variant and env keeps step_body: the bookkeeping variants, and the envs where this form measured no gain
 // (Pendulum) or a loss (MountainCar, ~1 %): docs/ledger.md §25.
 // ---------------------------------------------------------------------------------------------
 template <class Env, bool AUTORESET, bool EXTRAS>
 constexpr bool has_full_workgroup_body() {
-    return AUTORESET && !EXTRAS && Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && !has_split_reset<Env>() && has_done_of_inputs<Env>::value;
+    return AUTORESET && !EXTRAS && Env::HAS_SMALL_ANGLE_PATH && Env::OBS_ALIASES_STATE && !has_split_reset<Env>() && has_done_of_inputs<Env>::value &&
+           has_split_step<Env>::value;
 }
 
 // the part of a row a full workgroup owns, as a scalar pointer: row base + the workgroup's first lane
 template <class T>
 __device__ __forceinline__ T *wg_row(T *row, const WgLanes &wg) { return wave_uniform(row + wg.first); }
+
+#ifdef GYMNET_PROBE_RESET_BEHIND_ACTION      // probe builds only: the whole reset behind the wait for the action, for the A/B
+constexpr bool kResetDrawAhead = false;
+#else
+constexpr bool kResetDrawAhead = true;
+#endif
 
 template <class Env, int VEC, int NT, int RESETF>
 __device__ __forceinline__ void step_body_wg(const StepArgsT<typename Env::Real> &a, const WgLanes wg, const uint64_t tick, ResetScratch<Env> *sc) {
@@ -711,30 +763,54 @@ __device__ __forceinline__ void step_body_wg(const StepArgsT<typename Env::Real>
     for (int k = 0; k < S; ++k) load_row_wg<Real, VEC, NT_SL>(wg_row(static_cast<const Real *>(a.state) + k * a.state_stride, wg), wg.local, s[k]);
     load_row_wg<int32_t, VEC, NT_A>(wg_row(static_cast<const int32_t *>(a.action), wg), wg.local, act);
 
-    float reward[VEC];
+    // The action is the last of the five loads, and the only one no earlier launch has left in the Infinity Cache: what does not need it
+    // runs first.  No store goes out before the wait for it — with loads and stores both in flight the wait would cover the stores too.
+    typename Env::Pre pre[VEC];
     bool finished[VEC];
     uint64_t fmask[VEC];                 // the wave's ballot of finished[j]
-    advance_all_late_done<Env, VEC, true>(s, act, reward, finished, fmask);
+    pre_all_late_done<Env, VEC>(s, pre, finished, fmask);
 
-    // reward / done do not depend on the reset draw: get them on their way before the Philox rounds.  The done word comes straight from
-    // the compares' masks: one select of a constant per sub-lane.
-    {
+    float reward[VEC];
+    // reward / done go out with the state rows.  The done word comes straight from the compares' masks: one select of a constant per sub-lane.
+    auto store_reward_done = [&] {
         const uint32_t local = reissued(wg.local);
         store_row_wg<float, VEC, NT_O>(wg_row(a.reward, wg), local, reward);
         uint32_t w = 0;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) w |= finished[j] ? (1u << (8 * j)) : 0u;
         store_done_word_wg<VEC, NT_O>(wg_row(a.done, wg), local, w);
-    }
+    };
 
-    if constexpr (RESETF == 1) {
-        reset_finished_wave<Env, VEC, false>(finished, fmask, s, a, i0, wg.first + (int64_t)__builtin_amdgcn_readfirstlane(wg.local), a.n, tick, sc);
+    if constexpr (RESETF == 1 && kResetDrawAhead) {
+        // the reset's draw needs the flags only: it too runs in front of the wait, and only the hand-back of the drawn rows behind the rest of
+        // the step.  (The rest of the step is written once per route, so that the common route stays one straight run from the draw to the
+        // hand-back with the rare cases branching off it once.)
+        FinishedRanks<VEC> fr;
+        reset_finished_draw<Env, VEC, false>(finished, fmask, a, wg.first + (int64_t)__builtin_amdgcn_readfirstlane(wg.local), a.n, tick, sc, fr);
+        if (fr.single) {
+            post_all<Env, VEC>(pre, act, fmask, s, reward);
+            reset_finished_take<Env, VEC>(finished, fr, s, sc);
+        } else {
+            // (the lane index is rebuilt here, so that the 64-bit one of the kernel's entry does not stay in registers along the common route)
+            post_all<Env, VEC>(pre, act, fmask, s, reward);
+            reset_finished_rest<Env, VEC, false>(finished, fr, s, a, wg.first + (int64_t)reissued(wg.local), a.n, tick, sc);
+        }
+        store_reward_done();
     } else {
-        uint32_t pending = 0;
+        post_all<Env, VEC>(pre, act, fmask, s, reward);
+        store_reward_done();
+        if constexpr (RESETF == 1) {
+            FinishedRanks<VEC> fr;
+            reset_finished_draw<Env, VEC, false>(finished, fmask, a, wg.first + (int64_t)__builtin_amdgcn_readfirstlane(wg.local), a.n, tick, sc, fr);
+            if (fr.single) reset_finished_take<Env, VEC>(finished, fr, s, sc);
+            else reset_finished_rest<Env, VEC, false>(finished, fr, s, a, i0, a.n, tick, sc);
+        } else {
+            uint32_t pending = 0;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) pending |= finished[j] ? (1u << j) : 0u;
-        Real o_unused[Env::O][VEC];
-        reset_pending<Env, VEC, false>(pending, s, o_unused, a, i0, a.n, tick);
+            for (int j = 0; j < VEC; ++j) pending |= finished[j] ? (1u << j) : 0u;
+            Real o_unused[Env::O][VEC];
+            reset_pending<Env, VEC, false>(pending, s, o_unused, a, i0, a.n, tick);
+        }
     }
 
     const uint32_t local = reissued(wg.local);
