@@ -200,6 +200,9 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_view(IntPtr h, out IntPtr d_history, out long lane_stride, out int slot);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_set_exploration(IntPtr h, int explore, float temperature);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_get_exploration(IntPtr h, int* explore, float* temperature);
+        // the log-probability of the action taken (a Discrete actor): d_logp float [N], d_rec_logp float [T][N]; IntPtr.Zero forwards to the call without it
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_logp_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, float epsilon, ulong seed, ulong tick);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_logp_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp);
         // the Box actor (Pendulum, MountainCarContinuous): the last layer's one output, clamped to the env's bounds, is the action
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, float epsilon, ulong seed, ulong tick);

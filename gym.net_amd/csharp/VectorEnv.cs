@@ -311,6 +311,16 @@ namespace Gym.Envs.Amd {
             Native.Check(Native.gymnet_vecenv_actor_get_exploration(_h, &ex, &tp));
             explore = (GymnetActorExplore) ex; temperature = tp;
         }
+        /// ActorAct that also writes the log-probability of every lane's action under softmax(logits / temperature) into dLogp (float [N];
+        /// gymnet_vecenv_actor_act_logp_device): the actions and logits are ActorAct's, bit for bit.  IntPtr.Zero: ActorAct itself.
+        public void ActorActLogp(IntPtr dActions, IntPtr dLogp, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dLogits = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_act_logp_device(_h, dActions, dLogits, dLogp, epsilon, seed, tick));
+        /// RolloutFused with action_source = actor on a Discrete actor, also recording every step's log-probability into dRecLogp
+        /// (float [T][N]; gymnet_vecenv_rollout_fused_logp_device).  IntPtr.Zero: RolloutFused itself.
+        public void RolloutFusedLogp(GymnetRolloutSpec spec, IntPtr dRecLogp) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_fused_logp_device(_h, ref spec, dRecLogp));
+        }
         /// The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous with w_L = 1; its one output,
         /// clamped to the env's bounds, is the action.  No layers releases it.  LoadActorWeights / ResetActor / PushActor serve both kinds.
         public void ConfigureBoxActor(int history, int[] widths, float[] weights) {

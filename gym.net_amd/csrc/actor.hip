@@ -258,6 +258,7 @@ int actor_rollout_check(gymnet_vecenv *h) {
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
+    if (ac.rec_logp) return actor_logp_rollout_launch(h, records, a, r);    // gymnet_vecenv_rollout_fused_logp_device: either setting
     if (!ac.box && !ac.default_exploration()) return actor_softmax_rollout_launch(h, records, a, r);
     switch (h->cfg.env_id) {
         case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);

@@ -2,7 +2,8 @@
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), and the handle's Actor attachment
 // with the calls one unit makes into the other.  actor.hip serves the Discrete envs (argmax head) and owns the attachment; actor_box.hip
 // serves the Box envs (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete
-// envs under an exploration setting other than the default (a draw from the softmax of the logits).  Internal to the library.
+// envs under an exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when
+// the caller also asks for the log-probability of the action taken.  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -161,6 +162,9 @@ struct Actor {
     // actor.hip serve (UNIFORM at any temperature is that behaviour); SOFTMAX runs through actor_softmax.hip.  inv_tau = 1.0f / temperature
     int32_t discrete_explore = GYMNET_ACTOR_EXPLORE_UNIFORM; float temperature = 1.0f, inv_tau = 1.0f;
     bool default_exploration() const { return discrete_explore == GYMNET_ACTOR_EXPLORE_UNIFORM; }
+    // set only while gymnet_vecenv_rollout_fused_logp_device runs its rollout (actor_logp_rollout_arm / _disarm, actor_logp.hip): where the
+    // launch records every step's log-probability, [steps][n]; actor_rollout_launch sends a non-null pointer to actor_logp.hip
+    float *rec_logp = nullptr;
 };
 // what the kernels of actor_box_policy.hip take of it, as a kernel argument
 struct BoxPolicy { int32_t head, explore; float sigma; };
@@ -189,5 +193,7 @@ hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const
 hipError_t actor_softmax_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, const ActorExplore &ex,
                                     hipStream_t st);
 hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+// actor_logp.hip: the fused rollout of a Discrete handle that also records the log-probability of every action taken (Actor::rec_logp)
+hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 
 }  // namespace gymnet

@@ -1315,6 +1315,17 @@ int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout
     });
 }
 
+int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp) {
+    if (!d_rec_logp) return gymnet_vecenv_rollout_fused_ex_device(h, spec);
+    return guarded([&]() -> int {
+    ENTER(h);
+    // (a null or mis-sized spec is the rollout's own refusal: nothing is armed)
+    if (spec && spec->struct_size == sizeof(gymnet_rollout_spec)) ST_TRY(actor_logp_rollout_arm(h, spec->action_source, d_rec_logp));
+    struct Disarm { gymnet_vecenv *h; ~Disarm() { actor_logp_rollout_disarm(h); } } disarm{h};
+    return rollout_fused_entered(h, spec, 0, false);
+    });
+}
+
 int gymnet_vecenv_rollout_repeat_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t repeat) {
     return guarded([&]() -> int {
     ENTER(h);

@@ -281,6 +281,10 @@ int resident_stop(gymnet_vecenv *h);                                 // tells a 
 int actor_rollout_check(gymnet_vecenv *h);
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
+// gymnet_vecenv_rollout_fused_logp_device (actor_logp.hip): the checks that belong to the record pointer, after which the handle's actor
+// carries it into actor_rollout_launch; disarm clears it, and is called on every exit path
+int actor_logp_rollout_arm(gymnet_vecenv *h, int32_t action_source, float *d_rec_logp);
+void actor_logp_rollout_disarm(gymnet_vecenv *h);
 // the fused rollout with frame skip (action_repeat.hip): r.steps decisions of R sub-steps each under one action, one launch
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs &a, const RolloutArgs &r, int32_t R);
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const RolloutArgs64 &r, int32_t R);

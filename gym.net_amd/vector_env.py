@@ -55,6 +55,24 @@ def _count(value, name, low, high=None):
     return int(value)
 
 
+def _logp_buffer(x, shape, name, device=None):
+    """a device float32 tensor of exactly `shape` for log-probabilities, refused here before any native call"""
+    if not hasattr(x, "data_ptr") or not hasattr(x, "dtype") or not hasattr(x, "shape"):
+        raise ValueError(f"{name} must be a device float32 tensor of shape {tuple(shape)}, got {type(x).__name__}")
+    if str(x.dtype) != "torch.float32":
+        raise ValueError(f"{name} must be float32, got {x.dtype}")
+    if tuple(int(v) for v in x.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(x.shape)}")
+    if not getattr(x, "is_cuda", False):
+        raise ValueError(f"{name} must be on the handle's device, got a host tensor")
+    index = getattr(getattr(x, "device", None), "index", None)
+    if device is not None and index is not None and int(index) != int(device):
+        raise ValueError(f"{name} is on device {index}, the handle on {device}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return x
+
+
 class BatchStep:
     """What `Step[]` (IVecEnv.cs:15) becomes at 2^20 lanes: three arrays.  Indexing / iterating yields the
     reference's per-env Step records (Step.cs:7-20), materialised lazily."""
@@ -323,7 +341,7 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_rollout_device(self._h, _ptr(d_actions), int(steps), int(action_stride), int(ring)))
 
     def RolloutFusedDevice(self, d_actions, steps, action_stride=0, ring=1, rec_obs=None, rec_reward=None, rec_done=None, actions="ring",
-                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0):
+                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None):
         """`steps` vector steps in ONE kernel launch (state stays in registers); optional device-side rollout
         buffers rec_obs [T][D][N] (of the handle's dtype: float64 for a float64 handle), rec_reward [T][N], rec_done [T][N]
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
@@ -339,8 +357,21 @@ class VectorEnv:
                     below `capacity` (GYMNET_RECORDS_NO_OVERFLOW; count[1] > count[0] says so);
                     needs a bookkeeping handle (BasePlaySession.cs:58-69).
           repeat    frame skip (gymnet_vecenv_rollout_repeat_device): `steps` counts DECISIONS, each action is held for repeat + 1 env
-                    steps, the rec_* buffers and the records' step index are per decision ("actor" needs repeat = 0)."""
+                    steps, the rec_* buffers and the records' step index are per decision ("actor" needs repeat = 0).
+          rec_logp  device float32 [T, N] for the log-probability of every action taken, as Actor.Act(logp=) writes it at that step
+                    (gymnet_vecenv_rollout_fused_logp_device): needs actions="actor" on a Discrete actor."""
         repeat = _repeat(repeat)
+        if rec_logp is not None:
+            actor = getattr(self, "_actor", None)
+            if actions != "actor":
+                raise ValueError(f"rec_logp records the actor's log-probabilities: it needs actions=\"actor\", got {actions!r}")
+            if actor is None:
+                raise ValueError("rec_logp needs an actor (VectorEnv.Actor)")
+            if actor.IsBox:
+                raise ValueError("rec_logp belongs to a Discrete actor; this handle's actor chooses Box actions")
+            if repeat:
+                raise ValueError("rec_logp: the fused actor rollout has no frame skip (repeat must be 0)")
+            _logp_buffer(rec_logp, (_count(steps, "steps", 0), self.NumberOfEnvironments), "rec_logp", self.Device)
         src = {"ring": capi.ACTIONS_RING, "sample": capi.ACTIONS_SAMPLE, "epsilon_greedy": capi.ACTIONS_EPSILON_GREEDY,
                "actor": capi.ACTIONS_ACTOR}[actions]
         ep = episodes or {}
@@ -355,6 +386,8 @@ class VectorEnv:
                                 d_ep_length=_ptr(ep.get("length")), ep_capacity=int(ep.get("capacity", 0)), d_ep_count=_ptr(ep.get("count")))
         if repeat:
             capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
+        elif rec_logp is not None:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_logp_device(self._h, C.byref(spec), _ptr(rec_logp)))
         else:
             capi.check(self._lib.gymnet_vecenv_rollout_fused_ex_device(self._h, C.byref(spec)))
 
@@ -955,16 +988,26 @@ class Actor:
             raise ValueError("this actor was replaced or closed")
         return self._h
 
-    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None):
+    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None):
         """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
         compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
         float32 [N] — the network's one output clamped to the action bounds, or ActionSpace.Sample() as SampleActionsDevice(seed=seed,
         tick=tick) draws it where the lane explores — and logits takes the [N, 1] unclamped outputs.  That is the default policy;
         SetPolicy changes the head and what an exploring lane takes.  On a Discrete actor SetExploration("softmax", temperature) makes an
-        exploring lane draw from softmax(logits / temperature) instead."""
+        exploring lane draw from softmax(logits / temperature) instead.  logp (a Discrete actor): an optional device float32 [N] for the
+        log-probability of the action each lane takes under softmax(logits / temperature), the stored temperature whatever the exploration
+        setting (gymnet_vecenv_actor_act_logp_device); actions and logits are the same bits with and without it."""
+        if logp is not None:
+            if self.IsBox:
+                raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
+            _logp_buffer(logp, (self._env.NumberOfEnvironments,), "logp", self._env.Device)
         if out is None:
             out = self._actions()
+        if logp is not None:
+            capi.check(self._lib.gymnet_vecenv_actor_act_logp_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), float(epsilon),
+                                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+            return out
         act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
         capi.check(act(self._handle(), _ptr(out), _ptr(logits), float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
         return out
@@ -1072,13 +1115,15 @@ class Actor:
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
 
-    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0):
-        """Act(epsilon, seed, tick), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —, Push(): one
-        closed-loop decision; returns the device actions taken."""
+    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None):
+        """Act(epsilon, seed, tick, logp=logp), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
+        Push(): one closed-loop decision; returns the device actions taken."""
         repeat = _repeat(repeat)
+        if logp is not None and self.IsBox:
+            raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
         if self._out is None:
             self._out = self._actions()
-        self.Act(epsilon, seed, tick, out=self._out)
+        self.Act(epsilon, seed, tick, out=self._out, logp=logp)
         if repeat:
             self._env.StepRepeatDevice(self._out, repeat)
         else:

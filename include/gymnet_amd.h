@@ -674,11 +674,50 @@ int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_
  *   no actor, a Box actor, an unknown enum value, a temperature that is not finite, is <= 0, or is so small that 1.0f / temperature is
  *   not finite.
  * get_exploration: any out pointer may be NULL; the same refusals for a handle without a Discrete actor (outputs untouched).
- * Out of scope: recording logits or log-probabilities inside the fused rollout (re-evaluate the recorded inputs; for one step act_device's
- *   d_logits are the exact logits), a softmax for gymnet_vecenv_compose_actions_device, and the Box actor, whose policy is below. */
+ * The log-probability of the action taken is recorded by gymnet_vecenv_actor_act_logp_device and
+ *   gymnet_vecenv_rollout_fused_logp_device (below).  Out of scope: recording logits inside the fused rollout (re-evaluate the recorded
+ *   inputs; for one step act_device's d_logits are the exact logits), a softmax for gymnet_vecenv_compose_actions_device, and the Box
+ *   actor, whose policy is below. */
 typedef enum gymnet_actor_explore { GYMNET_ACTOR_EXPLORE_UNIFORM = 0, GYMNET_ACTOR_EXPLORE_SOFTMAX = 1 } gymnet_actor_explore;
 int gymnet_vecenv_actor_set_exploration(gymnet_vecenv *h, int32_t explore, float temperature);
 int gymnet_vecenv_actor_get_exploration(gymnet_vecenv *h, int32_t *explore, float *temperature);
+/* A Discrete actor's log-probability of the action taken (additive in ABI 6), for one act call and inside the fused rollout.
+ * The quantity is specified in float32, every operation rounded on its own, like the softmax draw.  For a lane with logits l_0 .. l_{A-1}
+ * (A = action_n <= 8), the actor's stored inv_tau = 1.0f / temperature, and the action j the lane takes, however it was chosen (greedy,
+ * uniform exploration or softmax exploration):
+ *   1. m = the greedy logit, the value the argmax settles on (step 1 of the draw).
+ *   2. a_k = (l_k - m) * inv_tau, e_k = exp_neg(a_k), S = (((e_0 + e_1) + ...) + e_{A-1}) in index order: steps 3-4 of the draw, the same
+ *      values (a wave that also runs the softmax draw computes them once).
+ *   3. If !(S >= 1.0f), logp is the canonical quiet NaN 0x7FC00000, written as those bits: an infinite or NaN greedy logit, where every
+ *      weight is +0.  With a finite m the greedy term is exactly 1.0f, so S lies in [1, 8].
+ *   4. Otherwise L = log_pos(S) (csrc/log_pos.hpp; not the device library's logf, whose bits a CPU cannot reproduce): i = bits(S) +
+ *      (0x3f800000 - 0x3f3504f3) as integers; k = float((i >> 23) - 127); f = float_of_bits((i & 0x007fffff) + 0x3f3504f3) - 1.0f;
+ *      z = f * f; p = the Horner chain of fmaf (((((((p0 f + p1) f + p2) f + p3) f + p4) f + p5) f + p6) f + p7) f + p8 with the Cephes
+ *      logf coefficients p0 = 7.0376836292e-2f .. p8 = 3.3333331174e-1f; r = fmaf(-0.5f, z, (f * z) * p); hi = k * 0.693359375f;
+ *      s = hi + f; c = f - (s - hi); L = s + (fmaf(k, -2.12194440e-4f, r) + c).  Over every float32 in [1, 8]: log_pos(1.0f) = +0.0f, no
+ *      result below +0, non-decreasing, within 1.20e-7 of the float64 log.
+ *   5. logp = a_j - L, one subtraction, a_j selected by compares over the A values (never an indexed load).  A NaN result is stored as
+ *      0x7FC00000 (possible only when uniform exploration takes an action whose own logit is NaN); -inf is stored as it comes.
+ * The stored temperature is used whatever explore is (set_exploration stores it whatever explore is).  Under the default (UNIFORM, 1.0)
+ *   logp is log softmax(logits)[j]; under (SOFTMAX, t) at epsilon = 1 it is exactly the behaviour policy's log-probability; for
+ *   0 < epsilon < 1 it is the policy's log-probability of the action, NOT the epsilon-mixture's.  Against the float64 log-softmax of the
+ *   same float32 logits at the true temperature the error is within 2^-20 * max(1, |logp|) (tests/test_actor_logp_host.py).
+ * act_logp_device: with d_logp == NULL it IS gymnet_vecenv_actor_act_device (the call forwards; the same kernels run).  Otherwise
+ *   d_actions and d_logits are bit for bit what act_device writes under the handle's setting, and d_logp [num_envs] is the quantity above
+ *   (4-byte aligned).  The same staleness rules and refusals as act_device, nothing written on a refusal; a Box actor gives
+ *   GYMNET_ERR_INVALID_ARG.  Served on float64 CartPole handles, as act_device is.  A request for logp runs kernels of their own
+ *   (csrc/actor_logp.hip) under either setting.
+ * rollout_fused_logp_device: with d_rec_logp == NULL it IS gymnet_vecenv_rollout_fused_ex_device(h, spec).  Otherwise
+ *   spec->action_source must be GYMNET_ACTIONS_ACTOR and the handle's actor Discrete (else GYMNET_ERR_INVALID_ARG, nothing launched),
+ *   every check of rollout_fused_ex_device applies, everything that call leaves for the spec is left bit for bit (state, observations,
+ *   done bytes, tick, history, bookkeeping, every d_rec_* array, episode records and counters), and in addition
+ *   d_rec_logp[t * num_envs + lane] is what act_logp_device(epsilon, action_seed, action_tick0 + t) writes at step t: the call is
+ *   bit-identical to steps x (act_logp_device, step_device, actor_push_device).  d_rec_logp needs 4-byte alignment only; steps == 0
+ *   writes nothing.
+ * Out of scope: the Box actor's log-density, recording logits or an entropy, carrying logp through the episode memory. */
+int gymnet_vecenv_actor_act_logp_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float *d_logp, float epsilon, uint64_t seed,
+                                        uint64_t tick);
+int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp);
 /* The Box actor (additive in ABI 6): the same actor on a Box action space — Pendulum-v1 (obs_dim 3, bounds -2 .. 2) and
  * MountainCarContinuous-v0 (obs_dim 2, bounds -1 .. 1), float32 handles (neither env has a float64 mode).
  * Network: as above — L in [1, 4] layers, every width in [1, 64], at most 8192 parameters, torch's nn.Linear layout, ReLU between the

@@ -397,6 +397,17 @@ public:
         check(gymnet_vecenv_actor_get_exploration(h_, &ex, &temperature));
         explore = (gymnet_actor_explore)ex;
     }
+    // The log-probability of the action every lane takes, under softmax(logits / the stored temperature) whatever the exploration setting
+    // (gymnet_vecenv_actor_act_logp_device): d_logp float32 [N]; actions and logits are ActorAct's, bit for bit.  d_logp null: ActorAct.
+    void ActorActLogp(int32_t *d_actions, float *d_logp, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_logits = nullptr) {
+        check(gymnet_vecenv_actor_act_logp_device(h_, d_actions, d_logits, d_logp, epsilon, seed, tick));
+    }
+    // The fused rollout with action_source = GYMNET_ACTIONS_ACTOR on a Discrete actor, also recording every step's log-probability into
+    // d_rec_logp float32 [T][N] (gymnet_vecenv_rollout_fused_logp_device); null: gymnet_vecenv_rollout_fused_ex_device itself.
+    void RolloutFusedLogp(gymnet_rollout_spec spec, float *d_rec_logp) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_fused_logp_device(h_, &spec, d_rec_logp));
+    }
     // The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous; its one output, clamped to the
     // env's bounds, is the action.  Empty widths release the actor.  LoadActorWeights / ResetActor / PushActor serve both kinds.
     void ConfigureBoxActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
