@@ -22,11 +22,12 @@
 //
 // What the Box actor (actor_box.hip: Pendulum, MountainCarContinuous) shares with this unit — the network and history structs, the forward
 // pass, load_input, the ring arithmetic, the push — is in actor_net.hpp; the Discrete head (argmax_logits, compose_one) stays here.
-// That head is the default exploration setting; under GYMNET_ACTOR_EXPLORE_SOFTMAX (gymnet_vecenv_actor_set_exploration) the two host entry
-// points that launch it hand over to actor_softmax.hip, and this unit's kernels stay what they were.
+// That head is the default exploration setting; the other settings and policies have kernels of their own in the sibling units, and this
+// unit's kernels stay what they were.
 //
-// The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, and the three calls the fused rollout
-// (capi.hip) makes when the actor chooses its actions.
+// The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, the prologue of every act entry point
+// (actor_act_enter), and the calls the fused rollout (capi.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
+// is the router: it alone says which of the five units runs a handle's rollout (actor_act_launch: the same for act).
 #include "actor_net.hpp"
 
 namespace gymnet {
@@ -168,18 +169,9 @@ __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_rollout_ke
 }
 
 template <class Env>
-static hipError_t launch_actor_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                    const ActorHist &hs, hipStream_t st) {
-    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist) = nullptr;
-    if (autoreset) {
-        if (!extras) k = actor_rollout_kernel<Env, true, false, false>;
-        else k = records ? actor_rollout_kernel<Env, true, true, true> : actor_rollout_kernel<Env, true, true, false>;
-    } else {
-        if (!extras) k = actor_rollout_kernel<Env, false, false, false>;
-        else k = records ? actor_rollout_kernel<Env, false, true, true> : actor_rollout_kernel<Env, false, true, false>;
-    }
-    const int64_t blocks = (a.n + 255) / 256;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, st, a, r, net, hs);
+static hipError_t launch_actor_rollout_env(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
+    const auto k = pick_rollout_form(h->autoreset, h->extras, records, [](auto ar, auto ex, auto rec) { return actor_rollout_kernel<Env, ar, ex, rec>; });
+    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, h->stream, a, r, h->actor->net, h->actor->hist);
     return hipGetLastError();
 }
 
@@ -254,19 +246,37 @@ int actor_rollout_check(gymnet_vecenv *h) {
     return GYMNET_OK;
 }
 
-// float32 CartPole / MountainCar / Acrobot here, Pendulum / MountainCarContinuous in actor_box.hip
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
-    const Actor &ac = *h->actor;
-    if (a.n <= 0) return hipSuccess;
-    if (ac.rec_logp) return actor_logp_rollout_launch(h, records, a, r);    // gymnet_vecenv_rollout_fused_logp_device: either setting
-    if (!ac.box && !ac.default_exploration()) return actor_softmax_rollout_launch(h, records, a, r);
+// gymnet_vecenv_rollout_fused_logp_device's checks of its record pointer, which run before the rollout's own
+int actor_logp_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp) {
+    if (action_source != GYMNET_ACTIONS_ACTOR)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: log-probabilities are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
+    ST_TRY(need_actor(h));
+    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: this handle's actor chooses Box actions; a log-probability belongs to a Discrete actor");
+    if (!aligned_to(d_rec_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
+    return GYMNET_OK;
+}
+
+// this unit's fused rollout: a Discrete actor under the default exploration setting
+static hipError_t actor_discrete_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
     switch (h->cfg.env_id) {
-        case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
-        case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
-        case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
-        case GYMNET_ENV_PENDULUM: case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS: return actor_box_rollout_launch(h, records, a, r);
+        case GYMNET_ENV_CARTPOLE: return launch_actor_rollout_env<CartPole>(h, records, a, r);
+        case GYMNET_ENV_MOUNTAINCAR: return launch_actor_rollout_env<MountainCar>(h, records, a, r);
+        case GYMNET_ENV_ACROBOT: return launch_actor_rollout_env<Acrobot>(h, records, a, r);
         default: return hipErrorInvalidValue;
     }
+}
+
+// The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: its policy decides.  Discrete: a
+// record pointer (gymnet_vecenv_rollout_fused_logp_device) goes to actor_logp.hip under either setting, else the setting decides
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp) {
+    const Actor &ac = *h->actor;
+    if (a.n <= 0) return hipSuccess;
+    if (ac.box) {
+        if (rec_logp) return hipErrorInvalidValue;                           // (actor_logp_rollout_check has refused it)
+        return ac.default_policy() ? actor_box_rollout_launch(h, records, a, r) : actor_box_policy_rollout_launch(h, records, a, r);
+    }
+    if (rec_logp) return actor_logp_rollout_launch(h, records, a, r, rec_logp);
+    return ac.default_exploration() ? actor_discrete_rollout_launch(h, records, a, r) : actor_softmax_rollout_launch(h, records, a, r);
 }
 
 // the kernel pushed every step: the history is current, its newest slot moved `steps` on
@@ -274,6 +284,26 @@ void actor_rollout_done(gymnet_vecenv *h, int64_t steps) {
     ActorHist &hs = h->actor->hist;
     hs.slot = (int32_t)(((int64_t)hs.slot + steps) % hs.history);
     h->actor->last = mark(h);
+}
+
+// the router's counterpart for act on a Discrete handle: the setting decides
+static hipError_t actor_act_launch(gymnet_vecenv *h, int32_t *actions, float *logits, const ActorAct &aa) {
+    const Actor &ac = *h->actor;
+    if (!ac.default_exploration()) return actor_softmax_act_launch(ac.net, ac.hist, actions, logits, aa, actor_explore(ac), h->stream);
+    return launch_actor_act(ac.net, ac.hist, actions, logits, aa, h->stream);
+}
+
+int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, const void *d_actions, const float *d_logp, float epsilon, uint64_t seed,
+                    uint64_t tick, ActorAct &aa) {
+    ST_TRY(need_actor(h));
+    if (h->actor->box != want_box) return fail(h, GYMNET_ERR_INVALID_ARG, "%s", wrong_kind);
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (!aligned_to(d_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_logp must be 4-byte aligned");
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
+    if (!actor_current(h))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
+    aa = ActorAct{epsilon, seed, (uint64_t)h->cfg.lane_offset, tick};
+    return GYMNET_OK;
 }
 
 // gymnet_vecenv_actor_config (box = false) and gymnet_vecenv_actor_box_config (box = true) behind ENTER: the same network, history and
@@ -380,20 +410,9 @@ int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
 int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick) {
     return guarded([&]() -> int {
     ENTER(h);
-    ST_TRY(need_actor(h));
-    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "this handle's actor chooses Box actions: gymnet_vecenv_actor_box_act_device");
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-    if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
-    ActorAct aa{};
-    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
-    const Actor &ac = *h->actor;
-    if (!ac.default_exploration()) {
-        HIP_TRY(h, actor_softmax_act_launch(ac.net, ac.hist, d_actions, d_logits, aa, ActorExplore{ac.discrete_explore, ac.inv_tau}, h->stream));
-        return GYMNET_OK;
-    }
-    HIP_TRY(h, launch_actor_act(ac.net, ac.hist, d_actions, d_logits, aa, h->stream));
+    ActorAct aa;
+    ST_TRY(actor_act_enter(h, false, "this handle's actor chooses Box actions: gymnet_vecenv_actor_box_act_device", d_actions, nullptr, epsilon, seed, tick, aa));
+    HIP_TRY(h, actor_act_launch(h, d_actions, d_logits, aa));
     return GYMNET_OK;
     });
 }

@@ -4,8 +4,8 @@
 // 46-52) carried over to a Box space: where word B of the aux stream is at or below coin_threshold(epsilon) the action is
 // ActionSpace.Sample() = low + (high - low) * u01_24(word A of the action stream), the value gymnet_vecenv_sample_actions_device writes
 // for the same (seed, global lane, tick).  The contract is gymnet_vecenv_actor_box_config in include/gymnet_amd.h.  That is the default
-// policy; under any other (gymnet_vecenv_actor_box_set_policy: tanh head, Gaussian noise) the two host entry points below hand over to
-// actor_box_policy.hip, and this unit's kernels stay what they were.
+// policy; any other (gymnet_vecenv_actor_box_set_policy: tanh head, Gaussian noise) runs the kernels of actor_box_policy.hip — the fused
+// rollout by actor.hip's router, act by actor_box_act_launch below — and this unit's kernels stay what they were.
 //
 // Fused rollout (actor_box_rollout_kernel): step_kernels.hpp's rollout_body, one lane per thread, with a hook whose choose() is the act
 // kernel's body and whose after() is the shared push: bit-identical to steps x (box_act, step, push).  Pendulum's observation has three
@@ -116,28 +116,16 @@ __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_box_rollou
 }
 
 template <class Env>
-static hipError_t launch_actor_box_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                               const ActorHist &hs, hipStream_t st) {
-    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist) = nullptr;
-    if (autoreset) {
-        if (!extras) k = actor_box_rollout_kernel<Env, true, false, false>;
-        else k = records ? actor_box_rollout_kernel<Env, true, true, true> : actor_box_rollout_kernel<Env, true, true, false>;
-    } else {
-        if (!extras) k = actor_box_rollout_kernel<Env, false, false, false>;
-        else k = records ? actor_box_rollout_kernel<Env, false, true, true> : actor_box_rollout_kernel<Env, false, true, false>;
-    }
-    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, st, a, r, net, hs);
+static hipError_t launch_actor_box_rollout_env(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
+    const auto k = pick_rollout_form(h->autoreset, h->extras, records, [](auto ar, auto ex, auto rec) { return actor_box_rollout_kernel<Env, ar, ex, rec>; });
+    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, h->stream, a, r, h->actor->net, h->actor->hist);
     return hipGetLastError();
 }
 
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
-    const Actor &ac = *h->actor;
-    if (a.n <= 0) return hipSuccess;
-    if (!ac.default_policy()) return actor_box_policy_rollout_launch(h, records, a, r);
     switch (h->cfg.env_id) {
-        case GYMNET_ENV_PENDULUM: return launch_actor_box_rollout_env<Pendulum>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
-        case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS:
-            return launch_actor_box_rollout_env<MountainCarContinuous>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, h->stream);
+        case GYMNET_ENV_PENDULUM: return launch_actor_box_rollout_env<Pendulum>(h, records, a, r);
+        case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS: return launch_actor_box_rollout_env<MountainCarContinuous>(h, records, a, r);
         default: return hipErrorInvalidValue;
     }
 }
@@ -160,6 +148,14 @@ hipError_t launch_actor_box_act(const ActorNet &net, const ActorHist &hs, float 
     return hipGetLastError();
 }
 
+// which unit's act kernel serves the handle: the policy decides
+hipError_t actor_box_act_launch(gymnet_vecenv *h, float *actions, float *raw, const ActorAct &aa) {
+    const Actor &ac = *h->actor;
+    const float low = h->desc->action_low, high = h->desc->action_high;
+    if (!ac.default_policy()) return actor_box_policy_act_launch(ac.net, ac.hist, actions, raw, low, high, aa, box_policy(ac), h->stream);
+    return launch_actor_box_act(ac.net, ac.hist, actions, raw, low, high, aa, h->stream);
+}
+
 }  // namespace
 
 }  // namespace gymnet
@@ -179,21 +175,9 @@ int gymnet_vecenv_actor_box_config(gymnet_vecenv *h, int32_t history, int32_t nu
 int gymnet_vecenv_actor_box_act_device(gymnet_vecenv *h, float *d_actions, float *d_raw, float epsilon, uint64_t seed, uint64_t tick) {
     return guarded([&]() -> int {
     ENTER(h);
-    ST_TRY(need_actor(h));
-    if (!h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "this handle's actor chooses Discrete actions: gymnet_vecenv_actor_act_device");
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-    if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
-    ActorAct aa{};
-    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
-    const Actor &ac = *h->actor;
-    if (!ac.default_policy()) {
-        HIP_TRY(h, actor_box_policy_act_launch(ac.net, ac.hist, d_actions, d_raw, h->desc->action_low, h->desc->action_high, aa,
-                                               BoxPolicy{ac.head, ac.explore, ac.sigma}, h->stream));
-        return GYMNET_OK;
-    }
-    HIP_TRY(h, launch_actor_box_act(ac.net, ac.hist, d_actions, d_raw, h->desc->action_low, h->desc->action_high, aa, h->stream));
+    ActorAct aa;
+    ST_TRY(actor_act_enter(h, true, "this handle's actor chooses Discrete actions: gymnet_vecenv_actor_act_device", d_actions, nullptr, epsilon, seed, tick, aa));
+    HIP_TRY(h, actor_box_act_launch(h, d_actions, d_raw, aa));
     return GYMNET_OK;
     });
 }

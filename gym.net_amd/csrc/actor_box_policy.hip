@@ -141,28 +141,16 @@ __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_box_policy
 }
 
 template <class Env>
-static hipError_t launch_policy_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                            const ActorHist &hs, const BoxPolicy &pol, hipStream_t st) {
-    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist, BoxPolicy) = nullptr;
-    if (autoreset) {
-        if (!extras) k = actor_box_policy_rollout_kernel<Env, true, false, false>;
-        else k = records ? actor_box_policy_rollout_kernel<Env, true, true, true> : actor_box_policy_rollout_kernel<Env, true, true, false>;
-    } else {
-        if (!extras) k = actor_box_policy_rollout_kernel<Env, false, false, false>;
-        else k = records ? actor_box_policy_rollout_kernel<Env, false, true, true> : actor_box_policy_rollout_kernel<Env, false, true, false>;
-    }
-    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, st, a, r, net, hs, pol);
+static hipError_t launch_policy_rollout_env(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
+    const auto k = pick_rollout_form(h->autoreset, h->extras, records, [](auto ar, auto ex, auto rec) { return actor_box_policy_rollout_kernel<Env, ar, ex, rec>; });
+    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, h->stream, a, r, h->actor->net, h->actor->hist, box_policy(*h->actor));
     return hipGetLastError();
 }
 
 hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
-    const Actor &ac = *h->actor;
-    if (a.n <= 0) return hipSuccess;
-    const BoxPolicy pol{ac.head, ac.explore, ac.sigma};
     switch (h->cfg.env_id) {
-        case GYMNET_ENV_PENDULUM: return launch_policy_rollout_env<Pendulum>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, pol, h->stream);
-        case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS:
-            return launch_policy_rollout_env<MountainCarContinuous>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, pol, h->stream);
+        case GYMNET_ENV_PENDULUM: return launch_policy_rollout_env<Pendulum>(h, records, a, r);
+        case GYMNET_ENV_MOUNTAINCAR_CONTINUOUS: return launch_policy_rollout_env<MountainCarContinuous>(h, records, a, r);
         default: return hipErrorInvalidValue;
     }
 }

@@ -11,8 +11,8 @@
 // actor_softmax.hip: one kernel serves both settings, and a request for logp always runs this unit, also under the default setting.
 //
 // The action is composed exactly as explore_compose_one (actor_softmax.hip) composes it — the same coin, the same words, the same c_k
-// and threshold — so actions and logits are what act_device writes under the handle's setting.  argmax, the draw and the composition are
-// this unit's own copies: the kernels of actor.hip and actor_softmax.hip stay instruction for instruction what they were.
+// and threshold — so actions and logits are what act_device writes under the handle's setting.  The draw and the composition are this
+// unit's own copies (argmax_value is actor_net.hpp's): the kernels of actor.hip and actor_softmax.hip stay instruction for instruction what they were.
 //
 // Fused rollout (actor_logp_rollout_kernel): actor_softmax_rollout_kernel with the record pointer as a sixth argument — rollout_body, one
 // lane per thread, behind a hook whose choose() is the act kernel's body (it stores logp itself, at rec_logp + t * n + i) and whose
@@ -24,17 +24,6 @@
 namespace gymnet {
 
 namespace {
-
-// actor.hip's argmax_logits, which also hands out the value it settles on
-__device__ __forceinline__ int32_t argmax_value(const float (&x)[kW], int32_t action_n, float &bv) {
-    int32_t best = 0;
-    bv = x[0];
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-        if (j < action_n && x[j] > bv) { bv = x[j]; best = j; }
-    }
-    return best;
-}
 
 // explore_compose_one (actor_softmax.hip) for one lane, which also hands out logp of the action it returns.  The scaled differences a_k
 // and the running sums c_k are computed before the coin: the draw reads them where the wave draws, logp reads them always
@@ -172,30 +161,18 @@ __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_logp_rollo
 }
 
 template <class Env>
-static hipError_t launch_logp_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                          const ActorHist &hs, const ActorExplore &ex, float *rec_logp, hipStream_t st) {
-    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist, ActorExplore, float *) = nullptr;
-    if (autoreset) {
-        if (!extras) k = actor_logp_rollout_kernel<Env, true, false, false>;
-        else k = records ? actor_logp_rollout_kernel<Env, true, true, true> : actor_logp_rollout_kernel<Env, true, true, false>;
-    } else {
-        if (!extras) k = actor_logp_rollout_kernel<Env, false, false, false>;
-        else k = records ? actor_logp_rollout_kernel<Env, false, true, true> : actor_logp_rollout_kernel<Env, false, true, false>;
-    }
-    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, st, a, r, net, hs, ex, rec_logp);
+static hipError_t launch_logp_rollout_env(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp) {
+    const auto k = pick_rollout_form(h->autoreset, h->extras, records, [](auto ar, auto ex, auto rec) { return actor_logp_rollout_kernel<Env, ar, ex, rec>; });
+    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, h->stream, a, r, h->actor->net, h->actor->hist, actor_explore(*h->actor), rec_logp);
     return hipGetLastError();
 }
 
-// actor_rollout_launch (actor.hip) sends a rollout whose actor carries a record pointer here: a Discrete actor, either setting
-hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
-    const Actor &ac = *h->actor;
-    if (a.n <= 0) return hipSuccess;
-    if (ac.box || !ac.rec_logp) return hipErrorInvalidValue;
-    const ActorExplore ex{ac.discrete_explore, ac.inv_tau};
+// actor.hip's router sends a Discrete actor's rollout with a record pointer here, under either setting
+hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp) {
     switch (h->cfg.env_id) {
-        case GYMNET_ENV_CARTPOLE: return launch_logp_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, ac.rec_logp, h->stream);
-        case GYMNET_ENV_MOUNTAINCAR: return launch_logp_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, ac.rec_logp, h->stream);
-        case GYMNET_ENV_ACROBOT: return launch_logp_rollout_env<Acrobot>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, ac.rec_logp, h->stream);
+        case GYMNET_ENV_CARTPOLE: return launch_logp_rollout_env<CartPole>(h, records, a, r, rec_logp);
+        case GYMNET_ENV_MOUNTAINCAR: return launch_logp_rollout_env<MountainCar>(h, records, a, r, rec_logp);
+        case GYMNET_ENV_ACROBOT: return launch_logp_rollout_env<Acrobot>(h, records, a, r, rec_logp);
         default: return hipErrorInvalidValue;
     }
 }
@@ -216,22 +193,6 @@ hipError_t launch_logp_act(const ActorNet &net, const ActorHist &hs, int32_t *ac
 
 }  // namespace
 
-// gymnet_vecenv_rollout_fused_logp_device (capi.hip) with a record pointer, before the rollout's own checks: the source and the actor's
-// kind; then the pointer rides on the Actor until the caller clears it (actor_logp_rollout_disarm), on every exit path
-int actor_logp_rollout_arm(gymnet_vecenv *h, int32_t action_source, float *d_rec_logp) {
-    if (action_source != GYMNET_ACTIONS_ACTOR)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: log-probabilities are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
-    ST_TRY(need_actor(h));
-    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: this handle's actor chooses Box actions; a log-probability belongs to a Discrete actor");
-    if (!aligned_to(d_rec_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
-    h->actor->rec_logp = d_rec_logp;
-    return GYMNET_OK;
-}
-
-void actor_logp_rollout_disarm(gymnet_vecenv *h) {
-    if (h->actor) h->actor->rec_logp = nullptr;
-}
-
 }  // namespace gymnet
 
 using namespace gymnet;
@@ -243,17 +204,10 @@ int gymnet_vecenv_actor_act_logp_device(gymnet_vecenv *h, int32_t *d_actions, fl
     if (!d_logp) return gymnet_vecenv_actor_act_device(h, d_actions, d_logits, epsilon, seed, tick);
     return guarded([&]() -> int {
     ENTER(h);
-    ST_TRY(need_actor(h));
-    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "this handle's actor chooses Box actions: a log-probability belongs to a Discrete actor");
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (!aligned_to(d_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_logp must be 4-byte aligned");
-    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-    if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
-    ActorAct aa{};
-    aa.epsilon = epsilon; aa.seed = seed; aa.lane_offset = (uint64_t)h->cfg.lane_offset; aa.tick = tick;
+    ActorAct aa;
+    ST_TRY(actor_act_enter(h, false, "this handle's actor chooses Box actions: a log-probability belongs to a Discrete actor", d_actions, d_logp, epsilon, seed, tick, aa));
     const Actor &ac = *h->actor;
-    HIP_TRY(h, launch_logp_act(ac.net, ac.hist, d_actions, d_logits, d_logp, aa, ActorExplore{ac.discrete_explore, ac.inv_tau}, h->stream));
+    HIP_TRY(h, launch_logp_act(ac.net, ac.hist, d_actions, d_logits, d_logp, aa, actor_explore(ac), h->stream));
     return GYMNET_OK;
     });
 }

@@ -1,9 +1,11 @@
-// actor_net.hpp — what the two actor units share: the network and the per-lane observation history as the kernels see them, the forward
-// pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), and the handle's Actor attachment
-// with the calls one unit makes into the other.  actor.hip serves the Discrete envs (argmax head) and owns the attachment; actor_box.hip
-// serves the Box envs (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete
-// envs under an exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when
-// the caller also asks for the log-probability of the action taken.  Internal to the library.
+// actor_net.hpp — what the five actor units share: the network and the per-lane observation history as the kernels see them, the forward
+// pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), the host helpers every unit launches
+// with (lane_grid, pick_rollout_form), and the handle's Actor attachment with each unit's launch calls.  actor.hip serves the Discrete
+// envs (argmax head) and owns the attachment, the act prologue (actor_act_enter) and the router: actor_rollout_launch there is the one
+// place that says which unit runs a handle's fused rollout, and no unit calls another on its own.  actor_box.hip serves the Box envs
+// (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete envs under an
+// exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when the caller
+// also asks for the log-probability of the action taken.  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -74,6 +76,18 @@ __device__ __forceinline__ void actor_forward(const ActorNet &net, float (&x)[kW
 #pragma unroll
         for (int i = 0; i < kW; ++i) x[i] = y[i];
     }
+}
+
+// first index of the largest of x[0 .. action_n) (moves only on a strictly greater value), which also hands out the value it settles on:
+// actor.hip's argmax_logits as actor_softmax.hip and actor_logp.hip need it
+__device__ __forceinline__ int32_t argmax_value(const float (&x)[kW], int32_t action_n, float &bv) {
+    int32_t best = 0;
+    bv = x[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+        if (j < action_n && x[j] > bv) { bv = x[j]; best = j; }
+    }
+    return best;
 }
 
 // the ring: the slot after `slot`, and the slot of input row s (oldest first, s < history) when `newest` holds the newest observation
@@ -149,6 +163,20 @@ template <bool EXTRAS> constexpr int kActorMinBlocks = EXTRAS ? 1 : 3;
 
 static inline dim3 lane_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// a fused rollout's three run-time switches as compile-time ones: f(AUTORESET, EXTRAS, RECORDS), each a std::bool_constant, for the six
+// forms every unit compiles.  Records without the bookkeeping is not a form: the lean kernel runs
+template <class F>
+auto pick_rollout_form(bool autoreset, bool extras, bool records, F f) {
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (autoreset) {
+        if (!extras) return f(yes, no, no);
+        return records ? f(yes, yes, yes) : f(yes, yes, no);
+    }
+    if (!extras) return f(no, no, no);
+    return records ? f(no, yes, yes) : f(no, yes, no);
+}
+
 // the configured actor: hist.slot is the ring slot of the newest observation; last: the handle's step counters at the last config, reset,
 // push or actor rollout, so act can tell that the history is current and push that exactly one vector step ran in between.  box: the
 // handle's env has a Box action space and the last layer's one value is the action (actor_box.hip); else its values are logits
@@ -162,14 +190,13 @@ struct Actor {
     // actor.hip serve (UNIFORM at any temperature is that behaviour); SOFTMAX runs through actor_softmax.hip.  inv_tau = 1.0f / temperature
     int32_t discrete_explore = GYMNET_ACTOR_EXPLORE_UNIFORM; float temperature = 1.0f, inv_tau = 1.0f;
     bool default_exploration() const { return discrete_explore == GYMNET_ACTOR_EXPLORE_UNIFORM; }
-    // set only while gymnet_vecenv_rollout_fused_logp_device runs its rollout (actor_logp_rollout_arm / _disarm, actor_logp.hip): where the
-    // launch records every step's log-probability, [steps][n]; actor_rollout_launch sends a non-null pointer to actor_logp.hip
-    float *rec_logp = nullptr;
 };
 // what the kernels of actor_box_policy.hip take of it, as a kernel argument
 struct BoxPolicy { int32_t head, explore; float sigma; };
-// ... and the kernels of actor_softmax.hip
+inline BoxPolicy box_policy(const Actor &ac) { return {ac.head, ac.explore, ac.sigma}; }
+// ... and the kernels of actor_softmax.hip and actor_logp.hip
 struct ActorExplore { int32_t explore; float inv_tau; };
+inline ActorExplore actor_explore(const Actor &ac) { return {ac.discrete_explore, ac.inv_tau}; }
 
 // the message names the config call that serves the handle's env
 inline int need_actor(gymnet_vecenv *h) {
@@ -182,18 +209,27 @@ inline bool actor_current(const gymnet_vecenv *h) { return since(h, h->actor->la
 
 // actor.hip: gymnet_vecenv_actor_config and gymnet_vecenv_actor_box_config behind ENTER (box: which of the two)
 int actor_configure(gymnet_vecenv *h, bool box, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
-// actor_box.hip: the push / fill of a three-row observation (Pendulum), and the fused rollout of a Box handle
-hipError_t launch_actor_box_push3(const ActorHist &hs, const float *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st);
+// actor.hip: what every act entry point checks behind ENTER, in this order — an actor of the kind the call serves (want_box; wrong_kind:
+// the entry point's own message), d_actions, d_logp's alignment (null: not asked for), epsilon, a current history — and the ActorAct of
+// the launch
+int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, const void *d_actions, const float *d_logp, float epsilon, uint64_t seed,
+                    uint64_t tick, ActorAct &aa);
+// Each unit's fused rollout of a handle it serves, a.n > 0 (records: the rollout keeps compact episode records), and the calls one unit
+// makes into another: actor.hip's router (actor_rollout_launch, handle.hpp) reads (box, default_policy(), default_exploration(), a record
+// pointer) and calls exactly one of these four or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
+// push reach a sibling's kernels through the rest.
+// actor_box.hip: the default policy's rollout, and the push / fill of a three-row observation (Pendulum)
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
-// actor_box_policy.hip: act and the fused rollout of a Box handle whose policy is not the default
+hipError_t launch_actor_box_push3(const ActorHist &hs, const float *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st);
+// actor_box_policy.hip: a Box handle whose policy is not the default
+hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 hipError_t actor_box_policy_act_launch(const ActorNet &net, const ActorHist &hs, float *actions, float *raw, float low, float high, const ActorAct &aa,
                                        const BoxPolicy &pol, hipStream_t st);
-hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
-// actor_softmax.hip: act and the fused rollout of a Discrete handle whose exploration setting is not the default
+// actor_softmax.hip: a Discrete handle whose exploration setting is not the default
+hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 hipError_t actor_softmax_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, const ActorExplore &ex,
                                     hipStream_t st);
-hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
-// actor_logp.hip: the fused rollout of a Discrete handle that also records the log-probability of every action taken (Actor::rec_logp)
-hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+// actor_logp.hip: a Discrete handle, either setting, that also records the log-probability of every action taken: rec_logp [steps][n]
+hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp);
 
 }  // namespace gymnet

@@ -1,7 +1,7 @@
 // actor_softmax.hip — the Discrete actor (actor.hip) under an exploration setting other than its default: a lane whose coin says explore
 // draws its action from softmax(logits / temperature) instead of uniformly over the actions.  The contract is
 // gymnet_vecenv_actor_set_exploration in include/gymnet_amd.h.  With x[0 .. A) the logits, A = action_n <= 8:
-//   greedy   the first index of the largest logit, m its value (argmax_logits of actor.hip)
+//   greedy   the first index of the largest logit, m its value (argmax_value, actor_net.hpp: argmax_logits of actor.hip)
 //   coin     word B of the aux stream <= coin_threshold(epsilon), as everywhere
 //   UNIFORM  an exploring lane takes __umulhi(word A, A), as under the default setting (the host entry points send UNIFORM to actor.hip's
 //            kernels, so this branch serves a caller inside the library only)
@@ -16,25 +16,14 @@
 //
 // Fused rollout (actor_softmax_rollout_kernel): actor_rollout_kernel with the setting as a fifth argument — rollout_body, one lane per
 // thread, behind a hook whose choose() is the act kernel's body and whose after() is the shared push.  Both kernels call explore_compose_one,
-// so the fused rollout is bit-identical to steps x (act, step, push).  argmax and the uniform draw are this unit's own copies: actor.hip's
-// kernels stay instruction for instruction what they were.
+// so the fused rollout is bit-identical to steps x (act, step, push).  The composition with its uniform draw is this unit's own copy:
+// actor.hip's kernels stay instruction for instruction what they were.
 #include "actor_net.hpp"
 #include "exp_neg.hpp"
 
 namespace gymnet {
 
 namespace {
-
-// actor.hip's argmax_logits, which also hands out the value it settles on
-__device__ __forceinline__ int32_t argmax_value(const float (&x)[kW], int32_t action_n, float &bv) {
-    int32_t best = 0;
-    bv = x[0];
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-        if (j < action_n && x[j] > bv) { bv = x[j]; best = j; }
-    }
-    return best;
-}
 
 // the draw from softmax(x / tau) for one lane: u in [0, 1)
 __device__ __forceinline__ int32_t softmax_draw(const float (&x)[kW], int32_t action_n, int32_t greedy, float m, float inv_tau, float u) {
@@ -155,28 +144,17 @@ __global__ __launch_bounds__(256, kActorMinBlocks<EXTRAS>) void actor_softmax_ro
 }
 
 template <class Env>
-static hipError_t launch_softmax_rollout_env(bool autoreset, bool extras, bool records, const StepArgs &a, const RolloutArgs &r, const ActorNet &net,
-                                             const ActorHist &hs, const ActorExplore &ex, hipStream_t st) {
-    void (*k)(StepArgs, RolloutArgs, ActorNet, ActorHist, ActorExplore) = nullptr;
-    if (autoreset) {
-        if (!extras) k = actor_softmax_rollout_kernel<Env, true, false, false>;
-        else k = records ? actor_softmax_rollout_kernel<Env, true, true, true> : actor_softmax_rollout_kernel<Env, true, true, false>;
-    } else {
-        if (!extras) k = actor_softmax_rollout_kernel<Env, false, false, false>;
-        else k = records ? actor_softmax_rollout_kernel<Env, false, true, true> : actor_softmax_rollout_kernel<Env, false, true, false>;
-    }
-    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, st, a, r, net, hs, ex);
+static hipError_t launch_softmax_rollout_env(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
+    const auto k = pick_rollout_form(h->autoreset, h->extras, records, [](auto ar, auto ex, auto rec) { return actor_softmax_rollout_kernel<Env, ar, ex, rec>; });
+    hipLaunchKernelGGL(k, lane_grid(a.n), dim3(256), 0, h->stream, a, r, h->actor->net, h->actor->hist, actor_explore(*h->actor));
     return hipGetLastError();
 }
 
 hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r) {
-    const Actor &ac = *h->actor;
-    if (a.n <= 0) return hipSuccess;
-    const ActorExplore ex{ac.discrete_explore, ac.inv_tau};
     switch (h->cfg.env_id) {
-        case GYMNET_ENV_CARTPOLE: return launch_softmax_rollout_env<CartPole>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, h->stream);
-        case GYMNET_ENV_MOUNTAINCAR: return launch_softmax_rollout_env<MountainCar>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, h->stream);
-        case GYMNET_ENV_ACROBOT: return launch_softmax_rollout_env<Acrobot>(h->autoreset, h->extras, records, a, r, ac.net, ac.hist, ex, h->stream);
+        case GYMNET_ENV_CARTPOLE: return launch_softmax_rollout_env<CartPole>(h, records, a, r);
+        case GYMNET_ENV_MOUNTAINCAR: return launch_softmax_rollout_env<MountainCar>(h, records, a, r);
+        case GYMNET_ENV_ACROBOT: return launch_softmax_rollout_env<Acrobot>(h, records, a, r);
         default: return hipErrorInvalidValue;
     }
 }

@@ -276,15 +276,14 @@ int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_
 int write_tick(gymnet_vecenv *h);
 int seed_handle(gymnet_vecenv *h, uint64_t seed);                    // Env.Seed(int): new key, tick 0, captured graphs dropped
 int resident_stop(gymnet_vecenv *h);                                 // tells a running resident kernel to leave and waits until it has
-// the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch
-// (records: the rollout keeps compact episode records); afterwards the history's newest slot has moved `steps` on and is current
+// the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch,
+// by the unit that serves the handle as it stands (records: the rollout keeps compact episode records; rec_logp: where it records every
+// step's log-probability, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps` on and is current
 int actor_rollout_check(gymnet_vecenv *h);
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp);
 void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
-// gymnet_vecenv_rollout_fused_logp_device (actor_logp.hip): the checks that belong to the record pointer, after which the handle's actor
-// carries it into actor_rollout_launch; disarm clears it, and is called on every exit path
-int actor_logp_rollout_arm(gymnet_vecenv *h, int32_t action_source, float *d_rec_logp);
-void actor_logp_rollout_disarm(gymnet_vecenv *h);
+// gymnet_vecenv_rollout_fused_logp_device: the checks that belong to its record pointer (the source, the actor's kind, the alignment)
+int actor_logp_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp);
 // the fused rollout with frame skip (action_repeat.hip): r.steps decisions of R sub-steps each under one action, one launch
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs &a, const RolloutArgs &r, int32_t R);
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const RolloutArgs64 &r, int32_t R);

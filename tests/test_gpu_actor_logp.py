@@ -291,15 +291,34 @@ def test_refusals_write_nothing(gpu_pkg):
         env.Sync()
         assert intact(b) and np.array_equal(env.GetState().view(np.uint32), state.view(np.uint32)) and env.Tick == tick
         assert np.array_equal(actor.History(), hist)
-        actor.Push()                                                                      # ... and after the push both serve again, and a refused
-        assert act_logp(lib, h, b) == capi.OK                                             # rollout left no record pointer behind: the plain
-        assert fused_logp(lib, h, b, capi.ACTIONS_RING, ring) == capi.ERR_INVALID_ARG     # actor rollout after it writes no logp
+        actor.Push()                                                                      # ... and after the push both serve again
+        assert act_logp(lib, h, b) == capi.OK
+        assert fused_logp(lib, h, b, capi.ACTIONS_RING, ring) == capi.ERR_INVALID_ARG
         rec_act = torch.empty((T, N), dtype=torch.int32, device="cuda")
-        env.RolloutFusedDevice(None, T, actions="actor", epsilon=0.5, action_seed=5, action_tick0=9, rec_actions=rec_act)
-        env.RolloutFusedDevice(None, T, actions="actor", epsilon=0.5, action_seed=5, action_tick0=9, rec_actions=rec_act, rec_logp=b["rec"])
-        env.RolloutFusedDevice(None, T, actions="actor", epsilon=0.5, action_seed=5, action_tick0=9, rec_actions=rec_act)
+        plain = dict(actions="actor", epsilon=0.5, action_seed=5, action_tick0=9, rec_actions=rec_act)
+
+        def plain_rollout_leaves_rec_alone():
+            env.RolloutFusedDevice(None, T, **plain)
+            env.Sync()
+            return bool((b["rec"] == POISON).all()) and env.KernelName() == name0
+
+        # the record pointer belongs to the one call that was given it: neither a served nor a refused logp rollout leaves it behind for
+        # the plain actor rollout after it to write through
+        name0 = env.KernelName()
+        assert plain_rollout_leaves_rec_alone()
+        env.RolloutFusedDevice(None, T, rec_logp=b["rec"], **plain)
         env.Sync()
-        assert not (b["logp"] == POISON).any() and not (b["rec"] == POISON).any() and env.Tick == tick + 3 * T
+        assert not (b["logp"] == POISON).any() and not (b["rec"] == POISON).any()
+        b["rec"].fill_(POISON)
+        torch.cuda.synchronize()
+        assert plain_rollout_leaves_rec_alone()                                           # after a served one
+        assert fused_logp(lib, h, b, capi.ACTIONS_RING, ring) == capi.ERR_INVALID_ARG     # refused by the pointer's own checks
+        assert plain_rollout_leaves_rec_alone()
+        env.StepDevice(actor.Act(0.5, 5, 3))                                              # refused by the rollout's checks, which come after them
+        assert fused_logp(lib, h, b, capi.ACTIONS_ACTOR) == capi.ERR_INVALID_ARG and b"stale" in lib.gymnet_last_error()
+        actor.Push()
+        assert plain_rollout_leaves_rec_alone()
+        assert env.Tick == tick + 5 * T + 1
     with gpu_pkg.VectorEnv(CARTPOLE, N, seed=SEED, auto_reset=True, dtype=np.float64) as env:          # float64: act serves, the fused rollout does not
         env.Reset()
         lib, h = env._lib, env._h
