@@ -219,6 +219,66 @@ def test_graph_rollout_equals_eager_steps_bitwise(gpu_pkg, monkeypatch, force_gr
         assert np.isfinite(st).all() and np.abs(st[0]).max() < 2.6 and np.abs(st[2]).max() < 0.3   # auto-reset keeps lanes in range
 
 
+@pytest.mark.parametrize("ring", [3, 1])
+@pytest.mark.parametrize("bookkeeping", [False, True])
+def test_graph_rollout_with_an_odd_ring_equals_eager_steps_bitwise(gpu_pkg, ring, bookkeeping):
+    """rollout_steps() captures 2 * ring steps for an odd ring, so that the device tick's slot, the done-count half and the
+    observation buffer are back where they were after every replay.  Three RolloutDevice calls with one eager StepDevice between
+    the first two (an odd number of launches: slot, half and buffer index all differ when the second call captures its own graph;
+    the third call finds the first call's graph again) against a twin stepped with StepDevice — plain, and with every piece of
+    bookkeeping a launch can carry, ping-ponged buffers and a time limit.  1003 lanes: a partial last wave."""
+    import torch
+    n, glen = 1003, 2 * ring
+    kw = dict(double_buffer=True, done_list=True, episode_stats=True, final_obs=True, max_episode_steps=9) if bookkeeping else {}
+    with gpu_pkg.VectorEnv("CartPole-v1", n, seed=SEED, auto_reset=True, launch_policy={"graph": 1}, **kw) as g, \
+            gpu_pkg.VectorEnv("CartPole-v1", n, seed=SEED, auto_reset=True, **kw) as e:
+        acts = torch.empty((ring, n), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        for t in range(ring):
+            g.SampleActionsDevice(acts[t], seed=SEED + 1, tick=t)
+        g.Sync()
+
+        def same(tag):
+            g.Sync(); e.Sync()
+            assert g.Tick == e.Tick and g.Counters() == e.Counters() and g.Counters()["tick"] == g.Tick, tag
+            assert g.ObsBufferIndex() == e.ObsBufferIndex(), tag
+            assert np.array_equal(g.GetState().view(np.uint32), e.GetState().view(np.uint32)), tag
+            r1, r2 = g.Read(), e.Read()
+            assert np.array_equal(r1.Observation.view(np.uint32), r2.Observation.view(np.uint32)), tag
+            assert np.array_equal(r1.Reward, r2.Reward) and np.array_equal(r1.Done, r2.Done) and np.array_equal(r1.Truncated, r2.Truncated), tag
+            if bookkeeping:
+                a, b = g.DoneRecords(), e.DoneRecords()
+                oa, ob = np.argsort(a["lanes"]), np.argsort(b["lanes"])
+                assert np.array_equal(a["lanes"][oa], np.nonzero(r2.Done)[0]) and np.array_equal(b["lanes"][ob], np.nonzero(r2.Done)[0]), tag
+                for k in ("return", "length", "final_obs"):
+                    assert np.array_equal(a[k][oa], b[k][ob]), (tag, k)
+                for x, y in zip(g.EpisodeStats() + (g.FinalObs(),), e.EpisodeStats() + (e.FinalObs(),)):
+                    assert np.array_equal(x, y), tag
+            return r2
+
+        g.ResetDevice(); e.ResetDevice()
+        finished = 0
+        # replays (+ eager steps) | the other parity: a second graph + one eager step | the first graph again.  With ring 1 the step in
+        # between is the 9th: every lane that got that far is truncated there, so the records compared after it are not empty
+        plan = {3: (2 * glen + 2, glen + 1, 2 * glen), 1: (4 * glen, glen + 1, 2 * glen)}[ring]
+        for call, steps in enumerate(plan):
+            g.RolloutDevice(acts, steps, n, ring)
+            for t in range(steps):
+                e.StepDevice(acts[t % ring])
+            finished += int(same(("rollout", call)).Done.sum())
+            if call == 0:
+                g.StepDevice(acts[ring - 1]); e.StepDevice(acts[ring - 1])
+                r = same("eager step in between")
+                finished += int(r.Done.sum())
+                assert r.Truncated.any() or not (bookkeeping and ring == 1)
+        assert g.Tick == 1 + sum(plan) + 1 and (plan[0] + 1) % 2 == 1
+        assert g.Counters()["lane_steps"] == (g.Tick - 1) * n
+        assert finished > 0                                                     # lanes finished at the compared steps (and were re-drawn)
+        if bookkeeping:                                                         # ... most lanes by the end, and none outlived the time limit
+            ln = e.EpisodeStats()[1]
+            assert (ln > 0).sum() > n // 2 and ln.max() <= 9
+
+
 def test_sharding_invariance_bitwise(gpu_pkg):
     # G logical shards with global lane offsets == one big batch (SURVEY §8(e)), incl. Philox resets
     n, G, steps = 1 << 16, 4, 30

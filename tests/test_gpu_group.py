@@ -365,18 +365,19 @@ rank, world, out_dir = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), s
 dist.init_process_group("gloo", rank=rank, world_size=world)        # control plane only: handle exchange + barrier
 dev = torch.device("cuda", 0); torch.cuda.set_device(0)              # both ranks share the one GPU of the box
 stream = torch.cuda.Stream(dev); torch.cuda.set_stream(stream)
-n, steps = 1 << 14, 16
+name, n, dtype, steps = sys.argv[2], int(sys.argv[3]), sys.argv[4], int(sys.argv[5])
+box = name == "Pendulum-v1"
 for overlap in (False, True):
-    env = pkg.ShardedVectorEnv("CartPole-v1", n, rank=rank, world_size=world, device=0, seed=0x5EED, auto_reset=True,
-                               gather_obs=True, tensor_device=dev, overlap=overlap, gather="direct")
+    env = pkg.ShardedVectorEnv(name, n, rank=rank, world_size=world, device=0, seed=0x5EED, auto_reset=True,
+                               gather_obs=True, tensor_device=dev, overlap=overlap, gather="direct", dtype=dtype)
     assert env.gather == "direct" and env.overlap == overlap
     rng = np.random.default_rng(1)
     lo, hi = env.lane_offset, env.lane_offset + env.local_num_envs
     env.ResetDevice()
-    acts = torch.empty(hi - lo, dtype=torch.int32, device=dev)
+    acts = torch.empty(hi - lo, dtype=torch.float32 if box else torch.int32, device=dev)
     snaps = []
     for t in range(steps):
-        a = rng.integers(0, 2, n).astype(np.int32)
+        a = rng.uniform(-2, 2, n).astype(np.float32) if box else rng.integers(0, 2, n).astype(np.int32)
         acts.copy_(torch.from_numpy(a[lo:hi])); torch.cuda.synchronize()
         env.StepDevice(acts)
         env.AllGatherObs(overlap=overlap)
@@ -389,10 +390,15 @@ dist.destroy_process_group()
 """
 
 
-def test_direct_allgather_between_two_processes_over_hip_ipc(gpu_pkg, tmp_path):
+@pytest.mark.parametrize("name,n,dtype,steps", [("CartPole-v1", 1 << 14, "float32", 16), ("Pendulum-v1", 2 * 1002, "float32", 10)])
+def test_direct_allgather_between_two_processes_over_hip_ipc(gpu_pkg, tmp_path, name, n, dtype, steps):
     """One process per GPU with the hand-written gather: two ranks (sharing this box's one GPU) export their replica
     buffers as HIP IPC peer buffers, map each other's, push their slices with gymnet_push_obs_device, and synchronise with
-    stream-sync + barrier.  Every rank's gathered [G][D][N/G] buffer must equal the single-handle batch bit for bit."""
+    stream-sync + barrier.  Every rank's gathered [G][D][N/G] buffer must equal the single-handle batch bit for bit.
+    The Pendulum row is the ragged one: D = 3 rows of 1002 lanes, so rank 1's slice starts 8 bytes off a 16-byte line in
+    every replica (the push takes its scalar branch on rank 1, its dwordx4 branch with a two-word tail on rank 0) and the
+    rows of both ranks alternate alignment; it runs 10 steps, the aligned row 16, so that it takes no longer (both are
+    dominated by starting two processes)."""
     import socket
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -402,14 +408,14 @@ def test_direct_allgather_between_two_processes_over_hip_ipc(gpu_pkg, tmp_path):
     procs = []
     for r in range(2):
         e = dict(os.environ, RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script), str(tmp_path)], cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        procs.append(subprocess.Popen([sys.executable, str(script), str(tmp_path), name, str(n), dtype, str(steps)], cwd=ROOT, env=e,
+                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [p.communicate(timeout=600)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n---\n".join(o[-2500:] for o in outs)
-    n, steps = 1 << 14, 16
-    with gpu_pkg.VectorEnv("CartPole-v1", n, seed=SEED, auto_reset=True) as one:
+    with gpu_pkg.VectorEnv(name, n, seed=SEED, auto_reset=True, dtype=dtype) as one:
         one.Reset()
         rng = np.random.default_rng(1)
-        want = [one.Step(rng.integers(0, 2, n).astype(np.int32)).Observation for _ in range(steps)]
+        want = [one.Step(_actions(rng, name, n)).Observation for _ in range(steps)]
     for overlap in (0, 1):
         got = [np.load(tmp_path / f"direct_{overlap}_rank{r}.npy") for r in range(2)]
         assert np.array_equal(got[0], got[1])
