@@ -1,4 +1,5 @@
-// capi.hip — the C ABI (include/gymnet_amd.h) over the HIP kernels.  Host code only; compiled by hipcc.
+// capi.hip — the C ABI (include/gymnet_amd.h) over the HIP kernels.  Host code only; compiled by hipcc.  The launch policy, the
+// resident mailbox and the graph-replay rollout have units of their own (launch_policy.hip, resident.hip, step_graph.hip; handle.hpp).
 //
 // There is NO CPU fallback in this library: without a usable AMD GPU every compute entry point fails
 // with GYMNET_ERR_NO_DEVICE / GYMNET_ERR_HIP.  The CPU restatement under oracle/ is test infrastructure
@@ -6,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -83,58 +83,6 @@ int ensure_staging(gymnet_vecenv *h, bool actions, bool pack, bool mask) {
     return GYMNET_OK;
 }
 
-void destroy_graph(GraphEntry &g) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-    g.exec = nullptr; g.graph = nullptr;
-}
-
-void drop_graphs(gymnet_vecenv *h) {
-    for (auto &g : h->graphs) destroy_graph(g);
-    h->graphs.clear();
-}
-
-template <class R>
-StepArgsT<R> make_step_args(gymnet_vecenv *h, const void *d_actions) {
-    StepArgsT<R> a{};
-    const bool alias = h->desc->alias;
-    a.state = static_cast<R *>(h->d_state);
-    a.state_out = static_cast<R *>((h->double_buffer && alias) ? h->d_state_alt : h->d_state);
-    a.obs = static_cast<R *>((h->double_buffer && !alias) ? h->d_obs_alt : h->d_obs);
-    a.obs_in = static_cast<const R *>(h->d_obs);
-    a.action = d_actions;
-    a.reward = h->d_reward;
-    a.done = h->d_done;
-    a.sbd = h->d_sbd;
-    a.tick2 = h->d_tick2;
-    // the dense "last finished episode per lane" arrays are maintained by the step kernel itself unless the caller opted for
-    // compact records only (GYMNET_FLAG_COMPACT_RECORDS_ONLY with DONE_LIST): then the getters apply the records on demand
-    const bool dense = !(h->compact_only && h->d_done_list);
-    a.final_obs = dense ? static_cast<R *>(h->d_final_obs) : nullptr;
-    a.done_list = h->d_done_list;
-    a.done_count2 = h->d_done_count2;
-    a.done_cap = h->done_cap;
-    a.ep_ret = h->d_ep_ret; a.ep_len = h->d_ep_len; a.fin_ret = dense ? h->d_fin_ret : nullptr; a.fin_len = dense ? h->d_fin_len : nullptr;
-    a.rec_ret = h->d_rec_ret; a.rec_len = h->d_rec_len; a.rec_obs = static_cast<R *>(h->d_rec_obs);
-    a.lane_seed = h->d_lane_seed;
-    a.after_done = h->d_after_done;
-    a.n = h->n; a.state_stride = h->sstride; a.obs_stride = h->ostride;
-    a.lane_offset = (uint64_t)h->cfg.lane_offset;
-    a.seed = h->seed;
-    a.parity = (int32_t)h->tslot;
-    a.cparity = (int32_t)(h->step_launches & 1u);
-    a.max_episode_steps = h->cfg.max_episode_steps;
-    return a;
-}
-
-// after a step launch with GYMNET_FLAG_DOUBLE_BUFFER: what was written becomes current
-void swap_buffers(gymnet_vecenv *h) {
-    if (!h->double_buffer) return;
-    if (h->desc->alias) { std::swap(h->d_state, h->d_state_alt); h->d_obs = h->d_state; h->d_obs_alt = h->d_state_alt; }
-    else std::swap(h->d_obs, h->d_obs_alt);
-    h->cur ^= 1;
-}
-
 // Gathers the sharded done list of the most recent step — and the records written beside it — into compact arrays
 // (stream-ordered, non-blocking); with `dense`, also applies the records to the dense per-lane arrays.  NULL outputs are skipped.
 template <class R>
@@ -162,177 +110,6 @@ void *state_row(gymnet_vecenv *h, int k) {
     return m < 0 ? row_at(h->d_state, k, h->sstride, h->esz) : row_at(h->d_obs, m, h->ostride, h->esz);
 }
 
-// The step kernel a launch with configuration `c` runs: the launcher's own selection (step_kernels.hpp select_step), its name and shape.
-StepForm next_step_kernel(const gymnet_vecenv *h, const LaunchCfg &c) {
-    if (h->f64) return h->launch_f64->select_step(h->autoreset, h->extras, c, h->n);
-    return h->launch_f32->select_step(h->autoreset, h->extras, c, h->n);
-}
-
-// Applies the fields of `p` that are not -1.  strict: a value the handle cannot run — or that would not take effect for it (a
-// multi-lane form on a batch that is not whole groups, a reset form the env has no use for) — is an error and nothing changes;
-// else it is ignored (probe builds).  gymnet_vecenv_kernel_name stays the authority on what the next launch runs.
-int apply_policy(gymnet_vecenv *h, const gymnet_launch_policy &p, bool strict) {
-    LaunchCfg c = h->lcfg;
-    int graph_mode = h->graph_mode;
-    const bool acrobot = h->cfg.env_id == GYMNET_ENV_ACROBOT;
-    const bool wide2 = acrobot || h->f64;            // the env's wide form is two lanes per thread (else four)
-    auto bad = [&](const char *what, int v) -> int {
-        return strict ? fail(h, GYMNET_ERR_INVALID_ARG, "launch policy: %s = %d is not available for this handle", what, v) : GYMNET_OK;
-    };
-    if (p.vec != -1) {
-        const bool ok = p.vec == 1 || (p.vec == 4 && h->can_vec4 && !wide2) || (p.vec == 2 && h->can_vec2 && wide2);
-        if (ok) c.vec = p.vec; else ST_TRY(bad("vec", p.vec));
-    }
-    if (p.block != -1) { if (p.block == 64 || p.block == 128 || p.block == 256) c.block = p.block; else ST_TRY(bad("block", p.block)); }
-    if (p.nt != -1) { if (p.nt == 0 || p.nt == 12 || p.nt == 15) c.nt = p.nt; else ST_TRY(bad("nt", p.nt)); }
-    if (p.sequential_lanes != -1) {
-        if (p.sequential_lanes >= 1 && p.sequential_lanes <= (h->f64 ? 4 : 5) && (acrobot || h->f64 || p.sequential_lanes == 1)) c.items = p.sequential_lanes;
-        else ST_TRY(bad("sequential_lanes", p.sequential_lanes));
-    }
-    if (p.reset_form != -1) {
-        const bool has_form1 = h->desc->alias;       // the wave-compacted reset hands back the state only (CartPole, MountainCar[Continuous])
-        if (p.reset_form == 0 || (p.reset_form == 1 && (has_form1 || !strict))) c.reset_form = p.reset_form; else ST_TRY(bad("reset_form", p.reset_form));
-    }
-    if (p.lds_pipe != -1) {
-        if (p.lds_pipe == 0 || (p.lds_pipe == 1 && h->lds_ok)) c.lds_pipe = p.lds_pipe; else ST_TRY(bad("lds_pipe", p.lds_pipe));
-    }
-    if (p.occupancy_lds_bytes != -1) {
-        if (p.occupancy_lds_bytes >= 0 && p.occupancy_lds_bytes <= 160 * 1024) c.lds_bytes = p.occupancy_lds_bytes;
-        else ST_TRY(bad("occupancy_lds_bytes", p.occupancy_lds_bytes));
-    }
-    if (p.graph != -1) { if (p.graph == 0 || p.graph == 1) graph_mode = p.graph; else if (p.graph == -2) graph_mode = -1; else ST_TRY(bad("graph", p.graph)); }
-    if (strict && p.sequential_lanes > 1) {
-        // an explicitly requested multi-lane form must be the one the launcher resolves to: lean variant, the lane
-        // width it is defined for, whole 2 * items * 256-lane groups for the pair form
-        const int rseq = next_step_kernel(h, c).sequential;
-        if (rseq != p.sequential_lanes)
-            return fail(h, GYMNET_ERR_INVALID_ARG, "launch policy: sequential_lanes = %d would not take effect for this handle (vec %d, %s variant, "
-                        "%lld lanes: the launcher resolves to %d)", p.sequential_lanes, c.vec, h->extras ? "bookkeeping" : "lean", (long long)h->n, rseq);
-    }
-    h->graph_mode = graph_mode;
-    if (std::memcmp(&c, &h->lcfg, sizeof c) != 0) {
-        h->lcfg = c;
-        drop_graphs(h);          // captured launches froze the old configuration
-    }
-    return GYMNET_OK;
-}
-
-// The launch configuration a handle starts with (gymnet_vecenv_set_launch_policy changes it afterwards).
-void default_policy(gymnet_vecenv *h) {
-    const EnvDesc &d = *h->desc;
-    const gymnet_config *cfg = &h->cfg;
-    if (h->f64) {
-        // float64 CartPole: two lanes per thread (one dwordx4 per state row and direction) where the rows are 16-byte aligned
-        // (external observation buffers may not be); stream policy by the bytes a vector step moves, with the thresholds of the
-        // float32 path below
-        const size_t step_bytes = (size_t)h->n * bytes_per_step(h);
-        const bool can2 = aligned16(h->d_state) && (h->sstride % 2 == 0) && (!h->d_state_alt || aligned16(h->d_state_alt));
-        h->can_vec4 = false; h->can_vec2 = can2; h->lds_ok = false;
-        // measured at 2^20 lanes (73 MiB per step; us per step, gpurun_out r4): every stream non-temporal 14.3, state cacheable 14.8,
-        // nothing non-temporal 16.2, one lane per thread 15.6
-        // reset_form 1 (two lanes per reset in the wave-compacted form, step_kernels.hpp) for the one-shot kernel and the fused rollout:
-        // one-shot 13.7 -> 13.4 us at 2^20 lanes, bookkeeping rollout 7.5 -> 6.9 us per step, lean rollout 5.9 -> 6.0
-        // (profiles/rollout_reset_forms_r05.txt); the multi-pair kernel below always draws once per thread-group of pairs
-        h->lcfg = LaunchCfg{can2 ? 2 : 1, 256, 15, 0, 1, can2 ? 1 : 0, 0, h->simds};
-        // Stream policy by the bytes a vector step moves (round 6, profiles/f64_sizes_r06.txt; us per 2^20 lanes, one-shot kernel,
-        // nothing non-temporal | state cacheable (12) | every stream non-temporal (15)):
-        //   2^21 lanes 12.9 | 14.8 | 13.7     3 * 2^20  11.8 | 13.4 | 12.6     2^22  12.1 | 13.8 | 14.1     2^23  13.1 | 13.5 | 12.6
-        // While everything a step touches fits the 256 MiB Infinity Cache (<= 300 MiB moved: the state is rewritten in place), plain
-        // cacheable accesses win by 6-13 % — the next launch finds its inputs on the die; beyond it nothing can stay and every stream
-        // is marked non-temporal (rounds 4-5 kept the state cacheable between 96 and 768 MiB: 4-7 % slower at every size measured).
-        if (step_bytes > ((size_t)96 << 20) && step_bytes <= ((size_t)300 << 20)) h->lcfg.nt = 0;
-        // The multi-pair kernel (step_kernel_pipe2<CartPole64, k>: a thread owns k lane pairs, all loads first, then advance pair after
-        // pair, ONE wave-compacted reset for all of them, then the state rows) wins where it runs as ONE resident generation that fills
-        // the chip: four pairs hold 185 VGPRs = two waves per SIMD (2048 waves of 512 lanes), two pairs three (3072 waves of 256 lanes).
-        // us per step, one-shot | 2 pairs | 4 pairs (profiles/f64_sizes_r05.txt, one box):
-        //   2^19 lanes 6.27 | 6.42 | 7.57      3 * 2^18  10.94 | 8.46 | 10.19      2^20  13.13 | 12.17 | 11.19
-        //   5 * 2^18   16.64 | 16.82 | 17.40   6 * 2^18  21.17 | 19.78 | 19.58     2^21  27.72 | 28.56 | 29.64   (larger: one-shot)
-        // (round 4, 271 VALU per env-step, per-pair drain-loop reset: one-shot 14.4, 2 pairs 13.1, 4 pairs 14.4 at 2^20; round 5 before
-        // the deferred reset: 13.4-13.6 | 13.1-13.4 | 12.8-13.2.)  Lean variant only; without auto-reset whole 2 * k * 256-lane groups
-        // only (the launcher falls back otherwise).  A wave count just under a whole number per SIMD is as good (10^6 lanes: 11.7 us against 13.0).
-        // Beyond one generation the kernel is launched slice by slice (step_kernels.hpp pipe2_chunks) and is no faster than the one-shot
-        // kernel — 2^21 lanes: 27.9 us in two slices, 35.2 as a looping grid, 27.4 one-shot with the same mask, 25.8 one-shot
-        // cacheable (profiles/f64_sizes_r06.txt): what makes 2^20 lanes fast is that the launch's written lines fit the L2s and leave
-        // after the kernel, not the launch shape — so it is not selected there.  (Round 5's window test also let FOUR pairs through at
-        // three waves per SIMD, which they cannot hold: 3 * 2^19 lanes ran at 16.6 us per 2^20 lanes against 13.3.  Fixed.)
-        if (can2 && h->n >= ((int64_t)3 << 18)) {            // (below: ramp-bound, fewer and fatter waves lose)
-            for (int items : {4, 2}) {
-                if (!h->autoreset && h->n % ((int64_t)512 * items) != 0) continue;     // (the auto-reset form takes any batch size)
-                const double waves_per_simd = (double)((h->n + 128 * items - 1) / ((int64_t)128 * items)) / (double)h->simds;   // MI355X: 256 CUs x 4 SIMDs
-                // NOT one wave more: the kernel holds 191 VGPRs, two waves per SIMD are resident, and a 2049th wave starts when an
-                // earlier one has finished — 2^20 + 2 lanes: 19.2 us against 11.1 (profiles/f64_sizes_r05.txt, second table)
-                const bool fills = items == 4 ? (waves_per_simd >= 1.9 && waves_per_simd <= 2.0) : (waves_per_simd >= 2.85 && waves_per_simd <= 3.0);
-                if (fills) { h->lcfg.items = items; h->lcfg.nt = 15; break; }
-            }
-        }
-        return;
-    }
-    // dwordx4 streams need 16-byte aligned component arrays; external buffers may not be
-    const bool can_vec4 = aligned16(h->d_state) && aligned16(h->d_obs) && (h->sstride % 4 == 0) && (h->ostride % 4 == 0) &&
-                          (!h->d_obs_alt || aligned16(h->d_obs_alt));
-    // Launch policy, measured on MI355X with tools/probe_step.hip and bench.py (profiles/probe_r01.txt),
-    // keyed on the bytes one vector step moves (lanes x algorithmic bytes per env-step):
-    //  - <= 2^19 lanes (round 1-4: "<= 24 MiB per vector step"): scalar lanes — 4x the waves hide latency better than dwordx4 on a small grid;
-    //  - <= 48 MiB (2^20 CartPole lanes): dwordx4, every stream non-temporal;
-    //  - <= 300 MiB (the step's whole footprint fits the 256 MiB Infinity Cache): dwordx4, nothing non-temporal (round 6);
-    //  - <= 768 MiB (the state fits it): dwordx4, state cacheable, action / reward / done streamed
-    //    past it, so the next launch re-reads the state from the cache;
-    //  - larger: nothing can stay resident — scalar lanes, every stream non-temporal;
-    //  - Acrobot (RK4, ALU-bound: ~650 VALU per env-step) always takes scalar lanes: 21.7 vs 27.7 us at 2^20.
-    const size_t step_bytes = (size_t)h->n * (size_t)d.algorithmic_bytes;
-    const bool alu_bound = cfg->env_id == GYMNET_ENV_ACROBOT;
-    h->lcfg.simds = h->simds;
-    // Round 5: the small-batch rule is a LANE count, not a byte count.  Scalar lanes win while the launch is ONE resident generation
-    // of waves — n <= 8 waves x 1024 SIMDs x 64 lanes = 2^19 — and lose beyond it (a second generation of 64-lane waves starts when the
-    // first retires); the byte threshold had been fitted on CartPole alone (2^19 lanes = 21.5 MB) and kept MountainCar (25 B per lane)
-    // on scalar lanes up to 10^6 lanes: 5.53 us against 4.53 with 16-byte lanes; 3 * 2^18 lanes 4.35 against 3.93
-    // (profiles/small_batches_r05.txt; CartPole and Pendulum cross over at the same lane count).
-    const bool one_generation = h->n <= ((int64_t)8 * h->simds * 64);
-    if (alu_bound || one_generation) { h->lcfg.vec = 1; h->lcfg.nt = 15; }
-    // Round 6 (profiles/trough_r06.txt): while everything a step touches fits the 256 MiB Infinity Cache — up to ~300 MiB
-    // moved, the state being rewritten in place — and the launch is more than ~1.25 generations of waves, NO stream is marked
-    // non-temporal.  us per 2^20 lanes, mask 0 against the former choice (15 up to 48 MiB, 12 beyond), two boxes:
-    //   CartPole     5 * 2^18 lanes 6.26 / 6.56   2^21 7.03 / 7.33   3 * 2^20 6.86 / 7.54   2^22 6.72 / 7.24   6 * 2^20 6.40 / 6.78
-    //                2^23 6.80 / 6.85 (the crossover)   2^24 7.96 / 6.52 (mask 12 stays)
-    //   MountainCar  3 * 2^19 4.31 / 5.10   2^21 3.83 / 4.48   2^22 4.14 / 4.33   2^23 3.92 / 4.10   2^24 3.85 / 3.87
-    //   Pendulum     3 * 2^19 5.93 / 5.42 and 2^21 6.05 / 5.30 (loses: two of its four written rows are never read back),
-    //                2^22 5.51 / 6.27   2^23 5.68 / 5.68 — hence its later start
-    // MountainCarContinuous moves MountainCar's 25 B per env-step and takes MountainCar's rule throughout.  Measured beside it in one run
-    // (profiles/mountaincar_continuous.txt, us per step, MountainCar / MountainCarContinuous): 2^19 lanes 4.51 / 4.50, 5 * 2^18 5.84 / 5.93,
-    // 2^20 4.79 / 4.67, 2^22 18.16 / 18.09 — the same kernels of both envs land within 2 % of each other at every size.
-    else if (h->n >= (cfg->env_id == GYMNET_ENV_PENDULUM ? (int64_t)3 << 20 : (int64_t)5 << 18) && step_bytes <= ((size_t)300 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 0; }
-    else if (step_bytes <= ((size_t)48 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 15; }
-    else if (step_bytes <= ((size_t)768 << 20)) { h->lcfg.vec = 4; h->lcfg.nt = 12; }
-    else { h->lcfg.vec = 1; h->lcfg.nt = 15; }
-    if (!can_vec4) h->lcfg.vec = 1;
-    // Acrobot's wide form is TWO lanes per thread whose arithmetic rides the packed FP32 instructions (envs.hpp).  Opt-in
-    // (gymnet_launch_policy.vec = 2): bit-identical, 287 instead of 454 VALU per env-step, and slower — 15.0 vs 14.2 us at 2^20
-    // lanes, 13.6 vs 12.3 us per 2^20 lanes at 2^23 (profiles/acrobot_probes_r02.txt, docs/ledger.md §4a).
-    const bool can_vec2 = aligned_to(h->d_state, 8) && aligned_to(h->d_obs, 8) && (h->sstride % 2 == 0) && (h->ostride % 2 == 0) &&
-                          (!h->d_obs_alt || aligned_to(h->d_obs_alt, 8));
-    // Acrobot's multi-lane kernel (step_kernel_pipe: all loads first, then compute / store lane after lane) wins where the
-    // one-shot kernel would run as ~2 lock-step wave generations: it turns the launch into ONE generation of 4096 waves whose
-    // stores drain under the next lane's arithmetic.  Measured (profiles/acrobot_probes_r02.txt, us per 2^20 lanes, one-shot
-    // vs k = ceil(n / 2^18) lanes per thread): n = 2^19 15.1 vs 14.5, 3*2^18 13.9 vs 13.9, 2^20 14.9 vs 13.1, 5*2^18 13.7 vs
-    // 13.1; beyond that the one-shot kernel's generations overlap by themselves (6*2^18: 13.7 vs 13.8; 2^21: 13.4 vs 13.3).
-    // k is n / 2^18 ROUNDED, not rounded up: one lane more than 2^20 used to select k = 5 — 17.5 us per step against 12.5 at 2^20 lanes
-    // (profiles/ragged_r05.txt); with k = 4 the 4097th workgroup is one more wave on a chip that holds eight per SIMD.
-    if (alu_bound && h->n >= ((int64_t)1 << 19) && h->n < ((int64_t)11 << 17)) h->lcfg.items = (int)((h->n + ((int64_t)1 << 17)) >> 18);
-    // Wave-compacted fused reset (kernels.hip: reset_pending_wave) wherever the dwordx4 lean kernel of an env whose observation IS
-    // its state runs: the wave's finished sub-lanes are drawn in ONE Philox pass by its first lanes instead of 1.6 mostly idle
-    // passes.  CartPole at 2^20 lanes: 6.91 -> 6.52 us per launch, bit-identical (profiles/forms_probe_r03.txt).
-    h->lcfg.reset_form = (d.alias && h->lcfg.vec == 4) ? 1 : 0;
-    // producer / consumer form of the multi-lane kernel (opt-in, gymnet_launch_policy.lds_pipe = 1): whole 512-lane tiles and
-    // 16-byte aligned rows only.  Bit-identical and SLOWER at 2^20 lanes — 13.5-14.9 vs 11.7-12.7 us (profiles/acrobot_lds_r03.txt):
-    // the computing waves' waits on memory instructions drop from 34 % to 21 % of their cycles, the s_barrier per tile adds more.
-    const bool lds_ok = alu_bound && can_vec4 && (h->n % 512) == 0;
-    // 64-thread workgroups for the dwordx4 kernels of the smallest payloads (< 40 MiB per vector step at dwordx4: MountainCar and
-    // Pendulum at 2^20 lanes): such a launch is ramp / drain bound, and one-wave workgroups ramp and retire faster — MountainCar 4.92-5.05
-    // -> 4.55-4.73 us, Pendulum 5.97 -> 5.88 us; CartPole (41 MiB) does not gain (tools/gpu_nt_ab_r03.sh, profiles/block_nt_probe_r03.txt)
-    if (h->lcfg.vec == 4 && step_bytes < ((size_t)40 << 20)) h->lcfg.block = 64;
-    h->can_vec4 = can_vec4; h->can_vec2 = can_vec2; h->lds_ok = lds_ok;
-}
-
 void recompute_extras(gymnet_vecenv *h) {
     h->extras = (h->cfg.flags & (GYMNET_FLAG_DONE_LIST | GYMNET_FLAG_EPISODE_STATS | GYMNET_FLAG_FINAL_OBS)) != 0 ||
                 h->d_lane_seed != nullptr;
@@ -350,6 +127,14 @@ int seed_handle(gymnet_vecenv *h, uint64_t seed) {
     h->d_lane_seed = nullptr;   // back to one key for all lanes (d_lane_seed_buf is kept for the next Seed(int[]))
     recompute_extras(h);
     return write_tick(h);
+}
+
+// after a step launch with GYMNET_FLAG_DOUBLE_BUFFER: what was written becomes current
+void swap_buffers(gymnet_vecenv *h) {
+    if (!h->double_buffer) return;
+    if (h->desc->alias) { std::swap(h->d_state, h->d_state_alt); h->d_obs = h->d_state; h->d_obs_alt = h->d_state_alt; }
+    else std::swap(h->d_obs, h->d_obs_alt);
+    h->cur ^= 1;
 }
 
 // one vector step = one kernel launch; bumps the host mirrors of the device-side counters
@@ -375,15 +160,7 @@ int launch_one_step(gymnet_vecenv *h, const void *d_actions) {
 
 template <class R>
 static int reset_lanes_typed(gymnet_vecenv *h, const uint8_t *d_mask) {
-    ResetArgsT<R> r{};
-    r.state = static_cast<R *>(h->d_state); r.obs = static_cast<R *>(h->d_obs); r.sbd = h->d_sbd; r.done = h->d_done;
-    r.mask = d_mask;
-    r.tick2 = h->d_tick2; r.lane_seed = h->d_lane_seed;
-    r.ep_ret = h->d_ep_ret; r.ep_len = h->d_ep_len;
-    r.n = h->n; r.state_stride = h->sstride; r.obs_stride = h->ostride;
-    r.lane_offset = (uint64_t)h->cfg.lane_offset; r.seed = h->seed;
-    r.parity = (int32_t)h->tslot;
-    HIP_TRY(h, launchers<R>(h).reset(r, h->stream));
+    HIP_TRY(h, launchers<R>(h).reset(make_reset_args<R>(h, d_mask), h->stream));
     h->tick += 1;
     h->tslot ^= 1;
     return GYMNET_OK;
@@ -460,11 +237,8 @@ int copy_out(gymnet_vecenv *h, void *obs_out, float *reward_out, uint8_t *done_o
 int validate_staged_actions(gymnet_vecenv *h, const void *d_actions) {
     const EnvDesc &d = *h->desc;
     if (!(h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) || d.box_action) return GYMNET_OK;
-    HIP_TRY(h, hipMemsetAsync(h->d_bad, 0, sizeof(uint32_t), h->stream));
-    HIP_TRY(h, launch_validate_discrete(static_cast<const int32_t *>(d_actions), h->n, d.action_n, h->d_bad, h->stream));
     uint32_t bad = 0;
-    HIP_TRY(h, hipMemcpyAsync(&bad, h->d_bad, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    ST_TRY(count_bad_actions(h, 1, [&](int64_t) { return d_actions; }, &bad));
     if (bad)
         return fail(h, GYMNET_ERR_INVALID_ACTION, "Action is outside of the configured action space. (%u of %lld lanes, Discrete(%d))",
                     bad, (long long)h->n, d.action_n);
@@ -484,192 +258,6 @@ int stage_host_actions(gymnet_vecenv *h, const void *actions, const void **d_use
     }
     return validate_now ? validate_staged_actions(h, *d_use) : GYMNET_OK;
 }
-
-// `steps` vector steps, one kernel launch each (caller has ENTERed the handle)
-int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride, int64_t ring, int graph_mode) {
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (steps < 0 || ring < 1 || action_stride < 0) return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride");
-    if (h->lcfg.vec > 1 && (!aligned_to(d_actions, 4 * h->lcfg.vec) || (action_stride % h->lcfg.vec) != 0))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions and action_stride must be %d-byte aligned", 4 * h->lcfg.vec);
-    const char *base = static_cast<const char *>(d_actions);
-    auto slice = [&](int64_t t) -> const void * { return base + (size_t)((t % ring) * action_stride) * 4; };
-    if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && !h->desc->box_action && steps > 0) {
-        // Discrete.Contains over every slice the rollout will read, before any state changes (one readback)
-        HIP_TRY(h, hipMemsetAsync(h->d_bad, 0, sizeof(uint32_t), h->stream));
-        for (int64_t k = 0; k < (steps < ring ? steps : ring); ++k)
-            HIP_TRY(h, launch_validate_discrete(static_cast<const int32_t *>(slice(k)), h->n, h->desc->action_n, h->d_bad, h->stream));
-        uint32_t bad = 0;
-        HIP_TRY(h, hipMemcpyAsync(&bad, h->d_bad, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (bad) return fail(h, GYMNET_ERR_INVALID_ACTION, "Action is outside of the configured action space. (%u lane-steps, Discrete(%d))", bad, h->desc->action_n);
-    }
-
-    // graph length: a multiple of `ring` (so every replay starts at slice 0) and even (so the double-buffered
-    // device tick, done-count halves and observation buffers are the same at every replay)
-    int64_t glen = (ring % 2 == 0) ? ring : 2 * ring;
-    int64_t t = 0;
-    // Graph replay only pays while the host launch path (~3.5 us per launch) is the bottleneck: measured on
-    // MI355X, replay beats eager launches up to ~2^18 CartPole lanes (2.6 vs 5.7 us/step at 2^16), ties at 2^19
-    // and loses at 2^20 (8.08 vs 7.85 us/step: a kernel node costs more than a back-to-back stream launch).
-    const bool launch_bound = (size_t)h->n * bytes_per_step(h) < ((size_t)24 << 20);
-    if (graph_mode < 0) graph_mode = h->graph_mode;          // gymnet_vecenv_set_launch_policy(.graph)
-    const bool use_graph = graph_mode >= 0 ? graph_mode != 0 : launch_bound;
-    if (use_graph && glen <= 4096 && steps >= glen) {
-        const int parity = h->tslot, cparity = (int)(h->step_launches & 1u), cur = h->cur;
-        GraphEntry *ge = nullptr;
-        for (auto &g : h->graphs)
-            if (g.actions == d_actions && g.len == glen && g.stride == action_stride && g.ring == ring && g.parity == parity &&
-                g.cparity == cparity && g.cur == cur)
-                ge = &g;
-        if (!ge) {
-            const uint64_t tick0 = h->tick, sl0 = h->step_launches, ls0 = h->lane_steps;
-            const int slot0 = h->tslot, cur0 = h->cur, lcp0 = h->last_cparity;
-            HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            int st = GYMNET_OK;
-            for (int64_t k = 0; k < glen && st == GYMNET_OK; ++k) st = launch_one_step(h, slice(k));
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamEndCapture(h->stream, &graph);
-            // capturing launched nothing: rewind the host mirrors (glen is even, so the buffer pair is back where it was)
-            h->tick = tick0; h->step_launches = sl0; h->lane_steps = ls0; h->tslot = slot0; h->last_cparity = lcp0;
-            if (h->cur != cur0) swap_buffers(h);
-            if (st != GYMNET_OK) { if (graph) (void)hipGraphDestroy(graph); return st; }
-            if (e != hipSuccess) return fail(h, GYMNET_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            hipGraphExec_t exec = nullptr;
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            if (e != hipSuccess) { (void)hipGraphDestroy(graph); return fail(h, GYMNET_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-            if (h->graphs.size() >= kMaxGraphs) {   // a trainer that keeps reallocating its action buffer must not leak graphs
-                size_t lru = 0;
-                for (size_t i = 1; i < h->graphs.size(); ++i) if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
-                HIP_TRY(h, hipStreamSynchronize(h->stream));          // the evicted exec may still be running
-                destroy_graph(h->graphs[lru]);
-                h->graphs.erase(h->graphs.begin() + (long)lru);
-            }
-            h->graphs.push_back(GraphEntry{d_actions, glen, action_stride, ring, parity, cparity, cur, graph, exec, 0});
-            ge = &h->graphs.back();
-        }
-        ge->last_use = ++h->graph_clock;
-        for (; t + glen <= steps; t += glen) {
-            HIP_TRY(h, hipGraphLaunch(ge->exec, h->stream));
-            h->tick += (uint64_t)glen;
-            h->step_launches += (uint64_t)glen;
-            h->lane_steps += (uint64_t)glen * (uint64_t)h->n;
-            h->last_cparity = (int)((h->step_launches - 1) & 1u);
-        }
-    }
-    for (; t < steps; ++t) ST_TRY(launch_one_step(h, slice(t)));
-    return GYMNET_OK;
-}
-
-// ~1.5 us per poll over PCIe: the resident kernel leaves after ~4-5 ms without a command (rounds 4-5: 40000 polls = 50-75 ms).  While
-// it spins it occupies the handle's stream and one wave, and anything that waits for the WHOLE device — hipDeviceSynchronize,
-// torch.cuda.synchronize(), a hipFree out of a caching allocator — or that serialises dispatch (rocprofv3 --pmc, AMD_SERIALIZE_KERNEL)
-// waits for this timeout: it bounds what a host that mixes an env loop with other GPU work in one process can lose per
-// such call.  A loop that steps back to back never sees it; a step after a longer pause pays one relaunch (~20 us, the launch path's
-// cost).  GYMNET_FLAG_RESIDENT is opt-in in every facade for the same reason.
-constexpr uint64_t kResidentIdlePolls = 3000;
-
-// a polite busy-wait: the host thread spins on a cache line the GPU writes over PCIe
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield" ::: "memory");
-#endif
-}
-
-template <class R>
-static int resident_start_typed(gymnet_vecenv *h) {
-    StepArgsT<R> a = make_step_args<R>(h, h->mb_dev->actions);       // the kernel reads its actions straight from the mailbox
-    ResetArgsT<R> r{};
-    r.state = static_cast<R *>(h->d_state); r.obs = static_cast<R *>(h->d_obs); r.sbd = h->d_sbd; r.done = h->d_done; r.mask = nullptr;
-    r.tick2 = h->d_tick2; r.lane_seed = h->d_lane_seed; r.ep_ret = h->d_ep_ret; r.ep_len = h->d_ep_len;
-    r.n = h->n; r.state_stride = h->sstride; r.obs_stride = h->ostride; r.lane_offset = (uint64_t)h->cfg.lane_offset; r.seed = h->seed;
-    r.parity = (int32_t)h->tslot;
-    HIP_TRY(h, launchers<R>(h).resident(h->autoreset, h->extras, a, r, h->mb_dev, kResidentIdlePolls, h->stream));
-    return GYMNET_OK;
-}
-
-static int resident_start(gymnet_vecenv *h) {
-    // the kernel picks the sequence number it continues from out of the mailbox: nothing is pending at this point
-    __atomic_store_n(&h->mb->exited, 0u, __ATOMIC_RELAXED);
-    __atomic_store_n(&h->mb->done_seq, h->mb_seq, __ATOMIC_RELAXED);
-    __atomic_store_n(&h->mb->cmd_seq, h->mb_seq, __ATOMIC_RELEASE);
-    ST_TRY(h->f64 ? resident_start_typed<double>(h) : resident_start_typed<float>(h));
-    h->resident_running = true;
-    return GYMNET_OK;
-}
-
-// Tells a running resident kernel to leave and waits until it has; the engine tick it kept in a register comes back through
-// the mailbox (and through both halves of d_tick2 for the next launch).
-int resident_stop(gymnet_vecenv *h) {
-    if (!h->resident_running) return GYMNET_OK;
-    if (!__atomic_load_n(&h->mb->exited, __ATOMIC_ACQUIRE)) {
-        h->mb->cmd = kMailboxExit;
-        __atomic_store_n(&h->mb->cmd_seq, ++h->mb_seq, __ATOMIC_RELEASE);
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->resident_running = false;
-    h->tick = h->mb->tick;
-    return GYMNET_OK;
-}
-
-// One command through the mailbox: post it, wait for its results, copy them out.  actions: host, or NULL (resets).
-static int resident_command(gymnet_vecenv *h, uint32_t cmd, const void *actions, void *obs_out, float *reward_out, uint8_t *done_out) {
-    const EnvDesc &d = *h->desc;
-    if (h->resident_running && __atomic_load_n(&h->mb->exited, __ATOMIC_ACQUIRE)) ST_TRY(resident_stop(h));   // it timed out since the last call
-    if (!h->resident_running) ST_TRY(resident_start(h));
-    if (actions) std::memcpy(h->mb->actions, actions, (size_t)h->n * 4);
-    h->mb->cmd = cmd;
-    const uint64_t seq = ++h->mb_seq;
-    __atomic_store_n(&h->mb->cmd_seq, seq, __ATOMIC_RELEASE);
-    uint64_t spins = 0;
-    const auto t_start = std::chrono::steady_clock::now();
-    while (__atomic_load_n(&h->mb->done_seq, __ATOMIC_ACQUIRE) != seq) {
-        if ((++spins & 0x3FFu) == 0) {
-            if (__atomic_load_n(&h->mb->exited, __ATOMIC_ACQUIRE)) {
-                // the kernel left (idle timeout) in the instant this command was posted, without serving it: it touches
-                // nothing any more — wait for it to be gone, start a new one, which finds the command pending
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                h->resident_running = false;
-                h->tick = h->mb->tick;
-                if (__atomic_load_n(&h->mb->done_seq, __ATOMIC_ACQUIRE) == seq) break;
-                __atomic_store_n(&h->mb->exited, 0u, __ATOMIC_RELAXED);
-                ST_TRY(h->f64 ? resident_start_typed<double>(h) : resident_start_typed<float>(h));
-                h->resident_running = true;
-            } else if (hipStreamQuery(h->stream) == hipSuccess) {
-                // the stream is empty although nobody answered: the kernel is gone.  Nothing will ever read the posted command; resync
-                // the tick from what the kernel last published so that the next call starts a fresh kernel on consistent state
-                h->resident_running = false;
-                h->tick = h->mb->tick;
-                __atomic_store_n(&h->mb->done_seq, seq, __ATOMIC_RELAXED);      // the command is void: a restarted kernel must not run it late
-                return fail(h, GYMNET_ERR_HIP, "the resident kernel ended without answering command %llu", (unsigned long long)seq);
-            }
-            if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(10)) {
-                //  do not leave the command in the mailbox for a late-waking kernel to apply to NEWER actions: overwrite it
-                // with EXIT, wait until the kernel has left (it publishes its tick on the way out), void the sequence number
-                h->mb->cmd = kMailboxExit;
-                __atomic_store_n(&h->mb->cmd_seq, ++h->mb_seq, __ATOMIC_RELEASE);
-                (void)hipStreamSynchronize(h->stream);
-                h->resident_running = false;
-                h->tick = h->mb->tick;
-                return fail(h, GYMNET_ERR_HIP, "the resident kernel did not answer command %llu within 10 s; it has been stopped and the next call starts a new one",
-                            (unsigned long long)seq);
-            }
-        }
-        cpu_relax();
-    }
-    const char *mb_obs = reinterpret_cast<const char *>(h->mb) + kMailboxObsOffset;
-    if (obs_out) std::memcpy(obs_out, mb_obs, (size_t)h->n * d.obs_dim * h->esz);
-    if (reward_out) std::memcpy(reward_out, h->mb->reward, (size_t)h->n * 4);
-    if (done_out) std::memcpy(done_out, h->mb->done, (size_t)h->n);
-    h->tick = h->mb->tick;
-    if (cmd == kMailboxStep) h->lane_steps += (uint64_t)h->n;
-    return GYMNET_OK;
-}
-
-// the resident path serves this handle's host-boundary steps right now (everything that changes what the kernel's arguments
-// describe — seeds, per-lane keys, state, policy — goes through ENTER, which makes the kernel leave first; it restarts with fresh arguments)
-static bool resident_serves(const gymnet_vecenv *h) { return h->resident && !h->async_pending; }
 
 }  // namespace gymnet
 
@@ -736,9 +324,8 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     if (!h) return GYMNET_OK;
     DeviceScope dev_scope;
     (void)hipSetDevice(h->device);
-    if (h->resident_running) (void)resident_stop(h);
+    resident_release(h);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->mb) (void)hipHostFree(h->mb);
     drop_graphs(h);
     for (void *p : h->owned) (void)hipFree(p);
     if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
@@ -873,16 +460,7 @@ int gymnet_vecenv_create(const gymnet_config *cfg, gymnet_vecenv **out) {
             h->hm_block = nullptr;             // fall back to the memcpy path
         }
     }
-    if (cfg->flags & GYMNET_FLAG_RESIDENT) {
-        void *blk = nullptr;
-        CREATE_HIP(hipHostMalloc(&blk, kMailboxBytes, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(blk, 0, kMailboxBytes);
-        h->mb = static_cast<Mailbox *>(blk);
-        void *dev = nullptr;
-        CREATE_HIP(hipHostGetDevicePointer(&dev, blk, 0));
-        h->mb_dev = static_cast<Mailbox *>(dev);
-        h->resident = true;
-    }
+    if (cfg->flags & GYMNET_FLAG_RESIDENT) CREATE_TRY(resident_create(h));
     if (d.has_sbd && !h->autoreset) CREATE_TRY(dalloc(h, &h->d_sbd, (size_t)padded));
     if (cfg->flags & GYMNET_FLAG_FINAL_OBS) CREATE_TRY(dalloc(h, (char **)&h->d_final_obs, (size_t)h->n * d.obs_dim * esz));
     if (cfg->flags & GYMNET_FLAG_DONE_LIST) {
@@ -988,7 +566,7 @@ int gymnet_vecenv_reset(gymnet_vecenv *h, void *obs_out) {
     return guarded([&]() -> int {
     ENTER_KEEP_RESIDENT(h);
     if (resident_serves(h)) return resident_command(h, kMailboxResetAll, nullptr, obs_out, nullptr, nullptr);
-    if (h->resident_running) ST_TRY(resident_stop(h));
+    if (h->res.running) ST_TRY(resident_stop(h));
     ST_TRY(launch_reset_lanes(h, nullptr));
     return copy_out(h, obs_out, nullptr, nullptr);
     });
@@ -998,7 +576,7 @@ int gymnet_vecenv_reset_where(gymnet_vecenv *h, const uint8_t *mask, void *obs_o
     return guarded([&]() -> int {
     ENTER_KEEP_RESIDENT(h);
     if (!mask && !h->autoreset && resident_serves(h)) return resident_command(h, kMailboxResetDone, nullptr, obs_out, nullptr, nullptr);
-    if (h->resident_running) ST_TRY(resident_stop(h));
+    if (h->res.running) ST_TRY(resident_stop(h));
     if (!mask && h->autoreset) return copy_out(h, obs_out, nullptr, nullptr);   // no-op, see gymnet_vecenv_reset_where_device
     if (mask) {
         ST_TRY(ensure_staging(h, false, false, true));
@@ -1397,27 +975,6 @@ int gymnet_vecenv_device_view(gymnet_vecenv *h, gymnet_device_view *out) {
     });
 }
 
-int gymnet_vecenv_launch_policy(gymnet_vecenv *h, int32_t *vec, int32_t *block, int32_t *nt, int32_t *sequential_lanes) {
-    return guarded([&]() -> int {
-    if (!h) return fail(nullptr, GYMNET_ERR_INVALID_ARG, "null handle");
-    if (vec) *vec = h->lcfg.vec;
-    if (block) *block = h->lcfg.block;
-    if (nt) *nt = h->lcfg.nt;
-    if (sequential_lanes) {      // what the launcher resolves to (lanes, or lane pairs, a thread works through one after another)
-        *sequential_lanes = next_step_kernel(h, h->lcfg).sequential;
-    }
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity) {
-    return guarded([&]() -> int {
-    if (!h || !buf || capacity < 1) return fail(h, GYMNET_ERR_INVALID_ARG, "null handle / buffer");
-    next_step_kernel(h, h->lcfg).name(buf, (size_t)capacity);
-    return GYMNET_OK;
-    });
-}
-
 int gymnet_vecenv_get_state(gymnet_vecenv *h, void *state_soa_v) {
     return guarded([&]() -> int {
     ENTER(h);
@@ -1712,28 +1269,6 @@ int gymnet_vecenv_sample_actions(gymnet_vecenv *h, void *actions_out, uint64_t s
     ENTER(h);
     HIP_TRY(h, hipMemcpyAsync(actions_out, h->d_actions, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GYMNET_OK;
-    });
-}
-
-int gymnet_vecenv_set_launch_policy(gymnet_vecenv *h, const gymnet_launch_policy *p) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (!p) return fail(h, GYMNET_ERR_INVALID_ARG, "policy is null");
-    if (p->struct_size != sizeof(gymnet_launch_policy))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "policy.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(gymnet_launch_policy));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));     // no launch of the old configuration is still being captured / replayed
-    return apply_policy(h, *p, /*strict=*/true);
-    });
-}
-
-int gymnet_vecenv_get_launch_policy(gymnet_vecenv *h, gymnet_launch_policy *out) {
-    return guarded([&]() -> int {
-    if (!h || !out) return fail(h, GYMNET_ERR_INVALID_ARG, "null argument");
-    out->struct_size = sizeof *out;
-    out->vec = h->lcfg.vec; out->block = h->lcfg.block; out->nt = h->lcfg.nt; out->sequential_lanes = h->lcfg.items;
-    out->reset_form = h->lcfg.reset_form; out->lds_pipe = h->lcfg.lds_pipe; out->occupancy_lds_bytes = h->lcfg.lds_bytes;
-    out->graph = h->graph_mode;
     return GYMNET_OK;
     });
 }

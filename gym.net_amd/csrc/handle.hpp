@@ -1,4 +1,7 @@
-// handle.hpp — what a gymnet_vecenv handle IS, plus the host-side helpers capi.hip, group.hip and the attachment units share.
+// handle.hpp — what a gymnet_vecenv handle IS, plus the host-side helpers the library's units share.  capi.hip holds the C entry points
+// of the handle itself and the host boundary; three subsystems with state of their own on the handle have a unit each —
+// launch_policy.hip (h->lcfg and what may replace it), resident.hip (h->res: the mailbox and its kernel), step_graph.hip (h->graph: the
+// captured rollouts) — beside group.hip and the attachment units.
 // Internal to the library: nothing here crosses the C ABI (include/gymnet_amd.h is the boundary).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,15 +33,21 @@ struct EnvDesc {
 };
 extern const EnvDesc kEnvs[kNumEnvs];
 
-struct GraphEntry {
-    const void *actions;
-    int64_t len, stride, ring;
-    int parity, cparity, cur;
-    hipGraph_t graph;
-    hipGraphExec_t exec;
-    uint64_t last_use;
+// GYMNET_FLAG_RESIDENT (num_envs <= 64): the mailbox in coherent host memory and the state of the resident kernel (resident.hip)
+struct Resident {
+    Mailbox *mb = nullptr;         // host address (page-locked, device-mapped, coherent)
+    Mailbox *mb_dev = nullptr;     // the same memory as the device sees it
+    bool enabled = false;          // the handle serves host-boundary steps / resets through the resident kernel
+    bool running = false;          // a resident kernel is (or may still be) on the stream
+    uint64_t seq = 0;              // sequence number of the last command posted
 };
-constexpr size_t kMaxGraphs = 8;       // per handle; least-recently-used entry is destroyed beyond this
+
+// the graph-replay rollout (step_graph.hip): the captured graphs, made on the first capture and gone with drop_graphs
+struct GraphCache;
+struct StepGraphs {
+    GraphCache *cache = nullptr;
+    int mode = -1;                 // gymnet_launch_policy.graph: -1 = by batch size, 0 = eager launches, 1 = hipGraph replay
+};
 
 struct RenderStaging;
 struct PixelStack;
@@ -102,12 +111,7 @@ struct gymnet_vecenv {
     float *pin_reward = nullptr;
     uint8_t *pin_done = nullptr;
     uint32_t *d_bad = nullptr;
-    // GYMNET_FLAG_RESIDENT (num_envs <= 64): the mailbox in coherent host memory and the state of the resident kernel
-    gymnet::Mailbox *mb = nullptr;         // host address (page-locked, device-mapped, coherent)
-    gymnet::Mailbox *mb_dev = nullptr;     // the same memory as the device sees it
-    bool resident = false;                 // the handle serves host-boundary steps / resets through the resident kernel
-    bool resident_running = false;         // a resident kernel is (or may still be) on the stream
-    uint64_t mb_seq = 0;                   // sequence number of the last command posted
+    gymnet::Resident res;
     void *d_ep_seg = nullptr;      // fused rollout: segmented episode records + shard counters (allocated on first use, grown on demand)
     int64_t ep_seg_cap = 0;        // records per shard segment
     int64_t ep_ov_cap = 0;         // records of the shared overflow segment (= the largest ep_capacity asked for so far)
@@ -125,11 +129,9 @@ struct gymnet_vecenv {
     std::atomic<bool> busy{false};
     int simds = 1024;              // SIMD units of the device (multiProcessorCount x 4), read at create
     gymnet::LaunchCfg lcfg{4, 256, 0, 0, 1};
-    int graph_mode = -1;           // gymnet_launch_policy.graph: -1 = by batch size, 0 = eager launches, 1 = hipGraph replay
     bool can_vec4 = false, can_vec2 = false, lds_ok = false;   // what the buffers' alignment / the batch size allow (set at create)
     bool compact_only = false;     // GYMNET_FLAG_COMPACT_RECORDS_ONLY
-    std::vector<gymnet::GraphEntry> graphs;
-    uint64_t graph_clock = 0;
+    gymnet::StepGraphs graph;
     std::vector<void *> owned;     // device allocations to free
     std::string err;
 };
@@ -184,7 +186,7 @@ struct BusyGuard {
     HIP_TRY(h, hipSetDevice((h)->device))
 #define ENTER(h)                                                                                                   \
     ENTER_KEEP_RESIDENT(h);                                                                                        \
-    if ((h)->resident_running) { int rs_ = ::gymnet::resident_stop(h); if (rs_ != GYMNET_OK) return rs_; }
+    if ((h)->res.running) { int rs_ = ::gymnet::resident_stop(h); if (rs_ != GYMNET_OK) return rs_; }
 
 // Nothing may throw across the C ABI: every entry point body runs inside this guard.
 template <class F>
@@ -263,19 +265,90 @@ inline size_t bytes_per_step(const gymnet_vecenv *h) { return h->f64 ? (size_t)7
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned_to(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
 
+// the arguments of a step launch that reads its actions at d_actions / of a reset of the lanes d_mask marks (NULL = all lanes), as the
+// handle stands
+template <class R>
+inline StepArgsT<R> make_step_args(gymnet_vecenv *h, const void *d_actions) {
+    StepArgsT<R> a{};
+    const bool alias = h->desc->alias;
+    a.state = static_cast<R *>(h->d_state);
+    a.state_out = static_cast<R *>((h->double_buffer && alias) ? h->d_state_alt : h->d_state);
+    a.obs = static_cast<R *>((h->double_buffer && !alias) ? h->d_obs_alt : h->d_obs);
+    a.obs_in = static_cast<const R *>(h->d_obs);
+    a.action = d_actions;
+    a.reward = h->d_reward;
+    a.done = h->d_done;
+    a.sbd = h->d_sbd;
+    a.tick2 = h->d_tick2;
+    // the dense "last finished episode per lane" arrays are maintained by the step kernel itself unless the caller opted for
+    // compact records only (GYMNET_FLAG_COMPACT_RECORDS_ONLY with DONE_LIST): then the getters apply the records on demand
+    const bool dense = !(h->compact_only && h->d_done_list);
+    a.final_obs = dense ? static_cast<R *>(h->d_final_obs) : nullptr;
+    a.done_list = h->d_done_list;
+    a.done_count2 = h->d_done_count2;
+    a.done_cap = h->done_cap;
+    a.ep_ret = h->d_ep_ret; a.ep_len = h->d_ep_len; a.fin_ret = dense ? h->d_fin_ret : nullptr; a.fin_len = dense ? h->d_fin_len : nullptr;
+    a.rec_ret = h->d_rec_ret; a.rec_len = h->d_rec_len; a.rec_obs = static_cast<R *>(h->d_rec_obs);
+    a.lane_seed = h->d_lane_seed;
+    a.after_done = h->d_after_done;
+    a.n = h->n; a.state_stride = h->sstride; a.obs_stride = h->ostride;
+    a.lane_offset = (uint64_t)h->cfg.lane_offset;
+    a.seed = h->seed;
+    a.parity = (int32_t)h->tslot;
+    a.cparity = (int32_t)(h->step_launches & 1u);
+    a.max_episode_steps = h->cfg.max_episode_steps;
+    return a;
+}
+template <class R>
+inline ResetArgsT<R> make_reset_args(gymnet_vecenv *h, const uint8_t *d_mask) {
+    ResetArgsT<R> r{};
+    r.state = static_cast<R *>(h->d_state); r.obs = static_cast<R *>(h->d_obs); r.sbd = h->d_sbd; r.done = h->d_done;
+    r.mask = d_mask;
+    r.tick2 = h->d_tick2; r.lane_seed = h->d_lane_seed;
+    r.ep_ret = h->d_ep_ret; r.ep_len = h->d_ep_len;
+    r.n = h->n; r.state_stride = h->sstride; r.obs_stride = h->ostride;
+    r.lane_offset = (uint64_t)h->cfg.lane_offset; r.seed = h->seed;
+    r.parity = (int32_t)h->tslot;
+    return r;
+}
+
 // ---- helpers that assume the caller already ENTERed the handle (device set, busy flag held) ----------------------
+// Discrete.Contains over `slices` device slices of h->n actions each, slice k at slice_of(k), with one readback; blocks.  *bad: how many
+// actions lie outside the space (the callers word the error: lanes of one batch, lane-steps of a rollout)
+template <class SliceOf>
+inline int count_bad_actions(gymnet_vecenv *h, int64_t slices, SliceOf slice_of, uint32_t *bad) {
+    HIP_TRY(h, hipMemsetAsync(h->d_bad, 0, sizeof(uint32_t), h->stream));
+    for (int64_t k = 0; k < slices; ++k)
+        HIP_TRY(h, launch_validate_discrete(static_cast<const int32_t *>(slice_of(k)), h->n, h->desc->action_n, h->d_bad, h->stream));
+    *bad = 0;
+    HIP_TRY(h, hipMemcpyAsync(bad, h->d_bad, sizeof *bad, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GYMNET_OK;
+}
+// capi.hip
 int launch_one_step(gymnet_vecenv *h, const void *d_actions);       // one vector step = one kernel launch
 int launch_reset_lanes(gymnet_vecenv *h, const uint8_t *d_mask);    // NULL = all lanes
+void swap_buffers(gymnet_vecenv *h);                                 // after a step launch with GYMNET_FLAG_DOUBLE_BUFFER: what was written becomes current
 int stage_host_actions(gymnet_vecenv *h, const void *actions, const void **d_use, bool validate_now);
 int validate_staged_actions(gymnet_vecenv *h, const void *d_actions);
 // obs_out: float32 [n, obs_dim], or float64 for a GYMNET_FLAG_F64 handle
 int queue_copy_out(gymnet_vecenv *h, void *obs_out, float *reward_out, uint8_t *done_out);   // no final sync (large-batch path)
 int copy_out(gymnet_vecenv *h, void *obs_out, float *reward_out, uint8_t *done_out);         // blocks
-// graph_mode: -1 = by batch size (replay only while launch-bound), 0 = eager launches, 1 = always replay a captured graph
-int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride, int64_t ring, int graph_mode = -1);
 int write_tick(gymnet_vecenv *h);
 int seed_handle(gymnet_vecenv *h, uint64_t seed);                    // Env.Seed(int): new key, tick 0, captured graphs dropped
+// launch_policy.hip
+void default_policy(gymnet_vecenv *h);                               // the launch configuration a handle starts with (launch_policy.hpp), at create
+// step_graph.hip
+// graph_mode: -1 = by batch size (replay only while launch-bound), 0 = eager launches, 1 = always replay a captured graph
+int rollout_steps(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride, int64_t ring, int graph_mode = -1);
+void drop_graphs(gymnet_vecenv *h);                                  // whatever a captured launch froze (configuration, seed, keys) changes
+// resident.hip
+int resident_create(gymnet_vecenv *h);                               // the mailbox of a GYMNET_FLAG_RESIDENT handle, at create
+void resident_release(gymnet_vecenv *h);                             // stops the kernel and frees the mailbox, at destroy
 int resident_stop(gymnet_vecenv *h);                                 // tells a running resident kernel to leave and waits until it has
+bool resident_serves(const gymnet_vecenv *h);                        // the resident path serves this handle's host-boundary steps right now
+// one command (kMailboxStep / ResetAll / ResetDone) through the mailbox: post it, wait for its results, copy them out
+int resident_command(gymnet_vecenv *h, uint32_t cmd, const void *actions, void *obs_out, float *reward_out, uint8_t *done_out);
 // the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch,
 // by the unit that serves the handle as it stands (records: the rollout keeps compact episode records; rec_logp: where it records every
 // step's log-probability, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps` on and is current

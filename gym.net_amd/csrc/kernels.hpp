@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_policy.hpp"
+
 namespace gymnet {
 
 // Everything one vector-step launch needs.  Passed by value (kernarg segment).
@@ -59,20 +61,10 @@ template <class R>
 using StepKernelFn = void (*)(R *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2, float *reward, int32_t block,
                               int32_t parity, StepArgsT<R> rest);
 
-// vec: envs per thread (4 = dwordx4 streams, 1 = scalar); block: threads per workgroup;
-// nt: non-temporal mask (0 none, 12 action + reward/done streams, 15 every stream)
 constexpr int kShards = 256;        // power of two; the gather kernels' workgroup size (kernels.hip static_assert)
 constexpr int kCountStride = 16;    // uint32 words between shard counters (64 bytes: one counter per cache line)
 constexpr int kAfterStride = 8;     // uint64 words between after_done shards (64 bytes)
-
-// lds_bytes: unused dynamic LDS requested per workgroup, for the ONE purpose of capping occupancy in probes (one-shot kernel)
-// items: lanes per thread of the fully unrolled software-pipelined kernel (envs with PIPELINED only; 1 = one-shot kernel)
-// reset_form: 1 = wave-compacted fused reset in the one-step kernel (reset_pending_wave: envs whose observation aliases the
-// state, dwordx4 lanes)
-// lds_pipe: 1 = the multi-lane kernel in its producer / consumer form (step_kernel_lds: `items` tiles per workgroup)
-// simds: SIMD units of the handle's device (multiProcessorCount x 4; 1024 on MI355X) — sizes the resident generation of the looped
-// multi-pair kernel (step_kernels.hpp pipe2_chunks) and the policy's waves-per-SIMD windows (capi.hip default_policy)
-struct LaunchCfg { int vec; int block; int nt; int lds_bytes = 0; int items = 1; int reset_form = 0; int lds_pipe = 0; int simds = 1024; };
+// (LaunchCfg, a launch's configuration, and the rules that choose a handle's first one: launch_policy.hpp)
 
 // Fused multi-step rollout: `steps` vector steps inside ONE launch; state stays in registers between steps.
 // Round 5: the rollout carries what its consumer needs (examples/.../PlaySessions/BasePlaySession.cs:58-69 accumulates the episode

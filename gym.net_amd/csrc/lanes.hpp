@@ -4,7 +4,7 @@
 // A thread owns VEC consecutive lanes i0 .. i0 + VEC - 1 (i0 a multiple of VEC) and moves them with the widest access the row
 // allows: up to 16 bytes per instruction (dwordx4) — 4 floats, 2 doubles, 4 int32 — so a 4-lane float row and a 2-lane double
 // row are ONE global_load_dwordx4 each; a VEC-lane row wider than 16 bytes (4 doubles) is split into 16-byte pieces.  The
-// launcher (capi: default_policy / apply_policy) only selects VEC > 1 when the row base and stride are aligned for it.
+// launcher (launch_policy.hpp default_policy / launch_policy.hip apply_policy) only selects VEC > 1 when the row base and stride are aligned for it.
 //   NT     non-temporal (streaming) access: `global_load/store ... nt`.  Which streams get it is a measured policy
 //          (tools/probe_step.hip): it decides what stays in the 256 MiB Infinity Cache between launches.
 //   GUARD  per-element bounds checks; only the last (partial) workgroup of a launch runs the guarded form.

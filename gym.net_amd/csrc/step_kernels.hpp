@@ -16,7 +16,7 @@
 // What the counters say (profiles/rocprof_pmc_r01.txt): every launch fetches all of its input bytes through the
 // fabric again — the per-XCD L2s keep nothing across a kernel boundary — so the only cross-launch reuse level
 // is the 256 MiB Infinity Cache, and an XCD-aware block remap would buy nothing here; what matters instead is
-// which streams are marked non-temporal (the NT template parameter, chosen from the batch size in capi.hip).
+// which streams are marked non-temporal (the NT template parameter, chosen from the batch size in launch_policy.hpp).
 // At 2^20 lanes all waves are resident at once and run load -> math -> store in lock-step, so beyond the memory
 // floor every VALU instruction is exposed: hence the in-house sincos, the fma-pair constant division and the
 // loop-compacted Philox reset (envs.hpp, below).  Done-lane compaction is one wave ballot + one atomic per wave.
@@ -1857,7 +1857,7 @@ static StepKernelT<typename Env::Real> select_step(bool autoreset, bool extras, 
         const bool any_n = has_split_reset<Env>() && autoreset;
         if (cfg.items > 1 && cfg.items <= 4 && !extras && cfg.vec == 2 && !cfg.lds_pipe && n > 0 && (any_n || n % (2 * (int64_t)cfg.items * 256) == 0)) {
             // every stream non-temporal, except that the four-pair form with the deferred reset also exists with the other two masks
-            // (the stream policy of a batch beyond one resident generation is a measured choice: capi.hip default_policy)
+            // (the stream policy of a batch beyond one resident generation is a measured choice: launch_policy.hpp default_policy)
             const int nt = (any_n && cfg.items == 4) ? cfg.nt : 15;
             with_bool(autoreset, [&](auto ar) {
                 with_int<2, 3, 4>(cfg.items, [&](auto items) {

@@ -533,7 +533,7 @@ int main(int argc, char **argv) {
         if (argc > 5) run_forms<Acrobot, 0>("Acrobot-v1 (16-byte lanes: not a library form)", LaunchCfg{1, 256, 15, 0, 4, 0, 0}, n, launches, rounds, st);
         return 0;
     }
-    // launch configurations: the library's defaults at 2^20 lanes (capi.hip default_policy); bytes MOVED per lane and step as in
+    // launch configurations: the library's defaults at 2^20 lanes (csrc/launch_policy.hpp default_policy); bytes MOVED per lane and step as in
     // profiles/roofline_r05.json (Pendulum keeps theta_dot in the observation array: 33, Acrobot 57)
     std::printf("[");
     run_env<CartPole>("CartPole-v1", 41, LaunchCfg{4, 256, 15, 0, 1, 1, 0}, n, launches, rounds, st, true);
