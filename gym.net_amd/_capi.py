@@ -225,6 +225,7 @@ PROTOTYPES = {
     "gymnet_vecenv_sample_actions_device": (C.c_int, [_H, _P, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_sample_actions": (C.c_int, [_H, _P, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_compose_actions_device": (C.c_int, [_H, _P, C.c_float, _P, C.c_uint64, C.c_uint64]),
+    "gymnet_gae_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P]),
     "gymnet_peer_buffer_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(IpcHandle)]),
     "gymnet_peer_buffer_open": (C.c_int, [C.c_int, C.POINTER(IpcHandle), C.POINTER(C.c_void_p)]),
     "gymnet_peer_buffer_close": (C.c_int, [C.c_int, _P]),

@@ -227,6 +227,7 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_sample_actions_masked_device(IntPtr h, IntPtr d_actions, IntPtr d_mask, long mask_stride, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_sample_actions(IntPtr h, void* actions_out, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_compose_actions_device(IntPtr h, IntPtr d_policy_actions, float epsilon, IntPtr d_actions_out, ulong seed, ulong tick);
+        [DllImport(Lib)] public static extern int gymnet_gae_device(int device, IntPtr stream, long steps, long count, long stride, IntPtr d_reward, IntPtr d_done, IntPtr d_value, IntPtr d_last_value, IntPtr d_boot, float gamma, float lambda, IntPtr d_advantage, IntPtr d_return);
 
         // ---- multi-GPU group (one process, G members)
         [DllImport(Lib)] public static extern int gymnet_group_create(ref GymnetGroupConfig cfg, out IntPtr group);

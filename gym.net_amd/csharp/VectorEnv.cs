@@ -29,6 +29,7 @@ namespace Gym.Envs.Amd {
         private int _stackDepth;
         private readonly int _obsDim;
         private readonly bool _boxAction;
+        private readonly int _device;
         private readonly bool _f64;                 // GymnetFlags.F64 (CartPole): every observation buffer holds doubles — the reference's
                                                     // actual dtype (CartPoleEnv.cs:166,185); the library writes 8 bytes per element
         internal ulong[] PendingLaneSeeds;          // filled by the lane proxies when the base-class Seed runs
@@ -37,7 +38,7 @@ namespace Gym.Envs.Amd {
         public VectorEnv(GymnetEnvId env, int numEnvs, int device = 0, ulong seed = 0, GymnetFlags flags = GymnetFlags.None,
                          long laneOffset = 0, int maxEpisodeSteps = 0)
             : base(numEnvs, MakeObservationSpace(env, out int obsDim), MakeActionSpace(env, out bool box)) {
-            _obsDim = obsDim; _boxAction = box;
+            _obsDim = obsDim; _boxAction = box; _device = device;
             _f64 = (flags & GymnetFlags.F64) != 0;
             var cfg = new GymnetConfig {
                 struct_size = (uint) sizeof(GymnetConfig), env_id = (int) env, num_envs = numEnvs, lane_offset = laneOffset,
@@ -320,6 +321,16 @@ namespace Gym.Envs.Amd {
         public void RolloutFusedLogp(GymnetRolloutSpec spec, IntPtr dRecLogp) {
             spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
             Native.Check(Native.gymnet_vecenv_rollout_fused_logp_device(_h, ref spec, dRecLogp));
+        }
+        /// GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written
+        /// out there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  dReward float [steps][N],
+        /// dDone byte [steps][N] (RolloutFused's records); dValue float [steps][N] or IntPtr.Zero (every value 0), dLastValue float [N],
+        /// dBoot float [steps][N] (V(terminal observation) of truncated lanes) or IntPtr.Zero; dAdvantage / dReturn float [steps][N],
+        /// either may be IntPtr.Zero.  dAdvantage may be dReward while dReturn is dValue, or the other way round.
+        public void AdvantagesDevice(long steps, IntPtr dReward, IntPtr dDone, IntPtr dValue, IntPtr dLastValue, IntPtr dAdvantage, IntPtr dReturn,
+                                     float gamma = 0.99f, float lambda = 0.95f, IntPtr dBoot = default) {
+            Native.Check(Native.gymnet_vecenv_device_view(_h, out GymnetDeviceView view));
+            Native.Check(Native.gymnet_gae_device(_device, view.stream, steps, NumberOfEnvironments, NumberOfEnvironments, dReward, dDone, dValue, dLastValue, dBoot, gamma, lambda, dAdvantage, dReturn));
         }
         /// The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous with w_L = 1; its one output,
         /// clamped to the env's bounds, is the action.  No layers releases it.  LoadActorWeights / ResetActor / PushActor serve both kinds.

@@ -391,6 +391,66 @@ class VectorEnv:
         else:
             capi.check(self._lib.gymnet_vecenv_rollout_fused_ex_device(self._h, C.byref(spec)))
 
+    def AdvantagesDevice(self, reward, done, values, advantage, returns, gamma=0.99, lam=0.95, last_value=None, boot=None):
+        """GAE(gamma, lam) advantages and advantage + value over the rows a rollout recorded, in one kernel launch on the handle's
+        device and stream (gymnet_gae_device: the recurrence is written out there), so it is ordered after the rollout with no
+        synchronise.  reward float32 [T, n] and done uint8 [T, n] are RolloutFusedDevice's rec_reward / rec_done (n = the handle's lanes).
+          values     None (every value is 0: with lam = 1 the advantage is the discounted reward-to-go), float32 [T, n] with last_value
+                     float32 [n] (None: 0), or float32 [T + 1, n] whose row T is the last value (last_value must then be None).
+                     values[t] is the value of the observation step t's action was chosen from: values[0] = V(observation before the
+                     rollout), values[t] = V(rec_obs[t - 1]), last value = V(rec_obs[T - 1])
+          boot       float32 [T, n]: V(terminal observation) where a time limit truncated the lane (done bit 1); None: a truncation counts
+                     as a termination
+          advantage, returns   caller-allocated float32 [T, n]; either may be None, not both.  advantage may be the reward tensor while
+                     returns is values' first T rows, or the other way round: each element is read before it is written.
+        Every argument is checked here, before any native call."""
+        dev = self.Device
+        reward = _logp_buffer(reward, getattr(reward, "shape", ()), "reward", dev)
+        if len(reward.shape) != 2 or int(reward.shape[1]) != self.NumberOfEnvironments:
+            raise ValueError(f"reward must have shape (T, {self.NumberOfEnvironments}), got {tuple(reward.shape)}")
+        T, n = int(reward.shape[0]), self.NumberOfEnvironments
+        if not hasattr(done, "data_ptr") or str(getattr(done, "dtype", None)) != "torch.uint8":
+            raise ValueError(f"done must be a device uint8 tensor of shape ({T}, {n}), got {getattr(done, 'dtype', type(done).__name__)}")
+        if tuple(int(v) for v in done.shape) != (T, n) or not getattr(done, "is_cuda", False) or not done.is_contiguous():
+            raise ValueError(f"done must be a contiguous device tensor of shape ({T}, {n}), got {tuple(done.shape)}")
+        index = getattr(getattr(done, "device", None), "index", None)
+        if dev is not None and index is not None and int(index) != int(dev):
+            raise ValueError(f"done is on device {index}, the handle on {dev}")
+        v_ptr = lv_ptr = None
+        if values is not None:
+            rows = int(values.shape[0]) if len(getattr(values, "shape", ())) == 2 else -1
+            if rows == T + 1:
+                if last_value is not None:
+                    raise ValueError("values has T + 1 rows (row T is the last value): last_value must be None")
+                _logp_buffer(values, (T + 1, n), "values", dev)
+                lv_ptr = C.c_void_p(values.data_ptr() + 4 * T * n)
+            else:
+                _logp_buffer(values, (T, n), "values", dev)
+            v_ptr = _ptr(values)
+        if last_value is not None:
+            lv_ptr = _ptr(_logp_buffer(last_value, (n,), "last_value", dev))
+        if boot is not None:
+            _logp_buffer(boot, (T, n), "boot", dev)
+        if advantage is None and returns is None:
+            raise ValueError("advantage and returns are both None")
+        if advantage is not None:
+            _logp_buffer(advantage, (T, n), "advantage", dev)
+        if returns is not None:
+            if values is not None and returns is values and int(values.shape[0]) == T + 1:
+                pass                                          # in place over the first T rows of a [T + 1, n] values tensor
+            else:
+                _logp_buffer(returns, (T, n), "returns", dev)
+        for name, g in (("gamma", gamma), ("lam", lam)):
+            if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, float, np.integer, np.floating)) or not 0.0 <= float(g) <= 1.0:
+                raise ValueError(f"{name} must be a number in [0, 1], got {g!r}")
+        if dev is None:
+            dev = getattr(getattr(reward, "device", None), "index", None)
+            if dev is None:
+                raise ValueError("the handle's device is not known and reward does not name one")
+        stream = self.DeviceView().stream
+        capi.check(self._lib.gymnet_gae_device(int(dev), C.c_void_p(stream), T, n, n, _ptr(reward), _ptr(done), v_ptr, lv_ptr, _ptr(boot),
+                                               float(gamma), float(lam), _ptr(advantage), _ptr(returns)))
+
     def SampleActionsDevice(self, d_actions, seed=0, tick=0):
         capi.check(self._lib.gymnet_vecenv_sample_actions_device(self._h, _ptr(d_actions), int(seed), int(tick)))
 

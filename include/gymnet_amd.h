@@ -842,6 +842,42 @@ int gymnet_vecenv_sample_actions_masked_device(gymnet_vecenv *h, int32_t *d_acti
 int gymnet_vecenv_compose_actions_device(gymnet_vecenv *h, const int32_t *d_policy_actions, float epsilon, int32_t *d_actions_out,
                                          uint64_t seed, uint64_t tick);
 
+/* ---- advantages and returns over a recorded rollout (the target of an on-policy update) ------------------------------------
+ * Generalized advantage estimation GAE(gamma, lambda) and advantage + value over the rows a fused rollout recorded (d_rec_reward,
+ * d_rec_done), one kernel launch, handle-less like the samplers above: on `stream` (a hipStream_t of `device`; NULL = default),
+ * stream-ordered, non-blocking, capturable (no allocation, copy or synchronise).  An added export: the ABI version stays 6.
+ * Arrays are [steps][stride] rows with stride >= count; lane i is column i, columns [count, stride) are neither read nor written:
+ *     r = d_reward[t][i] float32;  d = d_done[t][i] uint8 (bit 0 terminated, bit 1 truncated by max_episode_steps);
+ *     v = d_value[t][i] float32: the value of the observation the action of step t was chosen from;
+ *     d_last_value[i] float32: the value of the observation after step steps-1;  d_boot[t][i] float32 (optional, see below).
+ * Relative to a rollout's d_rec_obs: v[0] is the value of the observation before the rollout, v[t] = V(rec_obs[t-1]) and
+ * last_value = V(rec_obs[steps-1]).  With frame skip the rows are per DECISION and gamma discounts decisions; a discount that is
+ * exact per env step under idle sub-steps is not built.
+ * The arithmetic is float32, every operation rounds on its own, the only fusions are the two fmaf below; gl = gamma * lambda is one
+ * float32 product formed once.  Per lane, for t = steps-1 .. 0, carrying A (start +0.0f) and vnext (start d_last_value[i], or +0.0f
+ * where d_last_value is NULL):
+ *     cut   = d != 0
+ *     nv    = (d & 1) ? +0.0f : (d & 2) ? (d_boot ? d_boot[t][i] : +0.0f) : vnext          terminated wins over truncated
+ *     delta = fmaf(gamma, nv, r) - v
+ *     A     = cut ? delta : fmaf(gl, A, delta)
+ *     d_advantage[t][i] = A;   d_return[t][i] = A + v;   vnext = v
+ * d_value NULL: every v (and the vnext taken from it) is +0.0f; d_last_value and d_boot are still honoured if given (both are allowed
+ * without d_value: no combination of the three is refused).  With lambda = 1 the advantage is then the discounted reward-to-go, the
+ * REINFORCE target, and at gamma = 1 the episode return the reference trainer ranks by (BasePlaySession.cs:58-69).
+ * d_boot carries V(terminal observation) for lanes a time limit truncated: under GYMNET_FLAG_AUTORESET rec_obs[t] already holds the new
+ * episode's first observation there, so v[t+1] must not be used across a done row, and it is not.  Without d_boot a truncation is
+ * treated as a termination.
+ * Every input element is read exactly once (v[t+1] is the carried vnext, never a second load) and every thread reads row t of its
+ * columns before it writes row t, so two in-place forms are defined: d_return == d_value with d_advantage == d_reward, and
+ * d_advantage == d_value with d_return == d_reward (or either half of one).  Either output may be NULL, not both.
+ * steps == 0 or count == 0: a successful no-op.  GYMNET_ERR_INVALID_ARG (message: gymnet_last_error) for negative sizes,
+ * stride < count, a NULL d_reward / d_done, both outputs NULL, gamma or lambda not finite or outside [0, 1], a float pointer that is not
+ * 4-byte aligned, and any other aliasing equal pointers show: d_advantage == d_return, an output equal to d_done / d_boot / d_last_value.
+ * Nothing is written by a refused call. */
+int gymnet_gae_device(int device, void *stream, int64_t steps, int64_t count, int64_t stride,
+                      const float *d_reward, const uint8_t *d_done, const float *d_value, const float *d_last_value,
+                      const float *d_boot, float gamma, float lambda, float *d_advantage, float *d_return);
+
 /* ---- multi-GPU group: ONE process (e.g. a C# host) driving G members, one per GPU ----------------------------
  * The reference has no multi-device code; what shards is the independence of VecEnvWrapper's map (VecEnvWrapper.cs:22-24).
  * Member m owns the contiguous global lanes [m*N/G, (m+1)*N/G) (reset draws keyed by GLOBAL lane id: results do not depend

@@ -163,7 +163,7 @@ public:
         gymnet_config cfg{};
         cfg.struct_size = sizeof cfg; cfg.env_id = (int)env; cfg.num_envs = num_envs; cfg.lane_offset = lane_offset;
         cfg.device = device; cfg.flags = flags; cfg.seed = seed; cfg.stream = stream;
-        n_ = num_envs;
+        n_ = num_envs; device_ = device;
         check(gymnet_vecenv_create(&cfg, &h_));
     }
     VectorEnv(const VectorEnv &) = delete;
@@ -408,6 +408,15 @@ public:
         spec.struct_size = (uint32_t)sizeof spec;
         check(gymnet_vecenv_rollout_fused_logp_device(h_, &spec, d_rec_logp));
     }
+    // GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written out
+    // there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  d_reward float32 [steps][N], d_done
+    // uint8 [steps][N] (the fused rollout's records); d_value float32 [steps][N] or null (every value 0), d_last_value float32 [N], d_boot
+    // float32 [steps][N] (V(terminal observation) of truncated lanes) or null; d_advantage / d_return float32 [steps][N], either may be null.
+    // d_advantage may be d_reward while d_return is d_value, or the other way round.
+    void AdvantagesDevice(int64_t steps, const float *d_reward, const uint8_t *d_done, const float *d_value, const float *d_last_value,
+                          float *d_advantage, float *d_return, float gamma = 0.99f, float lambda = 0.95f, const float *d_boot = nullptr) {
+        check(gymnet_gae_device(device_, DeviceView().stream, steps, n_, n_, d_reward, d_done, d_value, d_last_value, d_boot, gamma, lambda, d_advantage, d_return));
+    }
     // The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous; its one output, clamped to the
     // env's bounds, is the action.  Empty widths release the actor.  LoadActorWeights / ResetActor / PushActor serve both kinds.
     void ConfigureBoxActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
@@ -440,7 +449,8 @@ private:
     gymnet_vecenv *h_ = nullptr;
     gymnet_env_info info_{};
     int64_t n_ = 0;
-    int32_t stack_depth_ = 0;          // of the pixel stack ConfigurePixelStack set up
+    int device_ = 0;                   // the handle's HIP device: what the handle-less calls (gymnet_gae_device) are given
+    int32_t stack_depth_ = 0;         // of the pixel stack ConfigurePixelStack set up
     std::unique_ptr<Discrete> action_discrete_;
     std::unique_ptr<Box> action_box_, observation_space_;
 };
