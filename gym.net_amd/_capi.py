@@ -201,6 +201,11 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_get_exploration": (C.c_int, [_H, _P, _P]),
     "gymnet_vecenv_actor_act_logp_device": (C.c_int, [_H, _P, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_rollout_fused_logp_device": (C.c_int, [_H, C.POINTER(RolloutSpec), _P]),
+    "gymnet_vecenv_actor_critic_config": (C.c_int, [_H, C.c_int32, _P, _P, C.c_int64]),
+    "gymnet_vecenv_actor_critic_load_device": (C.c_int, [_H, _P, C.c_int64]),
+    "gymnet_vecenv_actor_value_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_actor_act_value_device": (C.c_int, [_H, _P, _P, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
+    "gymnet_vecenv_rollout_fused_value_device": (C.c_int, [_H, C.POINTER(RolloutSpec), _P, _P]),
     "gymnet_vecenv_actor_box_config": (C.c_int, [_H, C.c_int32, C.c_int32, _P, _P, C.c_int64]),
     "gymnet_vecenv_actor_box_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_actor_box_set_policy": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_float]),

@@ -203,6 +203,12 @@ namespace Gym.Envs.Amd {
         // the log-probability of the action taken (a Discrete actor): d_logp float [N], d_rec_logp float [T][N]; IntPtr.Zero forwards to the call without it
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_logp_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_logp_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp);
+        // the critic: a second network over the actor's input whose one output is the value; d_value float [N], d_rec_value float [T][N]; IntPtr.Zero forwards
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_config(IntPtr h, int num_layers, int* widths, float* weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_load_device(IntPtr h, IntPtr d_weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_device(IntPtr h, IntPtr d_value);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_value_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, IntPtr d_value, float epsilon, ulong seed, ulong tick);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_value_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp, IntPtr d_rec_value);
         // the Box actor (Pendulum, MountainCarContinuous): the last layer's one output, clamped to the env's bounds, is the action
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_config(IntPtr h, int history, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, float epsilon, ulong seed, ulong tick);

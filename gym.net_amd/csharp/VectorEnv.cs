@@ -322,6 +322,28 @@ namespace Gym.Envs.Amd {
             spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
             Native.Check(Native.gymnet_vecenv_rollout_fused_logp_device(_h, ref spec, dRecLogp));
         }
+        /// The critic (gymnet_vecenv_actor_critic_config): a second network of the actor's kind over the actor's input, widths w_0 =
+        /// history * obs_dim .. w_L = 1, whose one output is the lane's value.  Needs a configured actor of either kind; no layers removes
+        /// it; ConfigureActor / ConfigureBoxActor drop it.
+        public void ConfigureActorCritic(int[] widths, float[] weights) {
+            if (widths == null || widths.Length == 0) { Native.Check(Native.gymnet_vecenv_actor_critic_config(_h, 0, null, null, 0)); return; }
+            fixed (int* pw = widths) fixed (float* pv = weights)
+                Native.Check(Native.gymnet_vecenv_actor_critic_config(_h, widths.Length - 1, pw, pv, weights.LongLength));
+        }
+        /// New device weights of the critic's widths, ordered on the handle's stream.
+        public void LoadActorCriticWeights(IntPtr dWeights, long count) => Native.Check(Native.gymnet_vecenv_actor_critic_load_device(_h, dWeights, count));
+        /// The critic over every lane's current history into dValue (float [N]): the last value after a rollout.
+        public void ActorValue(IntPtr dValue) => Native.Check(Native.gymnet_vecenv_actor_value_device(_h, dValue));
+        /// ActorActLogp that also writes the critic's value of the input each action was chosen from into dValue (float [N];
+        /// gymnet_vecenv_actor_act_value_device): actions, logits and logp are ActorActLogp's, bit for bit.  dValue IntPtr.Zero: ActorActLogp itself.
+        public void ActorActValue(IntPtr dActions, IntPtr dLogp, IntPtr dValue, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dLogits = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_act_value_device(_h, dActions, dLogits, dLogp, dValue, epsilon, seed, tick));
+        /// RolloutFusedLogp on a Discrete actor with a critic, also recording the value before every step into dRecValue (float [T][N];
+        /// gymnet_vecenv_rollout_fused_value_device); dRecLogp may be IntPtr.Zero.  dRecValue IntPtr.Zero: RolloutFusedLogp itself.
+        public void RolloutFusedValue(GymnetRolloutSpec spec, IntPtr dRecLogp, IntPtr dRecValue) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_fused_value_device(_h, ref spec, dRecLogp, dRecValue));
+        }
         /// GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written
         /// out there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  dReward float [steps][N],
         /// dDone byte [steps][N] (RolloutFused's records); dValue float [steps][N] or IntPtr.Zero (every value 0), dLastValue float [N],

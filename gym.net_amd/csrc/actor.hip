@@ -27,7 +27,7 @@
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, the prologue of every act entry point
 // (actor_act_enter), and the calls the fused rollout (capi.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
-// is the router: it alone says which of the five units runs a handle's rollout (actor_act_launch: the same for act).
+// is the router: it alone says which of the six units runs a handle's rollout (actor_act_launch: the same for act).
 #include "actor_net.hpp"
 
 namespace gymnet {
@@ -175,13 +175,13 @@ static hipError_t launch_actor_rollout_env(gymnet_vecenv *h, bool records, const
     return hipGetLastError();
 }
 
-namespace {
-
-// floats of the packed block for widths[0 .. layers]; off[l] = where layer l starts
-int64_t actor_packed_floats(const int32_t *widths, int32_t layers, int32_t (&off)[kActorMaxLayers]) {
+// the ActorNet of widths[0 .. layers] (w unset); returns the floats of its packed block, off[l] = where layer l starts
+int64_t actor_net_shape(ActorNet &net, int32_t layers, const int32_t *widths) {
+    net.layers = layers; net.action_n = widths[layers];
     int64_t total = 0;
     for (int l = 0; l < layers; ++l) {
-        off[l] = (int32_t)total;
+        net.win[l] = widths[l]; net.wout[l] = widths[l + 1];
+        net.off[l] = (int32_t)total;
         total += (int64_t)((widths[l + 1] + 3) >> 2) * group_floats(widths[l]);
     }
     return total;
@@ -191,6 +191,8 @@ hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *pack
     hipLaunchKernelGGL(actor_pack_kernel, lane_grid(packed_count), dim3(256), 0, st, net, flat, packed, packed_count);
     return hipGetLastError();
 }
+
+namespace {
 
 template <class R>
 hipError_t launch_actor_push_typed(const ActorHist &hs, const R *obs, int64_t obs_stride, const uint8_t *restart, bool push, hipStream_t st) {
@@ -266,15 +268,31 @@ static hipError_t actor_discrete_rollout_launch(gymnet_vecenv *h, bool records, 
     }
 }
 
-// The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: its policy decides.  Discrete: a
-// record pointer (gymnet_vecenv_rollout_fused_logp_device) goes to actor_logp.hip under either setting, else the setting decides
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp) {
+// gymnet_vecenv_rollout_fused_value_device's checks of its record pointers, which run before the rollout's own
+int actor_value_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp, const float *d_rec_value) {
+    if (action_source != GYMNET_ACTIONS_ACTOR)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: values are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
+    ST_TRY(need_actor(h));
+    if (h->actor->box)
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: this handle's actor chooses Box actions; the fused rollout records values for a Discrete actor "
+                    "(gymnet_vecenv_actor_value_device serves a Box actor)");
+    if (!h->actor->has_critic()) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: no critic configured (gymnet_vecenv_actor_critic_config)");
+    if (!aligned_to(d_rec_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
+    if (!aligned_to(d_rec_value, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value must be 4-byte aligned");
+    return GYMNET_OK;
+}
+
+// The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: its policy decides.  Discrete: a value
+// pointer (gymnet_vecenv_rollout_fused_value_device) goes to actor_value.hip, with or without a logp pointer; a logp pointer alone
+// (gymnet_vecenv_rollout_fused_logp_device) to actor_logp.hip under either setting; else the setting decides
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
     if (ac.box) {
-        if (rec_logp) return hipErrorInvalidValue;                           // (actor_logp_rollout_check has refused it)
+        if (rec_logp || rec_value) return hipErrorInvalidValue;              // (actor_logp / actor_value_rollout_check has refused it)
         return ac.default_policy() ? actor_box_rollout_launch(h, records, a, r) : actor_box_policy_rollout_launch(h, records, a, r);
     }
+    if (rec_value) return actor_value_rollout_launch(h, records, a, r, rec_logp, rec_value);
     if (rec_logp) return actor_logp_rollout_launch(h, records, a, r, rec_logp);
     return ac.default_exploration() ? actor_discrete_rollout_launch(h, records, a, r) : actor_softmax_rollout_launch(h, records, a, r);
 }
@@ -286,9 +304,10 @@ void actor_rollout_done(gymnet_vecenv *h, int64_t steps) {
     h->actor->last = mark(h);
 }
 
-// the router's counterpart for act on a Discrete handle: the setting decides
-static hipError_t actor_act_launch(gymnet_vecenv *h, int32_t *actions, float *logits, const ActorAct &aa) {
+// the router's counterpart for act on a Discrete handle: a logp pointer goes to actor_logp.hip under either setting, else the setting decides
+hipError_t actor_act_launch(gymnet_vecenv *h, int32_t *actions, float *logits, float *logp, const ActorAct &aa) {
     const Actor &ac = *h->actor;
+    if (logp) return actor_logp_act_launch(ac.net, ac.hist, actions, logits, logp, aa, actor_explore(ac), h->stream);
     if (!ac.default_exploration()) return actor_softmax_act_launch(ac.net, ac.hist, actions, logits, aa, actor_explore(ac), h->stream);
     return launch_actor_act(ac.net, ac.hist, actions, logits, aa, h->stream);
 }
@@ -303,6 +322,19 @@ int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, con
     if (!actor_current(h))
         return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
     aa = ActorAct{epsilon, seed, (uint64_t)h->cfg.lane_offset, tick};
+    return GYMNET_OK;
+}
+
+int actor_net_check(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, int64_t count, int32_t first, int32_t last, const char *last_name,
+                    int64_t &params) {
+    params = 0;
+    for (int l = 0; l <= num_layers; ++l)
+        if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
+    for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
+    if (widths[0] != first) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], first);
+    if (widths[num_layers] != last) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != %s = %d", num_layers, widths[num_layers], last_name, last);
+    if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
+    if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
     return GYMNET_OK;
 }
 
@@ -323,21 +355,12 @@ int actor_configure(gymnet_vecenv *h, bool box, int32_t history, int32_t num_lay
         return fail(h, GYMNET_ERR_INVALID_ARG, "history %d: history * obs_dim must be in [1, %d]", history, kActorMaxWidth);
     if (!box && d.action_n > kActorMaxActions) return fail(h, GYMNET_ERR_UNSUPPORTED, "more than %d actions", kActorMaxActions);
     int64_t params = 0;
-    for (int l = 0; l <= num_layers; ++l)
-        if (widths[l] < 1 || widths[l] > kActorMaxWidth) return fail(h, GYMNET_ERR_INVALID_ARG, "width %d of layer boundary %d not in [1, %d]", widths[l], l, kActorMaxWidth);
-    for (int l = 0; l < num_layers; ++l) params += (int64_t)widths[l + 1] * widths[l] + widths[l + 1];
-    if (widths[0] != history * d.obs_dim) return fail(h, GYMNET_ERR_INVALID_ARG, "widths[0] %d != history * obs_dim = %d", widths[0], history * d.obs_dim);
-    if (widths[num_layers] != last)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "widths[%d] %d != %s = %d", num_layers, widths[num_layers], box ? "the action dimension" : "action_n", last);
-    if (params > kActorMaxParams) return fail(h, GYMNET_ERR_INVALID_ARG, "%lld parameters > %d", (long long)params, kActorMaxParams);
-    if (count != params) return fail(h, GYMNET_ERR_INVALID_ARG, "count %lld != %lld parameters of these widths", (long long)count, (long long)params);
+    ST_TRY(actor_net_check(h, num_layers, widths, count, history * d.obs_dim, last, box ? "the action dimension" : "action_n", params));
     std::unique_ptr<Actor> fresh(new Actor);
     fresh->box = box;
     ActorNet &net = fresh->net;
-    net.layers = num_layers; net.action_n = last;
-    for (int l = 0; l < num_layers; ++l) { net.win[l] = widths[l]; net.wout[l] = widths[l + 1]; }
     fresh->count = params;
-    fresh->packed = actor_packed_floats(widths, num_layers, net.off);
+    fresh->packed = actor_net_shape(net, num_layers, widths);
     // the packed block, the weights as given (torch layout: the pack kernel's input) and the history: all three, or the old actor stays
     const size_t flat_bytes = sizeof(float) * (size_t)params;
     float *packed = static_cast<float *>(fresh->mem.take(sizeof(float) * (size_t)fresh->packed));
@@ -412,7 +435,7 @@ int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *
     ENTER(h);
     ActorAct aa;
     ST_TRY(actor_act_enter(h, false, "this handle's actor chooses Box actions: gymnet_vecenv_actor_box_act_device", d_actions, nullptr, epsilon, seed, tick, aa));
-    HIP_TRY(h, actor_act_launch(h, d_actions, d_logits, aa));
+    HIP_TRY(h, actor_act_launch(h, d_actions, d_logits, nullptr, aa));
     return GYMNET_OK;
     });
 }

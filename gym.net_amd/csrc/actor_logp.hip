@@ -11,65 +11,16 @@
 // actor_softmax.hip: one kernel serves both settings, and a request for logp always runs this unit, also under the default setting.
 //
 // The action is composed exactly as explore_compose_one (actor_softmax.hip) composes it — the same coin, the same words, the same c_k
-// and threshold — so actions and logits are what act_device writes under the handle's setting.  The draw and the composition are this
-// unit's own copies (argmax_value is actor_net.hpp's): the kernels of actor.hip and actor_softmax.hip stay instruction for instruction what they were.
+// and threshold — so actions and logits are what act_device writes under the handle's setting.  The draw and the composition are a copy
+// of actor_softmax.hip's (compose_one_logp in actor_compose_logp.hpp, which actor_value.hip includes too; argmax_value is
+// actor_net.hpp's): the kernels of actor.hip and actor_softmax.hip stay instruction for instruction what they were.
 //
 // Fused rollout (actor_logp_rollout_kernel): actor_softmax_rollout_kernel with the record pointer as a sixth argument — rollout_body, one
 // lane per thread, behind a hook whose choose() is the act kernel's body (it stores logp itself, at rec_logp + t * n + i) and whose
 // after() is the shared push: bit-identical to steps x (act_logp, step, push).
-#include "actor_net.hpp"
-#include "exp_neg.hpp"
-#include "log_pos.hpp"
+#include "actor_compose_logp.hpp"
 
 namespace gymnet {
-
-namespace {
-
-// explore_compose_one (actor_softmax.hip) for one lane, which also hands out logp of the action it returns.  The scaled differences a_k
-// and the running sums c_k are computed before the coin: the draw reads them where the wave draws, logp reads them always
-__device__ __forceinline__ int32_t compose_one_logp(const float (&x)[kW], int32_t action_n, const ActorExplore &ex, uint32_t explore_at_or_below,
-                                                    uint64_t seed, uint64_t gl, uint64_t tick, float &logp) {
-    float m;
-    const int32_t greedy = argmax_value(x, action_n, m);
-    float a[8], c[8];
-    float run = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        a[j] = 0.0f;
-        if (j < action_n) {                                                  // wave-uniform
-            const float d = x[j] - m;
-            a[j] = d * ex.inv_tau;
-            run = run + exp_neg(a[j]);
-        }
-        c[j] = run;
-    }
-    const bool explore = aux_word<true>(seed, gl, tick) <= explore_at_or_below;
-    int32_t act = greedy;
-    if (__ballot(explore)) {
-        const uint32_t wa = action_word<true>(seed, gl, tick);
-        int32_t drawn;
-        if (ex.explore == GYMNET_ACTOR_EXPLORE_SOFTMAX) {                    // wave-uniform: softmax_draw's second half
-            const float thr = u01_24(wa) * run;
-            drawn = greedy;
-#pragma unroll
-            for (int j = 7; j >= 0; --j) {                                   // descending: the first k with thr < c_k wins
-                if (j < action_n && thr < c[j]) drawn = j;
-            }
-        } else {
-            drawn = (int32_t)__umulhi(wa, (uint32_t)action_n);
-        }
-        act = explore ? drawn : greedy;
-    }
-    float aj = a[0];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) aj = q == act ? a[q] : aj;
-    const float lp = aj - log_pos(run);                                      // (run < 1: not stored)
-    const uint32_t bits = __builtin_bit_cast(uint32_t, lp);
-    logp = __builtin_bit_cast(float, (run >= 1.0f && lp == lp) ? bits : 0x7FC00000u);
-    return act;
-}
-
-}  // namespace
 
 template <int O>
 __global__ __launch_bounds__(256) void actor_logp_act_kernel(const ActorNet net, const ActorHist hs, int32_t *__restrict__ actions,
@@ -177,10 +128,8 @@ hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepA
     }
 }
 
-namespace {
-
-hipError_t launch_logp_act(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, float *logp, const ActorAct &aa,
-                           const ActorExplore &ex, hipStream_t st) {
+hipError_t actor_logp_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, float *logp, const ActorAct &aa,
+                                 const ActorExplore &ex, hipStream_t st) {
     if (hs.n <= 0) return hipSuccess;
     switch (hs.obs_dim) {
         case 2: hipLaunchKernelGGL(actor_logp_act_kernel<2>, lane_grid(hs.n), dim3(256), 0, st, net, hs, actions, logits, logp, aa, ex); break;
@@ -190,8 +139,6 @@ hipError_t launch_logp_act(const ActorNet &net, const ActorHist &hs, int32_t *ac
     }
     return hipGetLastError();
 }
-
-}  // namespace
 
 }  // namespace gymnet
 
@@ -206,8 +153,7 @@ int gymnet_vecenv_actor_act_logp_device(gymnet_vecenv *h, int32_t *d_actions, fl
     ENTER(h);
     ActorAct aa;
     ST_TRY(actor_act_enter(h, false, "this handle's actor chooses Box actions: a log-probability belongs to a Discrete actor", d_actions, d_logp, epsilon, seed, tick, aa));
-    const Actor &ac = *h->actor;
-    HIP_TRY(h, launch_logp_act(ac.net, ac.hist, d_actions, d_logits, d_logp, aa, actor_explore(ac), h->stream));
+    HIP_TRY(h, actor_act_launch(h, d_actions, d_logits, d_logp, aa));
     return GYMNET_OK;
     });
 }

@@ -1,11 +1,12 @@
-// actor_net.hpp — what the five actor units share: the network and the per-lane observation history as the kernels see them, the forward
+// actor_net.hpp — what the six actor units share: the network and the per-lane observation history as the kernels see them, the forward
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), the host helpers every unit launches
 // with (lane_grid, pick_rollout_form), and the handle's Actor attachment with each unit's launch calls.  actor.hip serves the Discrete
 // envs (argmax head) and owns the attachment, the act prologue (actor_act_enter) and the router: actor_rollout_launch there is the one
 // place that says which unit runs a handle's fused rollout, and no unit calls another on its own.  actor_box.hip serves the Box envs
 // (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete envs under an
 // exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when the caller
-// also asks for the log-probability of the action taken.  Internal to the library.
+// also asks for the log-probability of the action taken, actor_value.hip the critic: a second network over the same input whose one
+// output is the lane's value estimate.  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -14,7 +15,7 @@
 
 namespace gymnet {
 
-// a fully connected ReLU network of `layers` linear layers whose packed weights (actor_packed_floats) are read by every lane, and the
+// a fully connected ReLU network of `layers` linear layers whose packed weights (actor_net_shape) are read by every lane, and the
 // per-lane observation history it reads
 constexpr int kActorMaxLayers = 4, kActorMaxWidth = 64, kActorMaxParams = 8192, kActorMaxActions = 8;
 struct ActorNet {
@@ -190,6 +191,10 @@ struct Actor {
     // actor.hip serve (UNIFORM at any temperature is that behaviour); SOFTMAX runs through actor_softmax.hip.  inv_tau = 1.0f / temperature
     int32_t discrete_explore = GYMNET_ACTOR_EXPLORE_UNIFORM; float temperature = 1.0f, inv_tau = 1.0f;
     bool default_exploration() const { return discrete_explore == GYMNET_ACTOR_EXPLORE_UNIFORM; }
+    // the critic (gymnet_vecenv_actor_critic_config, actor_value.hip): a second network over the same input, last width 1, in an
+    // allocation of its own so that it comes and goes without the actor; critic.layers == 0: none
+    DeviceAllocs critic_mem; ActorNet critic{}; int64_t critic_count = 0, critic_packed = 0;
+    bool has_critic() const { return critic.layers > 0; }
 };
 // what the kernels of actor_box_policy.hip take of it, as a kernel argument
 struct BoxPolicy { int32_t head, explore; float sigma; };
@@ -209,6 +214,13 @@ inline bool actor_current(const gymnet_vecenv *h) { return since(h, h->actor->la
 
 // actor.hip: gymnet_vecenv_actor_config and gymnet_vecenv_actor_box_config behind ENTER (box: which of the two)
 int actor_configure(gymnet_vecenv *h, bool box, int32_t history, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
+// actor.hip: what both config calls and the critic's check of a network's shape once num_layers and the pointers are known good — every
+// width, the first (history * obs_dim) and the last (`last`, worded `last_name`), the parameter limit and count — with nothing changed on a
+// refusal, and then make of it: the ActorNet of these widths (w unset) and its packed size; flat device weights -> the packed block
+int actor_net_check(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, int64_t count, int32_t first, int32_t last, const char *last_name,
+                    int64_t &params);
+int64_t actor_net_shape(ActorNet &net, int32_t num_layers, const int32_t *widths);
+hipError_t launch_actor_pack(const ActorNet &net, const float *flat, float *packed, int64_t packed_count, hipStream_t st);
 // actor.hip: what every act entry point checks behind ENTER, in this order — an actor of the kind the call serves (want_box; wrong_kind:
 // the entry point's own message), d_actions, d_logp's alignment (null: not asked for), epsilon, a current history — and the ActorAct of
 // the launch
@@ -216,7 +228,7 @@ int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, con
                     uint64_t tick, ActorAct &aa);
 // Each unit's fused rollout of a handle it serves, a.n > 0 (records: the rollout keeps compact episode records), and the calls one unit
 // makes into another: actor.hip's router (actor_rollout_launch, handle.hpp) reads (box, default_policy(), default_exploration(), a record
-// pointer) and calls exactly one of these four or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
+// pointer) and calls exactly one of these five or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
 // push reach a sibling's kernels through the rest.
 // actor_box.hip: the default policy's rollout, and the push / fill of a three-row observation (Pendulum)
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
@@ -231,5 +243,12 @@ hipError_t actor_softmax_act_launch(const ActorNet &net, const ActorHist &hs, in
                                     hipStream_t st);
 // actor_logp.hip: a Discrete handle, either setting, that also records the log-probability of every action taken: rec_logp [steps][n]
 hipError_t actor_logp_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp);
+hipError_t actor_logp_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, float *logp, const ActorAct &aa,
+                                 const ActorExplore &ex, hipStream_t st);
+// actor.hip: act on a Discrete handle, by the unit that serves it as it stands (logp null: none asked for)
+hipError_t actor_act_launch(gymnet_vecenv *h, int32_t *actions, float *logits, float *logp, const ActorAct &aa);
+// actor_value.hip: a Discrete handle with a critic, either setting, that records the critic's value of every step's input: rec_value
+// [steps][n], and the log-probabilities as above where rec_logp is not null
+hipError_t actor_value_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value);
 
 }  // namespace gymnet

@@ -746,10 +746,10 @@ int ensure_episode_segments(gymnet_vecenv *h, int64_t capacity) {
     return GYMNET_OK;
 }
 
-// held: frame skip — sp.steps decisions of held + 1 sub-steps each (action_repeat.hip); 0: the fused rollout.  rec_logp: where an actor
-// rollout records every step's log-probability (null: nowhere)
+// held: frame skip — sp.steps decisions of held + 1 sub-steps each (action_repeat.hip); 0: the fused rollout.  rec_logp / rec_value: where an
+// actor rollout records every step's log-probability / critic value (null: nowhere)
 template <class R>
-int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchCfg cfg, bool episodes, int32_t held, float *rec_logp) {
+int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchCfg cfg, bool episodes, int32_t held, float *rec_logp, float *rec_value) {
     const StepArgsT<R> a = make_step_args<R>(h, sp.d_actions);
     RolloutArgsT<R> r{};
     r.steps = sp.steps; r.action_stride = sp.action_stride; r.ring = sp.ring;
@@ -773,7 +773,7 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
         HIP_TRY(h, repeat_rollout_launch(h, a, r, held + 1));
     } else if constexpr (sizeof(R) == 4) {
         if (sp.action_source == GYMNET_ACTIONS_ACTOR) {
-            HIP_TRY(h, actor_rollout_launch(h, episodes, a, r, rec_logp));
+            HIP_TRY(h, actor_rollout_launch(h, episodes, a, r, rec_logp, rec_value));
         } else {
             HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
         }
@@ -796,8 +796,8 @@ int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchC
 // gymnet_vecenv_rollout_fused_ex_device on a handle the caller has ENTERed.  held > 0: gymnet_vecenv_rollout_repeat_device — the same
 // checks, then spec.steps decisions of held + 1 sub-steps each.  validated: the caller has run VALIDATE_ACTIONS over the one slice read
 // (gymnet_vecenv_step_repeat_device).  rec_logp: gymnet_vecenv_rollout_fused_logp_device's record pointer, checked by the caller
-// (actor_logp_rollout_check); null: none.
-int rollout_fused_entered(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t held, bool validated, float *rec_logp) {
+// (actor_logp_rollout_check); null: none.  rec_value: gymnet_vecenv_rollout_fused_value_device's, the same (actor_value_rollout_check).
+int rollout_fused_entered(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t held, bool validated, float *rec_logp, float *rec_value = nullptr) {
     if (!spec) return fail(h, GYMNET_ERR_INVALID_ARG, "spec is null");
     if (spec->struct_size != sizeof(gymnet_rollout_spec))
         return fail(h, GYMNET_ERR_INVALID_ARG, "spec.struct_size %u != %zu (ABI mismatch)", spec->struct_size, sizeof(gymnet_rollout_spec));
@@ -857,7 +857,7 @@ int rollout_fused_entered(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int
         else if (!streams_fit(w)) cfg.vec = 1;
     }
     if (episodes) ST_TRY(ensure_episode_segments(h, sp.ep_capacity));
-    ST_TRY(h->f64 ? rollout_fused_typed<double>(h, sp, cfg, episodes, held, rec_logp) : rollout_fused_typed<float>(h, sp, cfg, episodes, held, rec_logp));
+    ST_TRY(h->f64 ? rollout_fused_typed<double>(h, sp, cfg, episodes, held, rec_logp, rec_value) : rollout_fused_typed<float>(h, sp, cfg, episodes, held, rec_logp, rec_value));
     swap_buffers(h);                     // DOUBLE_BUFFER: the launch read one buffer and wrote the other, once
     const uint64_t ticks = (uint64_t)sp.steps * ((uint64_t)held + 1);       // a sub-step is an engine tick
     h->tick += ticks;
@@ -902,6 +902,16 @@ int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollo
     // (a null or mis-sized spec is the rollout's own refusal)
     if (spec && spec->struct_size == sizeof(gymnet_rollout_spec)) ST_TRY(actor_logp_rollout_check(h, spec->action_source, d_rec_logp));
     return rollout_fused_entered(h, spec, 0, false, d_rec_logp);
+    });
+}
+
+int gymnet_vecenv_rollout_fused_value_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value) {
+    if (!d_rec_value) return gymnet_vecenv_rollout_fused_logp_device(h, spec, d_rec_logp);
+    return guarded([&]() -> int {
+    ENTER(h);
+    // (a null or mis-sized spec is the rollout's own refusal)
+    if (spec && spec->struct_size == sizeof(gymnet_rollout_spec)) ST_TRY(actor_value_rollout_check(h, spec->action_source, d_rec_logp, d_rec_value));
+    return rollout_fused_entered(h, spec, 0, false, d_rec_logp, d_rec_value);
     });
 }
 

@@ -350,13 +350,16 @@ bool resident_serves(const gymnet_vecenv *h);                        // the resi
 // one command (kMailboxStep / ResetAll / ResetDone) through the mailbox: post it, wait for its results, copy them out
 int resident_command(gymnet_vecenv *h, uint32_t cmd, const void *actions, void *obs_out, float *reward_out, uint8_t *done_out);
 // the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch,
-// by the unit that serves the handle as it stands (records: the rollout keeps compact episode records; rec_logp: where it records every
-// step's log-probability, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps` on and is current
+// by the unit that serves the handle as it stands (records: the rollout keeps compact episode records; rec_logp / rec_value: where it
+// records every step's log-probability / critic value, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps`
+// on and is current
 int actor_rollout_check(gymnet_vecenv *h);
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp);
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value);
 void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
 // gymnet_vecenv_rollout_fused_logp_device: the checks that belong to its record pointer (the source, the actor's kind, the alignment)
 int actor_logp_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp);
+// gymnet_vecenv_rollout_fused_value_device: the same for its two record pointers, and that the Discrete actor has a critic
+int actor_value_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp, const float *d_rec_value);
 // the fused rollout with frame skip (action_repeat.hip): r.steps decisions of R sub-steps each under one action, one launch
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs &a, const RolloutArgs &r, int32_t R);
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const RolloutArgs64 &r, int32_t R);

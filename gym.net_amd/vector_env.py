@@ -341,7 +341,7 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_rollout_device(self._h, _ptr(d_actions), int(steps), int(action_stride), int(ring)))
 
     def RolloutFusedDevice(self, d_actions, steps, action_stride=0, ring=1, rec_obs=None, rec_reward=None, rec_done=None, actions="ring",
-                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None):
+                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None, rec_value=None):
         """`steps` vector steps in ONE kernel launch (state stays in registers); optional device-side rollout
         buffers rec_obs [T][D][N] (of the handle's dtype: float64 for a float64 handle), rec_reward [T][N], rec_done [T][N]
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
@@ -359,8 +359,28 @@ class VectorEnv:
           repeat    frame skip (gymnet_vecenv_rollout_repeat_device): `steps` counts DECISIONS, each action is held for repeat + 1 env
                     steps, the rec_* buffers and the records' step index are per decision ("actor" needs repeat = 0).
           rec_logp  device float32 [T, N] for the log-probability of every action taken, as Actor.Act(logp=) writes it at that step
-                    (gymnet_vecenv_rollout_fused_logp_device): needs actions="actor" on a Discrete actor."""
+                    (gymnet_vecenv_rollout_fused_logp_device): needs actions="actor" on a Discrete actor.
+          rec_value device float32 [T, N] or [T + 1, N] for the critic's value of the input every action was chosen from, as
+                    Actor.Value() would write it before that step (gymnet_vecenv_rollout_fused_value_device): needs actions="actor" on a
+                    Discrete actor with a critic (Actor.SetCritic).  With T + 1 rows, row T takes Actor.Value() after the rollout — the
+                    last value — and AdvantagesDevice(rec_reward, rec_done, rec_value, ...) takes the tensor as it stands."""
         repeat = _repeat(repeat)
+        value_rows = None
+        if rec_value is not None:
+            actor = getattr(self, "_actor", None)
+            if actions != "actor":
+                raise ValueError(f"rec_value records the critic's values where the actor chooses: it needs actions=\"actor\", got {actions!r}")
+            if actor is None:
+                raise ValueError("rec_value needs an actor (VectorEnv.Actor)")
+            if actor.IsBox:
+                raise ValueError("rec_value belongs to a Discrete actor's fused rollout; this handle's actor chooses Box actions (Actor.Value serves it)")
+            if getattr(actor, "CriticWidths", None) is None:
+                raise ValueError("rec_value needs a critic (Actor.SetCritic)")
+            if repeat:
+                raise ValueError("rec_value: the fused actor rollout has no frame skip (repeat must be 0)")
+            T = _count(steps, "steps", 0)
+            value_rows = T + 1 if tuple(getattr(rec_value, "shape", ()))[:1] == (T + 1,) else T
+            _logp_buffer(rec_value, (value_rows, self.NumberOfEnvironments), "rec_value", self.Device)
         if rec_logp is not None:
             actor = getattr(self, "_actor", None)
             if actions != "actor":
@@ -386,6 +406,11 @@ class VectorEnv:
                                 d_ep_length=_ptr(ep.get("length")), ep_capacity=int(ep.get("capacity", 0)), d_ep_count=_ptr(ep.get("count")))
         if repeat:
             capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
+        elif rec_value is not None:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
+            if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
+                last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
+                capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
         elif rec_logp is not None:
             capi.check(self._lib.gymnet_vecenv_rollout_fused_logp_device(self._h, C.byref(spec), _ptr(rec_logp)))
         else:
@@ -1041,6 +1066,7 @@ class Actor:
             prev._h = None                      # the handle holds one actor: the previous one is gone
         env._actor = self
         self.History_, self.Widths, self.Count = history, tuple(int(w) for w in widths), int(flat.size)
+        self.CriticWidths, self.CriticCount = None, 0          # (a new actor has no critic: the config call dropped it)
         self._out = None
 
     def _handle(self):
@@ -1048,7 +1074,66 @@ class Actor:
             raise ValueError("this actor was replaced or closed")
         return self._h
 
-    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None):
+    def _critic_pack(self, net):
+        """actor_pack of a critic's network, its first and last width checked against this actor before any native call"""
+        widths, flat = actor_pack(net)
+        if int(widths[0]) != self.Widths[0]:
+            raise ValueError(f"the critic's first layer takes {int(widths[0])} inputs; the actor's input is history * obs_dim = {self.Widths[0]}")
+        if int(widths[-1]) != 1:
+            raise ValueError(f"the critic's last layer gives the one value; this one is {int(widths[-1])} wide")
+        return widths, flat
+
+    def SetCritic(self, net):
+        """Attaches a critic (gymnet_vecenv_actor_critic_config): a second network — an nn.Sequential of Linear / ReLU layers or (W, b)
+        pairs, as VectorEnv.Actor takes — over the input this actor reads, history * obs_dim wide, whose last layer is one wide: the
+        lane's value.  Depth and hidden widths are its own.  None removes it.  Either kind of actor takes one; a new VectorEnv.Actor
+        drops it; Load, Push, Reset, SetExploration and SetPolicy keep it."""
+        if net is None:
+            capi.check(self._lib.gymnet_vecenv_actor_critic_config(self._handle(), 0, None, None, 0))
+            self.CriticWidths, self.CriticCount = None, 0
+            return
+        widths, flat = self._critic_pack(net)
+        capi.check(self._lib.gymnet_vecenv_actor_critic_config(self._handle(), len(widths) - 1, _host(widths), _host(flat), flat.size))
+        self.CriticWidths, self.CriticCount = tuple(int(w) for w in widths), int(flat.size)
+
+    def LoadCritic(self, net):
+        """New critic weights of the configured widths (gymnet_vecenv_actor_critic_load_device), as Load takes the actor's: a flat device
+        float32 tensor in the config layout is copied device to device, anything else goes through actor_pack and the host."""
+        if getattr(self, "CriticWidths", None) is None:
+            raise ValueError("this actor has no critic (SetCritic)")
+        if hasattr(net, "data_ptr") and getattr(net, "is_cuda", False):
+            if net.numel() != self.CriticCount or str(net.dtype) != "torch.float32" or not net.is_contiguous():
+                raise ValueError(f"a device weight tensor must be {self.CriticCount} contiguous float32 values")
+            capi.check(self._lib.gymnet_vecenv_actor_critic_load_device(self._handle(), _ptr(net), self.CriticCount))
+            return
+        widths, flat = self._critic_pack(net)
+        if tuple(int(w) for w in widths) != self.CriticWidths:
+            raise ValueError(f"widths {tuple(int(w) for w in widths)} != the critic's {self.CriticWidths}")
+        import torch
+        d = torch.from_numpy(flat).to(f"cuda:{self._env.Device}")
+        capi.check(self._lib.gymnet_vecenv_actor_critic_load_device(self._handle(), _ptr(d), self.CriticCount))
+        self._env.Sync()
+
+    def _value_buffer(self, value, name="value"):
+        if getattr(self, "CriticWidths", None) is None:
+            raise ValueError(f"{name} needs a critic (SetCritic)")
+        return _logp_buffer(value, (self._env.NumberOfEnvironments,), name, self._env.Device)
+
+    def Value(self, out=None):
+        """The critic's value of every lane's current history into `out` (device float32 [N]; None: a new torch tensor, returned), one
+        kernel on the handle's stream (gymnet_vecenv_actor_value_device).  Serves Box actors and float64 handles too; the history must be
+        current, as for Act.  After a rollout this is the last value."""
+        if out is None:
+            if getattr(self, "CriticWidths", None) is None:
+                raise ValueError("value needs a critic (SetCritic)")
+            import torch
+            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.float32, device=f"cuda:{self._env.Device}")
+        else:
+            self._value_buffer(out, "out")
+        capi.check(self._lib.gymnet_vecenv_actor_value_device(self._handle(), _ptr(out)))
+        return out
+
+    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None, value=None):
         """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
         compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
@@ -1057,13 +1142,23 @@ class Actor:
         SetPolicy changes the head and what an exploring lane takes.  On a Discrete actor SetExploration("softmax", temperature) makes an
         exploring lane draw from softmax(logits / temperature) instead.  logp (a Discrete actor): an optional device float32 [N] for the
         log-probability of the action each lane takes under softmax(logits / temperature), the stored temperature whatever the exploration
-        setting (gymnet_vecenv_actor_act_logp_device); actions and logits are the same bits with and without it."""
+        setting (gymnet_vecenv_actor_act_logp_device); actions and logits are the same bits with and without it.  value (a Discrete actor
+        with a critic): an optional device float32 [N] for what Value() writes, from the same call
+        (gymnet_vecenv_actor_act_value_device); actions, logits and logp are the same bits with and without it."""
         if logp is not None:
             if self.IsBox:
                 raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
             _logp_buffer(logp, (self._env.NumberOfEnvironments,), "logp", self._env.Device)
+        if value is not None:
+            if self.IsBox:
+                raise ValueError("Act(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
+            self._value_buffer(value)
         if out is None:
             out = self._actions()
+        if value is not None:
+            capi.check(self._lib.gymnet_vecenv_actor_act_value_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), _ptr(value), float(epsilon),
+                                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+            return out
         if logp is not None:
             capi.check(self._lib.gymnet_vecenv_actor_act_logp_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), float(epsilon),
                                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
@@ -1175,15 +1270,17 @@ class Actor:
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
 
-    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None):
-        """Act(epsilon, seed, tick, logp=logp), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
+    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None):
+        """Act(epsilon, seed, tick, logp=logp, value=value), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
         Push(): one closed-loop decision; returns the device actions taken."""
         repeat = _repeat(repeat)
         if logp is not None and self.IsBox:
             raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
+        if value is not None and self.IsBox:
+            raise ValueError("Step(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
         if self._out is None:
             self._out = self._actions()
-        self.Act(epsilon, seed, tick, out=self._out, logp=logp)
+        self.Act(epsilon, seed, tick, out=self._out, logp=logp, value=value)
         if repeat:
             self._env.StepRepeatDevice(self._out, repeat)
         else:

@@ -718,6 +718,47 @@ int gymnet_vecenv_actor_get_exploration(gymnet_vecenv *h, int32_t *explore, floa
 int gymnet_vecenv_actor_act_logp_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float *d_logp, float epsilon, uint64_t seed,
                                         uint64_t tick);
 int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp);
+/* The critic (additive in ABI 6): a second fully connected ReLU network attached to a configured actor, Discrete or Box, whose one output
+ * is the lane's value estimate, for one call and inside the fused rollout.  Training stays with the caller.
+ * Network: the actor's packed layout and limits — L in [1, 4] layers, every width in [1, 64], at most 8192 parameters, torch's nn.Linear
+ *   layout, ReLU between the layers — with w_0 = the actor's input width S * obs_dim and w_L = 1; depth and hidden widths are the
+ *   critic's own.
+ * Value: the same fmaf chain in the same ascending input order that gives the actor its logits (gymnet_vecenv_actor_config, above), over
+ *   the same input x = o_{p-S+1} .. o_p, taking the last layer's one value.  No new arithmetic: tests/_actor_twin.py's forward reproduces
+ *   it bit for bit up to the sign of a zero.  value[t] is the value of the input step t's action is chosen from: the convention
+ *   gymnet_gae_device documents for d_value.
+ * actor_critic_config: host weights in actor_config's layout; needs a configured actor.  GYMNET_ERR_INVALID_ARG, nothing changed (a
+ *   critic configured before stays): no actor, num_layers outside [0, 4], null pointers, a width outside [1, 64], widths[0] != S * obs_dim,
+ *   widths[L] != 1, more than 8192 parameters, count != the parameters of these widths; GYMNET_ERR_OOM likewise.  num_layers == 0 removes
+ *   the critic (the other arguments are not looked at).  Blocks until the weights are on the device, like actor_config.  A new
+ *   actor_config or actor_box_config drops the critic — also a re-config, also num_layers 0 there; actor_load_device, actor_push_device,
+ *   actor_reset_device, actor_set_exploration and actor_box_set_policy keep it.  The critic changes no history and no staleness state.
+ * actor_critic_load_device: count floats of device weights of the configured shape replace the critic's, ordered on the handle's stream:
+ *   the twin of actor_load_device.  GYMNET_ERR_INVALID_ARG: no actor, no critic, a null pointer, another count.
+ * actor_value_device: d_value [num_envs] float32 = the critic over the current history, one kernel, ordered on the stream.  Serves every
+ *   handle an actor serves, Box actors and float64 CartPole handles included.  The staleness rule of act_device.  GYMNET_ERR_INVALID_ARG,
+ *   nothing written: no actor, no critic, a null or not 4-byte aligned pointer, a stale history.  This is the call that gives the last
+ *   value after a rollout.
+ * actor_act_value_device: with d_value == NULL it IS gymnet_vecenv_actor_act_logp_device (the call forwards).  Otherwise d_actions,
+ *   d_logits and d_logp (which may be NULL) are bit for bit what that call writes, and d_value is what actor_value_device writes: the same
+ *   act launch, then the value kernel behind it on the stream.  Discrete actors only (a Box actor: GYMNET_ERR_INVALID_ARG; call
+ *   actor_box_act_device, then actor_value_device); every refusal of either call applies and nothing is written on a refusal.
+ * rollout_fused_value_device: with d_rec_value == NULL it IS gymnet_vecenv_rollout_fused_logp_device(h, spec, d_rec_logp).  Otherwise
+ *   spec->action_source must be GYMNET_ACTIONS_ACTOR, the handle's actor Discrete, and it must have a critic (else
+ *   GYMNET_ERR_INVALID_ARG, nothing launched); every check of rollout_fused_ex_device applies; everything the logp call leaves is left bit
+ *   for bit — d_rec_logp included, which may be NULL —, and in addition d_rec_value[t * num_envs + lane] is what actor_value_device would
+ *   write before step t: the call is bit-identical to steps x (act_value_device, step_device, actor_push_device).  Both record pointers
+ *   need 4-byte alignment only; steps == 0 writes nothing.  One kernel per form serves both exploration settings, with and without
+ *   d_rec_logp (csrc/actor_value.hip).
+ * Out of scope: a value for Box actors inside the fused rollout (it waits for their log-density; actor_value_device serves them
+ *   stand-alone); V(terminal observation) for gymnet_gae_device's d_boot on time-limit rows (without it a time limit counts as a
+ *   termination, as documented there); a trunk shared between actor and critic; values carried through the episode memory; any gradient. */
+int gymnet_vecenv_actor_critic_config(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
+int gymnet_vecenv_actor_critic_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count);
+int gymnet_vecenv_actor_value_device(gymnet_vecenv *h, float *d_value);
+int gymnet_vecenv_actor_act_value_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float *d_logp, float *d_value, float epsilon,
+                                         uint64_t seed, uint64_t tick);
+int gymnet_vecenv_rollout_fused_value_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value);
 /* The Box actor (additive in ABI 6): the same actor on a Box action space — Pendulum-v1 (obs_dim 3, bounds -2 .. 2) and
  * MountainCarContinuous-v0 (obs_dim 2, bounds -1 .. 1), float32 handles (neither env has a float64 mode).
  * Network: as above — L in [1, 4] layers, every width in [1, 64], at most 8192 parameters, torch's nn.Linear layout, ReLU between the

@@ -408,6 +408,28 @@ public:
         spec.struct_size = (uint32_t)sizeof spec;
         check(gymnet_vecenv_rollout_fused_logp_device(h_, &spec, d_rec_logp));
     }
+    // The critic (gymnet_vecenv_actor_critic_config): a second network of the actor's kind over the actor's input, widths w_0 = history *
+    // obs_dim .. w_L = 1, whose one output is the lane's value.  Needs a configured actor of either kind; empty widths remove it;
+    // ConfigureActor / ConfigureBoxActor drop it.
+    void ConfigureActorCritic(const std::vector<int32_t> &widths, const std::vector<float> &weights) {
+        if (widths.empty()) { check(gymnet_vecenv_actor_critic_config(h_, 0, nullptr, nullptr, 0)); return; }
+        check(gymnet_vecenv_actor_critic_config(h_, (int32_t)widths.size() - 1, widths.data(), weights.data(), (int64_t)weights.size()));
+    }
+    void LoadActorCriticWeights(const float *d_weights, int64_t count) { check(gymnet_vecenv_actor_critic_load_device(h_, d_weights, count)); }
+    /// the critic over every lane's current history into d_value float32 [N]: the last value after a rollout
+    void ActorValue(float *d_value) { check(gymnet_vecenv_actor_value_device(h_, d_value)); }
+    // ActorActLogp that also writes the critic's value of the input each action was chosen from into d_value float32 [N]
+    // (gymnet_vecenv_actor_act_value_device): actions, logits and logp are ActorActLogp's, bit for bit.  d_value null: ActorActLogp.
+    void ActorActValue(int32_t *d_actions, float *d_logp, float *d_value, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0,
+                       float *d_logits = nullptr) {
+        check(gymnet_vecenv_actor_act_value_device(h_, d_actions, d_logits, d_logp, d_value, epsilon, seed, tick));
+    }
+    // RolloutFusedLogp on a Discrete actor with a critic, also recording the value before every step into d_rec_value float32 [T][N]
+    // (gymnet_vecenv_rollout_fused_value_device); d_rec_logp may be null.  d_rec_value null: RolloutFusedLogp itself.
+    void RolloutFusedValue(gymnet_rollout_spec spec, float *d_rec_logp, float *d_rec_value) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_fused_value_device(h_, &spec, d_rec_logp, d_rec_value));
+    }
     // GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written out
     // there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  d_reward float32 [steps][N], d_done
     // uint8 [steps][N] (the fused rollout's records); d_value float32 [steps][N] or null (every value 0), d_last_value float32 [N], d_boot
