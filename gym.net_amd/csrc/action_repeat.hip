@@ -88,3 +88,61 @@ hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const Ro
 }
 
 }  // namespace gymnet
+
+// ---- the host side: the entry points, which reach the rollout through rollout_fused_entered (handle.hpp) ---------------------------
+using namespace gymnet;
+
+namespace {
+
+bool repeat_in_range(gymnet_vecenv *h, int32_t repeat) {
+    if (repeat >= 0 && repeat <= 255) return true;
+    fail(h, GYMNET_ERR_INVALID_ARG, "repeat must be in [0, 255] (skipped frames per decision), got %d", repeat);
+    return false;
+}
+
+// one decision: d_actions held for repeat + 1 env steps (repeat > 0; VALIDATE_ACTIONS has been applied by the caller)
+int launch_one_decision(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
+    gymnet_rollout_spec spec{};
+    spec.struct_size = sizeof spec;
+    spec.action_source = GYMNET_ACTIONS_RING;
+    spec.d_actions = d_actions; spec.steps = 1; spec.action_stride = 0; spec.ring = 1;
+    return rollout_fused_entered(h, FusedRequest{&spec, repeat, true});
+}
+
+}  // namespace
+
+extern "C" {
+
+int gymnet_vecenv_rollout_repeat_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t repeat) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    return rollout_fused_entered(h, FusedRequest{spec, repeat});
+    });
+}
+
+int gymnet_vecenv_step_repeat_device(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
+    if (repeat == 0 && h->lcfg.vec > 1 && !aligned_to(d_actions, 4 * h->lcfg.vec))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions must be %d-byte aligned", 4 * h->lcfg.vec);
+    ST_TRY(validate_staged_actions(h, d_actions));
+    return repeat == 0 ? launch_one_step(h, d_actions) : launch_one_decision(h, d_actions, repeat);
+    });
+}
+
+int gymnet_vecenv_step_repeat(gymnet_vecenv *h, const void *actions, int32_t repeat, void *obs_out, float *reward_out, uint8_t *done_out) {
+    return guarded([&]() -> int {
+    ENTER(h);                            // (not served by the resident kernel: a resident handle leaves residency first)
+    if (h->async_pending) return fail(h, GYMNET_ERR_ALREADY_STEPPING, "already running an async step");
+    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
+    const void *d_act = nullptr;
+    ST_TRY(stage_host_actions(h, actions, &d_act, true));
+    ST_TRY(repeat == 0 ? launch_one_step(h, d_act) : launch_one_decision(h, d_act, repeat));
+    return copy_out(h, obs_out, reward_out, done_out);
+    });
+}
+
+}  // extern "C"

@@ -26,7 +26,7 @@
 // unit's kernels stay what they were.
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, the prologue of every act entry point
-// (actor_act_enter), and the calls the fused rollout (capi.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
+// (actor_act_enter), and the calls the fused rollout (rollout_fused.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
 // is the router: it alone says which of the six units runs a handle's rollout (actor_act_launch: the same for act).
 #include "actor_net.hpp"
 
@@ -242,20 +242,10 @@ int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
 
 }  // namespace
 
-int actor_rollout_check(gymnet_vecenv *h) {
-    ST_TRY(need_actor(h));
-    if (!actor_current(h)) return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: reset the actor (or push) before an actor rollout");
-    return GYMNET_OK;
-}
-
-// gymnet_vecenv_rollout_fused_logp_device's checks of its record pointer, which run before the rollout's own
-int actor_logp_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp) {
-    if (action_source != GYMNET_ACTIONS_ACTOR)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: log-probabilities are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
-    ST_TRY(need_actor(h));
-    if (h->actor->box) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp: this handle's actor chooses Box actions; a log-probability belongs to a Discrete actor");
-    if (!aligned_to(d_rec_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
-    return GYMNET_OK;
+// what the fused rollout's plan (rollout_plan.hpp) reads of the handle's actor: its refusals are worded there
+ActorFacts actor_facts(const gymnet_vecenv *h) {
+    if (!h->actor) return {};
+    return {h->actor->box ? ActorKind::Box : ActorKind::Discrete, h->actor->has_critic(), actor_current(h)};
 }
 
 // this unit's fused rollout: a Discrete actor under the default exploration setting
@@ -268,32 +258,18 @@ static hipError_t actor_discrete_rollout_launch(gymnet_vecenv *h, bool records, 
     }
 }
 
-// gymnet_vecenv_rollout_fused_value_device's checks of its record pointers, which run before the rollout's own
-int actor_value_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp, const float *d_rec_value) {
-    if (action_source != GYMNET_ACTIONS_ACTOR)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: values are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
-    ST_TRY(need_actor(h));
-    if (h->actor->box)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: this handle's actor chooses Box actions; the fused rollout records values for a Discrete actor "
-                    "(gymnet_vecenv_actor_value_device serves a Box actor)");
-    if (!h->actor->has_critic()) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value: no critic configured (gymnet_vecenv_actor_critic_config)");
-    if (!aligned_to(d_rec_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
-    if (!aligned_to(d_rec_value, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_value must be 4-byte aligned");
-    return GYMNET_OK;
-}
-
 // The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: its policy decides.  Discrete: a value
 // pointer (gymnet_vecenv_rollout_fused_value_device) goes to actor_value.hip, with or without a logp pointer; a logp pointer alone
 // (gymnet_vecenv_rollout_fused_logp_device) to actor_logp.hip under either setting; else the setting decides
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value) {
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, const FusedRequest &rq) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
     if (ac.box) {
-        if (rec_logp || rec_value) return hipErrorInvalidValue;              // (actor_logp / actor_value_rollout_check has refused it)
+        if (rq.rec_logp || rq.rec_value) return hipErrorInvalidValue;        // (the plan has refused it: rollout_plan.hpp record_pointers)
         return ac.default_policy() ? actor_box_rollout_launch(h, records, a, r) : actor_box_policy_rollout_launch(h, records, a, r);
     }
-    if (rec_value) return actor_value_rollout_launch(h, records, a, r, rec_logp, rec_value);
-    if (rec_logp) return actor_logp_rollout_launch(h, records, a, r, rec_logp);
+    if (rq.rec_value) return actor_value_rollout_launch(h, records, a, r, rq.rec_logp, rq.rec_value);
+    if (rq.rec_logp) return actor_logp_rollout_launch(h, records, a, r, rq.rec_logp);
     return ac.default_exploration() ? actor_discrete_rollout_launch(h, records, a, r) : actor_softmax_rollout_launch(h, records, a, r);
 }
 

@@ -205,8 +205,7 @@ inline ActorExplore actor_explore(const Actor &ac) { return {ac.discrete_explore
 
 // the message names the config call that serves the handle's env
 inline int need_actor(gymnet_vecenv *h) {
-    return h->actor ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, "no actor configured (%s)",
-                                       h->desc->box_action ? "gymnet_vecenv_actor_box_config" : "gymnet_vecenv_actor_config");
+    return h->actor ? GYMNET_OK : fail(h, GYMNET_ERR_INVALID_ARG, kNoActorFormat, actor_config_call(h->desc->box_action));   // (rollout_plan.hpp)
 }
 
 // the history is current: no vector step since the last actor config, reset, push or actor rollout

@@ -113,7 +113,7 @@ static hipError_t launch_value_rollout_env(gymnet_vecenv *h, bool records, const
 
 // actor.hip's router sends a Discrete actor's rollout with a value pointer here, under either setting, with or without a logp pointer
 hipError_t actor_value_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value) {
-    if (!h->actor->has_critic()) return hipErrorInvalidValue;               // (actor_value_rollout_check has refused it)
+    if (!h->actor->has_critic()) return hipErrorInvalidValue;               // (the plan has refused it: rollout_plan.hpp)
     switch (h->cfg.env_id) {
         case GYMNET_ENV_CARTPOLE: return launch_value_rollout_env<CartPole>(h, records, a, r, rec_logp, rec_value);
         case GYMNET_ENV_MOUNTAINCAR: return launch_value_rollout_env<MountainCar>(h, records, a, r, rec_logp, rec_value);

@@ -1,5 +1,6 @@
 // capi.hip — the C ABI (include/gymnet_amd.h) over the HIP kernels.  Host code only; compiled by hipcc.  The launch policy, the
-// resident mailbox and the graph-replay rollout have units of their own (launch_policy.hip, resident.hip, step_graph.hip; handle.hpp).
+// resident mailbox, the graph-replay rollout and the fused rollout have units of their own (launch_policy.hip, resident.hip,
+// step_graph.hip, rollout_fused.hip; handle.hpp); frame skip's entry points are in action_repeat.hip.
 //
 // There is NO CPU fallback in this library: without a usable AMD GPU every compute entry point fails
 // with GYMNET_ERR_NO_DEVICE / GYMNET_ERR_HIP.  The CPU restatement under oracle/ is test infrastructure
@@ -328,7 +329,7 @@ int gymnet_vecenv_destroy(gymnet_vecenv *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_graphs(h);
     for (void *p : h->owned) (void)hipFree(p);
-    if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
+    if (h->ep.d) (void)hipFree(h->ep.d);
     (void)release_render(h); (void)release_stack(h); (void)release_memory(h); (void)release_actor(h);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->pin_block) (void)hipHostFree(h->pin_block);
@@ -710,240 +711,6 @@ int gymnet_vecenv_rollout_device(gymnet_vecenv *h, const void *d_actions, int64_
     return guarded([&]() -> int {
     ENTER(h);
     return rollout_steps(h, d_actions, steps, action_stride, ring);
-    });
-}
-
-int gymnet_vecenv_rollout_fused_device(gymnet_vecenv *h, const void *d_actions, int64_t steps, int64_t action_stride,
-                                       int64_t ring, const gymnet_rollout_buffers *rec) {
-    gymnet_rollout_spec spec{};
-    spec.struct_size = sizeof spec;
-    spec.action_source = GYMNET_ACTIONS_RING;
-    spec.d_actions = d_actions; spec.steps = steps; spec.action_stride = action_stride; spec.ring = ring;
-    if (rec) { spec.d_rec_obs = rec->d_obs; spec.d_rec_reward = rec->d_reward; spec.d_rec_done = rec->d_done; }
-    return gymnet_vecenv_rollout_fused_ex_device(h, &spec);
-}
-
-}  // extern "C"
-
-namespace {
-
-// segment buffers of the fused rollout's episode records: kShards segments of `cap` records each (t, lane, return, length) +
-// the shard counters.  Random lanes do not fill the shards evenly, so a segment gets twice its share of the caller's capacity —
-// and what a shard still cannot hold (lanes that finish very unevenly) goes to ONE shared overflow segment of `capacity` records
-// (round 6): records are dropped only when more episodes end than the caller's arrays hold.
-int ensure_episode_segments(gymnet_vecenv *h, int64_t capacity) {
-    const int64_t cap = 2 * ((capacity + kShards - 1) / kShards) + 64;
-    if (h->d_ep_seg && cap <= h->ep_seg_cap && capacity <= h->ep_ov_cap) return GYMNET_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));          // a previous rollout's gather may still read the old segments
-    if (h->d_ep_seg) (void)hipFree(h->d_ep_seg);
-    h->d_ep_seg = nullptr; h->ep_seg_cap = 0; h->ep_ov_cap = 0;
-    void *q = nullptr;
-    // four arrays of [kShards segments of cap | one overflow segment of capacity] records, then kShards + 1 counters (a cache line each)
-    const size_t bytes = ((size_t)kShards * (size_t)cap + (size_t)capacity) * 16 + (size_t)(kShards + 1) * kCountStride * 4 + 8;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(h, GYMNET_ERR_OOM, "hipMalloc(%zu bytes) for the rollout's episode records failed: %s", bytes, hipGetErrorString(e));
-    h->d_ep_seg = q; h->ep_seg_cap = cap; h->ep_ov_cap = capacity;
-    return GYMNET_OK;
-}
-
-// held: frame skip — sp.steps decisions of held + 1 sub-steps each (action_repeat.hip); 0: the fused rollout.  rec_logp / rec_value: where an
-// actor rollout records every step's log-probability / critic value (null: nowhere)
-template <class R>
-int rollout_fused_typed(gymnet_vecenv *h, const gymnet_rollout_spec &sp, LaunchCfg cfg, bool episodes, int32_t held, float *rec_logp, float *rec_value) {
-    const StepArgsT<R> a = make_step_args<R>(h, sp.d_actions);
-    RolloutArgsT<R> r{};
-    r.steps = sp.steps; r.action_stride = sp.action_stride; r.ring = sp.ring;
-    r.rec_obs = static_cast<R *>(sp.d_rec_obs); r.rec_reward = sp.d_rec_reward; r.rec_done = sp.d_rec_done;
-    r.rec_action = sp.d_rec_actions;
-    r.action_source = sp.action_source; r.epsilon = sp.epsilon; r.action_seed = sp.action_seed; r.action_tick0 = sp.action_tick0;
-    if (episodes) {
-        char *seg = static_cast<char *>(h->d_ep_seg);
-        const size_t one = ((size_t)kShards * (size_t)h->ep_seg_cap + (size_t)h->ep_ov_cap) * 4;
-        r.ep_t = reinterpret_cast<int32_t *>(seg); r.ep_lane = reinterpret_cast<int32_t *>(seg + one);
-        r.ep_ret = h->d_ep_ret ? reinterpret_cast<float *>(seg + 2 * one) : nullptr;
-        r.ep_len = h->d_ep_ret ? reinterpret_cast<int32_t *>(seg + 3 * one) : nullptr;
-        r.ep_count = reinterpret_cast<uint32_t *>(seg + 4 * one);
-        r.ep_cap = h->ep_seg_cap;
-        r.ov_cap = sp.ep_capacity < h->ep_ov_cap ? sp.ep_capacity : h->ep_ov_cap;
-        r.records_no_overflow = (sp.record_flags & GYMNET_RECORDS_NO_OVERFLOW) ? 1 : 0;
-        // the kShards + 1 counters, zeroed on the stream by a kernel of our own
-        HIP_TRY(h, launch_fill_i32(reinterpret_cast<int32_t *>(r.ep_count), 0, (int64_t)(kShards + 1) * kCountStride, h->stream));
-    }
-    if (held > 0) {
-        HIP_TRY(h, repeat_rollout_launch(h, a, r, held + 1));
-    } else if constexpr (sizeof(R) == 4) {
-        if (sp.action_source == GYMNET_ACTIONS_ACTOR) {
-            HIP_TRY(h, actor_rollout_launch(h, episodes, a, r, rec_logp, rec_value));
-        } else {
-            HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
-        }
-    } else {
-        HIP_TRY(h, launchers<R>(h).rollout(h->autoreset, h->extras, a, r, cfg, h->stream));
-    }
-    if (episodes) {
-        EpisodeGatherArgs g{};
-        g.counts = r.ep_count; g.cap = r.ep_cap;
-        g.ep_t = r.ep_t; g.ep_lane = r.ep_lane; g.ep_ret = r.ep_ret; g.ep_len = r.ep_len;
-        g.ov_cap = r.ov_cap;
-        g.out_t = sp.d_ep_step; g.out_lane = sp.d_ep_lane; g.out_ret = sp.d_ep_return; g.out_len = sp.d_ep_length;
-        g.out_capacity = sp.ep_capacity; g.out_count = sp.d_ep_count;
-        HIP_TRY(h, launch_gather_episodes(g, h->stream));
-    }
-    h->last_cparity = a.cparity;          // the done list (if any) describes the rollout's last step
-    return GYMNET_OK;
-}
-
-// gymnet_vecenv_rollout_fused_ex_device on a handle the caller has ENTERed.  held > 0: gymnet_vecenv_rollout_repeat_device — the same
-// checks, then spec.steps decisions of held + 1 sub-steps each.  validated: the caller has run VALIDATE_ACTIONS over the one slice read
-// (gymnet_vecenv_step_repeat_device).  rec_logp: gymnet_vecenv_rollout_fused_logp_device's record pointer, checked by the caller
-// (actor_logp_rollout_check); null: none.  rec_value: gymnet_vecenv_rollout_fused_value_device's, the same (actor_value_rollout_check).
-int rollout_fused_entered(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t held, bool validated, float *rec_logp, float *rec_value = nullptr) {
-    if (!spec) return fail(h, GYMNET_ERR_INVALID_ARG, "spec is null");
-    if (spec->struct_size != sizeof(gymnet_rollout_spec))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "spec.struct_size %u != %zu (ABI mismatch)", spec->struct_size, sizeof(gymnet_rollout_spec));
-    const gymnet_rollout_spec &sp = *spec;
-    const EnvDesc &d = *h->desc;
-    if (sp.action_source < GYMNET_ACTIONS_RING || sp.action_source > GYMNET_ACTIONS_ACTOR) return fail(h, GYMNET_ERR_INVALID_ARG, "bad action_source %d", sp.action_source);
-    const bool actor = sp.action_source == GYMNET_ACTIONS_ACTOR;
-    const bool ring_read = sp.action_source != GYMNET_ACTIONS_SAMPLE && !actor;
-    if (ring_read && !sp.d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (sp.steps < 0 || (ring_read && (sp.ring < 1 || sp.action_stride < 0))) return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride");
-    if (sp.steps > INT32_MAX) return fail(h, GYMNET_ERR_INVALID_ARG, "steps must fit an int32 (episode records carry the step index)");
-    // ABI 5 called this field `reserved`: a caller that left it uninitialised must not select the lossy no-overflow variant by accident
-    if (sp.record_flags & ~GYMNET_RECORDS_NO_OVERFLOW) return fail(h, GYMNET_ERR_INVALID_ARG, "unknown record_flags bits 0x%x", (unsigned)sp.record_flags);
-    if (sp.action_source == GYMNET_ACTIONS_EPSILON_GREEDY) {
-        if (d.box_action) return fail(h, GYMNET_ERR_UNSUPPORTED, "epsilon-greedy composition is defined for Discrete action spaces");
-        if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-    }
-    if (actor && held > 0)
-        return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout has no frame skip: run the unfused loop, one decision at a time "
-                    "(actor_act_device, step_repeat_device, actor_push_device)");
-    if (held > 0 && sp.steps * ((int64_t)held + 1) > INT32_MAX)
-        return fail(h, GYMNET_ERR_INVALID_ARG, "steps * (repeat + 1) must fit an int32");
-    if (actor) {
-        if (h->f64) return fail(h, GYMNET_ERR_UNSUPPORTED, "the fused actor rollout runs float32 handles (float64: act / step / push)");
-        if (!(sp.epsilon >= 0.0f && sp.epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
-        ST_TRY(actor_rollout_check(h));
-    }
-    if ((h->cfg.flags & GYMNET_FLAG_VALIDATE_ACTIONS) && ring_read && !validated)
-        return fail(h, GYMNET_ERR_UNSUPPORTED, "VALIDATE_ACTIONS is per step; use gymnet_vecenv_rollout_device (sampled actions are valid by construction)");
-    const bool episodes = sp.d_ep_lane || sp.d_ep_step || sp.d_ep_return || sp.d_ep_length || sp.d_ep_count;
-    if (episodes) {
-        if (!h->extras) return fail(h, GYMNET_ERR_UNSUPPORTED, "episode records need a bookkeeping handle (GYMNET_FLAG_EPISODE_STATS / DONE_LIST / FINAL_OBS)");
-        if ((sp.d_ep_return || sp.d_ep_length) && !h->d_ep_ret) return fail(h, GYMNET_ERR_UNSUPPORTED, "episode return / length records need GYMNET_FLAG_EPISODE_STATS");
-        if (sp.ep_capacity < 0 || !sp.d_ep_count) return fail(h, GYMNET_ERR_INVALID_ARG, "episode records need ep_capacity >= 0 and d_ep_count");
-    }
-    if (sp.d_rec_actions && !h->extras && sp.action_source == GYMNET_ACTIONS_RING)
-        return fail(h, GYMNET_ERR_UNSUPPORTED, "d_rec_actions: the actions of a plain ring rollout ARE the ring (recorded for sampled / epsilon-greedy actions and on bookkeeping handles)");
-    if (sp.steps == 0) {
-        if (episodes) HIP_TRY(h, hipMemsetAsync(sp.d_ep_count, 0, 2 * sizeof(uint32_t), h->stream));
-        return GYMNET_OK;
-    }
-    LaunchCfg cfg = h->lcfg;
-    // wide accesses on the streams a rollout touches: 16-byte rows of observations (4 floats / 2 doubles per thread), vec rewards /
-    // actions, vec done bytes; anything less aligned runs one lane per thread (same bits)
-    if (cfg.vec > 1) {
-        auto streams_fit = [&](int w) {
-            bool ok = (h->n % w) == 0;
-            if (ring_read) ok = ok && aligned_to(sp.d_actions, 4 * w) && (sp.action_stride % w) == 0;
-            return ok && (!sp.d_rec_obs || aligned16(sp.d_rec_obs)) && (!sp.d_rec_reward || aligned_to(sp.d_rec_reward, 4 * w)) &&
-                   (!sp.d_rec_done || aligned_to(sp.d_rec_done, w)) && (!sp.d_rec_actions || aligned_to(sp.d_rec_actions, 4 * w));
-        };
-        const int w = h->f64 ? 2 : cfg.vec;               // the fused rollout's wide form: 2 doubles / 4 floats (2: Acrobot) per thread
-        // the FAT form where every stream allows it — float64: FOUR lanes per thread (the state sits in registers for the whole rollout, so
-        // this is about how many lanes share a wave's per-step overheads, not about access width; launch_rollout_env) — else two, else one;
-        // (float32 has no fat form: eight floats per thread were measured slower, step_kernels.hpp rollout_fat_lanes)
-        if (h->f64 && h->desc->alias && (h->sstride % 4) == 0 && streams_fit(4)) cfg.vec = 4;
-        else if (!streams_fit(w)) cfg.vec = 1;
-    }
-    if (episodes) ST_TRY(ensure_episode_segments(h, sp.ep_capacity));
-    ST_TRY(h->f64 ? rollout_fused_typed<double>(h, sp, cfg, episodes, held, rec_logp, rec_value) : rollout_fused_typed<float>(h, sp, cfg, episodes, held, rec_logp, rec_value));
-    swap_buffers(h);                     // DOUBLE_BUFFER: the launch read one buffer and wrote the other, once
-    const uint64_t ticks = (uint64_t)sp.steps * ((uint64_t)held + 1);       // a sub-step is an engine tick
-    h->tick += ticks;
-    h->held_ticks += ticks - (uint64_t)sp.steps;
-    h->tslot ^= 1;                       // one launch: it read one half of d_tick2 and wrote the other
-    h->step_launches += 1;
-    h->lane_steps += ticks * (uint64_t)h->n;      // slots: the host does not know which sub-steps found their lane idle
-    if (actor) actor_rollout_done(h, sp.steps);
-    return GYMNET_OK;
-}
-
-bool repeat_in_range(gymnet_vecenv *h, int32_t repeat) {
-    if (repeat >= 0 && repeat <= 255) return true;
-    fail(h, GYMNET_ERR_INVALID_ARG, "repeat must be in [0, 255] (skipped frames per decision), got %d", repeat);
-    return false;
-}
-
-// one decision: d_actions held for repeat + 1 env steps (repeat > 0; VALIDATE_ACTIONS has been applied by the caller)
-int launch_one_decision(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
-    gymnet_rollout_spec spec{};
-    spec.struct_size = sizeof spec;
-    spec.action_source = GYMNET_ACTIONS_RING;
-    spec.d_actions = d_actions; spec.steps = 1; spec.action_stride = 0; spec.ring = 1;
-    return rollout_fused_entered(h, &spec, repeat, true, nullptr);
-}
-
-}  // namespace
-
-extern "C" {
-
-int gymnet_vecenv_rollout_fused_ex_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    return rollout_fused_entered(h, spec, 0, false, nullptr);
-    });
-}
-
-int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp) {
-    if (!d_rec_logp) return gymnet_vecenv_rollout_fused_ex_device(h, spec);
-    return guarded([&]() -> int {
-    ENTER(h);
-    // (a null or mis-sized spec is the rollout's own refusal)
-    if (spec && spec->struct_size == sizeof(gymnet_rollout_spec)) ST_TRY(actor_logp_rollout_check(h, spec->action_source, d_rec_logp));
-    return rollout_fused_entered(h, spec, 0, false, d_rec_logp);
-    });
-}
-
-int gymnet_vecenv_rollout_fused_value_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value) {
-    if (!d_rec_value) return gymnet_vecenv_rollout_fused_logp_device(h, spec, d_rec_logp);
-    return guarded([&]() -> int {
-    ENTER(h);
-    // (a null or mis-sized spec is the rollout's own refusal)
-    if (spec && spec->struct_size == sizeof(gymnet_rollout_spec)) ST_TRY(actor_value_rollout_check(h, spec->action_source, d_rec_logp, d_rec_value));
-    return rollout_fused_entered(h, spec, 0, false, d_rec_logp, d_rec_value);
-    });
-}
-
-int gymnet_vecenv_rollout_repeat_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, int32_t repeat) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
-    return rollout_fused_entered(h, spec, repeat, false, nullptr);
-    });
-}
-
-int gymnet_vecenv_step_repeat_device(gymnet_vecenv *h, const void *d_actions, int32_t repeat) {
-    return guarded([&]() -> int {
-    ENTER(h);
-    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
-    if (!d_actions) return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions is null");
-    if (repeat == 0 && h->lcfg.vec > 1 && !aligned_to(d_actions, 4 * h->lcfg.vec))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "d_actions must be %d-byte aligned", 4 * h->lcfg.vec);
-    ST_TRY(validate_staged_actions(h, d_actions));
-    return repeat == 0 ? launch_one_step(h, d_actions) : launch_one_decision(h, d_actions, repeat);
-    });
-}
-
-int gymnet_vecenv_step_repeat(gymnet_vecenv *h, const void *actions, int32_t repeat, void *obs_out, float *reward_out, uint8_t *done_out) {
-    return guarded([&]() -> int {
-    ENTER(h);                            // (not served by the resident kernel: a resident handle leaves residency first)
-    if (h->async_pending) return fail(h, GYMNET_ERR_ALREADY_STEPPING, "already running an async step");
-    if (!repeat_in_range(h, repeat)) return GYMNET_ERR_INVALID_ARG;
-    const void *d_act = nullptr;
-    ST_TRY(stage_host_actions(h, actions, &d_act, true));
-    ST_TRY(repeat == 0 ? launch_one_step(h, d_act) : launch_one_decision(h, d_act, repeat));
-    return copy_out(h, obs_out, reward_out, done_out);
     });
 }
 

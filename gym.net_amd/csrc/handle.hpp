@@ -1,7 +1,8 @@
 // handle.hpp — what a gymnet_vecenv handle IS, plus the host-side helpers the library's units share.  capi.hip holds the C entry points
 // of the handle itself and the host boundary; three subsystems with state of their own on the handle have a unit each —
 // launch_policy.hip (h->lcfg and what may replace it), resident.hip (h->res: the mailbox and its kernel), step_graph.hip (h->graph: the
-// captured rollouts) — beside group.hip and the attachment units.
+// captured rollouts) — beside group.hip and the attachment units.  The fused rollout has rollout_fused.hip (h->ep: the episode-segment
+// block; what a call will do is rollout_plan.hpp's pure function), frame skip's entry points sit beside its kernels in action_repeat.hip.
 // Internal to the library: nothing here crosses the C ABI (include/gymnet_amd.h is the boundary).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +48,12 @@ struct GraphCache;
 struct StepGraphs {
     GraphCache *cache = nullptr;
     int mode = -1;                 // gymnet_launch_policy.graph: -1 = by batch size, 0 = eager launches, 1 = hipGraph replay
+};
+
+// the fused rollout's segmented episode records + shard counters (rollout_fused.hip): allocated on first use, grown on demand
+struct EpisodeBlock {
+    void *d = nullptr;
+    EpisodeSegments seg;           // its layout (rollout_plan.hpp)
 };
 
 struct RenderStaging;
@@ -112,9 +119,7 @@ struct gymnet_vecenv {
     uint8_t *pin_done = nullptr;
     uint32_t *d_bad = nullptr;
     gymnet::Resident res;
-    void *d_ep_seg = nullptr;      // fused rollout: segmented episode records + shard counters (allocated on first use, grown on demand)
-    int64_t ep_seg_cap = 0;        // records per shard segment
-    int64_t ep_ov_cap = 0;         // records of the shared overflow segment (= the largest ep_capacity asked for so far)
+    gymnet::EpisodeBlock ep;
     // the four attachments (render.hip, pixel_stack.hip, episode_memory.hip, actor.hip): each unit defines its own type, creates it on
     // config / first use and frees it in its release function below; NULL: none configured
     gymnet::RenderStaging *render = nullptr;
@@ -262,8 +267,7 @@ inline void *row_at(void *base, int64_t k, int64_t stride, size_t esz) { return 
 // (32 B state read + 4 B action + 32 B state written + 4 B reward + 1 B done)
 inline size_t bytes_per_step(const gymnet_vecenv *h) { return h->f64 ? (size_t)73 : (size_t)h->desc->algorithmic_bytes; }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned_to(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+// (aligned16, aligned_to: rollout_plan.hpp)
 
 // the arguments of a step launch that reads its actions at d_actions / of a reset of the lanes d_mask marks (NULL = all lanes), as the
 // handle stands
@@ -349,17 +353,16 @@ int resident_stop(gymnet_vecenv *h);                                 // tells a 
 bool resident_serves(const gymnet_vecenv *h);                        // the resident path serves this handle's host-boundary steps right now
 // one command (kMailboxStep / ResetAll / ResetDone) through the mailbox: post it, wait for its results, copy them out
 int resident_command(gymnet_vecenv *h, uint32_t cmd, const void *actions, void *obs_out, float *reward_out, uint8_t *done_out);
-// the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): may it run (an actor is configured and its history is current); the launch,
-// by the unit that serves the handle as it stands (records: the rollout keeps compact episode records; rec_logp / rec_value: where it
-// records every step's log-probability / critic value, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps`
-// on and is current
-int actor_rollout_check(gymnet_vecenv *h);
-hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value);
+// rollout_fused.hip
+// gymnet_vecenv_rollout_fused_ex_device on a handle the caller has ENTERed (rollout_plan.hpp FusedRequest: the spec, frame skip, the
+// record pointers of the logp / value calls): gather the facts, plan or refuse, allocate and launch, move the ticks
+int rollout_fused_entered(gymnet_vecenv *h, const FusedRequest &rq);
+// the fused rollout with GYMNET_ACTIONS_ACTOR (actor.hip): what the plan reads of the handle's actor; the launch, by the unit that serves
+// the handle as it stands (records: the rollout keeps compact episode records; rq.rec_logp / rq.rec_value: where it records every step's
+// log-probability / critic value, [steps][n], null: nowhere); afterwards the history's newest slot has moved `steps` on and is current
+ActorFacts actor_facts(const gymnet_vecenv *h);
+hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, const FusedRequest &rq);
 void actor_rollout_done(gymnet_vecenv *h, int64_t steps);
-// gymnet_vecenv_rollout_fused_logp_device: the checks that belong to its record pointer (the source, the actor's kind, the alignment)
-int actor_logp_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp);
-// gymnet_vecenv_rollout_fused_value_device: the same for its two record pointers, and that the Discrete actor has a critic
-int actor_value_rollout_check(gymnet_vecenv *h, int32_t action_source, const float *d_rec_logp, const float *d_rec_value);
 // the fused rollout with frame skip (action_repeat.hip): r.steps decisions of R sub-steps each under one action, one launch
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs &a, const RolloutArgs &r, int32_t R);
 hipError_t repeat_rollout_launch(gymnet_vecenv *h, const StepArgs64 &a, const RolloutArgs64 &r, int32_t R);

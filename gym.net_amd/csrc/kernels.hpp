@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "launch_policy.hpp"
+#include "rollout_plan.hpp"
 
 namespace gymnet {
 
@@ -61,8 +62,7 @@ template <class R>
 using StepKernelFn = void (*)(R *state, const void *action, int64_t n, int64_t state_stride, uint64_t *tick2, float *reward, int32_t block,
                               int32_t parity, StepArgsT<R> rest);
 
-constexpr int kShards = 256;        // power of two; the gather kernels' workgroup size (kernels.hip static_assert)
-constexpr int kCountStride = 16;    // uint32 words between shard counters (64 bytes: one counter per cache line)
+// (kShards, kCountStride: rollout_plan.hpp, whose EpisodeSegments lays a rollout's episode records out by them)
 constexpr int kAfterStride = 8;     // uint64 words between after_done shards (64 bytes)
 // (LaunchCfg, a launch's configuration, and the rules that choose a handle's first one: launch_policy.hpp)
 

@@ -304,3 +304,68 @@ def test_bookkeeping_rollout_variants_equal_the_oracle_replay(gpu_pkg, oracle, n
         explored = (got_a != policy[np.arange(T) % ring]).mean() if actions == "epsilon_greedy" else None
         if explored is not None:
             assert abs(explored - eps * (1 - 1 / nvals)) < 0.01                      # explored AND drew a different action
+
+
+_POISON = {"int32": -559038737, "float32": -7777.0, "float64": -7777.0, "uint8": 0xA5}
+_GUARD = 16                      # poison elements on either side: a multiple of 16 bytes for every dtype, so offset 0 is aligned
+
+
+def _inside(torch, shape, dtype, off):
+    """A tensor of `shape` that starts `off` elements past a 16-byte line inside a larger allocation filled with poison; returns
+    (the whole allocation, the view)."""
+    size = int(np.prod(shape))
+    flat = torch.full((size + 2 * _GUARD + 8,), _POISON[str(dtype).split(".")[-1]], dtype=dtype, device="cuda")
+    return flat, flat[_GUARD + off:_GUARD + off + size].view(shape)
+
+
+def _poison_intact(flat, view, off):
+    size = view.numel()
+    p = _POISON[str(flat.dtype).split(".")[-1]]
+    return bool((flat[:_GUARD + off] == p).all()) and bool((flat[_GUARD + off + size:] == p).all())
+
+
+@pytest.mark.parametrize("name,dtype,launch", [("CartPole-v1", np.float32, {"vec": 4}), ("CartPole-v1", np.float64, None),
+                                                ("Acrobot-v1", np.float32, {"vec": 2})])
+def test_ring_rollout_is_the_same_wherever_its_streams_start(gpu_pkg, name, dtype, launch):
+    """The lane width of the rollout kernel is chosen per call from n, the action stride and the alignment of the action ring and the four
+    record streams (four lanes per thread for CartPole under vec = 4 and for the float64 handle, two for Acrobot under vec = 2 and for
+    float64 streams that allow no more, else one); every width computes the same bits.  8 steps at 1024 lanes from a ring on an
+    EPISODE_STATS handle, recording observation, reward, done and actions: once with every stream on a 16-byte line, then with each
+    stream in turn one element further on inside its allocation (and the done bytes two), poison on both sides.  Every run equals the
+    first bitwise — records, state, tick, Counters() — and no poison word is touched."""
+    import torch
+    n, T, ring = 1024, 8, 2
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    nvals = 2 if name.startswith("CartPole") else 3
+    acts = torch.from_numpy(np.random.default_rng(11).integers(0, nvals, (ring, n)).astype(np.int32)).cuda()
+
+    def run(moved, by):
+        off = {k: (by if k == moved else 0) for k in ("ring", "obs", "reward", "done", "actions")}
+        # (a 5-step time limit: every lane is truncated and re-drawn inside the rollout, so the fused reset runs at every width)
+        with gpu_pkg.VectorEnv(name, n, seed=SEED, auto_reset=True, dtype=dtype, episode_stats=True, max_episode_steps=5, launch_policy=launch) as env:
+            env.ResetDevice()
+            D = env.ObsDim
+            bufs = {"ring": _inside(torch, (ring, n), torch.int32, off["ring"]), "obs": _inside(torch, (T, D, n), tdt, off["obs"]),
+                    "reward": _inside(torch, (T, n), torch.float32, off["reward"]), "done": _inside(torch, (T, n), torch.uint8, off["done"]),
+                    "actions": _inside(torch, (T, n), torch.int32, off["actions"])}
+            bufs["ring"][1].copy_(acts)
+            torch.cuda.synchronize()
+            env.RolloutFusedDevice(bufs["ring"][1], T, n, ring, rec_obs=bufs["obs"][1], rec_reward=bufs["reward"][1], rec_done=bufs["done"][1],
+                                   rec_actions=bufs["actions"][1])
+            env.Sync()
+            for k, (flat, view) in bufs.items():
+                assert _poison_intact(flat, view, off[k]), (moved, by, k)
+            out = {k: bufs[k][1].cpu().numpy().copy() for k in ("obs", "reward", "done", "actions")}
+            out["state"] = env.GetState()
+            for arr in ("episode_return", "episode_length"):
+                out[arr] = env.GetArray(arr)
+            return out, env.Tick, env.Counters()
+
+    want, tick, counters = run(None, 0)
+    assert tick == T + 1 and want["done"].any() and np.array_equal(want["actions"], acts.cpu().numpy()[np.arange(T) % ring])
+    for moved, by in [("ring", 1), ("obs", 1), ("reward", 1), ("done", 1), ("actions", 1), ("done", 2)]:
+        got, got_tick, got_counters = run(moved, by)
+        for k in want:
+            a, b = want[k], got[k]
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (moved, by, k)
+        assert got_tick == tick and got_counters == counters, (moved, by)
