@@ -86,12 +86,18 @@ __device__ __forceinline__ void sincos_bounded(T x, T &s_out, T &c_out) {
     }
 }
 
-// sin/cos for SMALL arguments, |x| < 24 (|n| <= 15): Acrobot's wrapped angles and RK4 stage angles (|x| < 12 for every state
-// the dynamics can produce).  Two instructions shorter than sincos_bounded, per call: a TWO-constant Cody-Waite reduction —
-// with n at most 4 bits wide, C1 = pi/2 cut to 20 bits makes n*C1 exact, and the one remaining constant carries the next 24
-// bits (|r - (x - n pi/2)| < 2^-40) — and the cosine polynomial in Horner form (4 fma instead of 3 fma + 2 mul).  Same
-// minimax coefficients; |error| <= 1.2e-7 against float64 over |x| <= 16 (tests/test_oracle.py).  Its results differ from
-// sincos_bounded's in the last bit for some arguments, so the CPU twin has its own restatement (ref_sincos_f32_small).
+// sin/cos for SMALL arguments: Acrobot's wrapped angles and RK4 stage angles.  MEASURED range of use (float64 RK4 over the closed
+// state box |theta| <= pi, |dtheta1| <= 4 pi, |dtheta2| <= 9 pi — corners, 2^24 random states, hill-climbing;
+// tests/test_env_edge_tables_host.py): stage angles reach 33.32 rad, |n| <= 21 — not the "|x| < 12" this comment claimed before, nor
+// the |x| < 24 (|n| <= 15) the function was tested for.  Two
+// instructions shorter than sincos_bounded, per call: a TWO-constant Cody-Waite reduction — C1 = pi/2 cut to 20 bits, so that n * C1
+// is exact for |n| <= 15 (beyond that the product no longer fits 24 bits, but it is formed inside an fma, which rounds x - n C1
+// once), and the one remaining constant carries the next 24 bits (|r - (x - n pi/2)| < 2^-40 for |n| <= 15) — and the cosine polynomial
+// in Horner form (4 fma instead of 3 fma + 2 mul).  Same minimax coefficients; |error| <= 1.2e-7 against float64, swept over
+// |x| <= 36.5 — the measured maximum plus pi — where the largest error found is 7e-8, the same as below 16 (tests/test_oracle.py):
+// the bar did not have to move.  Its results differ from sincos_bounded's in the last bit for some arguments, so the CPU twin has
+// its own restatement (ref_sincos_f32_small).  Outside the state box (SetState) the arguments are whatever the state makes them:
+// the result is the twin's, bit for bit, and loses accuracy as |n| grows.
 template <class T>
 __device__ __forceinline__ void sincos_small(T x, T &s_out, T &c_out) {
     T n;
@@ -135,8 +141,8 @@ __device__ __forceinline__ void sincos_tiny(float x, float &s_out, float &c_out)
     c_out = fmaf(z * z, pc, fmaf(-0.5f, z, 1.0f));
 }
 
-// BOUNDED = true drops the OCML fallback: for callers whose argument is bounded by construction (Acrobot's wrapped
-// angles and RK4 stage angles, |x| < 16).  Same bits as the full version for every |x| <= 65536; beyond that the result
+// BOUNDED = true drops the OCML fallback: for callers whose argument is bounded by construction (the Box actor's noise angle in
+// [0, 2 pi), actor_box_policy.hip; Acrobot's angles, |x| <= 33.32 on its state box, take sincos_small).  Same bits as the full version for every |x| <= 65536; beyond that the result
 // is unspecified (finite garbage or NaN, never a hang).  It exists because the ten inlined Payne-Hanek fallbacks made the
 // ALU-bound Acrobot kernel 2.5x longer than its hot path.
 template <bool BOUNDED = false>
@@ -504,7 +510,7 @@ struct Acrobot {
     //    reciprocal is recip_p() below: 6 fma for the narrow range d1*det lives in;
     //  - every a*b+c is an explicit fmaf (one instruction, one rounding), products are factored
     //    (B^2 s2/2 + A B s2 = s2 B (B/2 + A));
-    //  - sincos without the OCML fallback (arguments are bounded here).
+    //  - sincos without the OCML fallback (stage angles stay below 33.32 rad on the state box: sincos_small's comment).
     // ~35 instructions + two sincos per stage instead of ~54 + two.  Mathematically identical to upstream; in float32 it
     // differs from the literal transcription by rounding only; the float64 oracle keeps upstream's literal formula and the
     // float32 "kernel semantics" twin of the CPU test infrastructure mirrors THIS sequence operation for operation.
@@ -541,18 +547,32 @@ struct Acrobot {
         d[0] = A; d[1] = B; d[2] = ddth1; d[3] = ddth2;
     }
 
-    // upstream loops `while x > M: x -= diff` / `while x < m: x += diff` with m = -M.  One RK4 step of dt = 0.2 moves a clamped
-    // state by at most ~10 rad, i.e. two wraps; this is the same repeated subtraction, at most FOUR times and written without a
-    // loop: identical results whenever four suffice (every state the dynamics can produce), a non-finite or absurd state cannot
-    // hang the GPU, and — no back-edge — the compiler's s_waitcnt bookkeeping stays exact across the step.  Only one of the two
-    // upstream loops can ever run, and x + diff == -(|x| - diff) bit for bit, so the magnitude is wrapped and the sign put
-    // back (the subtraction of a magnitude in (M, M + diff] lands in (-M, M]: the sign of the RESULT may flip, which is why
-    // the sign is applied by multiplication-free xor of the original sign bit): 14 instructions per angle instead of 24.
+    // upstream loops `while x > M: x -= diff` / `while x < m: x += diff` with m = -M.  This is the same repeated subtraction, at most
+    // WRAP_K = 6 times and written without a loop: a non-finite or absurd state cannot hang the GPU, and — no back-edge — the
+    // compiler's s_waitcnt bookkeeping stays exact across the step.  MEASURED over the closed state box |theta| <= pi, |dtheta1| <= 4 pi,
+    // |dtheta2| <= 9 pi in float64 (tests/test_env_edge_tables_host.py: corners, 2^24 random states, hill-climbing): the angle before
+    // the wrap reaches 29.73 rad, which takes FIVE subtractions (4 cover 9 pi = 28.27 only: states with both velocities near
+    // their clamps left [-pi, pi] under the four this function had before); with one full turn of margin, 36.01 <= (2 k + 1) pi gives k = 6,
+    // good for |x| <= 13 pi = 40.84.  THE CONTRACT (also include/gymnet_amd.h): inside the state bounds the step is upstream's; outside
+    // them (SetState) it is the float32 CPU twin's of the test infrastructure (its wrap_f_k) — an angle beyond 13 pi, +-inf or NaN keeps what
+    // six subtractions leave of it.  Only one of the two upstream loops can ever run, and x + diff == -(|x| - diff) bit for bit, so
+    // the magnitude is wrapped and the sign put back (the subtraction of a magnitude in (M, M + diff] lands in (-M, M]: the sign
+    // of the RESULT may flip, which is why the sign is applied by multiplication-free xor of the original sign bit).
+    // The chain is NESTED — each subtraction sits inside the branch of the one before — because a wave in which no lane wraps, which
+    // is nearly every wave of a rollout from reset states, then skips all of it on one execz branch: the flat select form of the same
+    // chain cost 10 % of the 2^20-lane step (docs/ledger.md §36).
+    static constexpr int WRAP_K = 6;
+    template <int K>
+    __device__ __forceinline__ static float wrap_chain(float ax, float M, float diff) {
+        if constexpr (K > 0) {
+            if (ax > M) ax = wrap_chain<K - 1>(ax - diff, M, diff);
+        }
+        return ax;
+    }
     __device__ __forceinline__ static float wrap(float x, float M) {
         const float diff = M + M;
         const uint32_t sign = __float_as_uint(x) & 0x80000000u;
-        float ax = fabsf(x);
-        if (ax > M) { ax -= diff; if (ax > M) { ax -= diff; if (ax > M) { ax -= diff; if (ax > M) ax -= diff; } } }
+        const float ax = wrap_chain<WRAP_K>(fabsf(x), M, diff);          // (NaN compares false and passes through)
         return __uint_as_float(__float_as_uint(ax) ^ sign);
     }
 
@@ -580,9 +600,13 @@ struct Acrobot {
         constexpr float mv1 = 4.0f * PI, mv2 = 9.0f * PI;
         y[0] = wrap(y[0], PI);
         y[1] = wrap(y[1], PI);
-        // v_med3_f32: the clamp in one instruction; identical to the compare/select pair for every non-NaN velocity
-        y[2] = __builtin_amdgcn_fmed3f(y[2], -mv1, mv1);
-        y[3] = __builtin_amdgcn_fmed3f(y[3], -mv2, mv2);
+        // upstream's min(max(v, -mv), mv), which hands a NaN on — as the compare / select pair of every other env here does.  v_med3_f32
+        // is that pair in one instruction for every non-NaN velocity, but for a NaN it gives a clamp value (it stood here alone before,
+        // and hid a poisoned lane behind -4 pi / -9 pi for good: never done, never reset).  One unordered compare and one select put
+        // the NaN back, payload and all: 3 instructions per velocity where the pair takes 4, bit-identical to it on every input.
+        const float v1 = __builtin_amdgcn_fmed3f(y[2], -mv1, mv1), v2 = __builtin_amdgcn_fmed3f(y[3], -mv2, mv2);
+        y[2] = y[2] != y[2] ? y[2] : v1;
+        y[3] = y[3] != y[3] ? y[3] : v2;
     }
 
     // One env: RK4, wrap / clamp; the sin/cos of the new angles serve both the termination test and the observation.
@@ -641,7 +665,7 @@ struct Acrobot {
     }
 
     // any state (set_state hands over arbitrary angles).  Angles a step or a reset can produce (|x| <= pi, far inside sincos_small's
-    // |x| < 24) take the step's OWN sin / cos, so SetState(GetState()) reproduces the observation the step wrote bit for bit
+    // tested |x| <= 36.5) take the step's OWN sin / cos, so SetState(GetState()) reproduces the observation the step wrote bit for bit
     // (sincos_f32 and sincos_small differ in the last bit for some arguments); anything larger keeps the full-range form.
     __device__ __forceinline__ static void observe(const float (&s)[S], float (&o)[O]) {
         float s1, c1, s2, c2;

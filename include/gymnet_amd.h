@@ -420,7 +420,14 @@ int gymnet_vecenv_kernel_name(gymnet_vecenv *h, char *buf, int32_t capacity);
 
 /* ---- state access: teacher-forced parity tests, checkpoint / resume -------------------------- */
 /* host [state_dim][num_envs] (structure-of-arrays), float32 — float64 for a GYMNET_FLAG_F64 handle.
- * CartPole: x, x_dot, theta, theta_dot (CartPoleEnv.cs:141-144). */
+ * CartPole: x, x_dot, theta, theta_dot (CartPoleEnv.cs:141-144).
+ * set_state checks nothing: it may put a lane outside the env's state bounds, or hand it NaN / inf.  The contract of the next step:
+ *   - inside the bounds (Acrobot: |theta| <= pi, |dtheta1| <= 4 pi, |dtheta2| <= 9 pi) the step is the upstream algorithm's;
+ *   - outside them it is that of the project's float32 CPU restatement (the tests' twin), bit for bit.  Acrobot wraps an angle by at most six
+ *     subtractions of 2 pi (enough for |theta| <= 13 pi before the wrap; the state bounds reach 29.73 rad): a larger angle, +-inf or
+ *     NaN keeps what six subtractions leave, where upstream's loop would run on — or never end;
+ *   - NaN is handed on by every clamp (upstream's min(max())): a poisoned lane stays NaN, is never done and is never reset by
+ *     GYMNET_FLAG_AUTORESET, until max_episode_steps truncates it or the caller resets it. */
 int gymnet_vecenv_get_state(gymnet_vecenv *h, void *state_soa);
 int gymnet_vecenv_set_state(gymnet_vecenv *h, const void *state_soa);
 /* steps_beyond_done per lane (CartPoleEnv.cs:41); only for CartPole without AUTORESET, else GYMNET_ERR_UNSUPPORTED. */

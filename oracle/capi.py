@@ -88,6 +88,8 @@ def lib():
     L.ref_acrobot_step_f32.restype = C.c_int
     L.ref_acrobot_step_batch_f32_literal.argtypes = [_f32p, _i32p, _f32p, _f32p, _u8p, C.c_int64]
     L.ref_acrobot_reset_f32.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, _f32p]
+    L.ref_acrobot_wrap_k.restype = C.c_int
+    L.ref_acrobot_domain_probe.argtypes = [_f32p, _i32p, C.c_int32, C.c_int64, _f64p, _f32p, _f32p, _f64p, _f32p, _i32p, _i32p, _u8p, _u8p]
     L.ref_env_step_batch_f32.argtypes = [C.c_int, _f32p, C.c_void_p, C.c_void_p, _f32p, _f32p, _u8p, C.c_int64]
     L.ref_env_step_batch_f64.argtypes = [C.c_int, _f64p, C.c_void_p, C.c_void_p, _f64p, _f64p, _u8p, C.c_int64]
     L.ref_env_reset_batch_f32.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _f32p, C.c_void_p, C.c_int64]
@@ -331,6 +333,27 @@ def acrobot_step_f32_literal(state, action):
     obs = np.zeros((6, n), np.float32); rew = np.zeros(n, np.float32); done = np.zeros(n, np.uint8)
     lib().ref_acrobot_step_batch_f32_literal(s, a, obs, rew, done, n)
     return s, obs, rew, done
+
+
+def acrobot_wrap_k():
+    """The number of subtractions in the kernel's (and the twin's) bounded angle wrap."""
+    return int(lib().ref_acrobot_wrap_k())
+
+
+def acrobot_domain_probe(state, action, k=None):
+    """One Acrobot step of float32 states [4, n] three ways — upstream semantics in float64 (unbounded wrap loop), kernel semantics
+    with at most k subtractions per wrap (default: the kernel's k), the literal float32 transcription — with the facts of the domain
+    proof.  Returns a dict: next64 [4,n], nextk [4,n], nextlit [4,n], pre64 / prek [3,n] (the two pre-wrap angles, the largest stage
+    |angle|), wraps64 / wrapsk [2,n], done64 / donek [n]."""
+    s = np.ascontiguousarray(np.asarray(state, dtype=np.float32))
+    n = s.shape[1]
+    a = np.ascontiguousarray(np.asarray(action, dtype=np.int32))
+    out = dict(next64=np.zeros((4, n)), nextk=np.zeros((4, n), np.float32), nextlit=np.zeros((4, n), np.float32),
+               pre64=np.zeros((3, n)), prek=np.zeros((3, n), np.float32), wraps64=np.zeros((2, n), np.int32),
+               wrapsk=np.zeros((2, n), np.int32), done64=np.zeros(n, np.uint8), donek=np.zeros(n, np.uint8))
+    lib().ref_acrobot_domain_probe(s, a, acrobot_wrap_k() if k is None else int(k), n, out["next64"], out["nextk"], out["nextlit"],
+                                   out["pre64"], out["prek"], out["wraps64"], out["wrapsk"], out["done64"], out["donek"])
+    return out
 
 
 def cpu_baseline(n_envs, steps, threads, alloc_faithful=True, seed=0x5EED):

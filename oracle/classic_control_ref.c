@@ -127,7 +127,8 @@ void ref_sincos_f32_kernel(float x, float *s_out, float *c_out) {
 }
 /* The small-argument sin/cos of the Acrobot kernel (envs.hpp: sincos_small), operation for operation: two-constant
  * Cody-Waite reduction (pi/2 cut to 20 bits, so n * C1 is exact for |n| <= 15) + the same minimax polynomials with the
- * cosine in Horner form.  Meant for |x| < 24; Acrobot's arguments stay below 12. */
+ * cosine in Horner form.  Acrobot's stage angles reach 33.32 rad on the env's state bounds (measured: tests/test_env_edge_tables_host.py);
+ * tests/test_oracle.py holds it to 1.2e-7 of float64 over |x| <= 36.5. */
 void ref_sincos_f32_small(float x, float *s_out, float *c_out) {
     const float n = rintf(x * 0.636619772367581343f);
     float r = fmaf(-0x1.921fap+0f, n, x);
@@ -643,27 +644,39 @@ static void acrobot_dsdt_f64(const double s[4], double tau, double d[4]) {
     d[0] = dth1; d[1] = dth2; d[2] = ddth1; d[3] = ddth2;
 }
 
-static double wrap_d(double x, double m, double M) {
+/* upstream's loops, unbounded.  (An infinite angle would never leave them — upstream hangs there — so it is handed back as it came;
+ * no test reads that as upstream's answer.)  count: how many times the body ran. */
+static double wrap_d_count(double x, double m, double M, int *count) {
     double diff = M - m;
-    while (x > M) x -= diff;
-    while (x < m) x += diff;
+    int c = 0;
+    if (isinf(x)) { if (count) *count = -1; return x; }
+    while (x > M) { x -= diff; ++c; }
+    while (x < m) { x += diff; ++c; }
+    if (count) *count = c;
     return x;
 }
+static double wrap_d(double x, double m, double M) { return wrap_d_count(x, m, M, 0); }
 
-int ref_acrobot_step_f64(double *state, int a, double *obs6, double *reward) {
+static int acrobot_step_f64_probe(double *state, int a, double *obs6, double *reward, int *wraps2, double *probe3) {
     const double dt = 0.2, mv1 = 4.0 * PI_D, mv2 = 9.0 * PI_D;
     double tau = (double)(a - 1);
-    double k1[4], k2[4], k3[4], k4[4], y[4];
+    double k1[4], k2[4], k3[4], k4[4], y[4], big = fmax(fabs(state[0]), fabs(state[1]));
+    int w[2];
     acrobot_dsdt_f64(state, tau, k1);
     for (int i = 0; i < 4; ++i) y[i] = state[i] + dt / 2.0 * k1[i];
+    big = fmax(big, fmax(fabs(y[0]), fabs(y[1])));
     acrobot_dsdt_f64(y, tau, k2);
     for (int i = 0; i < 4; ++i) y[i] = state[i] + dt / 2.0 * k2[i];
+    big = fmax(big, fmax(fabs(y[0]), fabs(y[1])));
     acrobot_dsdt_f64(y, tau, k3);
     for (int i = 0; i < 4; ++i) y[i] = state[i] + dt * k3[i];
+    big = fmax(big, fmax(fabs(y[0]), fabs(y[1])));
     acrobot_dsdt_f64(y, tau, k4);
     for (int i = 0; i < 4; ++i) y[i] = state[i] + dt / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
-    y[0] = wrap_d(y[0], -PI_D, PI_D);
-    y[1] = wrap_d(y[1], -PI_D, PI_D);
+    if (probe3) { probe3[0] = y[0]; probe3[1] = y[1]; probe3[2] = big; }
+    y[0] = wrap_d_count(y[0], -PI_D, PI_D, &w[0]);
+    y[1] = wrap_d_count(y[1], -PI_D, PI_D, &w[1]);
+    if (wraps2) { wraps2[0] = w[0]; wraps2[1] = w[1]; }
     y[2] = y[2] < -mv1 ? -mv1 : (y[2] > mv1 ? mv1 : y[2]);
     y[3] = y[3] < -mv2 ? -mv2 : (y[3] > mv2 ? mv2 : y[3]);
     for (int i = 0; i < 4; ++i) state[i] = y[i];
@@ -672,6 +685,10 @@ int ref_acrobot_step_f64(double *state, int a, double *obs6, double *reward) {
     obs6[0] = cos(y[0]); obs6[1] = sin(y[0]); obs6[2] = cos(y[1]); obs6[3] = sin(y[1]);
     obs6[4] = y[2]; obs6[5] = y[3];
     return done;
+}
+
+int ref_acrobot_step_f64(double *state, int a, double *obs6, double *reward) {
+    return acrobot_step_f64_probe(state, a, obs6, reward, 0, 0);
 }
 
 /* 1/P for P = d1 * det in [6.4, 11.6] (kernel semantics, gym.net_amd/csrc/envs.hpp Acrobot::recip_p): quadratic minimax
@@ -704,27 +721,50 @@ static void acrobot_dsdt_f32(const float s[4], float tau, float d[4]) {
     d[0] = A; d[1] = B; d[2] = ddth1; d[3] = ddth2;
 }
 
-static float wrap_f(float x, float m, float M) {
-    float diff = M - m;
-    while (x > M) x -= diff;
-    while (x < m) x += diff;
-    return x;
+/* kernel semantics (envs.hpp Acrobot::wrap): upstream's `while x > M: x -= diff` / `while x < m: x += diff` with m = -M, as a
+ * BOUNDED chain on the magnitude — at most k subtractions, then the sign bit of the input put back by xor.  Only one of the two
+ * upstream loops can ever run and x + diff == -(|x| - diff) bit for bit, so whenever k subtractions suffice (|x| <= (2k + 1) M)
+ * this is upstream's result; beyond that — and for +-inf / NaN, where upstream's loop never ends — the angle keeps what is left
+ * after k subtractions.  ACROBOT_WRAP_K is the kernel's k: the measured pre-wrap maximum over the closed state box, 29.73 rad,
+ * plus one full turn needs (2k + 1) pi >= 36.01, i.e. k = 6 (tests/test_env_edge_tables_host.py measures it again). */
+#define ACROBOT_WRAP_K 6
+static float wrap_f_k(float x, float M, int k, int *count) {
+    const float diff = M + M;
+    uint32_t bits, sign;
+    float ax = fabsf(x);
+    int c = 0;
+    memcpy(&bits, &x, 4);
+    sign = bits & 0x80000000u;
+    for (int i = 0; i < k && ax > M; ++i) { ax -= diff; ++c; }
+    if (count) *count = c;
+    memcpy(&bits, &ax, 4);
+    bits ^= sign;
+    memcpy(&ax, &bits, 4);
+    return ax;
 }
+static float wrap_f(float x, float m, float M) { (void)m; return wrap_f_k(x, M, ACROBOT_WRAP_K, 0); }
 
-int ref_acrobot_step_f32(float *state, int a, float *obs6, float *reward) {
+/* probe (optional, may be null): [0..1] the angles before the wrap, [2] the largest |angle| handed to sin / cos by the four stages */
+static int acrobot_step_f32_k(float *state, int a, float *obs6, float *reward, int k, int *wraps2, float *probe3) {
     const float dt = 0.2f, mv1 = 4.0f * PI_F, mv2 = 9.0f * PI_F;
     float tau = (float)(a - 1);
-    float k1[4], k2[4], k3[4], k4[4], y[4];
+    float k1[4], k2[4], k3[4], k4[4], y[4], big = fmaxf(fabsf(state[0]), fabsf(state[1]));
+    int w[2];
     acrobot_dsdt_f32(state, tau, k1);
     for (int i = 0; i < 4; ++i) y[i] = fmaf(dt / 2.0f, k1[i], state[i]);
+    big = fmaxf(big, fmaxf(fabsf(y[0]), fabsf(y[1])));
     acrobot_dsdt_f32(y, tau, k2);
     for (int i = 0; i < 4; ++i) y[i] = fmaf(dt / 2.0f, k2[i], state[i]);
+    big = fmaxf(big, fmaxf(fabsf(y[0]), fabsf(y[1])));
     acrobot_dsdt_f32(y, tau, k3);
     for (int i = 0; i < 4; ++i) y[i] = fmaf(dt, k3[i], state[i]);
+    big = fmaxf(big, fmaxf(fabsf(y[0]), fabsf(y[1])));
     acrobot_dsdt_f32(y, tau, k4);
     for (int i = 0; i < 4; ++i) y[i] = fmaf(dt / 6.0f, fmaf(2.0f, k3[i], fmaf(2.0f, k2[i], k1[i])) + k4[i], state[i]);
-    y[0] = wrap_f(y[0], -PI_F, PI_F);
-    y[1] = wrap_f(y[1], -PI_F, PI_F);
+    if (probe3) { probe3[0] = y[0]; probe3[1] = y[1]; probe3[2] = big; }
+    y[0] = wrap_f_k(y[0], PI_F, k, &w[0]);
+    y[1] = wrap_f_k(y[1], PI_F, k, &w[1]);
+    if (wraps2) { wraps2[0] = w[0]; wraps2[1] = w[1]; }
     y[2] = y[2] < -mv1 ? -mv1 : (y[2] > mv1 ? mv1 : y[2]);
     y[3] = y[3] < -mv2 ? -mv2 : (y[3] > mv2 ? mv2 : y[3]);
     for (int i = 0; i < 4; ++i) state[i] = y[i];
@@ -734,6 +774,12 @@ int ref_acrobot_step_f32(float *state, int a, float *obs6, float *reward) {
     obs6[4] = y[2]; obs6[5] = y[3];
     return done;
 }
+
+int ref_acrobot_step_f32(float *state, int a, float *obs6, float *reward) {
+    return acrobot_step_f32_k(state, a, obs6, reward, ACROBOT_WRAP_K, 0, 0);
+}
+
+int ref_acrobot_wrap_k(void) { return ACROBOT_WRAP_K; }
 
 /* A LITERAL binary32 transcription of upstream's dsdt / rk4 (the float64 code above with every double replaced by float, libm
  * sinf / cosf, IEEE division, upstream's association order) — NOT what the kernel runs.  It exists for one purpose: the accuracy
@@ -794,6 +840,28 @@ void ref_acrobot_reset_f32(uint64_t seed, uint64_t lane, uint64_t tick, float st
     uint32_t w[4];
     ref_reset_words(seed, lane, tick, w);
     for (int k = 0; k < 4; ++k) state[k] = -0.1f + 0.2f * u01_24(w[k]);
+}
+
+/* The Acrobot domain probe of tests/test_env_edge_tables_host.py: every float32 state is stepped three times — upstream semantics in
+ * binary64 (unbounded wrap loop), kernel semantics with at most k subtractions in the wrap, and the literal binary32 transcription
+ * (the yardstick) — and the facts the domain proof needs come back per lane.  All arrays are structure-of-arrays over n lanes:
+ * next64 [4], nextk [4], nextlit [4]; pre64 [3] = the two angles before the wrap and the largest |angle| handed to sin / cos by a stage,
+ * prek [3] the same of the twin; wraps64 [2], wrapsk [2] = how often each wrap subtracted; done64 / donek the termination flags. */
+void ref_acrobot_domain_probe(const float *state_soa, const int32_t *action, int32_t k, int64_t n,
+                              double *next64, float *nextk, float *nextlit, double *pre64, float *prek,
+                              int32_t *wraps64, int32_t *wrapsk, uint8_t *done64, uint8_t *donek) {
+    for (int64_t i = 0; i < n; ++i) {
+        double s64[4], o64[6], r64, p64[3];
+        float sk[4], sl[4], ok[6], ol[6], rk, rl, pk[3];
+        int w64[2], wk[2];
+        for (int c = 0; c < 4; ++c) { sk[c] = sl[c] = state_soa[(int64_t)c * n + i]; s64[c] = (double)sk[c]; }
+        done64[i] = (uint8_t)acrobot_step_f64_probe(s64, action[i], o64, &r64, w64, p64);
+        donek[i] = (uint8_t)acrobot_step_f32_k(sk, action[i], ok, &rk, k, wk, pk);
+        ref_acrobot_step_f32_literal(sl, action[i], ol, &rl);
+        for (int c = 0; c < 4; ++c) { next64[(int64_t)c * n + i] = s64[c]; nextk[(int64_t)c * n + i] = sk[c]; nextlit[(int64_t)c * n + i] = sl[c]; }
+        for (int c = 0; c < 3; ++c) { pre64[(int64_t)c * n + i] = p64[c]; prek[(int64_t)c * n + i] = pk[c]; }
+        for (int c = 0; c < 2; ++c) { wraps64[(int64_t)c * n + i] = w64[c]; wrapsk[(int64_t)c * n + i] = wk[c]; }
+    }
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -305,11 +305,19 @@ def test_kernel_sincos_accuracy(oracle):
 
 
 def test_small_argument_sincos_of_the_acrobot_kernel(oracle):
-    """envs.hpp sincos_small (two-constant Cody-Waite, Horner cosine; Acrobot's RK4 stage angles, |x| < 12): accuracy against
-    float64 over its whole intended range and beyond, exact odd / even symmetry, and the reduction's premise — n * C1 is
-    exact for every |n| <= 15."""
+    """envs.hpp sincos_small (two-constant Cody-Waite, Horner cosine; Acrobot's wrapped angles and RK4 stage angles): accuracy against
+    float64 over its whole range of use and beyond, exact odd / even symmetry, and the reduction's premise — n * C1 is exact for
+    every |n| <= 15.  The range of use is MEASURED (tests/test_env_edge_tables_host.py: stage angles reach 33.32 rad on the env's
+    state bounds, not the 12 once claimed), and the sweep goes pi beyond it: 36.5 rad, |n| <= 23.  The bar did not have to move:
+    beyond |n| = 15 the product n * C1 no longer fits 24 bits, but it is formed inside an fma, which rounds x - n * C1 once."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from _env_edge_tables import SINCOS_SMALL_SWEEP as sweep                    # 36.5; the domain test holds it to the measured maximum
     rng = np.random.default_rng(44)
-    x = np.concatenate([rng.uniform(-16, 16, 60_000), rng.uniform(-3.2, 3.2, 60_000), np.linspace(-24, 24, 4001)]).astype(f32)
+    x = np.concatenate([rng.uniform(-16, 16, 60_000), rng.uniform(-3.2, 3.2, 60_000), np.linspace(-24, 24, 4001),
+                        rng.uniform(-sweep, sweep, 60_000), rng.uniform(24, sweep, 30_000), -rng.uniform(24, sweep, 30_000),
+                        np.linspace(-sweep, sweep, 8001)]).astype(f32)
     s, c = oracle.sincos_kernel(x, small=True)
     xs = x.astype(np.float64)
     assert np.abs(s - np.sin(xs)).max() <= 1.2e-7 and np.abs(c - np.cos(xs)).max() <= 1.2e-7
