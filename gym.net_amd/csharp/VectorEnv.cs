@@ -374,6 +374,18 @@ namespace Gym.Envs.Amd {
             Native.Check(Native.gymnet_vecenv_actor_box_get_policy(_h, &hd, &ex, &sg));
             head = (GymnetBoxHead) hd; explore = (GymnetBoxExplore) ex; sigma = sg;
         }
+        /// BoxActorAct that also writes the log-density of every lane's action under the handle's policy, sigma > 0, into dLogd (float [N];
+        /// gymnet_vecenv_actor_box_act_logd_device): log N(action; greedy, sigma^2); actions and raw outputs are BoxActorAct's, bit for bit.
+        /// IntPtr.Zero: BoxActorAct itself.
+        public void BoxActorActLogd(IntPtr dActions, IntPtr dLogd, float epsilon = 0f, ulong seed = 0, ulong tick = 0, IntPtr dRaw = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_box_act_logd_device(_h, dActions, dRaw, dLogd, epsilon, seed, tick));
+        /// RolloutFused with the actor source on a Box actor, also recording every step's log-density into dRecLogd and, with a critic, the
+        /// value before every step into dRecValue (float [T][N] each; gymnet_vecenv_rollout_fused_box_logd_device); either may be
+        /// IntPtr.Zero.  Both IntPtr.Zero: RolloutFused itself.
+        public void RolloutFusedBoxLogd(GymnetRolloutSpec spec, IntPtr dRecLogd, IntPtr dRecValue) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_fused_box_logd_device(_h, ref spec, dRecLogd, dRecValue));
+        }
 
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));

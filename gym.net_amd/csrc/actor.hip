@@ -27,7 +27,7 @@
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, the prologue of every act entry point
 // (actor_act_enter), and the calls the fused rollout (rollout_fused.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
-// is the router: it alone says which of the six units runs a handle's rollout (actor_act_launch: the same for act).
+// is the router: it alone says which of the seven units runs a handle's rollout (actor_act_launch: the same for act).
 #include "actor_net.hpp"
 
 namespace gymnet {
@@ -245,7 +245,7 @@ int actor_refill(gymnet_vecenv *h, const uint8_t *d_mask) {
 // what the fused rollout's plan (rollout_plan.hpp) reads of the handle's actor: its refusals are worded there
 ActorFacts actor_facts(const gymnet_vecenv *h) {
     if (!h->actor) return {};
-    return {h->actor->box ? ActorKind::Box : ActorKind::Discrete, h->actor->has_critic(), actor_current(h)};
+    return {h->actor->box ? ActorKind::Box : ActorKind::Discrete, h->actor->has_critic(), actor_current(h), h->actor->sigma};
 }
 
 // this unit's fused rollout: a Discrete actor under the default exploration setting
@@ -258,13 +258,15 @@ static hipError_t actor_discrete_rollout_launch(gymnet_vecenv *h, bool records, 
     }
 }
 
-// The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: its policy decides.  Discrete: a value
+// The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: a log-density or value pointer
+// (gymnet_vecenv_rollout_fused_box_logd_device) goes to actor_box_logd.hip under any policy, else its policy decides.  Discrete: a value
 // pointer (gymnet_vecenv_rollout_fused_value_device) goes to actor_value.hip, with or without a logp pointer; a logp pointer alone
 // (gymnet_vecenv_rollout_fused_logp_device) to actor_logp.hip under either setting; else the setting decides
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, const FusedRequest &rq) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
     if (ac.box) {
+        if (rq.rec_logd || rq.box_value) return actor_box_logd_rollout_launch(h, records, a, r, rq.rec_logd, rq.box_value ? rq.rec_value : nullptr);
         if (rq.rec_logp || rq.rec_value) return hipErrorInvalidValue;        // (the plan has refused it: rollout_plan.hpp record_pointers)
         return ac.default_policy() ? actor_box_rollout_launch(h, records, a, r) : actor_box_policy_rollout_launch(h, records, a, r);
     }

@@ -14,69 +14,19 @@
 //
 // Fused rollout (actor_box_policy_rollout_kernel): actor_box_rollout_kernel with the policy as a fifth argument — rollout_body, one lane
 // per thread, behind a hook whose choose() is the act kernel's body and whose after() is the shared push.  Both kernels call policy_choose,
-// so the fused rollout is bit-identical to steps x (box_act, step, push) whichever tanh / log / cos the functions below use.
-#include "actor_net.hpp"
+// (actor_box_compose.hpp, which actor_box_logd.hip runs too), so the fused rollout is bit-identical to steps x (box_act, step, push)
+// whichever tanh / log / cos that function uses.
+#include "actor_box_compose.hpp"
 
 namespace gymnet {
-
-namespace {
-
-// the envs' own clamp (Pendulum::step): a NaN fails both compares and passes
-__device__ __forceinline__ float clamp_action(float raw, float low, float high) { return raw < low ? low : (raw > high ? high : raw); }
-
-__device__ __forceinline__ float policy_greedy(float raw, float low, float high, int32_t head) {
-    if (head == GYMNET_BOX_HEAD_TANH) {                                      // wave-uniform
-        const float mid = 0.5f * (low + high), half = 0.5f * (high - low);
-        const float scaled = half * tanhf(raw);
-        return mid + scaled;
-    }
-    return clamp_action(raw, low, high);
-}
-
-// compose_box_one (actor_box.hip) under a policy: words A and N are drawn only when some lane of the wave explores
-__device__ __forceinline__ float policy_compose_one(float greedy, float low, float high, const BoxPolicy &pol, uint32_t explore_at_or_below, uint64_t seed,
-                                                    uint64_t gl, uint64_t tick) {
-    const bool explore = aux_word<true>(seed, gl, tick) <= explore_at_or_below;
-    float act = greedy;
-    if (__ballot(explore)) {
-        const uint32_t wa = action_word<true>(seed, gl, tick);
-        float drawn;
-        if (pol.explore == GYMNET_BOX_EXPLORE_GAUSSIAN) {                    // wave-uniform
-            const float u1 = (float)((wa >> 8) + 1u) * (1.0f / 16777216.0f);   // (0, 1]
-            const float u2 = u01_24(noise_word<true>(seed, gl, tick));
-            float sn, cs;
-            sincos_f32<true>(6.283185307179586f * u2, sn, cs);
-            const float z = sqrtf(-2.0f * logf(u1)) * cs;
-            const float noise = pol.sigma * z;
-            drawn = clamp_action(greedy + noise, low, high);
-        } else {
-            drawn = low + (high - low) * u01_24(wa);
-        }
-        act = explore ? drawn : greedy;
-    }
-    return act;
-}
-
-// history -> forward -> raw -> head -> compose, for lane i; raw receives the network's output unchanged
-template <int O>
-__device__ __forceinline__ float policy_choose(const ActorNet &net, const ActorHist &hs, int32_t newest, int64_t i, float low, float high,
-                                               const BoxPolicy &pol, uint32_t explore_at_or_below, uint64_t seed, uint64_t gl, uint64_t tick, float &raw) {
-    float x[kW];
-    load_input<O>(hs, newest, i, x);
-    actor_forward(net, x);
-    raw = x[0];
-    return policy_compose_one(policy_greedy(raw, low, high, pol.head), low, high, pol, explore_at_or_below, seed, gl, tick);
-}
-
-}  // namespace
 
 template <int O>
 __global__ __launch_bounds__(256) void actor_box_policy_act_kernel(const ActorNet net, const ActorHist hs, float *__restrict__ actions,
                                                                    float *__restrict__ raw, float low, float high, const ActorAct aa, const BoxPolicy pol) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= hs.n) return;
-    float r;
-    actions[i] = policy_choose<O>(net, hs, hs.slot, i, low, high, pol, coin_threshold(aa.epsilon), aa.seed, aa.lane_offset + (uint64_t)i, aa.tick, r);
+    float r, g;
+    actions[i] = policy_choose<O>(net, hs, hs.slot, i, low, high, pol, coin_threshold(aa.epsilon), aa.seed, aa.lane_offset + (uint64_t)i, aa.tick, r, g);
     if (raw) raw[i] = r;
 }
 
@@ -96,9 +46,9 @@ struct ActorBoxPolicyHook {
 
     // gymnet_vecenv_actor_box_act_device(epsilon, action_seed, action_tick0 + t) under the handle's policy
     __device__ __forceinline__ void choose(int64_t t, int64_t i, float (&act)[1]) const {
-        float raw;
+        float raw, g;
         act[0] = policy_choose<O>(net, hs, newest, i, Env::ACTION_LOW, Env::ACTION_HIGH, pol, explore_at_or_below, ro.action_seed, lane_offset + (uint64_t)i,
-                                  ro.action_tick0 + (uint64_t)t, raw);
+                                  ro.action_tick0 + (uint64_t)t, raw, g);
     }
 
     // gymnet_vecenv_actor_push_device (actor_net.hpp)

@@ -1,9 +1,10 @@
-// actor_net.hpp — what the six actor units share: the network and the per-lane observation history as the kernels see them, the forward
+// actor_net.hpp — what the seven actor units share: the network and the per-lane observation history as the kernels see them, the forward
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), the host helpers every unit launches
 // with (lane_grid, pick_rollout_form), and the handle's Actor attachment with each unit's launch calls.  actor.hip serves the Discrete
 // envs (argmax head) and owns the attachment, the act prologue (actor_act_enter) and the router: actor_rollout_launch there is the one
 // place that says which unit runs a handle's fused rollout, and no unit calls another on its own.  actor_box.hip serves the Box envs
-// (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_softmax.hip the Discrete envs under an
+// (clamp head), actor_box_policy.hip their other policies (tanh head, Gaussian noise), actor_box_logd.hip the Box envs when the caller also
+// asks for the log-density of the action taken or, inside the rollout, the critic's value, actor_softmax.hip the Discrete envs under an
 // exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when the caller
 // also asks for the log-probability of the action taken, actor_value.hip the critic: a second network over the same input whose one
 // output is the lane's value estimate.  Internal to the library.
@@ -227,7 +228,7 @@ int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, con
                     uint64_t tick, ActorAct &aa);
 // Each unit's fused rollout of a handle it serves, a.n > 0 (records: the rollout keeps compact episode records), and the calls one unit
 // makes into another: actor.hip's router (actor_rollout_launch, handle.hpp) reads (box, default_policy(), default_exploration(), a record
-// pointer) and calls exactly one of these five or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
+// pointer) and calls exactly one of these six or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
 // push reach a sibling's kernels through the rest.
 // actor_box.hip: the default policy's rollout, and the push / fill of a three-row observation (Pendulum)
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
@@ -236,6 +237,9 @@ hipError_t launch_actor_box_push3(const ActorHist &hs, const float *obs, int64_t
 hipError_t actor_box_policy_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 hipError_t actor_box_policy_act_launch(const ActorNet &net, const ActorHist &hs, float *actions, float *raw, float low, float high, const ActorAct &aa,
                                        const BoxPolicy &pol, hipStream_t st);
+// actor_box_logd.hip: a Box handle, any policy with sigma > 0, that records the log-density of every action taken (rec_logd [steps][n]) and
+// / or, with a critic, the value of every step's input (rec_value [steps][n]); either may be null
+hipError_t actor_box_logd_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logd, float *rec_value);
 // actor_softmax.hip: a Discrete handle whose exploration setting is not the default
 hipError_t actor_softmax_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
 hipError_t actor_softmax_act_launch(const ActorNet &net, const ActorHist &hs, int32_t *actions, float *logits, const ActorAct &aa, const ActorExplore &ex,

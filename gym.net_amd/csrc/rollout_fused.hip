@@ -1,4 +1,4 @@
-// rollout_fused.hip — the fused rollout's host side: gymnet_vecenv_rollout_fused_device and its _ex / _logp / _value siblings, and the
+// rollout_fused.hip — the fused rollout's host side: gymnet_vecenv_rollout_fused_device and its _ex / _logp / _value / _box_logd siblings, and the
 // handle's episode-segment block (h->ep).  Host code only; this unit holds no kernel.  What a call will do — every refusal, the lane width,
 // the segment block, the ticks — is decided by rollout_plan.hpp's pure function; here the facts are gathered, the plan is carried out.
 #include <hip/hip_runtime.h>
@@ -145,6 +145,18 @@ int gymnet_vecenv_rollout_fused_value_device(gymnet_vecenv *h, const gymnet_roll
     return guarded([&]() -> int {
     ENTER(h);
     return rollout_fused_entered(h, FusedRequest{spec, 0, false, d_rec_logp, d_rec_value});
+    });
+}
+
+// the Box actor's pair (actor_box_logd.hip): either pointer or both; neither: the plain call.  Their checks are the plan's too
+// (box_record_pointers)
+int gymnet_vecenv_rollout_fused_box_logd_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logd, float *d_rec_value) {
+    if (!d_rec_logd && !d_rec_value) return gymnet_vecenv_rollout_fused_ex_device(h, spec);
+    return guarded([&]() -> int {
+    ENTER(h);
+    FusedRequest rq{spec};
+    rq.rec_value = d_rec_value; rq.rec_logd = d_rec_logd; rq.box_value = d_rec_value != nullptr;
+    return rollout_fused_entered(h, rq);
     });
 }
 

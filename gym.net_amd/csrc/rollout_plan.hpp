@@ -5,6 +5,7 @@
 // for kShards / kCountStride.  Pointers are read for being null and for their alignment only; nothing here follows one (but the spec's).
 #pragma once
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -43,6 +44,7 @@ struct ActorFacts {
     ActorKind kind = ActorKind::None;
     bool critic = false;           // a critic is configured (actor_value.hip)
     bool current = false;          // the history is current: no vector step since the last actor config, reset, push or actor rollout
+    float box_sigma = 0;           // a Box actor's policy's sigma (gymnet_vecenv_actor_box_set_policy)
 };
 struct FusedFacts {
     int64_t n = 0, sstride = 0;
@@ -60,12 +62,16 @@ struct FusedFacts {
 // record pointers).  spec: gymnet_vecenv_rollout_fused_ex_device's, as given (null and a wrong struct_size are the plan's to refuse).
 // held: frame skip — spec.steps decisions of held + 1 sub-steps each (action_repeat.hip); 0: the fused rollout.  validated: the caller has
 // run VALIDATE_ACTIONS over the one slice read (gymnet_vecenv_step_repeat_device).  rec_logp / rec_value: where an actor rollout records
-// every step's log-probability / critic value (gymnet_vecenv_rollout_fused_logp_device, _value_device; null: nowhere)
+// every step's log-probability / critic value (gymnet_vecenv_rollout_fused_logp_device, _value_device; null: nowhere).  rec_logd: where a
+// Box actor's rollout records every step's log-density, and box_value: rec_value is that call's (gymnet_vecenv_rollout_fused_box_logd_device
+// alone sets it, so that rec_value without rec_logd reaches a Box actor there and nowhere else)
 struct FusedRequest {
     const gymnet_rollout_spec *spec = nullptr;
     int32_t held = 0;
     bool validated = false;
     float *rec_logp = nullptr, *rec_value = nullptr;
+    float *rec_logd = nullptr;
+    bool box_value = false;
 };
 
 struct FusedPlan {
@@ -87,6 +93,15 @@ struct FusedOutcome { int status = GYMNET_OK; FusedPlan plan; char text[512]; };
 constexpr char kNoActorFormat[] = "no actor configured (%s)";
 inline const char *actor_config_call(bool box_action) { return box_action ? "gymnet_vecenv_actor_box_config" : "gymnet_vecenv_actor_config"; }
 constexpr char kStaleForRollout[] = "the actor's history is stale: reset the actor (or push) before an actor rollout";
+
+// The Box actor's log-density (actor_box_logd.hip): what the kernels take of sigma, computed in float64 and rounded once, and the sigmas
+// it is defined for: > 0 with a finite float32 reciprocal
+struct BoxLogd { float inv_sigma, c; };
+inline bool box_sigma_ok(float sigma) { return sigma > 0.0f && std::isfinite(1.0f / sigma); }
+inline BoxLogd box_logd_args(float sigma) {
+    return {(float)(1.0 / (double)sigma), (float)(-std::log((double)sigma) - 0.91893853320467274178)};     // -ln sigma - ln(2 pi) / 2
+}
+constexpr char kBadSigmaFormat[] = "%s: the log-density needs a policy with sigma > 0 and a finite 1 / sigma (gymnet_vecenv_actor_box_set_policy), not %g";
 
 namespace plan_detail {
 
@@ -117,13 +132,34 @@ inline int record_pointers(const FusedFacts &f, const FusedRequest &rq, int32_t 
     return GYMNET_OK;
 }
 
+// gymnet_vecenv_rollout_fused_box_logd_device's checks of its two record pointers, which run before the rollout's own: the source, an
+// actor, its kind, its sigma, a critic where values are asked for, the alignments
+inline int box_record_pointers(const FusedFacts &f, const FusedRequest &rq, int32_t action_source, char (&text)[512]) {
+    const char *what = rq.rec_logd ? "d_rec_logd" : "d_rec_value";
+    const bool value = rq.box_value && rq.rec_value != nullptr;
+    if (action_source != GYMNET_ACTIONS_ACTOR)
+        return refuse(text, GYMNET_ERR_INVALID_ARG, "%s: log-densities and values are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", what, action_source);
+    if (f.actor.kind == ActorKind::None) return refuse(text, GYMNET_ERR_INVALID_ARG, kNoActorFormat, actor_config_call(f.box_action));
+    if (f.actor.kind == ActorKind::Discrete)
+        return refuse(text, GYMNET_ERR_INVALID_ARG, "%s: this handle's actor chooses Discrete actions; a log-density belongs to a Box actor "
+                      "(gymnet_vecenv_rollout_fused_value_device records a Discrete actor's log-probability and value)", what);
+    if (!box_sigma_ok(f.actor.box_sigma)) return refuse(text, GYMNET_ERR_INVALID_ARG, kBadSigmaFormat, what, (double)f.actor.box_sigma);
+    if (value && !f.actor.critic) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value: no critic configured (gymnet_vecenv_actor_critic_config)");
+    if (!aligned_to(rq.rec_logd, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_logd must be 4-byte aligned");
+    if (value && !aligned_to(rq.rec_value, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value must be 4-byte aligned");
+    return GYMNET_OK;
+}
+
 inline int plan(const FusedFacts &f, const FusedRequest &rq, FusedPlan &p, char (&text)[512]) {
     const int32_t held = rq.held;
     if (!rq.spec) return refuse(text, GYMNET_ERR_INVALID_ARG, "spec is null");
     if (rq.spec->struct_size != sizeof(gymnet_rollout_spec))
         return refuse(text, GYMNET_ERR_INVALID_ARG, "spec.struct_size %u != %zu (ABI mismatch)", rq.spec->struct_size, sizeof(gymnet_rollout_spec));
     const gymnet_rollout_spec &sp = *rq.spec;
-    if (rq.rec_logp || rq.rec_value) {
+    if (rq.rec_logd || rq.box_value) {
+        const int s = box_record_pointers(f, rq, sp.action_source, text);
+        if (s != GYMNET_OK) return s;
+    } else if (rq.rec_logp || rq.rec_value) {
         const int s = record_pointers(f, rq, sp.action_source, text);
         if (s != GYMNET_OK) return s;
     }

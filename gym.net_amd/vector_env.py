@@ -341,7 +341,7 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_rollout_device(self._h, _ptr(d_actions), int(steps), int(action_stride), int(ring)))
 
     def RolloutFusedDevice(self, d_actions, steps, action_stride=0, ring=1, rec_obs=None, rec_reward=None, rec_done=None, actions="ring",
-                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None, rec_value=None):
+                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None, rec_value=None, rec_logd=None):
         """`steps` vector steps in ONE kernel launch (state stays in registers); optional device-side rollout
         buffers rec_obs [T][D][N] (of the handle's dtype: float64 for a float64 handle), rec_reward [T][N], rec_done [T][N]
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
@@ -363,17 +363,42 @@ class VectorEnv:
           rec_value device float32 [T, N] or [T + 1, N] for the critic's value of the input every action was chosen from, as
                     Actor.Value() would write it before that step (gymnet_vecenv_rollout_fused_value_device): needs actions="actor" on a
                     Discrete actor with a critic (Actor.SetCritic).  With T + 1 rows, row T takes Actor.Value() after the rollout — the
-                    last value — and AdvantagesDevice(rec_reward, rec_done, rec_value, ...) takes the tensor as it stands."""
+                    last value — and AdvantagesDevice(rec_reward, rec_done, rec_value, ...) takes the tensor as it stands.  On a Box actor
+                    rec_value is accepted together with rec_logd, in either shape.
+          rec_logd  device float32 [T, N] for the log-density of every action taken, as Actor.Act(logd=) writes it at that step
+                    (gymnet_vecenv_rollout_fused_box_logd_device): needs actions="actor" on a Box actor whose policy has sigma > 0, and
+                    repeat = 0."""
         repeat = _repeat(repeat)
         value_rows = None
-        if rec_value is not None:
+        box_logd = rec_logd is not None
+        if box_logd:
+            actor = getattr(self, "_actor", None)
+            if actions != "actor":
+                raise ValueError(f"rec_logd records the actor's log-densities: it needs actions=\"actor\", got {actions!r}")
+            if actor is None:
+                raise ValueError("rec_logd needs an actor (VectorEnv.Actor)")
+            if not actor.IsBox:
+                raise ValueError("rec_logd belongs to a Box actor; this handle's actor chooses Discrete actions (rec_logp)")
+            if rec_logp is not None:
+                raise ValueError("rec_logp belongs to a Discrete actor; this handle's actor chooses Box actions (rec_logd)")
+            if repeat:
+                raise ValueError("rec_logd: the fused actor rollout has no frame skip (repeat must be 0)")
+            T = _count(steps, "steps", 0)
+            _logp_buffer(rec_logd, (T, self.NumberOfEnvironments), "rec_logd", self.Device)
+            if rec_value is not None:
+                if getattr(actor, "CriticWidths", None) is None:
+                    raise ValueError("rec_value needs a critic (Actor.SetCritic)")
+                value_rows = T + 1 if tuple(getattr(rec_value, "shape", ()))[:1] == (T + 1,) else T
+                _logp_buffer(rec_value, (value_rows, self.NumberOfEnvironments), "rec_value", self.Device)
+        if rec_value is not None and not box_logd:
             actor = getattr(self, "_actor", None)
             if actions != "actor":
                 raise ValueError(f"rec_value records the critic's values where the actor chooses: it needs actions=\"actor\", got {actions!r}")
             if actor is None:
                 raise ValueError("rec_value needs an actor (VectorEnv.Actor)")
             if actor.IsBox:
-                raise ValueError("rec_value belongs to a Discrete actor's fused rollout; this handle's actor chooses Box actions (Actor.Value serves it)")
+                raise ValueError("rec_value alone belongs to a Discrete actor's fused rollout; this handle's actor chooses Box actions: pass "
+                                 "rec_logd with it (Actor.Value serves a single step)")
             if getattr(actor, "CriticWidths", None) is None:
                 raise ValueError("rec_value needs a critic (Actor.SetCritic)")
             if repeat:
@@ -381,7 +406,7 @@ class VectorEnv:
             T = _count(steps, "steps", 0)
             value_rows = T + 1 if tuple(getattr(rec_value, "shape", ()))[:1] == (T + 1,) else T
             _logp_buffer(rec_value, (value_rows, self.NumberOfEnvironments), "rec_value", self.Device)
-        if rec_logp is not None:
+        if rec_logp is not None and not box_logd:
             actor = getattr(self, "_actor", None)
             if actions != "actor":
                 raise ValueError(f"rec_logp records the actor's log-probabilities: it needs actions=\"actor\", got {actions!r}")
@@ -406,6 +431,11 @@ class VectorEnv:
                                 d_ep_length=_ptr(ep.get("length")), ep_capacity=int(ep.get("capacity", 0)), d_ep_count=_ptr(ep.get("count")))
         if repeat:
             capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
+        elif box_logd:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_box_logd_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value)))
+            if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
+                last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
+                capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
         elif rec_value is not None:
             capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
             if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
@@ -1133,7 +1163,7 @@ class Actor:
         capi.check(self._lib.gymnet_vecenv_actor_value_device(self._handle(), _ptr(out)))
         return out
 
-    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None, value=None):
+    def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None, value=None, logd=None):
         """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
         compose it.  logits: an optional device float32 [N, action_n].  A Box actor (gymnet_vecenv_actor_box_act_device): `out` is
@@ -1144,7 +1174,13 @@ class Actor:
         log-probability of the action each lane takes under softmax(logits / temperature), the stored temperature whatever the exploration
         setting (gymnet_vecenv_actor_act_logp_device); actions and logits are the same bits with and without it.  value (a Discrete actor
         with a critic): an optional device float32 [N] for what Value() writes, from the same call
-        (gymnet_vecenv_actor_act_value_device); actions, logits and logp are the same bits with and without it."""
+        (gymnet_vecenv_actor_act_value_device); actions, logits and logp are the same bits with and without it.  logd (a Box actor whose
+        policy has sigma > 0): an optional device float32 [N] for the log-density log N(action; greedy action, sigma^2) of the action each
+        lane takes (gymnet_vecenv_actor_box_act_logd_device); actions and the unclamped outputs are the same bits with and without it."""
+        if logd is not None:
+            if not self.IsBox:
+                raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
+            _logp_buffer(logd, (self._env.NumberOfEnvironments,), "logd", self._env.Device)
         if logp is not None:
             if self.IsBox:
                 raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
@@ -1155,6 +1191,10 @@ class Actor:
             self._value_buffer(value)
         if out is None:
             out = self._actions()
+        if logd is not None:
+            capi.check(self._lib.gymnet_vecenv_actor_box_act_logd_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logd), float(epsilon),
+                                                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+            return out
         if value is not None:
             capi.check(self._lib.gymnet_vecenv_actor_act_value_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), _ptr(value), float(epsilon),
                                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
@@ -1270,17 +1310,19 @@ class Actor:
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
 
-    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None):
-        """Act(epsilon, seed, tick, logp=logp, value=value), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
+    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None, logd=None):
+        """Act(epsilon, seed, tick, logp=logp, value=value, logd=logd), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
         Push(): one closed-loop decision; returns the device actions taken."""
         repeat = _repeat(repeat)
         if logp is not None and self.IsBox:
             raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
         if value is not None and self.IsBox:
             raise ValueError("Step(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
+        if logd is not None and not self.IsBox:
+            raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
         if self._out is None:
             self._out = self._actions()
-        self.Act(epsilon, seed, tick, out=self._out, logp=logp, value=value)
+        self.Act(epsilon, seed, tick, out=self._out, logp=logp, value=value, logd=logd)
         if repeat:
             self._env.StepRepeatDevice(self._out, repeat)
         else:

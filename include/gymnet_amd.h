@@ -721,7 +721,8 @@ int gymnet_vecenv_actor_get_exploration(gymnet_vecenv *h, int32_t *explore, floa
  *   d_rec_logp[t * num_envs + lane] is what act_logp_device(epsilon, action_seed, action_tick0 + t) writes at step t: the call is
  *   bit-identical to steps x (act_logp_device, step_device, actor_push_device).  d_rec_logp needs 4-byte alignment only; steps == 0
  *   writes nothing.
- * Out of scope: the Box actor's log-density, recording logits or an entropy, carrying logp through the episode memory. */
+ * Out of scope: recording logits or an entropy, carrying logp through the episode memory.  (The Box actor's log-density has calls of its
+ *   own: gymnet_vecenv_actor_box_act_logd_device, below.) */
 int gymnet_vecenv_actor_act_logp_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float *d_logp, float epsilon, uint64_t seed,
                                         uint64_t tick);
 int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp);
@@ -756,9 +757,9 @@ int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollo
  *   for bit — d_rec_logp included, which may be NULL —, and in addition d_rec_value[t * num_envs + lane] is what actor_value_device would
  *   write before step t: the call is bit-identical to steps x (act_value_device, step_device, actor_push_device).  Both record pointers
  *   need 4-byte alignment only; steps == 0 writes nothing.  One kernel per form serves both exploration settings, with and without
- *   d_rec_logp (csrc/actor_value.hip).
- * Out of scope: a value for Box actors inside the fused rollout (it waits for their log-density; actor_value_device serves them
- *   stand-alone); V(terminal observation) for gymnet_gae_device's d_boot on time-limit rows (without it a time limit counts as a
+ *   d_rec_logp (csrc/actor_value.hip).  A Box actor's values inside the fused rollout come from
+ *   gymnet_vecenv_rollout_fused_box_logd_device (below).
+ * Out of scope: V(terminal observation) for gymnet_gae_device's d_boot on time-limit rows (without it a time limit counts as a
  *   termination, as documented there); a trunk shared between actor and critic; values carried through the episode memory; any gradient. */
 int gymnet_vecenv_actor_critic_config(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
 int gymnet_vecenv_actor_critic_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count);
@@ -813,6 +814,47 @@ typedef enum gymnet_box_head    { GYMNET_BOX_HEAD_CLAMP = 0,     GYMNET_BOX_HEAD
 typedef enum gymnet_box_explore { GYMNET_BOX_EXPLORE_SAMPLE = 0, GYMNET_BOX_EXPLORE_GAUSSIAN = 1 } gymnet_box_explore;
 int gymnet_vecenv_actor_box_set_policy(gymnet_vecenv *h, int32_t head, int32_t explore, float sigma);
 int gymnet_vecenv_actor_box_get_policy(gymnet_vecenv *h, int32_t *head, int32_t *explore, float *sigma);
+/* A Box actor's log-density of the action taken, and the critic's value inside its fused rollout (additive in ABI 6).  A Box action has
+ * a density, not a probability: the calls and arguments are named logd.  Under any policy (head, explore, sigma) with sigma > 0, with g
+ * the greedy action after the head and a the float32 action the lane takes — what d_actions / d_rec_actions receive, after the clamp:
+ *     inv_sigma = (float)(1.0 / (double)sigma)                              on the host, once per launch
+ *     c         = (float)(-log((double)sigma) - 0.91893853320467274178)     on the host, once per launch: -ln sigma - ln(2 pi) / 2
+ *     d    = (a - g) * inv_sigma        float32, each operation rounding on its own
+ *     h    = -0.5f * d
+ *     logd = fmaf(h, d, c)
+ *   This is log N(a; g, sigma^2), the density of the unclamped Gaussian at the action taken; a caller reproduces it as
+ *   Normal(g_new, sigma).log_prob(rec_actions).  tests/_actor_box_logd_twin.py restates the lines and reproduces the bits; against the
+ *   float64 closed form of the same float32 inputs the error is within 2^-21 * max(1, d^2, |c|) (tests/test_actor_box_logd_host.py).
+ *   - The noise is added after the head, so a TANH head needs no Jacobian term.
+ *   - It is recorded for every lane at the stored sigma, whatever explore is and whatever the coin says, as the Discrete logp reports
+ *     the policy's probability under (UNIFORM, temperature) too.  A lane that does not explore has a == g and gets exactly c.  Under
+ *     SAMPLE it is the Gaussian policy's density at the uniformly drawn action.  It is exactly the behaviour policy's density only at
+ *     epsilon = 1 under GAUSSIAN, away from the bounds.
+ *   - Where the clamp bit, it is the density at the bound; the point mass there is ignored (the usual PPO treatment).
+ *   - A NaN g gives a NaN; a d^2 that overflows gives -inf.
+ *   - sigma == 0 (the fresh default) or a sigma so small that 1.0f / sigma is not finite: GYMNET_ERR_INVALID_ARG from the two calls
+ *     below, nothing written.  set_policy still stores such a sigma: the check is made where logd is asked for.
+ *   Actions and raw outputs are the same bits with and without the request (one function composes them for both,
+ *   csrc/actor_box_compose.hpp).
+ * actor_box_act_logd_device: with d_logd == NULL it IS gymnet_vecenv_actor_box_act_device (the call forwards).  Otherwise d_actions and
+ *   d_raw are bit for bit what that call writes under the handle's policy and d_logd [num_envs] float32 (4-byte aligned) is the quantity
+ *   above.  The checks of box_act_device, then d_logd's alignment and the sigma; a Discrete actor gives GYMNET_ERR_INVALID_ARG (its call
+ *   is gymnet_vecenv_actor_act_logp_device).  A request for logd runs kernels of their own (csrc/actor_box_logd.hip) under every policy,
+ *   the default (CLAMP, SAMPLE) with sigma > 0 included.  A single step's value stays gymnet_vecenv_actor_value_device.
+ * rollout_fused_box_logd_device: with both pointers NULL it IS gymnet_vecenv_rollout_fused_ex_device(h, spec).  Otherwise it refuses with
+ *   GYMNET_ERR_INVALID_ARG, nothing launched, in this order: an action_source other than GYMNET_ACTIONS_ACTOR, no actor, a Discrete
+ *   actor, a bad sigma, d_rec_value without a critic, a d_rec_logd that is not 4-byte aligned, a d_rec_value that is not; then every check
+ *   of rollout_fused_ex_device applies.  Everything that call leaves for the spec is left bit for bit, and in addition
+ *   d_rec_logd[t * num_envs + lane] is what box_act_logd_device(epsilon, action_seed, action_tick0 + t) writes at step t and
+ *   d_rec_value[t * num_envs + lane] what actor_value_device would write before step t: the call is bit-identical to steps x
+ *   (box_act_logd_device, actor_value_device, step_device, actor_push_device).  Either pointer may be NULL: d_rec_value alone is served
+ *   here (and only here: the Discrete calls' d_rec_logp / d_rec_value and d_logp keep refusing a Box actor).  steps == 0 writes nothing.
+ *   One kernel per form serves every policy and either pointer.
+ * Out of scope: the Discrete calls' names lifted for a Box actor; noise before the TANH head (a squashed Gaussian with its Jacobian);
+ *   a learned or per-lane sigma; V(terminal observation) for gymnet_gae_device's d_boot rows; logd carried through the episode memory. */
+int gymnet_vecenv_actor_box_act_logd_device(gymnet_vecenv *h, float *d_actions, float *d_raw, float *d_logd, float epsilon, uint64_t seed,
+                                            uint64_t tick);
+int gymnet_vecenv_rollout_fused_box_logd_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logd, float *d_rec_value);
 
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */

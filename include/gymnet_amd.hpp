@@ -459,6 +459,19 @@ public:
         check(gymnet_vecenv_actor_box_get_policy(h_, &hd, &ex, &sigma));
         head = (gymnet_box_head)hd; explore = (gymnet_box_explore)ex;
     }
+    // BoxActorAct that also writes the log-density of every lane's action under the handle's policy, sigma > 0, into d_logd float32 [N]
+    // (gymnet_vecenv_actor_box_act_logd_device): log N(action; greedy, sigma^2); actions and raw outputs are BoxActorAct's, bit for bit.
+    // d_logd null: BoxActorAct.
+    void BoxActorActLogd(float *d_actions, float *d_logd, float epsilon = 0.0f, uint64_t seed = 0, uint64_t tick = 0, float *d_raw = nullptr) {
+        check(gymnet_vecenv_actor_box_act_logd_device(h_, d_actions, d_raw, d_logd, epsilon, seed, tick));
+    }
+    // RolloutFused with GYMNET_ACTIONS_ACTOR on a Box actor, also recording every step's log-density into d_rec_logd and, with a critic, the
+    // value before every step into d_rec_value, float32 [T][N] each (gymnet_vecenv_rollout_fused_box_logd_device); either may be null.
+    // Both null: RolloutFused itself.
+    void RolloutFusedBoxLogd(gymnet_rollout_spec spec, float *d_rec_logd, float *d_rec_value) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_fused_box_logd_device(h_, &spec, d_rec_logd, d_rec_value));
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
