@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cartpole_done_filter.hpp"
 #include "philox.hpp"
 
 namespace gymnet {
@@ -290,6 +291,28 @@ struct CartPole {
         term[0] = __builtin_fabs(vx) > (double)x_threshold;
         term[1] = __builtin_fabs(vtheta) > (double)theta_threshold;
     }
+
+    // The float32 pre-filter of done_terms_of_inputs (cartpole_done_filter.hpp: the bound on |nx - vx| and the band derived from it).  Per
+    // term three compares of values the step holds anyway — the position it started with and the float32 sum step_pre() formed:
+    //     decided = inside && (below || above),     and where decided the flag is `above`.
+    // Where a term is not decided (within 4 ulps of its threshold, a position at or beyond it, a NaN) the caller evaluates
+    // done_terms_of_inputs.  Handed out as the three compares, not as their combination: a kernel takes each compare's ballot (its result
+    // register) and combines the masks on the scalar unit.
+    __device__ __forceinline__ static void done_terms_filter(const float (&s)[S], const Pre &p, bool (&inside)[DONE_TERMS], bool (&below)[DONE_TERMS],
+                                                             bool (&above)[DONE_TERMS]) {
+        using B = CartPoleDoneBand;
+        static_assert(B::x_threshold == x_threshold && B::theta_threshold == theta_threshold, "one pair of thresholds");
+        cartpole_done_compares(s[0], p.nx, B::x_lo, B::x_hi, inside[0], below[0], above[0]);
+        cartpole_done_compares(s[2], p.ntheta, B::theta_lo, B::theta_hi, inside[1], below[1], above[1]);
+    }
+
+#ifdef GYMNET_PROBE_STEP_CHAIN
+    // probe builds only (step_kernels.hpp kProbeStepChain, switch 1): the flag of the ROUNDED sums — not the reference's within ~2 ulps of a threshold
+    __device__ __forceinline__ static void done_terms_rounded(const Pre &p, bool (&term)[DONE_TERMS]) {
+        term[0] = fabsf(p.nx) > x_threshold;
+        term[1] = fabsf(p.ntheta) > theta_threshold;
+    }
+#endif
 
     // :63-67 — state = uniform(-0.05, 0.05, 4) as low + (high-low)*u
     __device__ __forceinline__ static void reset(float (&s)[S], const PhiloxWords &r) {

@@ -158,11 +158,30 @@ __device__ __forceinline__ void advance_all(typename Env::Real (&s)[Env::S][VEC]
 template <class Env, class = void> struct has_done_of_inputs : std::false_type {};
 template <class Env> struct has_done_of_inputs<Env, std::void_t<decltype(&Env::done_terms_of_inputs)>> : std::true_type {};
 
+// Probe builds only (-DGYMNET_PROBE_STEP_CHAIN=<mask>, never the shipped library): what three pieces of the headline route's serial chain
+// cost (docs/ledger.md §38, profiles/step_chain.txt).  A probe build keeps the PARENT's form of the flags and of the kernel's entry (mask 0
+// is the parent's kernel); each switch then gives a kernel that is WRONG ON PURPOSE but moves the same bytes:
+//   1  the done flags from the rounded float32 sums (wrong within ~2 ulps of a threshold) instead of the binary64 ones
+//   2  the entry reduced to the loads: no full-workgroup guard (wrong for a ragged batch), 32-bit lane and stride arithmetic (wrong past
+//      2^32 bytes), the next tick written behind the body
+//   4  the reset's draw takes the lane's own index for its slot instead of reading the slot table (wrong draws)
+#ifdef GYMNET_PROBE_STEP_CHAIN
+constexpr int kProbeStepChain = GYMNET_PROBE_STEP_CHAIN;
+constexpr bool kStepChainShipped = false;
+#else
+constexpr int kProbeStepChain = 0;
+constexpr bool kStepChainShipped = true;
+#endif
+
 // The step itself comes in the two parts the env cuts it into where the action enters (Env::step_pre / step_post: envs.hpp).  The action is
 // the one input stream of a launch that no earlier launch has touched, so it is the last to arrive: everything that can be decided without it
 // — the action-free part of the dynamics, the flags, and with them the whole reset draw — runs in front of the wait for it.
 template <class Env, class = void> struct has_split_step : std::false_type {};
 template <class Env> struct has_split_step<Env, std::void_t<typename Env::Pre>> : std::true_type {};
+
+// an env whose flags a float32 pre-filter decides exactly almost everywhere (Env::done_terms_filter: CartPole, cartpole_done_filter.hpp)
+template <class Env, class = void> struct has_done_filter : std::false_type {};
+template <class Env> struct has_done_filter<Env, std::void_t<decltype(&Env::done_terms_filter)>> : std::true_type {};
 
 // the action-free part of the step of ALL VEC sub-lanes (the wave-uniform choice of the trigonometry path encloses nothing else), and the flags
 template <class Env, int VEC>
@@ -182,20 +201,57 @@ __device__ __forceinline__ void pre_all_late_done(const typename Env::Real (&s)[
     };
     if (wave_angles_small<Env, VEC>(s)) all_sublanes(std::true_type{});
     else all_sublanes(std::false_type{});
+    // the flags as the reference decides them: the binary64 compares, sub-lane by sub-lane
+    auto exact_flags = [&] {
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        Real wj[S];
+        for (int j = 0; j < VEC; ++j) {
+            Real wj[S];
 #pragma unroll
-        for (int k = 0; k < S; ++k) wj[k] = s[k][j];
-        bool term[Env::DONE_TERMS];
-        Env::done_terms_of_inputs(wj, term);
-        bool any = false;
-        uint64_t m = 0;
+            for (int k = 0; k < S; ++k) wj[k] = s[k][j];
+            bool term[Env::DONE_TERMS];
+            if constexpr ((kProbeStepChain & 1) != 0) Env::done_terms_rounded(pre[j], term);   // probe builds only: WRONG flags near a threshold
+            else Env::done_terms_of_inputs(wj, term);
+            bool any = false;
+            uint64_t m = 0;
 #pragma unroll
-        for (int q = 0; q < Env::DONE_TERMS; ++q) { any = any || term[q]; m |= __builtin_amdgcn_ballot_w64(term[q]); }
-        dn[j] = any;
-        dmask[j] = m;
-    }
+            for (int q = 0; q < Env::DONE_TERMS; ++q) { any = any || term[q]; m |= __builtin_amdgcn_ballot_w64(term[q]); }
+            dn[j] = any;
+            dmask[j] = m;
+        }
+    };
+    if constexpr (has_done_filter<Env>::value && kStepChainShipped) {
+        // Env::done_terms_filter: float32 compares of values the front part holds anyway decide a term exactly unless it is within a few ulps
+        // of its threshold (or a NaN).  Each compare's ballot is its result register and the masks are combined on the scalar unit, as above.
+        // Undecided anywhere in the wave — about one wave in thousands with states a rollout visits — and the whole wave takes the binary64
+        // compares: wave-uniform, the two sides meet in front of the reset's draw.
+        uint64_t undecided = 0;
+        uint64_t above_mask[VEC];
+        bool any_above[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            Real wj[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) wj[k] = s[k][j];
+            bool inside[Env::DONE_TERMS], below[Env::DONE_TERMS], above[Env::DONE_TERMS];
+            Env::done_terms_filter(wj, pre[j], inside, below, above);
+            uint64_t m = 0;
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < Env::DONE_TERMS; ++q) {
+                const uint64_t hi = __builtin_amdgcn_ballot_w64(above[q]);
+                undecided |= ~(__builtin_amdgcn_ballot_w64(inside[q]) & (__builtin_amdgcn_ballot_w64(below[q]) | hi));
+                m |= hi;
+                any = any || above[q];
+            }
+            above_mask[j] = m;
+            any_above[j] = any;
+        }
+        if (__builtin_expect((undecided & __builtin_amdgcn_ballot_w64(true)) != 0, 0)) exact_flags();
+        else {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { dmask[j] = above_mask[j]; dn[j] = any_above[j]; }
+        }
+    } else exact_flags();
 }
 
 // The wait for the action, and the rest of the step.  The compiler puts the wait in front of the first instruction that reads the action's
@@ -440,7 +496,7 @@ __device__ __forceinline__ void reset_finished_draw(const bool (&fin)[VEC], cons
     wave_lds_fence();
     {
         // every lane draws (kResetFullExec's reason: reset_pending_wave); the lanes without a slot redo slot 0's draw into a row nobody reads
-        const uint32_t sl = sc->slot[lane < total ? lane : 0u];
+        const uint32_t sl = (kProbeStepChain & 4) != 0 ? lane : sc->slot[lane < total ? lane : 0u];
         const int64_t gl = wave_i0 + (int64_t)sl;
         Real sj[S];
         bool drawn = false;
@@ -759,8 +815,18 @@ __device__ __forceinline__ void step_body_wg(const StepArgsT<typename Env::Real>
 
     Real s[S][VEC];
     typename Env::Action act[VEC];
+    if constexpr (kStepChainShipped) {
+        // each row's base from the row before it (one add with carry): `k * state_stride` costs a 64-bit multiply for the rows that are no shift
+        const Real *row = wg_row(static_cast<const Real *>(a.state), wg);
 #pragma unroll
-    for (int k = 0; k < S; ++k) load_row_wg<Real, VEC, NT_SL>(wg_row(static_cast<const Real *>(a.state) + k * a.state_stride, wg), wg.local, s[k]);
+        for (int k = 0; k < S; ++k) {
+            load_row_wg<Real, VEC, NT_SL>(row, wg.local, s[k]);
+            row = wave_uniform(row + a.state_stride);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < S; ++k) load_row_wg<Real, VEC, NT_SL>(wg_row(static_cast<const Real *>(a.state) + k * a.state_stride, wg), wg.local, s[k]);
+    }
     load_row_wg<int32_t, VEC, NT_A>(wg_row(static_cast<const int32_t *>(a.action), wg), wg.local, act);
 
     // The action is the last of the five loads, and the only one no earlier launch has left in the Infinity Cache: what does not need it
@@ -1219,6 +1285,48 @@ __global__ __launch_bounds__(256) void step_kernel(typename Env::Real *state, co
     // engine tick (Philox counter word): double-buffered in device memory so that a replayed
     // hipGraph, whose kernel arguments are frozen, still advances it.
     const uint64_t tick = a.tick2[a.parity];
+    if constexpr ((kProbeStepChain & 2) != 0 && has_full_workgroup_body<Env, AUTORESET, EXTRAS>() && VEC == 4 && RESETF == 1) {
+        // probe builds only (kProbeStepChain): the loads with nothing in front of them that a host could have computed
+        StepArgsT<typename Env::Real> b = a;
+        b.state_stride = (int64_t)(uint32_t)state_stride;
+        const WgLanes wg32{(int64_t)((uint32_t)blockIdx.x * (uint32_t)block * (uint32_t)VEC), (uint32_t)threadIdx.x * (uint32_t)VEC};
+        step_body_wg<Env, VEC, NT, RESETF>(b, wg32, tick, sc);
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.tick2[a.parity ^ 1] = tick + 1;
+        return;
+    }
+    if constexpr (kStepChainShipped && has_full_workgroup_body<Env, AUTORESET, EXTRAS>()) {
+        // The headline family's entry: as little as possible in front of the five loads, and all of it on the scalar unit (docs/ledger.md §38).
+        //   * the workgroup's first lane is ONE unsigned 32 x 32 -> 64 multiply (s_mul_i32 + s_mul_hi_u32) of the workgroup's index and its
+        //     lane count — valid for every batch size, so there is no narrower form to fall back from; widened as signed values, as the
+        //     general entry below writes it, the same product is a chain of five multiplies and adds;
+        //   * the full-workgroup guard is the sign of n - (first + lanes), taken from the difference's high word: a scalar subtract with
+        //     borrow and a 32-bit scalar compare, where a 64-bit ordering compare exists on the vector unit only;
+        //   * the next tick is written BEHIND the body, by the same one thread: nobody reads it before the next launch.  The test of the
+        //     workgroup's index is a scalar branch of its own (the empty asm keeps it from being folded into the thread's test), so no
+        //     wave but those of workgroup 0 meets the vector compare and the exec-mask branch.
+        const uint32_t wg_lanes = (uint32_t)block * (uint32_t)VEC;
+        const uint64_t first = (uint64_t)(uint32_t)blockIdx.x * (uint64_t)wg_lanes;
+        const uint64_t room = (uint64_t)n - (first + wg_lanes);            // lanes behind this workgroup's last one; "negative": a ragged workgroup
+        const WgLanes wgu{(int64_t)first, (uint32_t)threadIdx.x * (uint32_t)VEC};
+        uint32_t room_hi = (uint32_t)(room >> 32);
+        asm volatile("" : "+s"(room_hi));                                  // (a scalar word of its own: seen as 64 bits the test goes back to the vector unit)
+        auto write_next_tick = [&] {
+            if (blockIdx.x == 0) {
+                asm volatile("");
+                if (threadIdx.x == 0) a.tick2[a.parity ^ 1] = tick + 1;
+            }
+        };
+        // (each side ends the kernel itself: with one shared end the full body, the route of every wave but the batch's last few, was laid
+        // out behind the ragged one and reached by two taken branches)
+        if (__builtin_expect((int32_t)room_hi < 0, 0)) {
+            if (wgu.first + (int64_t)wgu.local < a.n) step_body<Env, VEC, AUTORESET, EXTRAS, NT, true, RESETF>(a, wgu.first + (int64_t)wgu.local, tick, sc);
+            write_next_tick();
+            return;
+        }
+        step_body_wg<Env, VEC, NT, RESETF>(a, wgu, tick, sc);
+        write_next_tick();
+        return;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.tick2[a.parity ^ 1] = tick + 1;
     }
