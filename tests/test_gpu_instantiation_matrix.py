@@ -19,11 +19,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _instantiation_matrix as M  # noqa: E402
+from _handle_replay import KEYS, SEED, Replay, _lane_seeds  # noqa: E402,F401  (the replay: the handle's semantics on the CPU)
 
 pytestmark = pytest.mark.gpu
-SEED, ASEED = 0x5EED, 0xAC710
+ASEED = 0xAC710
 STEPS, T_ROLLOUT, RING, EPS = 18, 16, 5, 0.4
-KEYS = np.array([0x1234567, 0x9ABCDEF0123, 77], dtype=np.uint64)     # per-lane Philox keys: lane i gets KEYS[i % 3]
 
 RECIPES = M.recipes()
 
@@ -97,78 +97,12 @@ def _actions(r, rng, n):
     return rng.integers(0, M.ENVS[r["env"]]["nvals"], n).astype(np.int32)
 
 
-def _lane_seeds(n):
-    return KEYS[np.arange(n) % 3]
-
-
 def _open(gpu_pkg, r, **more):
     kw = dict(seed=SEED, auto_reset=r["auto_reset"], dtype=np.float64 if r["f64"] else np.float32, lane_offset=r["lane_offset"],
               done_list=r["done_list"], episode_stats=r["episode_stats"], final_obs=r["final_obs"], max_episode_steps=r["max_episode_steps"],
               double_buffer=r["double_buffer"], resident=r["resident"])
     kw.update(more)
     return gpu_pkg.VectorEnv(r["gym"], r["n"], **kw)
-
-
-# ---- the replay ------------------------------------------------------------------------------------------------------------
-class Replay:
-    """The handle's semantics on the CPU: the oracle's step and reset draws, the episode bookkeeping in NumPy."""
-
-    def __init__(self, oracle, r, s0, sbd0=None, ln0=None, ret0=None):
-        self.o, self.r, self.n = oracle, r, r["n"]
-        self.f64, self.alias = r["f64"], M.ENVS[r["env"]]["alias"]
-        self.s = s0.astype(np.float64 if self.f64 else np.float32)
-        self.seeds = _lane_seeds(self.n) if r["lane_seeds"] else None
-        self.sbd = None if (r["auto_reset"] or r["env"] not in ("CartPole", "CartPole64")) else np.ascontiguousarray(sbd0, dtype=np.int32)
-        self.stats, self.limit = r["episode_stats"], r["max_episode_steps"]
-        self.ln = np.zeros(self.n, np.int32) if ln0 is None else ln0.astype(np.int32)
-        self.ret = np.zeros(self.n, np.float32) if ret0 is None else ret0.astype(np.float32)
-        self.fin_ret, self.fin_len = np.zeros(self.n, np.float32), np.zeros(self.n, np.int32)
-        O = 4 if r["env"].startswith("CartPole") else {"Pendulum": 3, "MountainCar": 2, "Acrobot": 6}[r["env"]]
-        self.final = np.zeros((O, self.n), self.s.dtype)
-
-    def fresh(self, tick):
-        r, n, lo = self.r, self.n, self.r["lane_offset"]
-        if self.f64:
-            s = self.o.cartpole_reset_f64(SEED, lo, tick, n, lane_seed=self.seeds)
-            return s, s
-        if self.seeds is None:
-            return self.o.env_reset(r["gym"], SEED, lo, tick, n, with_obs=True)
-        s, o = self.o.env_reset(r["gym"], int(KEYS[0]), lo, tick, n, with_obs=True)
-        for j in (1, 2):
-            sj, oj = self.o.env_reset(r["gym"], int(KEYS[j]), lo, tick, n, with_obs=True)
-            m = np.arange(n) % 3 == j
-            s[:, m], o[:, m] = sj[:, m], oj[:, m]
-        return s, o
-
-    def step(self, a, tick):
-        """One vector step at engine tick `tick`: returns (obs [O, n], reward, done byte, finished mask)."""
-        if self.f64:
-            stepped, rw, d, b = self.o.cartpole_step(self.s, a, sbd=self.sbd, dtype=np.float64, kernel_sincos=True)
-            if self.sbd is not None:
-                self.sbd = b
-            obs = stepped
-        else:
-            stepped, obs, rw, d = self.o.env_step(self.r["gym"], self.s, a, sbd=self.sbd, dtype=np.float32)
-        rw = rw.astype(np.float32)
-        db = d.astype(np.uint8)
-        if self.stats:
-            self.ret += rw
-            self.ln += 1
-            if self.limit:
-                db |= np.where(self.ln >= self.limit, 2, 0).astype(np.uint8)
-        fin = db != 0
-        if self.r["final_obs"]:
-            self.final[:, fin] = (stepped if self.alias else obs)[:, fin]
-        if self.stats:
-            self.fin_ret[fin], self.fin_len[fin] = self.ret[fin], self.ln[fin]
-            if self.r["auto_reset"]:
-                self.ret[fin], self.ln[fin] = 0.0, 0
-        if self.r["auto_reset"] and fin.any():
-            fs, fo = self.fresh(tick)
-            stepped = np.where(fin, fs, stepped)
-            obs = np.where(fin, fo, obs)
-        self.s = stepped
-        return obs, rw, db, fin
 
 
 def _prepare(env, r, golden, rng):
