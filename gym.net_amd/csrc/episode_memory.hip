@@ -9,13 +9,17 @@
 // reward [N].  The step's action and reward go to slot pos, the post-step observation (the next step's o_p, or an auto-reset's o_0) to
 // slot pos + 1; an episode of len <= L steps that ends at push pos occupies slots pos - len + 1 .. pos, and pos + 1 is never one of them.
 // A lane whose episode ends compares its return with the pool's lowest kept return (read from the previous merge): a newer episode wins
-// ties, so when the pool is full ret >= thr admits.  Survivors are appended to the candidate list with one atomic per wave.
+// ties, so when the pool is full ret >= thr admits.  An episode whose return is NaN is never a candidate, whatever the pool holds
+// (memory_admits, episode_memory_key.hpp): the pool, thr and the host's sort stay free of NaN.  Survivors are appended to the candidate
+// list with one atomic per wave.
 //
 // Merge (a second launch, one workgroup; it returns at once when no episode was admitted, which is the common case after warm-up).  It
 // keeps the top `capacity` keys of pool + candidates: a 16-digit radix select finds the K-th key, evicted pool blocks join the free
-// list, and each winner copies its rows out of the ring into a free block [L][row].  Then it publishes the new threshold.
+// list, and each winner copies its rows out of the ring into a free block [L][row].  Then it publishes the new threshold.  Keys can
+// repeat (a tick set backwards, a replay after a restored checkpoint): the kept set is then the top-`capacity` MULTISET of keys — keys
+// above the K-th stay or win first, keys equal to it fill what is left, pool entries ahead of candidates.
 //
-// Dataset (not per step): rank the kept keys (count of larger keys), scan the row counts floor(len * 2 / 3) in that order, then write
+// Dataset (not per step): rank the kept keys (count of larger keys, and of equal keys at a lower pool index), scan the row counts floor(len * 2 / 3) in that order, then write
 // params rows (one thread per row) or frames re-rendered from the stored observations with cartpole_raster.hpp (one wave per 1024
 // pixels of one frame, as the pixel stack draws them).
 //
@@ -32,6 +36,7 @@
 #include <type_traits>
 
 #include "cartpole_raster.hpp"
+#include "episode_memory_key.hpp"
 #include "handle.hpp"
 
 namespace gymnet {
@@ -93,48 +98,6 @@ struct MemDatasetArgs {
     FrameGeom geo;
 };
 
-// a float's order as an unsigned integer (+0 and -0 are one value)
-__device__ __forceinline__ uint32_t ret_bits(float r) {
-    const uint32_t u = __float_as_uint(r == 0.0f ? 0.0f : r);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float bits_ret(uint32_t b) { return __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b); }
-
-struct Key { uint32_t w[4]; };      // (return, tick high, tick low, lane): 16 digits of 8 bits, most significant first
-
-__device__ __forceinline__ Key make_key(float ret, uint64_t tick, int32_t lane) {
-    Key k;
-    k.w[0] = ret_bits(ret); k.w[1] = (uint32_t)(tick >> 32); k.w[2] = (uint32_t)tick; k.w[3] = (uint32_t)lane;
-    return k;
-}
-
-__device__ __forceinline__ bool key_less(const Key &a, const Key &b) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (a.w[q] != b.w[q]) return a.w[q] < b.w[q];
-    return false;
-}
-
-__device__ __forceinline__ uint32_t digit(const Key &k, int d) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) if (q == (d >> 2)) w = k.w[q];
-    return (w >> (24 - 8 * (d & 3))) & 255u;
-}
-
-// digits 0 .. d-1 of k equal those of t
-__device__ __forceinline__ bool prefix_match(const Key &k, const uint32_t (&t)[4], int d) {
-    const int wd = d >> 2, b = d & 3;
-    const uint32_t mask = b ? 0xFFFFFFFFu << (32 - 8 * b) : 0u;
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q < wd) ok &= k.w[q] == t[q];
-        else if (q == wd) ok &= (k.w[q] & mask) == (t[q] & mask);
-    }
-    return ok;
-}
-
 __device__ __forceinline__ uint32_t wave_rank(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
@@ -189,7 +152,7 @@ __global__ __launch_bounds__(kPushBlock) void memory_push_kernel(MemoryArgs m, M
         if (done) {
             ended = true;
             too_long = len > m.max_len;
-            cand = !too_long && (!m.ctl->full || ret >= m.ctl->thr);
+            cand = memory_admits(too_long, m.ctl->full != 0, ret, m.ctl->thr);
         }
         if (!done || p.autoreset) {                       // the next step's o_p, or the auto-reset episode's o_0
             const int64_t nxt = p.slot + 1 == m.ring_slots ? 0 : p.slot + 1;
@@ -230,27 +193,27 @@ __device__ __forceinline__ Key entry_key(const MemoryArgs &m, const MemCand *can
 // one merge by one workgroup of kMergeBlock: the candidates cand[0, *count) of the step staged in `slot`, whose episodes end at end_tick.
 // REFILTER (the rollout ingest, whose scan filtered against the pool as it stood before the pass): a candidate counts only if it also
 // passes the single push's filter against the pool as it stands now, so the merge sees exactly the candidates a single push would have
-// made — also for a return that compares false with everything (NaN) when the pool filled earlier in the pass.
+// made.  (A NaN return never gets this far: the scan's filter refuses it, as the push's does.)
 template <int ESZ, bool REFILTER>
 __device__ __forceinline__ void merge_body(const MemoryArgs &m, const MemCand *cand, uint32_t *count, int64_t slot, uint64_t end_tick) {
     using W = typename std::conditional<ESZ == 8, uint64_t, uint32_t>::type;
     __shared__ uint32_t hist[256];
     __shared__ uint32_t tau[4];
     __shared__ uint32_t need_s, min_bits;
-    __shared__ int32_t n_keep, n_free, n_win;
+    __shared__ int32_t n_keep, n_free, n_win, n_above, n_equal;
     const uint32_t cands = *count;
     if (cands == 0) return;
     const int32_t kept = m.ctl->kept, cap = m.capacity;
     const int32_t full_now = REFILTER ? m.ctl->full : 0;
     const float thr_now = REFILTER ? m.ctl->thr : 0.0f;
-    auto counts = [&](const MemCand &c) { return !REFILTER || !full_now || c.ret >= thr_now; };
+    auto counts = [&](const MemCand &c) { return !REFILTER || memory_admits(false, full_now != 0, c.ret, thr_now); };
     const int64_t total = (int64_t)kept + cands;
     // (REFILTER: total counts every candidate, so with a full pool the caller must have found one that counts — memory_merge_rollout_kernel's
     // pre-check — or the selection would look for a key that is not there)
     const bool select = total > cap;
     const int tid = threadIdx.x;
     if (tid < 4) tau[tid] = 0u;
-    if (tid == 0) { need_s = (uint32_t)cap; min_bits = 0xFFFFFFFFu; n_keep = 0; n_free = 0; n_win = 0; }
+    if (tid == 0) { need_s = (uint32_t)cap; min_bits = 0xFFFFFFFFu; n_keep = 0; n_free = 0; n_win = 0; n_above = 0; n_equal = 0; }
     __syncthreads();
     // the cap-th largest key: digit by digit, the bin where the count from the top reaches the rank still needed
     if (select) {
@@ -280,24 +243,42 @@ __device__ __forceinline__ void merge_body(const MemoryArgs &m, const MemCand *c
     Key t;
 #pragma unroll
     for (int q = 0; q < 4; ++q) t.w[q] = tau[q];
-    // kept entries at or above the threshold stay; the others' blocks, and the blocks of the unused entries, are free
+    // After a selection t is the cap-th largest key.  Whatever is ABOVE it stays or wins; what EQUALS it (more than one entry only when keys
+    // repeat: a tick set backwards, a replay from a restored checkpoint) takes the places that are left, pool entries ahead of candidates,
+    // so a greater key is never dropped for an equal one and the kept set is the top-cap multiset of keys.
+    if (select) {
+        int32_t mine = 0;
+        for (int64_t i = tid; i < total; i += kMergeBlock) {
+            if (i >= kept && !counts(cand[i - kept])) continue;
+            mine += key_less(t, entry_key(m, cand, i, kept, end_tick)) ? 1 : 0;
+        }
+        if (mine) atomicAdd(&n_above, mine);
+        __syncthreads();
+    }
+    const int32_t room = cap - n_above;      // places for keys equal to t: at least one, t being the cap-th largest
+    auto place = [&](const Key &k) {         // does this key stay in / enter the pool?
+        if (!select) return true;
+        if (key_less(k, t)) return false;
+        return key_less(t, k) || atomicAdd(&n_equal, 1) < room;
+    };
+    // kept entries that have a place stay; the others' blocks, and the blocks of the unused entries, are free
     for (int i = tid; i < cap; i += kMergeBlock) {
         const MemEntry e = m.meta[i];
-        if (i < kept && (!select || !key_less(make_key(e.ret, e.tick, e.lane), t))) m.meta_tmp[atomicAdd(&n_keep, 1)] = e;
+        if (i < kept && place(make_key(e.ret, e.tick, e.lane))) m.meta_tmp[atomicAdd(&n_keep, 1)] = e;
         else m.scratch[atomicAdd(&n_free, 1)] = e.block;
     }
     __syncthreads();
     const int32_t keep = n_keep;
     for (int64_t j = tid; j < cands; j += kMergeBlock) {
         const MemCand c = cand[j];
-        if (counts(c) && (!select || !key_less(make_key(c.ret, end_tick, c.lane), t))) {
+        if (counts(c) && place(make_key(c.ret, end_tick, c.lane))) {
             const int32_t s = atomicAdd(&n_win, 1);
             if (keep + s < cap) m.meta_tmp[keep + s] = MemEntry{c.ret, c.len, end_tick, c.lane, m.scratch[s]};
         }
     }
     __syncthreads();
-    // keys are unique while ticks only grow, so exactly cap - keep candidates pass a selection; the clamp keeps a tick that was set
-    // backwards (equal keys) inside the pool
+    // exactly cap - keep candidates pass a selection (the places above t and the places equal to it add up to cap), and without one
+    // kept + cands <= cap; the clamp only restates that bound where the blocks are handed out
     const int32_t win = n_win < cap - keep ? n_win : cap - keep, live = keep + win;
     for (int i = live + tid; i < cap; i += kMergeBlock) m.meta_tmp[i] = MemEntry{0.0f, 0, 0ull, -1, m.scratch[i - keep]};
     __syncthreads();
@@ -400,7 +381,7 @@ __global__ __launch_bounds__(kPushBlock) void memory_scan_rollout_kernel(MemoryA
             if (done) {
                 ended = true;
                 too_long = len > m.max_len;
-                cand = !too_long && (!full || ret >= thr);
+                cand = memory_admits(too_long, full != 0, ret, thr);
                 ep_ret = ret; ep_len = len;
             }
             if (!done || p.autoreset) {
@@ -456,7 +437,7 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_rollout_kernel(Memor
             const int32_t full = m.ctl->full;
             const float thr = m.ctl->thr;
             bool any = false;
-            for (uint32_t i = threadIdx.x; i < cands; i += kMergeBlock) any |= !full || cand[i].ret >= thr;
+            for (uint32_t i = threadIdx.x; i < cands; i += kMergeBlock) any |= memory_admits(false, full != 0, cand[i].ret, thr);
             if (any) pass = 1u;
             __syncthreads();
             if (pass) {
@@ -473,7 +454,7 @@ __global__ __launch_bounds__(kMergeBlock) void memory_merge_rollout_kernel(Memor
 
 // ---- dataset -----------------------------------------------------------------------------------------------------------------
 
-// scratch[rank] = the entry of that rank, 0 the largest key
+// scratch[rank] = the entry of that rank, 0 the largest key; equal keys rank by pool index, so scratch[0, kept) is a permutation
 __global__ __launch_bounds__(256) void memory_rank_kernel(MemoryArgs m) {
     const int32_t kept = m.ctl->kept;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -483,7 +464,7 @@ __global__ __launch_bounds__(256) void memory_rank_kernel(MemoryArgs m) {
     int r = 0;
     for (int j = 0; j < kept; ++j) {
         const MemEntry f = m.meta[j];
-        r += key_less(ki, make_key(f.ret, f.tick, f.lane)) ? 1 : 0;
+        r += key_ranks_before(make_key(f.ret, f.tick, f.lane), j, ki, i) ? 1 : 0;
     }
     m.scratch[r] = i;
 }
@@ -849,11 +830,9 @@ int gymnet_vecenv_memory_episodes(gymnet_vecenv *h, float *ret, int32_t *len, ui
     MemCtl ctl{};
     std::vector<MemEntry> meta;
     ST_TRY(read_pool(h, &ctl, &meta));
-    auto ret_order = [](float r) { return r == 0.0f ? 0.0f : r; };
-    std::sort(meta.begin(), meta.end(), [&](const MemEntry &a, const MemEntry &b) {     // descending key (return, tick, lane)
-        if (ret_order(a.ret) != ret_order(b.ret)) return ret_order(a.ret) > ret_order(b.ret);
-        if (a.tick != b.tick) return a.tick > b.tick;
-        return a.lane > b.lane;
+    // descending key (return, tick, lane); equal keys in pool order, as the dataset ranks them
+    std::stable_sort(meta.begin(), meta.end(), [](const MemEntry &a, const MemEntry &b) {
+        return key_before(make_key(a.ret, a.tick, a.lane), make_key(b.ret, b.tick, b.lane));
     });
     const int64_t m = (int64_t)meta.size() < capacity ? (int64_t)meta.size() : capacity;
     for (int64_t i = 0; i < m; ++i) {

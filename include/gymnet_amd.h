@@ -550,6 +550,16 @@ int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_la
  *   That is the reference's rule applied to episodes in (tick, lane) order — add when fewer than K are kept or return >= the lowest kept,
  *   then drop the lowest — with a newer episode winning ties of return.  An episode longer than L is not kept, in part or whole: it is
  *   counted as too_long.
+ *   The order of returns is the float32 order with +0 and -0 as ONE return; +inf, -inf and denormals are ordinary values.  An episode
+ *   whose return is NaN (a NaN or inf - inf among its rewards) is never kept, whatever the pool holds at the time: it counts in `ended`
+ *   and in neither `admitted` nor — unless it is longer than L, which goes by the length alone — `too_long`.  The pool, the lowest kept
+ *   return and the listing therefore never hold a NaN, and ordinary episodes go on being admitted after one.
+ *   Equal keys: ticks only grow on their own, but a caller can set the tick backwards or restore a checkpoint (the memory is not part
+ *   of one) and replay, so two ended episodes can have the same (return, end_tick, lane).  The kept set is then the top-K MULTISET of
+ *   keys, which is unique: a greater key is never dropped for an equal one.  Every kept entry appears exactly once in `episodes` and
+ *   in the dataset.  Among equal keys an entry already kept stays ahead of one that arrives, and their order in `episodes` and in the
+ *   dataset is their order in the pool (pool index), the same in both; which of several equal kept entries a later push evicts is
+ *   not specified.
  * Dataset: the kept episodes in descending key order; from each the first floor(len * 2 / 3) steps (DataBuilder.cs:33); one row per
  *   step: x, the action, for Discrete the one-hot of the action (float32 [action_n]) and the reward.
  *   GYMNET_MEMORY_PARAMS: x = float32 [S * obs_dim] = o_{p-S+1} .. o_p, oldest first, indices below 0 clamped to o_0 (float64

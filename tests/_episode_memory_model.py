@@ -3,7 +3,13 @@ EndEpisode rule under the key order (return, end_tick, lane), the top-K-per-push
 what the step API returned (observations after the step, actions, rewards, done bytes) that yields the kept set and the dataset.
 
 The model mirrors the device's bookkeeping: `obs[t]` is the observation stored for history index t (one index per push, plus the one
-open at config), lane k's open episode started at index start[k], and a memory reset overwrites the pending index of the masked lanes."""
+open at config), lane k's open episode started at index start[k], and a memory reset overwrites the pending index of the masked lanes.
+
+The order of returns (include/gymnet_amd.h, "Keeping the best K"): +0 and -0 are one return; +-inf and denormals are ordinary values.  An
+episode whose return is NaN is never kept, whatever the pool holds: it counts in `ended` and nowhere else (`too_long` goes by the length
+alone).  Keys can be equal (a tick set backwards, a replay after Restore): the kept set is the top-K multiset of keys, every kept entry
+is listed and built into the dataset exactly once, and among equal keys the order is the pool's — here the list's, an entry already kept
+ahead of a newcomer."""
 import numpy as np
 
 # The scenario whose end ticks cross 2^32 (tests/test_gpu_episode_memory.py runs it on the device, tests/test_episode_memory_host.py drives
@@ -24,25 +30,45 @@ def ticks_on_both_sides(m):
     return bool(ticks) and min(ticks) < 2 ** 32 <= max(ticks)
 
 
+def ret_bits(ret):
+    """A float32 return's place in the order, as an integer: +0 and -0 are one value, +-inf and denormals ordinary ones (the kernel's
+    ret_bits, csrc/episode_memory_key.hpp).  A NaN has no place in it: no kept episode has one."""
+    r = np.float32(ret)
+    assert not np.isnan(r), "a NaN return is never kept, so it is never ordered"
+    u = int(np.float32(0.0 if r == 0 else r).view(np.uint32))
+    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
+
+
+def is_nan(ret):
+    return bool(np.isnan(np.float32(ret)))
+
+
 def key(e):
-    """The total order of kept episodes: (return, end_tick, lane); a later tick, then a higher lane, is newer and wins ties."""
-    return (float(e["ret"]), int(e["tick"]), int(e["lane"]))
+    """The total order of kept episodes: (return, end_tick, lane); a later tick, then a higher lane, is newer and wins ties.  The
+    return enters as its order bits, so the order is defined on every return a kept episode can have.  Equal keys can exist (a tick set
+    backwards, a replay after Restore): the kept set is then the top-K MULTISET of keys, and among equal keys the entry already kept
+    stays ahead of a newcomer."""
+    return (ret_bits(e["ret"]), int(e["tick"]), int(e["lane"]))
 
 
 def end_episode_sequential(pool, episode, capacity):
     """ReplayMemory.EndEpisode (MemoryTypes/ReplayMemory.cs:53-67) for ONE episode: add it when fewer than `capacity` are kept or its
-    return is >= the lowest kept, then drop the lowest (by key) while more than `capacity` are kept."""
+    return is >= the lowest kept, then drop the lowest (by key; of equal keys the newest arrival) while more than `capacity` are kept.
+    An episode whose return is NaN is never kept: the rule does not depend on what the pool holds."""
+    if is_nan(episode["ret"]):
+        return pool
     if len(pool) < capacity or float(episode["ret"]) >= min(float(e["ret"]) for e in pool):
         pool = pool + [episode]
     while len(pool) > capacity:
-        low = min(range(len(pool)), key=lambda i: key(pool[i]))
+        low = min(range(len(pool)), key=lambda i: (key(pool[i]), -i))
         pool = pool[:low] + pool[low + 1:]
     return pool
 
 
 def top_k_per_push(pool, ended, capacity):
-    """What the device keeps after a push: the top `capacity` keys of (kept set + episodes that ended in that push)."""
-    return sorted(pool + list(ended), key=key, reverse=True)[:capacity]
+    """What the device keeps after a push: the top `capacity` keys of (kept set + episodes that ended in that push with a return that
+    is a number).  The sort is stable, so of equal keys the kept entries come first, in the pool's order."""
+    return sorted(pool + [e for e in ended if not is_nan(e["ret"])], key=key, reverse=True)[:capacity]
 
 
 class EpisodeMemoryModel:
@@ -79,7 +105,8 @@ class EpisodeMemoryModel:
         nxt = np.asarray(obs_after).copy()
         done = np.asarray(done) != 0
         live = self.open.copy()
-        self.ret[live] = (self.ret[live] + self.rew[-1][live]).astype(np.float32)
+        with np.errstate(invalid="ignore", over="ignore"):                 # inf - inf and overflow are returns like any other
+            self.ret[live] = (self.ret[live] + self.rew[-1][live]).astype(np.float32)
         self.length[live] += 1
         ended = []
         for k in np.flatnonzero(live & done):
