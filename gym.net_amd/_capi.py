@@ -212,6 +212,9 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_box_get_policy": (C.c_int, [_H, _P, _P, _P]),
     "gymnet_vecenv_actor_box_act_logd_device": (C.c_int, [_H, _P, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_rollout_fused_box_logd_device": (C.c_int, [_H, C.POINTER(RolloutSpec), _P, _P]),
+    "gymnet_vecenv_actor_boot_device": (C.c_int, [_H, _P]),
+    "gymnet_vecenv_rollout_fused_value_boot_device": (C.c_int, [_H, C.POINTER(RolloutSpec), _P, _P, _P]),
+    "gymnet_vecenv_rollout_fused_box_boot_device": (C.c_int, [_H, C.POINTER(RolloutSpec), _P, _P, _P]),
     "gymnet_vecenv_get_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_set_array": (C.c_int, [_H, C.c_int32, _P, C.c_int64]),
     "gymnet_vecenv_get_seed": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

@@ -216,6 +216,10 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_get_policy(IntPtr h, int* head, int* explore, float* sigma);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_act_logd_device(IntPtr h, IntPtr d_actions, IntPtr d_raw, IntPtr d_logd, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_box_logd_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logd, IntPtr d_rec_value);
+        // V(terminal observation) on time-limit rows (gymnet_gae_device's d_boot): d_boot float [N], d_rec_boot float [T][N]; IntPtr.Zero forwards
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_boot_device(IntPtr h, IntPtr d_boot);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_value_boot_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp, IntPtr d_rec_value, IntPtr d_rec_boot);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_box_boot_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logd, IntPtr d_rec_value, IntPtr d_rec_boot);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_array(IntPtr h, int which, void* out_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_set_array(IntPtr h, int which, void* in_array, long bytes);
         [DllImport(Lib)] public static extern int gymnet_vecenv_get_seed(IntPtr h, out ulong seed, out int per_lane);

@@ -386,6 +386,21 @@ namespace Gym.Envs.Amd {
             spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
             Native.Check(Native.gymnet_vecenv_rollout_fused_box_logd_device(_h, ref spec, dRecLogd, dRecValue));
         }
+        /// V(terminal observation) of every lane whose done byte has bit 1 set (a time limit), +0 for every other lane, into dBoot (float [N]):
+        /// one row of AdvantagesDevice's dBoot (gymnet_vecenv_actor_boot_device).  After a vector step and before PushActor; needs a critic
+        /// and max_episode_steps > 0, and on an auto-reset handle FinalObs.  Changes neither the history nor what PushActor does next.
+        public void ActorBoot(IntPtr dBoot) => Native.Check(Native.gymnet_vecenv_actor_boot_device(_h, dBoot));
+        /// RolloutFusedValue / RolloutFusedBoxLogd that also record ActorBoot's row after every step into dRecBoot (float [T][N];
+        /// gymnet_vecenv_rollout_fused_value_boot_device, _box_boot_device): needs dRecValue; FinalObs is not needed.  dRecBoot IntPtr.Zero:
+        /// the call without it.
+        public void RolloutFusedValueBoot(GymnetRolloutSpec spec, IntPtr dRecLogp, IntPtr dRecValue, IntPtr dRecBoot) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_fused_value_boot_device(_h, ref spec, dRecLogp, dRecValue, dRecBoot));
+        }
+        public void RolloutFusedBoxBoot(GymnetRolloutSpec spec, IntPtr dRecLogd, IntPtr dRecValue, IntPtr dRecBoot) {
+            spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
+            Native.Check(Native.gymnet_vecenv_rollout_fused_box_boot_device(_h, ref spec, dRecLogd, dRecValue, dRecBoot));
+        }
 
         public void ResetDevice() => Native.Check(Native.gymnet_vecenv_reset_device(_h));      // device-resident path: nothing crosses PCIe
         public void Sync() => Native.Check(Native.gymnet_vecenv_sync(_h));

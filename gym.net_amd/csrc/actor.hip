@@ -27,7 +27,7 @@
 //
 // The host side follows the kernels: gymnet_vecenv_actor_*, the handle's Actor attachment, the prologue of every act entry point
 // (actor_act_enter), and the calls the fused rollout (rollout_fused.hip) makes when the actor chooses its actions.  actor_rollout_launch among them
-// is the router: it alone says which of the seven units runs a handle's rollout (actor_act_launch: the same for act).
+// is the router: it alone says which of the eight units runs a handle's rollout (actor_act_launch: the same for act).
 #include "actor_net.hpp"
 
 namespace gymnet {
@@ -261,10 +261,14 @@ static hipError_t actor_discrete_rollout_launch(gymnet_vecenv *h, bool records, 
 // The router: which unit runs the fused rollout of this handle, as it stands at the launch.  Box: a log-density or value pointer
 // (gymnet_vecenv_rollout_fused_box_logd_device) goes to actor_box_logd.hip under any policy, else its policy decides.  Discrete: a value
 // pointer (gymnet_vecenv_rollout_fused_value_device) goes to actor_value.hip, with or without a logp pointer; a logp pointer alone
-// (gymnet_vecenv_rollout_fused_logp_device) to actor_logp.hip under either setting; else the setting decides
+// (gymnet_vecenv_rollout_fused_logp_device) to actor_logp.hip under either setting; else the setting decides.  A boot pointer
+// (gymnet_vecenv_rollout_fused_value_boot_device, _box_boot_device) goes to actor_boot.hip for either kind
 hipError_t actor_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, const FusedRequest &rq) {
     const Actor &ac = *h->actor;
     if (a.n <= 0) return hipSuccess;
+    if (rq.rec_boot)                                                         // (actor_boot.hip: both kinds)
+        return ac.box ? actor_box_boot_rollout_launch(h, records, a, r, rq.rec_logd, rq.rec_value, rq.rec_boot)
+                      : actor_value_boot_rollout_launch(h, records, a, r, rq.rec_logp, rq.rec_value, rq.rec_boot);
     if (ac.box) {
         if (rq.rec_logd || rq.box_value) return actor_box_logd_rollout_launch(h, records, a, r, rq.rec_logd, rq.box_value ? rq.rec_value : nullptr);
         if (rq.rec_logp || rq.rec_value) return hipErrorInvalidValue;        // (the plan has refused it: rollout_plan.hpp record_pointers)

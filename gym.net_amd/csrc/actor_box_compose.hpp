@@ -59,6 +59,13 @@ __device__ __forceinline__ float policy_choose(const ActorNet &net, const ActorH
     return policy_compose_one(greedy, low, high, pol, explore_at_or_below, seed, gl, tick);
 }
 
+// the log-density of the action a taken around the greedy action g (the five lines at the head of actor_box_logd.hip), for one lane
+__device__ __forceinline__ float box_logd(float a, float g, const BoxLogd &ld) {
+    const float d = (a - g) * ld.inv_sigma;
+    const float h = -0.5f * d;
+    return __builtin_fmaf(h, d, ld.c);
+}
+
 }  // namespace
 
 }  // namespace gymnet

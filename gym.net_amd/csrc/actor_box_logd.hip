@@ -30,22 +30,13 @@
 // bit-identical to steps x (box_act_logd, value, step, push).
 //
 // Not built: the old names (d_logp, d_rec_logp, d_rec_value alone) lifted for a Box actor, noise before the tanh head (a squashed
-// Gaussian with its Jacobian), a learned or per-lane sigma, V(terminal observation) for gymnet_gae_device's boot rows, logd carried
-// through the episode memory.
+// Gaussian with its Jacobian), a learned or per-lane sigma, logd carried through the episode memory.  (V(terminal observation) for
+// gymnet_gae_device's boot rows: actor_boot.hip.)
 #include "actor_box_compose.hpp"
 
 namespace gymnet {
 
-namespace {
-
-// the five lines above, for one lane
-__device__ __forceinline__ float box_logd(float a, float g, const BoxLogd &ld) {
-    const float d = (a - g) * ld.inv_sigma;
-    const float h = -0.5f * d;
-    return __builtin_fmaf(h, d, ld.c);
-}
-
-}  // namespace
+// (the five lines above, for one lane: box_logd, actor_box_compose.hpp, which actor_boot.hip's rollout runs too)
 
 template <int O>
 __global__ __launch_bounds__(256) void actor_box_logd_act_kernel(const ActorNet net, const ActorHist hs, float *__restrict__ actions,

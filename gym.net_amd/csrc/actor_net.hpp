@@ -1,4 +1,4 @@
-// actor_net.hpp — what the seven actor units share: the network and the per-lane observation history as the kernels see them, the forward
+// actor_net.hpp — what the eight actor units share: the network and the per-lane observation history as the kernels see them, the forward
 // pass, the ring arithmetic, the push (as a kernel and as the `after` half of rollout_body's hook), the host helpers every unit launches
 // with (lane_grid, pick_rollout_form), and the handle's Actor attachment with each unit's launch calls.  actor.hip serves the Discrete
 // envs (argmax head) and owns the attachment, the act prologue (actor_act_enter) and the router: actor_rollout_launch there is the one
@@ -7,7 +7,8 @@
 // asks for the log-density of the action taken or, inside the rollout, the critic's value, actor_softmax.hip the Discrete envs under an
 // exploration setting other than the default (a draw from the softmax of the logits), actor_logp.hip the Discrete envs when the caller
 // also asks for the log-probability of the action taken, actor_value.hip the critic: a second network over the same input whose one
-// output is the lane's value estimate.  Internal to the library.
+// output is the lane's value estimate, actor_boot.hip either kind when the caller also asks for the critic's value of the terminal
+// observation on time-limit rows.  Internal to the library.
 #pragma once
 #include "step_kernels.hpp"
 
@@ -228,7 +229,7 @@ int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, con
                     uint64_t tick, ActorAct &aa);
 // Each unit's fused rollout of a handle it serves, a.n > 0 (records: the rollout keeps compact episode records), and the calls one unit
 // makes into another: actor.hip's router (actor_rollout_launch, handle.hpp) reads (box, default_policy(), default_exploration(), a record
-// pointer) and calls exactly one of these six or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
+// pointer) and calls exactly one of these eight or its own unit's; the act entry points of actor.hip and actor_box.hip and actor.hip's
 // push reach a sibling's kernels through the rest.
 // actor_box.hip: the default policy's rollout, and the push / fill of a three-row observation (Pendulum)
 hipError_t actor_box_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r);
@@ -253,5 +254,11 @@ hipError_t actor_act_launch(gymnet_vecenv *h, int32_t *actions, float *logits, f
 // actor_value.hip: a Discrete handle with a critic, either setting, that records the critic's value of every step's input: rec_value
 // [steps][n], and the log-probabilities as above where rec_logp is not null
 hipError_t actor_value_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value);
+// actor_boot.hip: either kind with a critic on a handle with a time limit (a bookkeeping handle), that records the values as above and
+// V(terminal observation) on time-limit rows: rec_boot [steps][n]; rec_logp / rec_logd may be null
+hipError_t actor_value_boot_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logp, float *rec_value,
+                                           float *rec_boot);
+hipError_t actor_box_boot_rollout_launch(gymnet_vecenv *h, bool records, const StepArgs &a, const RolloutArgs &r, float *rec_logd, float *rec_value,
+                                         float *rec_boot);
 
 }  // namespace gymnet

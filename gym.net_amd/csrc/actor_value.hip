@@ -16,8 +16,9 @@
 // the critic over it and stores output 0 at rec_value + t * n + i.  Loading twice keeps one x[64] live at a time; holding the input
 // across the first network would double it.  after() is the shared push: bit-identical to steps x (act_value, step, push).
 //
-// A Box actor's values inside the fused rollout are actor_box_logd.hip's.  Out of scope: V(terminal observation) for gymnet_gae_device's boot rows (without it a time limit counts as a termination, as documented there), a
-// trunk shared between actor and critic, values carried through the episode memory, and any gradient.
+// A Box actor's values inside the fused rollout are actor_box_logd.hip's; V(terminal observation) for gymnet_gae_device's boot rows is
+// actor_boot.hip's, for both kinds.  Out of scope: a trunk shared between actor and critic, values carried through the episode memory,
+// and any gradient.
 #include "actor_compose_logp.hpp"
 
 namespace gymnet {

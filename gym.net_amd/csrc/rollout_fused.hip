@@ -1,4 +1,4 @@
-// rollout_fused.hip — the fused rollout's host side: gymnet_vecenv_rollout_fused_device and its _ex / _logp / _value / _box_logd siblings, and the
+// rollout_fused.hip — the fused rollout's host side: gymnet_vecenv_rollout_fused_device and its _ex / _logp / _value / _box_logd / _value_boot / _box_boot siblings, and the
 // handle's episode-segment block (h->ep).  Host code only; this unit holds no kernel.  What a call will do — every refusal, the lane width,
 // the segment block, the ticks — is decided by rollout_plan.hpp's pure function; here the facts are gathered, the plan is carried out.
 #include <hip/hip_runtime.h>
@@ -81,6 +81,7 @@ FusedFacts fused_facts(const gymnet_vecenv *h) {
     f.vec = h->lcfg.vec;
     f.actor = actor_facts(h);
     f.has_segments = h->ep.d != nullptr; f.segments = h->ep.seg;
+    f.max_episode_steps = h->cfg.max_episode_steps;
     return f;
 }
 
@@ -156,6 +157,27 @@ int gymnet_vecenv_rollout_fused_box_logd_device(gymnet_vecenv *h, const gymnet_r
     ENTER(h);
     FusedRequest rq{spec};
     rq.rec_value = d_rec_value; rq.rec_logd = d_rec_logd; rq.box_value = d_rec_value != nullptr;
+    return rollout_fused_entered(h, rq);
+    });
+}
+
+// the two calls that also record V(terminal observation) on time-limit rows (actor_boot.hip): without a boot pointer, the calls above
+int gymnet_vecenv_rollout_fused_value_boot_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value, float *d_rec_boot) {
+    if (!d_rec_boot) return gymnet_vecenv_rollout_fused_value_device(h, spec, d_rec_logp, d_rec_value);
+    return guarded([&]() -> int {
+    ENTER(h);
+    FusedRequest rq{spec, 0, false, d_rec_logp, d_rec_value};
+    rq.rec_boot = d_rec_boot;
+    return rollout_fused_entered(h, rq);
+    });
+}
+
+int gymnet_vecenv_rollout_fused_box_boot_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logd, float *d_rec_value, float *d_rec_boot) {
+    if (!d_rec_boot) return gymnet_vecenv_rollout_fused_box_logd_device(h, spec, d_rec_logd, d_rec_value);
+    return guarded([&]() -> int {
+    ENTER(h);
+    FusedRequest rq{spec};
+    rq.rec_value = d_rec_value; rq.rec_logd = d_rec_logd; rq.box_value = true; rq.rec_boot = d_rec_boot;
     return rollout_fused_entered(h, rq);
     });
 }

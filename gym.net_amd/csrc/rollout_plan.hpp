@@ -56,6 +56,7 @@ struct FusedFacts {
     ActorFacts actor;
     bool has_segments = false;     // a segment block is allocated, of ...
     EpisodeSegments segments;      // ... these capacities
+    int32_t max_episode_steps = 0; // the handle's time limit (0: none; > 0 implies EPISODE_STATS, so a bookkeeping handle)
 };
 
 // What the caller asked for; also the one argument the rollout's host code hands down to the launch (actor_rollout_launch reads the two
@@ -64,7 +65,9 @@ struct FusedFacts {
 // run VALIDATE_ACTIONS over the one slice read (gymnet_vecenv_step_repeat_device).  rec_logp / rec_value: where an actor rollout records
 // every step's log-probability / critic value (gymnet_vecenv_rollout_fused_logp_device, _value_device; null: nowhere).  rec_logd: where a
 // Box actor's rollout records every step's log-density, and box_value: rec_value is that call's (gymnet_vecenv_rollout_fused_box_logd_device
-// alone sets it, so that rec_value without rec_logd reaches a Box actor there and nowhere else)
+// alone sets it, so that rec_value without rec_logd reaches a Box actor there and nowhere else; the _box_boot_ call sets it whenever it
+// has a boot pointer).  rec_boot: where an actor rollout records every step's V(terminal observation) on time-limit rows
+// (gymnet_vecenv_rollout_fused_value_boot_device, _box_boot_device, actor_boot.hip; null: nowhere)
 struct FusedRequest {
     const gymnet_rollout_spec *spec = nullptr;
     int32_t held = 0;
@@ -72,6 +75,7 @@ struct FusedRequest {
     float *rec_logp = nullptr, *rec_value = nullptr;
     float *rec_logd = nullptr;
     bool box_value = false;
+    float *rec_boot = nullptr;
 };
 
 struct FusedPlan {
@@ -115,9 +119,20 @@ __attribute__((format(printf, 3, 4))) inline int refuse(char (&text)[512], int s
 
 // gymnet_vecenv_rollout_fused_logp_device's checks of its record pointer (the source, the actor's kind, the alignment) and
 // gymnet_vecenv_rollout_fused_value_device's of its two (the same, and that the Discrete actor has a critic), which run before the
-// rollout's own.  A value pointer makes it the value call: the logp call forwards there only without one
+// rollout's own.  A value pointer makes it the value call: the logp call forwards there only without one.  A boot pointer
+// (gymnet_vecenv_rollout_fused_value_boot_device) needs the value pointer — asked first, it says which call this is —, then every check of
+// the value call applies in its order, then the boot's own: a time limit, the alignment
+constexpr char kBootNeedsValue[] = "d_rec_boot: V(terminal observation) is recorded beside the values: d_rec_value is null";
+constexpr char kBootNeedsLimit[] = "d_rec_boot: this handle has no time limit (max_episode_steps == 0): no episode is truncated and no row needs a boot";
+inline int boot_pointer(const FusedFacts &f, const FusedRequest &rq, char (&text)[512]) {
+    if (!rq.rec_boot) return GYMNET_OK;
+    if (f.max_episode_steps <= 0) return refuse(text, GYMNET_ERR_INVALID_ARG, "%s", kBootNeedsLimit);
+    if (!aligned_to(rq.rec_boot, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_boot must be 4-byte aligned");
+    return GYMNET_OK;
+}
 inline int record_pointers(const FusedFacts &f, const FusedRequest &rq, int32_t action_source, char (&text)[512]) {
     const bool value = rq.rec_value != nullptr;
+    if (rq.rec_boot && !value) return refuse(text, GYMNET_ERR_INVALID_ARG, "%s", kBootNeedsValue);
     if (action_source != GYMNET_ACTIONS_ACTOR)
         return value ? refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value: values are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source)
                      : refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_logp: log-probabilities are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", action_source);
@@ -129,14 +144,16 @@ inline int record_pointers(const FusedFacts &f, const FusedRequest &rq, int32_t 
     if (value && !f.actor.critic) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value: no critic configured (gymnet_vecenv_actor_critic_config)");
     if (!aligned_to(rq.rec_logp, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_logp must be 4-byte aligned");
     if (value && !aligned_to(rq.rec_value, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value must be 4-byte aligned");
-    return GYMNET_OK;
+    return boot_pointer(f, rq, text);
 }
 
 // gymnet_vecenv_rollout_fused_box_logd_device's checks of its two record pointers, which run before the rollout's own: the source, an
-// actor, its kind, its sigma, a critic where values are asked for, the alignments
+// actor, its kind, its sigma, a critic where values are asked for, the alignments; with a boot pointer
+// (gymnet_vecenv_rollout_fused_box_boot_device) around them what record_pointers puts around its own
 inline int box_record_pointers(const FusedFacts &f, const FusedRequest &rq, int32_t action_source, char (&text)[512]) {
     const char *what = rq.rec_logd ? "d_rec_logd" : "d_rec_value";
     const bool value = rq.box_value && rq.rec_value != nullptr;
+    if (rq.rec_boot && !value) return refuse(text, GYMNET_ERR_INVALID_ARG, "%s", kBootNeedsValue);
     if (action_source != GYMNET_ACTIONS_ACTOR)
         return refuse(text, GYMNET_ERR_INVALID_ARG, "%s: log-densities and values are recorded where the actor chooses (action_source GYMNET_ACTIONS_ACTOR), not %d", what, action_source);
     if (f.actor.kind == ActorKind::None) return refuse(text, GYMNET_ERR_INVALID_ARG, kNoActorFormat, actor_config_call(f.box_action));
@@ -147,7 +164,7 @@ inline int box_record_pointers(const FusedFacts &f, const FusedRequest &rq, int3
     if (value && !f.actor.critic) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value: no critic configured (gymnet_vecenv_actor_critic_config)");
     if (!aligned_to(rq.rec_logd, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_logd must be 4-byte aligned");
     if (value && !aligned_to(rq.rec_value, 4)) return refuse(text, GYMNET_ERR_INVALID_ARG, "d_rec_value must be 4-byte aligned");
-    return GYMNET_OK;
+    return boot_pointer(f, rq, text);
 }
 
 inline int plan(const FusedFacts &f, const FusedRequest &rq, FusedPlan &p, char (&text)[512]) {
@@ -159,7 +176,7 @@ inline int plan(const FusedFacts &f, const FusedRequest &rq, FusedPlan &p, char 
     if (rq.rec_logd || rq.box_value) {
         const int s = box_record_pointers(f, rq, sp.action_source, text);
         if (s != GYMNET_OK) return s;
-    } else if (rq.rec_logp || rq.rec_value) {
+    } else if (rq.rec_logp || rq.rec_value || rq.rec_boot) {
         const int s = record_pointers(f, rq, sp.action_source, text);
         if (s != GYMNET_OK) return s;
     }

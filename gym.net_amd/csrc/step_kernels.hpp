@@ -1417,7 +1417,12 @@ struct EpisodeStage { int32_t t[kStageRecords], lane[kStageRecords]; float ret[k
 //           rollout GYMNET_ACTIONS_ACTOR) is called twice per step: choose(t, i0, act) fills the step's actions in place of the ring and
 //           the sampler, and after(t, i0, done, s, o) sees the post-step state once the fused reset and the rec_obs store are through.
 //           Its actions are recorded on every handle, like sampled ones.  Both calls are compiled out for NoHook.
+//           A hook that declares `static constexpr bool BOOTS = true` (actor_boot.hip) is called a third time per step:
+//           terminal(t, i0, done, s, o) sees the step's done bytes (bit 1: truncated) and the post-step state BEFORE the fused reset
+//           overwrites it — the terminal observation of a lane that finished.  Absent or false (every other hook): compiled out.
 struct NoHook { static constexpr bool CHOOSES = false; };
+template <class Hook, class = void> struct hook_boots : std::false_type {};
+template <class Hook> struct hook_boots<Hook, std::enable_if_t<Hook::BOOTS>> : std::true_type {};
 
 //   Rep     frame skip (action_repeat.hip; the contract is gymnet_vecenv_rollout_repeat_device in include/gymnet_amd.h).  NoRepeat: every
 //           trip of the loop is one step, as described above.  HeldAction{R}: a trip is a DECISION — ro.steps counts decisions, t is the
@@ -1692,6 +1697,7 @@ __device__ __forceinline__ void rollout_body(const StepArgsT<typename Env::Real>
                 else store_i32<VEC, true, GUARD>(static_cast<int32_t *>(ro.rec_action) + t * n, i0, n, act);
             }
         }
+        if constexpr (hook_boots<Hook>::value) hook.terminal(t, i0, done, s, o);     // the terminal observation is still in s / o
     scalars_recorded:
         if constexpr (Rep::ON) {           // the reset draw of the SUB-STEP's tick: the one a single step at that tick makes
             const uint64_t tick = tick0 + (uint64_t)t * (uint64_t)rep.R + (uint64_t)sub;

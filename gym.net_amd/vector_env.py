@@ -341,7 +341,8 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_rollout_device(self._h, _ptr(d_actions), int(steps), int(action_stride), int(ring)))
 
     def RolloutFusedDevice(self, d_actions, steps, action_stride=0, ring=1, rec_obs=None, rec_reward=None, rec_done=None, actions="ring",
-                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None, rec_value=None, rec_logd=None):
+                           action_seed=0, action_tick0=0, epsilon=0.0, rec_actions=None, episodes=None, repeat=0, rec_logp=None, rec_value=None, rec_logd=None,
+                           rec_boot=None):
         """`steps` vector steps in ONE kernel launch (state stays in registers); optional device-side rollout
         buffers rec_obs [T][D][N] (of the handle's dtype: float64 for a float64 handle), rec_reward [T][N], rec_done [T][N]
         (ReplayMemory.cs:25-67, batched).  gymnet_vecenv_rollout_fused_ex_device:
@@ -367,9 +368,21 @@ class VectorEnv:
                     rec_value is accepted together with rec_logd, in either shape.
           rec_logd  device float32 [T, N] for the log-density of every action taken, as Actor.Act(logd=) writes it at that step
                     (gymnet_vecenv_rollout_fused_box_logd_device): needs actions="actor" on a Box actor whose policy has sigma > 0, and
-                    repeat = 0."""
+                    repeat = 0.
+          rec_boot  device float32 [T, N] for V(terminal observation) on time-limit rows, as Actor.Boot() writes it after that step
+                    (+0.0 on every other row): what AdvantagesDevice takes as boot= (gymnet_vecenv_rollout_fused_value_boot_device,
+                    _box_boot_device).  Needs rec_value (on a Box actor rec_logd too), actions="actor", repeat = 0 and a handle with
+                    max_episode_steps > 0; final_obs is not needed."""
         repeat = _repeat(repeat)
         value_rows = None
+        if rec_boot is not None:
+            if actions != "actor":
+                raise ValueError(f"rec_boot records the critic's value of terminal observations where the actor chooses: it needs actions=\"actor\", got {actions!r}")
+            if rec_value is None:
+                raise ValueError("rec_boot needs rec_value (V(terminal observation) is recorded beside the values)")
+            if repeat:
+                raise ValueError("rec_boot: the fused actor rollout has no frame skip (repeat must be 0)")
+            _logp_buffer(rec_boot, (_count(steps, "steps", 0), self.NumberOfEnvironments), "rec_boot", self.Device)
         box_logd = rec_logd is not None
         if box_logd:
             actor = getattr(self, "_actor", None)
@@ -432,12 +445,18 @@ class VectorEnv:
         if repeat:
             capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
         elif box_logd:
-            capi.check(self._lib.gymnet_vecenv_rollout_fused_box_logd_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value)))
+            if rec_boot is not None:
+                capi.check(self._lib.gymnet_vecenv_rollout_fused_box_boot_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value), _ptr(rec_boot)))
+            else:
+                capi.check(self._lib.gymnet_vecenv_rollout_fused_box_logd_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value)))
             if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
                 last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
                 capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
         elif rec_value is not None:
-            capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
+            if rec_boot is not None:
+                capi.check(self._lib.gymnet_vecenv_rollout_fused_value_boot_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value), _ptr(rec_boot)))
+            else:
+                capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
             if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
                 last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
                 capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
@@ -1163,6 +1182,22 @@ class Actor:
         capi.check(self._lib.gymnet_vecenv_actor_value_device(self._handle(), _ptr(out)))
         return out
 
+    def Boot(self, out=None):
+        """V(terminal observation) of every lane whose done byte has bit 1 set (a time limit), +0.0 for every other lane, into `out`
+        (device float32 [N]; None: a new torch tensor, returned): one row of AdvantagesDevice's boot= (gymnet_vecenv_actor_boot_device).
+        Call it after a vector step and before Push.  The terminal observation is read from the dense final observations on an
+        auto_reset handle (final_obs=True) and from the current observation otherwise; the handle needs max_episode_steps > 0.  Changes
+        neither the history nor what Push does next."""
+        if out is None:
+            if getattr(self, "CriticWidths", None) is None:
+                raise ValueError("boot needs a critic (SetCritic)")
+            import torch
+            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.float32, device=f"cuda:{self._env.Device}")
+        else:
+            self._value_buffer(out, "out")
+        capi.check(self._lib.gymnet_vecenv_actor_boot_device(self._handle(), _ptr(out)))
+        return out
+
     def Act(self, epsilon=0.0, seed=0, tick=0, out=None, logits=None, logp=None, value=None, logd=None):
         """Every lane's action into `out` (device int32 [N]; None: a torch tensor on the handle's device, returned): the argmax of the
         network's logits over the lane's history, epsilon-greedy as ComposeActionsDevice(greedy, epsilon, seed=seed, tick=tick) would
@@ -1310,9 +1345,10 @@ class Actor:
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
 
-    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None, logd=None):
+    def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None, logd=None, boot=None):
         """Act(epsilon, seed, tick, logp=logp, value=value, logd=logd), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,
-        Push(): one closed-loop decision; returns the device actions taken."""
+        Push(): one closed-loop decision; returns the device actions taken.  boot: an optional device float32 [N] that takes Boot()
+        between the step and the push."""
         repeat = _repeat(repeat)
         if logp is not None and self.IsBox:
             raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
@@ -1320,6 +1356,8 @@ class Actor:
             raise ValueError("Step(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
         if logd is not None and not self.IsBox:
             raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
+        if boot is not None:
+            self._value_buffer(boot, "boot")
         if self._out is None:
             self._out = self._actions()
         self.Act(epsilon, seed, tick, out=self._out, logp=logp, value=value, logd=logd)
@@ -1327,6 +1365,8 @@ class Actor:
             self._env.StepRepeatDevice(self._out, repeat)
         else:
             self._env.StepDevice(self._out)
+        if boot is not None:
+            self.Boot(boot)
         self.Push()
         return self._out
 

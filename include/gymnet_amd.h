@@ -769,8 +769,9 @@ int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollo
  *   need 4-byte alignment only; steps == 0 writes nothing.  One kernel per form serves both exploration settings, with and without
  *   d_rec_logp (csrc/actor_value.hip).  A Box actor's values inside the fused rollout come from
  *   gymnet_vecenv_rollout_fused_box_logd_device (below).
- * Out of scope: V(terminal observation) for gymnet_gae_device's d_boot on time-limit rows (without it a time limit counts as a
- *   termination, as documented there); a trunk shared between actor and critic; values carried through the episode memory; any gradient. */
+ * Out of scope: a trunk shared between actor and critic; values carried through the episode memory; any gradient.  (V(terminal
+ *   observation) for gymnet_gae_device's d_boot on time-limit rows: gymnet_vecenv_actor_boot_device and
+ *   gymnet_vecenv_rollout_fused_value_boot_device, below.) */
 int gymnet_vecenv_actor_critic_config(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
 int gymnet_vecenv_actor_critic_load_device(gymnet_vecenv *h, const float *d_weights, int64_t count);
 int gymnet_vecenv_actor_value_device(gymnet_vecenv *h, float *d_value);
@@ -861,10 +862,43 @@ int gymnet_vecenv_actor_box_get_policy(gymnet_vecenv *h, int32_t *head, int32_t 
  *   here (and only here: the Discrete calls' d_rec_logp / d_rec_value and d_logp keep refusing a Box actor).  steps == 0 writes nothing.
  *   One kernel per form serves every policy and either pointer.
  * Out of scope: the Discrete calls' names lifted for a Box actor; noise before the TANH head (a squashed Gaussian with its Jacobian);
- *   a learned or per-lane sigma; V(terminal observation) for gymnet_gae_device's d_boot rows; logd carried through the episode memory. */
+ *   a learned or per-lane sigma; logd carried through the episode memory.  (V(terminal observation) for gymnet_gae_device's d_boot rows:
+ *   gymnet_vecenv_rollout_fused_box_boot_device, below.) */
 int gymnet_vecenv_actor_box_act_logd_device(gymnet_vecenv *h, float *d_actions, float *d_raw, float *d_logd, float epsilon, uint64_t seed,
                                             uint64_t tick);
 int gymnet_vecenv_rollout_fused_box_logd_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logd, float *d_rec_value);
+/* V(terminal observation) on time-limit rows (additive in ABI 6): the array gymnet_gae_device takes as d_boot, for one step and inside the
+ * fused actor rollout, for a Discrete or a Box actor with a critic on a handle with max_episode_steps > 0.  For a lane with this step's
+ * done byte d, history depth S, ring o_{p-S+1} .. o_p (the input the step's action was chosen from) and terminal observation o_term (the
+ * post-step observation before any reset):
+ *     boot = (d & 2) ? critic(o_{p-S+2}, .., o_p, (float)o_term)[0] : +0.0f
+ *   The critic is the fmaf chain of actor_value_device over the input that call would read had o_term been pushed with a done byte of 0
+ *   (S == 1: o_term alone).  No new arithmetic: tests/_actor_twin.py's forward reproduces it bit for bit up to the sign of a zero.
+ *   d == 3 (terminated and truncated in the same step) gets the value too; gymnet_gae_device lets "terminated" win and ignores it.  A row
+ *   without bit 1 gets +0.0f, never stale memory.
+ * actor_boot_device: d_boot [num_envs] float32 (4-byte aligned), one kernel, ordered on the stream.  Call it after a vector step and
+ *   before actor_push_device: it needs exactly the state a push needs — one vector step since the last actor config, reset or push, on
+ *   the decision clock, so it also follows step_repeat_device — and reads the handle's done bytes and o_term from memory: on an AUTORESET
+ *   handle the dense GYMNET_FLAG_FINAL_OBS rows, otherwise the handle's current observation (cast to float32 as actor_push_device casts:
+ *   float64 handles are served).  It changes nothing else: not the history, not the staleness state, not the tick.
+ *   GYMNET_ERR_INVALID_ARG, nothing written, in this order: no actor, no critic, a null or misaligned pointer, any other step count since
+ *   the last push, max_episode_steps == 0 (nothing can be truncated), an AUTORESET handle without GYMNET_FLAG_FINAL_OBS, or with
+ *   GYMNET_FLAG_COMPACT_RECORDS_ONLY + GYMNET_FLAG_DONE_LIST (the dense rows are not maintained then).
+ * rollout_fused_value_boot_device: with d_rec_boot == NULL it IS gymnet_vecenv_rollout_fused_value_device(h, spec, d_rec_logp,
+ *   d_rec_value).  rollout_fused_box_boot_device: with d_rec_boot == NULL it IS gymnet_vecenv_rollout_fused_box_logd_device(h, spec,
+ *   d_rec_logd, d_rec_value).  Otherwise, for both: d_rec_boot without d_rec_value is GYMNET_ERR_INVALID_ARG; then every check and refusal
+ *   text of the forwarding target applies in its order (so: a critic); then max_episode_steps == 0 and a d_rec_boot that is not 4-byte
+ *   aligned are GYMNET_ERR_INVALID_ARG; then every check of rollout_fused_ex_device.  Nothing is launched on a refusal.  Everything the
+ *   forwarding target leaves is left bit for bit, and in addition d_rec_boot[t * num_envs + lane] is what actor_boot_device would write
+ *   after step t: the call is bit-identical to steps x (act_value_device / box_act_logd_device + actor_value_device, step_device,
+ *   actor_boot_device, actor_push_device).  GYMNET_FLAG_FINAL_OBS is not needed: o_term is taken from the kernel's registers before the
+ *   fused reset.  steps == 0 writes nothing.  A wave in which no lane is truncated skips the evaluation (csrc/actor_boot.hip).
+ * Out of scope: boot carried through the episode memory's rows; the fused actor rollout's frame skip; any gradient. */
+int gymnet_vecenv_actor_boot_device(gymnet_vecenv *h, float *d_boot);
+int gymnet_vecenv_rollout_fused_value_boot_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value,
+                                                  float *d_rec_boot);
+int gymnet_vecenv_rollout_fused_box_boot_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logd, float *d_rec_value,
+                                                float *d_rec_boot);
 
 /* ---- episode bookkeeping (the step AFTER the path: BasePlaySession.cs:58-69) ------------------ */
 /* Lanes that finished in the most recent step (unordered). Needs GYMNET_FLAG_DONE_LIST. */

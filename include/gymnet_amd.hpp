@@ -472,6 +472,21 @@ public:
         spec.struct_size = (uint32_t)sizeof spec;
         check(gymnet_vecenv_rollout_fused_box_logd_device(h_, &spec, d_rec_logd, d_rec_value));
     }
+    // V(terminal observation) of every lane whose done byte has bit 1 set (a time limit), +0 for every other lane, into d_boot float32 [N]:
+    // one row of AdvantagesDevice's d_boot (gymnet_vecenv_actor_boot_device).  After a vector step and before PushActor; needs a critic and
+    // max_episode_steps > 0, and on an auto-reset handle GYMNET_FLAG_FINAL_OBS.  Changes neither the history nor what PushActor does next.
+    void ActorBoot(float *d_boot) { check(gymnet_vecenv_actor_boot_device(h_, d_boot)); }
+    // RolloutFusedValue / RolloutFusedBoxLogd that also record ActorBoot's row after every step into d_rec_boot float32 [T][N]
+    // (gymnet_vecenv_rollout_fused_value_boot_device, _box_boot_device): needs d_rec_value; GYMNET_FLAG_FINAL_OBS is not needed.
+    // d_rec_boot null: the call without it.
+    void RolloutFusedValueBoot(gymnet_rollout_spec spec, float *d_rec_logp, float *d_rec_value, float *d_rec_boot) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_fused_value_boot_device(h_, &spec, d_rec_logp, d_rec_value, d_rec_boot));
+    }
+    void RolloutFusedBoxBoot(gymnet_rollout_spec spec, float *d_rec_logd, float *d_rec_value, float *d_rec_boot) {
+        spec.struct_size = (uint32_t)sizeof spec;
+        check(gymnet_vecenv_rollout_fused_box_boot_device(h_, &spec, d_rec_logd, d_rec_value, d_rec_boot));
+    }
     gymnet_vecenv *handle() const { return h_; }
 
 private:
