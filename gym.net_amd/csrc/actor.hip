@@ -302,7 +302,8 @@ int actor_act_enter(gymnet_vecenv *h, bool want_box, const char *wrong_kind, con
     if (!aligned_to(d_logp, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_logp must be 4-byte aligned");
     if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(h, GYMNET_ERR_INVALID_ARG, "epsilon must be in [0, 1]");
     if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor; after a reset, "
+                    "seed, set_tick or set_state of the handle only a reset of the actor serves)");
     aa = ActorAct{epsilon, seed, (uint64_t)h->cfg.lane_offset, tick};
     return GYMNET_OK;
 }
@@ -401,8 +402,9 @@ int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done) {
     Actor &ac = *h->actor;
     if (!(since(h, ac.last) == StepMark{1, 1}))
         return fail(h, GYMNET_ERR_INVALID_ARG, "an actor push needs exactly one vector step since the last actor config, reset or push (tick %llu -> %llu, "
-                    "%llu step launches); after a reset of the handle call gymnet_vecenv_actor_reset_device", (unsigned long long)ac.last.tick,
-                    (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)since(h, ac.last).launches);   // (both on the decision clock: StepMark)
+                    "%llu step launches, %llu reset / seed / set_tick / set_state calls); after a reset, seed, set_tick or set_state of the handle call "
+                    "gymnet_vecenv_actor_reset_device", (unsigned long long)ac.last.tick, (unsigned long long)(h->tick - h->held_ticks),
+                    (unsigned long long)since(h, ac.last).launches, (unsigned long long)since(h, ac.last).epoch);   // (ticks on the decision clock: StepMark)
     ActorHist hs = ac.hist;
     hs.slot = ring_next(hs.slot, hs.history);
     HIP_TRY(h, launch_actor_push(h->f64, hs, h->d_obs, h->ostride, d_done ? d_done : h->d_done, true, h->stream));

@@ -320,8 +320,8 @@ int gymnet_vecenv_actor_boot_device(gymnet_vecenv *h, float *d_boot) {
     if (!aligned_to(d_boot, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_boot must be 4-byte aligned");
     if (!(since(h, ac.last) == StepMark{1, 1}))
         return fail(h, GYMNET_ERR_INVALID_ARG, "an actor boot needs exactly one vector step since the last actor config, reset or push: call it after the "
-                    "step and before gymnet_vecenv_actor_push_device (%llu steps, %llu step launches)", (unsigned long long)since(h, ac.last).tick,
-                    (unsigned long long)since(h, ac.last).launches);
+                    "step and before gymnet_vecenv_actor_push_device (%llu steps, %llu step launches, %llu reset / seed / set_tick / set_state calls)",
+                    (unsigned long long)since(h, ac.last).tick, (unsigned long long)since(h, ac.last).launches, (unsigned long long)since(h, ac.last).epoch);
     if (h->cfg.max_episode_steps == 0)
         return fail(h, GYMNET_ERR_INVALID_ARG, "this handle has no time limit (max_episode_steps == 0): no episode is truncated and no row needs a boot");
     const void *obs = h->d_obs;

@@ -142,7 +142,8 @@ int value_enter(gymnet_vecenv *h, const float *d_value) {
     if (!d_value) return fail(h, GYMNET_ERR_INVALID_ARG, "d_value is null");
     if (!aligned_to(d_value, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_value must be 4-byte aligned");
     if (!actor_current(h))
-        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor)");
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor; after a reset, "
+                    "seed, set_tick or set_state of the handle only a reset of the actor serves)");
     return GYMNET_OK;
 }
 

@@ -124,6 +124,7 @@ namespace gymnet {
 int seed_handle(gymnet_vecenv *h, uint64_t seed) {
     h->seed = seed;
     h->tick = 0;
+    touch_epoch(h);
     drop_graphs(h);   // the seed is a (frozen) kernel argument of captured launches
     h->d_lane_seed = nullptr;   // back to one key for all lanes (d_lane_seed_buf is kept for the next Seed(int[]))
     recompute_extras(h);
@@ -163,6 +164,7 @@ template <class R>
 static int reset_lanes_typed(gymnet_vecenv *h, const uint8_t *d_mask) {
     HIP_TRY(h, launchers<R>(h).reset(make_reset_args<R>(h, d_mask), h->stream));
     h->tick += 1;
+    touch_epoch(h);
     h->tslot ^= 1;
     return GYMNET_OK;
 }
@@ -539,6 +541,7 @@ int gymnet_vecenv_seed_lanes(gymnet_vecenv *h, const uint64_t *seeds, int64_t co
     h->d_lane_seed = h->d_lane_seed_buf;
     recompute_extras(h);
     h->tick = 0;
+    touch_epoch(h);
     drop_graphs(h);
     return write_tick(h);   // synchronizes: `seeds` is the caller's again on return
     });
@@ -769,6 +772,7 @@ int gymnet_vecenv_set_state(gymnet_vecenv *h, const void *state_soa_v) {
     ENTER(h);
     if (!state_soa_v) return fail(h, GYMNET_ERR_INVALID_ARG, "state_soa is null");
     const size_t row = (size_t)h->n * h->esz;
+    touch_epoch(h);           // (before the first copy: a call that fails half way has changed observations too)
     for (int k = 0; k < h->desc->state_dim; ++k)
         HIP_TRY(h, hipMemcpyAsync(state_row(h, k), static_cast<const char *>(state_soa_v) + (size_t)k * row, row, hipMemcpyHostToDevice, h->stream));
     if (!h->desc->alias)      // (float32 envs only: the float64 handle's observation IS its state)
@@ -812,6 +816,7 @@ int gymnet_vecenv_set_tick(gymnet_vecenv *h, uint64_t tick) {
     return guarded([&]() -> int {
     ENTER(h);
     h->tick = tick;
+    touch_epoch(h);           // whatever the value: the same tick stored again is still no step an attachment saw
     return write_tick(h);
     });
 }
@@ -1120,6 +1125,7 @@ int gymnet_vecenv_set_array(gymnet_vecenv *h, int32_t which, const void *in, int
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the compacted done list / records describe the step that produced the PREVIOUS flags: not part of a restored state
     if (which == GYMNET_ARRAY_DONE) h->last_cparity = -1;
+    if (which == GYMNET_ARRAY_LANE_SEEDS) touch_epoch(h);   // new keys: what seed_lanes does, less the tick
     return GYMNET_OK;
     });
 }

@@ -668,9 +668,10 @@ int check_push_follows(gymnet_vecenv *h, const EpisodeMemory &em, int64_t asked)
     if (asked >= 1 && s == StepMark{(uint64_t)asked, 1}) return GYMNET_OK;
     return fail(h, GYMNET_ERR_INVALID_ARG, "a push needs exactly one vector step since the last memory config, reset or push (tick %llu -> %llu, "
                 "%llu step launches); after a reset of the handle call gymnet_vecenv_memory_reset_device [%llu step(s) seen, %lld asked: a "
-                "launch of several steps goes in through gymnet_vecenv_memory_push_rollout_device]", (unsigned long long)em.last.tick,
+                "launch of several steps goes in through gymnet_vecenv_memory_push_rollout_device; %llu reset / seed / set_tick / set_state calls "
+                "of the handle since: any makes the memory stale]", (unsigned long long)em.last.tick,
                 (unsigned long long)(h->tick - h->held_ticks), (unsigned long long)s.launches, (unsigned long long)s.tick,
-                (long long)asked);   // (both on the decision clock: StepMark)
+                (long long)asked, (unsigned long long)s.epoch);   // (ticks on the decision clock: StepMark)
 }
 
 // gymnet_vecenv_memory_config (chunk 1) and gymnet_vecenv_memory_config_rollout, on a handle the caller has ENTERed
@@ -781,11 +782,14 @@ int gymnet_vecenv_memory_push_rollout_device(gymnet_vecenv *h, int64_t steps, co
         return fail(h, GYMNET_ERR_INVALID_ARG, "d_rec_obs, d_actions, d_rec_reward or d_rec_done is null");
     if (steps < 1 || ring < 1 || action_stride < 0)
         return fail(h, GYMNET_ERR_INVALID_ARG, "bad steps/ring/action_stride (%lld, %lld, %lld)", (long long)steps, (long long)ring, (long long)action_stride);
-    ST_TRY(check_push_follows(h, em, steps));
-    // the launch's engine ticks per decision (frame skip: R sub-steps each): row t ends at tick_before + (t + 1) * R
+    // the launch's engine ticks per decision (frame skip: R sub-steps each): row t ends at tick_before + (t + 1) * R.  One launch moves
+    // the engine tick by steps * R, so any other distance over the right number of decisions means set_tick came in between; that is
+    // said in its own words, ahead of the staleness gate (which refuses every set_tick, this one included)
     const uint64_t ticks = h->tick - em.last_tick;
-    if (ticks < (uint64_t)steps || ticks % (uint64_t)steps != 0)
+    const StepMark moved = since(h, em.last);
+    if (moved.tick == (uint64_t)steps && moved.launches == 1 && (ticks < (uint64_t)steps || ticks % (uint64_t)steps != 0))
         return fail(h, GYMNET_ERR_INVALID_ARG, "the tick moved by %llu over %lld steps: not one launch's", (unsigned long long)ticks, (long long)steps);
+    ST_TRY(check_push_follows(h, em, steps));
     const uint64_t dtick = ticks / (uint64_t)steps;
     MemRolloutArgs p{};
     p.rec_obs = d_rec_obs; p.actions = static_cast<const uint32_t *>(d_actions); p.action_stride = action_stride; p.ring = ring;

@@ -128,6 +128,7 @@ struct gymnet_vecenv {
     gymnet::Actor *actor = nullptr;
     uint64_t seed = 0, tick = 0, lane_steps = 0, step_launches = 0;
     uint64_t held_ticks = 0;       // engine ticks that repeated a decision's action (frame skip: R - 1 per decision), see StepMark
+    uint64_t obs_epoch = 0;        // entered calls that changed observations, keys or the tick outside a step launch (touch_epoch), see StepMark
     int tslot = 0;                 // which half of d_tick2 the NEXT launch reads (it writes the other half)
     int last_cparity = -1;
     bool async_pending = false;
@@ -250,10 +251,18 @@ int release_memory(gymnet_vecenv *h), release_actor(gymnet_vecenv *h);      // e
 // since(h, m) == {1, 1}, "none" is {0, 0}.  A decision is one vector step, or one action held for R sub-steps in one launch
 // (action_repeat.hip): the tick counts DECISION ticks here — engine ticks less h->held_ticks, the R - 1 ticks per decision a frame-skip
 // launch holds its action for — so a fused rollout of R steps still reads {R, 1} and T > 1 held decisions read {T, 1}.
-struct StepMark { uint64_t tick = 0, launches = 0; };
-inline StepMark mark(const gymnet_vecenv *h) { return {h->tick - h->held_ticks, h->step_launches}; }
-inline StepMark since(const gymnet_vecenv *h, StepMark m) { return {h->tick - h->held_ticks - m.tick, h->step_launches - m.launches}; }
-inline bool operator==(StepMark a, StepMark b) { return a.tick == b.tick && a.launches == b.launches; }
+// The tick and the launch count alone can be brought back to a marked position (seed rewinds the tick to 0 and a reset adds one; set_tick
+// stores any value; set_state moves neither), so the mark also carries h->obs_epoch, which only grows: every entered call that changes
+// observations, keys or the tick outside a step launch bumps it (touch_epoch), and since() of a mark taken before such a call has
+// epoch != 0 — equal to neither {1, 1} nor {0, 0}, so every gate refuses until the attachment is reset.
+struct StepMark { uint64_t tick = 0, launches = 0, epoch = 0; };
+inline StepMark mark(const gymnet_vecenv *h) { return {h->tick - h->held_ticks, h->step_launches, h->obs_epoch}; }
+inline StepMark since(const gymnet_vecenv *h, StepMark m) {
+    return {h->tick - h->held_ticks - m.tick, h->step_launches - m.launches, h->obs_epoch - m.epoch};
+}
+inline bool operator==(StepMark a, StepMark b) { return a.tick == b.tick && a.launches == b.launches && a.epoch == b.epoch; }
+// a reset launch, seed, seed_lanes, set_tick, set_state, per-lane keys installed by set_array: the attachments' marks are void
+inline void touch_epoch(gymnet_vecenv *h) { h->obs_epoch += 1; }
 
 // the handle's launcher table, for code typed by its state scalar R
 template <class R>

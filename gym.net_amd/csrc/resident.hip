@@ -139,6 +139,7 @@ int resident_command(gymnet_vecenv *h, uint32_t cmd, const void *actions, void *
     if (done_out) std::memcpy(done_out, h->res.mb->done, (size_t)h->n);
     h->tick = h->res.mb->tick;
     if (cmd == kMailboxStep) h->lane_steps += (uint64_t)h->n;
+    else touch_epoch(h);      // a reset the resident kernel served: new observations outside a step launch
     return GYMNET_OK;
 }
 

@@ -579,7 +579,9 @@ int gymnet_vecenv_pixel_stack_read(gymnet_vecenv *h, void *out, int64_t first_la
  *   the counters.
  * push_device: once after each single vector step; d_actions are the actions that step took (device, [num_envs] of 4 bytes), d_done
  *   NULL means the handle's own done bytes.  Refused unless exactly one vector step ran since the last config, memory reset or push
- *   (a missed push, a multi-step rollout, or a reset of the handle without a memory reset in between).
+ *   (a missed push, a multi-step rollout, or a reset of the handle without a memory reset in between), and after gymnet_vecenv_seed /
+ *   _seed_lanes, set_tick (whatever the value), set_state, per-lane keys through set_array or a restored checkpoint until a memory reset:
+ *   the open episodes describe observations that are gone.  The same holds for push_rollout_device.
  * push_rollout_device: the `steps` recorded rows of ONE step launch, ingested as `steps` single pushes would have been.  Accepted only when
  *   exactly one step launch of `steps` decisions ran since the last config, memory reset or push: any fused rollout
  *   (gymnet_vecenv_rollout_fused_device / _fused_ex_device / _rollout_repeat_device, every action source), or a single step with steps = 1.
@@ -642,11 +644,16 @@ int gymnet_vecenv_memory_dataset_device(gymnet_vecenv *h, int32_t format, int32_
  * load_device: count floats of device weights in the config layout replace the weights, ordered on the stream; the history is kept.
  * Staleness (GYMNET_ERR_INVALID_ARG, nothing written): act unless the history is current — no vector step since the last config,
  *   reset, push or actor rollout; push unless exactly one vector step ran since then.  A fused rollout with GYMNET_ACTIONS_ACTOR leaves
- *   the history current; any other rollout leaves it stale until an actor reset.  Every call that moves the engine tick without
- *   being the one vector step a push expects — a reset of the handle (gymnet_vecenv_reset(_device), _reset_where(_device): their
- *   draws take a tick), gymnet_vecenv_seed / _seed_lanes, set_tick, restoring a checkpoint — also leaves the history stale: call
- *   actor_reset_device after it (the actor tells by the tick and the step-launch count, so act and push are refused after any of them
- *   that moved the tick).  So without AUTORESET the order is step, push, masked reset of the handle, actor_reset_device(mask).  On a GYMNET_FLAG_RESIDENT handle the host-boundary steps the resident kernel serves advance the tick
+ *   the history current; any other rollout leaves it stale until an actor reset.  Every call that changes observations, Philox keys or
+ *   the engine tick without being the one vector step a push expects — a reset of the handle that launches (gymnet_vecenv_reset(_device),
+ *   _reset_where(_device); not the documented no-op of _reset_where with a NULL mask on an AUTORESET handle), gymnet_vecenv_seed /
+ *   _seed_lanes, set_tick (whatever the value), set_state, per-lane keys through set_array, restoring a checkpoint — also leaves the
+ *   history stale: call actor_reset_device after it.  act, push, value, boot and the actor rollout are refused after any of them, also
+ *   where tick and step-launch count read as before (seed then reset; set_tick back to the old value): the handle counts these calls.
+ *   gymnet_vecenv_set_array of any other array (reward, done, the episode arrays, terminal observations, steps_beyond_done) does NOT
+ *   leave the history or the memory stale: a caller who rewrites the done bytes or the reward between a step and its push or boot gets
+ *   the push or boot of what it wrote.
+ *   So without AUTORESET the order is step, push, masked reset of the handle, actor_reset_device(mask).  On a GYMNET_FLAG_RESIDENT handle the host-boundary steps the resident kernel serves advance the tick
  *   but are not step launches, so a push after them is refused: drive an actor there with gymnet_vecenv_step_device (or the fused
  *   actor rollout).
  * Envs: Discrete-action envs (CartPole, MountainCar, Acrobot) on float32 handles, and float64 CartPole handles for config / reset /

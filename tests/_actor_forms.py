@@ -59,7 +59,7 @@ def records(ep):
 
 
 def fused_equals_single_steps(gpu_pkg, name, n, T, kw, records_on, pairs, S=4, eps=0.3, seed=99, tick0=1000, full=False, prepare=None,
-                              capacity=None, env_seed=0xAC7, warm=0):
+                              capacity=None, env_seed=0xAC7, warm=0, per_handle=None, configure=None):
     """Handle a runs T x actor.Step (Act, StepDevice, Push), its twin b one fused actor rollout; asserts that the recorded actions,
     observations, rewards and dones, the state, done bytes, tick, history, episode statistics, the episode records (as sets, return and
     length included), count[1], CartPole's steps_beyond_done and the stepped-after-done counter of a handle without auto-reset, and (full)
@@ -68,16 +68,23 @@ def fused_equals_single_steps(gpu_pkg, name, n, T, kw, records_on, pairs, S=4, e
     from a ring slot other than 0 and from histories whose slots differ.  capacity None: T * n records (at most one per lane and step);
     "exact": as many as the single steps ended; a number below that: the records kept are that many distinct true ones.  Returns what
     handle a saw: dict(actions, obs, reward, done [T, ...], finished [(return, length)] per step, want = the records the steps imply,
-    got / kept / ended = the fused rollout's records and its two counts)."""
+    got / kept / ended = the fused rollout's records and its two counts).
+    per_handle(k), k = 0 for a and 1 for b: what the two handles cannot share, as dict(kwargs=more VectorEnv arguments of that handle
+    alone (caller-owned observation buffers), after=a callable(env) run on it once everything has been compared (the buffers' sentinels)).
+    configure(env, actor) runs on each handle once its actor exists (an exploration setting).  Both default to nothing."""
     import torch
     bookkeeping = bool(kw.get("episode_stats"))
     assert not records_on or bookkeeping
-    with gpu_pkg.VectorEnv(name, n, seed=env_seed, **kw) as a, gpu_pkg.VectorEnv(name, n, seed=env_seed, **kw) as b:
+    own = [per_handle(k) for k in (0, 1)] if per_handle else [{}, {}]
+    with gpu_pkg.VectorEnv(name, n, seed=env_seed, **kw, **own[0].get("kwargs", {})) as a, \
+            gpu_pkg.VectorEnv(name, n, seed=env_seed, **kw, **own[1].get("kwargs", {})) as b:
         a.Reset(); b.Reset()
         if prepare:
             prepare(a); prepare(b)
         O = a.ObsDim
         actor_a, actor_b = a.Actor(pairs, S), b.Actor(pairs, S)
+        if configure:
+            configure(a, actor_a); configure(b, actor_b)
         for t in range(warm):
             actor_a.Step(eps, seed + 1, t); actor_b.Step(eps, seed + 1, t)
         obs_a, rew_a, done_a, act_a, fin_a = [], [], [], [], []
@@ -138,4 +145,7 @@ def fused_equals_single_steps(gpu_pkg, name, n, T, kw, records_on, pairs, S=4, e
             out["stepped_after_done"] = ca["stepped_after_done"]
             if name == "CartPole-v1":
                 out["steps_beyond_done"] = a.GetArray("steps_beyond_done")      # (after the extra step above)
+        for env, o in zip((a, b), own):
+            if o.get("after"):
+                o["after"](env)
         return out
