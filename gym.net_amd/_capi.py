@@ -197,6 +197,7 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_push_device": (C.c_int, [_H, _P]),
     "gymnet_vecenv_actor_act_device": (C.c_int, [_H, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_actor_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "gymnet_vecenv_actor_history_device": (C.c_int, [_H, _P, C.c_int64]),
     "gymnet_vecenv_actor_set_exploration": (C.c_int, [_H, C.c_int32, C.c_float]),
     "gymnet_vecenv_actor_get_exploration": (C.c_int, [_H, _P, _P]),
     "gymnet_vecenv_actor_act_logp_device": (C.c_int, [_H, _P, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
@@ -236,6 +237,8 @@ PROTOTYPES = {
     "gymnet_vecenv_sample_actions": (C.c_int, [_H, _P, C.c_uint64, C.c_uint64]),
     "gymnet_vecenv_compose_actions_device": (C.c_int, [_H, _P, C.c_float, _P, C.c_uint64, C.c_uint64]),
     "gymnet_gae_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P]),
+    "gymnet_rollout_inputs_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64,
+                                               _P, C.c_int64, _P, C.c_int64, _P, C.c_int64]),
     "gymnet_peer_buffer_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(IpcHandle)]),
     "gymnet_peer_buffer_open": (C.c_int, [C.c_int, C.POINTER(IpcHandle), C.POINTER(C.c_void_p)]),
     "gymnet_peer_buffer_close": (C.c_int, [C.c_int, _P]),

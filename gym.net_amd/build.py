@@ -19,8 +19,8 @@ OUT = os.path.join(HERE, "lib", "libgymnet_amd.so")
 SOURCES = ["env_cartpole.hip", "env_cartpole64.hip", "env_acrobot.hip", "env_pendulum.hip", "env_mountaincar.hip",
            "env_mountaincar_continuous.hip", "kernels.hip", "capi.hip", "launch_policy.hip", "resident.hip", "step_graph.hip",
            "group.hip", "render.hip", "pixel_stack.hip", "episode_memory.hip", "actor.hip", "actor_box.hip", "actor_box_policy.hip", "actor_box_logd.hip",
-           "actor_softmax.hip", "actor_logp.hip", "actor_value.hip", "actor_boot.hip", "action_repeat.hip", "advantage.hip", "rollout_fused.hip"]
-DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "cartpole_done_filter.hpp", "cartpole64.hpp", "philox.hpp", "handle.hpp", "launch_policy.hpp", "rollout_plan.hpp", "cartpole_raster.hpp", "actor_net.hpp", "actor_compose_logp.hpp", "actor_box_compose.hpp", "exp_neg.hpp", "log_pos.hpp", "advantage.hpp", "episode_memory_key.hpp",
+           "actor_softmax.hip", "actor_logp.hip", "actor_value.hip", "actor_boot.hip", "action_repeat.hip", "advantage.hip", "rollout_inputs.hip", "rollout_fused.hip"]
+DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "cartpole_done_filter.hpp", "cartpole64.hpp", "philox.hpp", "handle.hpp", "launch_policy.hpp", "rollout_plan.hpp", "cartpole_raster.hpp", "actor_net.hpp", "actor_compose_logp.hpp", "actor_box_compose.hpp", "exp_neg.hpp", "log_pos.hpp", "advantage.hpp", "rollout_inputs.hpp", "episode_memory_key.hpp",
                   os.path.join("..", "..", "include", "gymnet_amd.h")]
 # -fno-slp-vectorize: on gfx950 a packed FP32 instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) occupies the SIMD about
 # as long as the two scalar instructions it replaces (~5 cycles against ~2.4 each in these kernels' instruction mix:

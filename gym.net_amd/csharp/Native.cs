@@ -198,6 +198,7 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_push_device(IntPtr h, IntPtr d_done);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_view(IntPtr h, out IntPtr d_history, out long lane_stride, out int slot);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_history_device(IntPtr h, IntPtr d_out, long out_stride);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_set_exploration(IntPtr h, int explore, float temperature);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_get_exploration(IntPtr h, int* explore, float* temperature);
         // the log-probability of the action taken (a Discrete actor): d_logp float [N], d_rec_logp float [T][N]; IntPtr.Zero forwards to the call without it
@@ -240,6 +241,8 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_sample_actions(IntPtr h, void* actions_out, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_compose_actions_device(IntPtr h, IntPtr d_policy_actions, float epsilon, IntPtr d_actions_out, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_gae_device(int device, IntPtr stream, long steps, long count, long stride, IntPtr d_reward, IntPtr d_done, IntPtr d_value, IntPtr d_last_value, IntPtr d_boot, float gamma, float lambda, IntPtr d_advantage, IntPtr d_return);
+        // the network inputs of a recorded rollout: d_x float [steps][count][history * obs_dim], or [num_rows][..] of the flat rows d_rows (long) names
+        [DllImport(Lib)] public static extern int gymnet_rollout_inputs_device(int device, IntPtr stream, long steps, long count, long stride, int obs_dim, int history, int obs_f64, IntPtr d_rec_obs, IntPtr d_rec_done, IntPtr d_history0, long history0_stride, IntPtr d_rows, long num_rows, IntPtr d_x, long x_row_stride, IntPtr d_history_out, long history_out_stride);
 
         // ---- multi-GPU group (one process, G members)
         [DllImport(Lib)] public static extern int gymnet_group_create(ref GymnetGroupConfig cfg, out IntPtr group);

@@ -354,6 +354,19 @@ namespace Gym.Envs.Amd {
             Native.Check(Native.gymnet_vecenv_device_view(_h, out GymnetDeviceView view));
             Native.Check(Native.gymnet_gae_device(_device, view.stream, steps, NumberOfEnvironments, NumberOfEnvironments, dReward, dDone, dValue, dLastValue, dBoot, gamma, lambda, dAdvantage, dReturn));
         }
+        /// The actor's history as the caller's own float [history][obs_dim][N], oldest first (gymnet_vecenv_actor_history_device): one kernel
+        /// on the handle's stream.  Taken before a fused actor rollout it is the dHistory0 of RolloutInputsDevice.
+        public void ActorHistoryDevice(IntPtr dOut) => Native.Check(Native.gymnet_vecenv_actor_history_device(_h, dOut, NumberOfEnvironments));
+        /// The network inputs a recorded rollout's actions were chosen from (gymnet_rollout_inputs_device: the rule is written out there), on
+        /// the handle's device and stream: ordered after the rollout, no synchronise.  dRecObs [steps][obs_dim][N] in the handle's
+        /// observation type, dRecDone byte [steps][N], dHistory0 float [history][obs_dim][N].  dRows IntPtr.Zero: dX is float
+        /// [steps][N][history * obs_dim]; else dRows long [numRows] flat indices t * N + lane and dX is [numRows][history * obs_dim].
+        /// dHistoryOut (optional) float [history][obs_dim][N]: the history after the last step, the next call's dHistory0.
+        public void RolloutInputsDevice(long steps, int history, IntPtr dRecObs, IntPtr dRecDone, IntPtr dHistory0, IntPtr dX,
+                                        IntPtr dRows = default, long numRows = 0, IntPtr dHistoryOut = default) {
+            Native.Check(Native.gymnet_vecenv_device_view(_h, out GymnetDeviceView view));
+            Native.Check(Native.gymnet_rollout_inputs_device(_device, view.stream, steps, NumberOfEnvironments, NumberOfEnvironments, _obsDim, history, _f64 ? 1 : 0, dRecObs, dRecDone, dHistory0, NumberOfEnvironments, dRows, numRows, dX, (long) history * _obsDim, dHistoryOut, NumberOfEnvironments));
+        }
         /// The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous with w_L = 1; its one output,
         /// clamped to the env's bounds, is the action.  No layers releases it.  LoadActorWeights / ResetActor / PushActor serve both kinds.
         public void ConfigureBoxActor(int history, int[] widths, float[] weights) {

@@ -80,6 +80,17 @@ __global__ __launch_bounds__(256) void actor_act_kernel(const ActorNet net, cons
     actions[i] = compose_one(greedy, net.action_n, coin_threshold(aa.epsilon), aa.seed, aa.lane_offset + (uint64_t)i, aa.tick);
 }
 
+// gymnet_vecenv_actor_history_device: the ring unrolled, oldest first, into the caller's [history][obs_dim][out_stride]
+__global__ __launch_bounds__(256) void actor_history_kernel(const ActorHist hs, float *__restrict__ out, int64_t out_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hs.n) return;
+    for (int32_t s = 0; s < hs.history; ++s) {
+        const int32_t row = ring_row(hs.slot, s, hs.history);
+        for (int32_t k = 0; k < hs.obs_dim; ++k)
+            out[((int64_t)s * hs.obs_dim + k) * out_stride + i] = hs.hist[((int64_t)row * hs.obs_dim + k) * hs.stride + i];
+    }
+}
+
 // flat torch layout (per layer W [wout][win] row-major, then b [wout]) -> the packed block actor_forward reads
 __global__ __launch_bounds__(256) void actor_pack_kernel(const ActorNet net, const float *__restrict__ flat, float *__restrict__ packed,
                                                          int64_t packed_count) {
@@ -431,6 +442,25 @@ int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_
     if (d_history) *d_history = h->actor->hist.hist;
     if (lane_stride) *lane_stride = h->actor->hist.stride;
     if (slot) *slot = h->actor->hist.slot;
+    return GYMNET_OK;
+    });
+}
+
+int gymnet_vecenv_actor_history_device(gymnet_vecenv *h, float *d_out, int64_t out_stride) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    ST_TRY(need_actor(h));
+    if (!d_out) return fail(h, GYMNET_ERR_INVALID_ARG, "d_out is null");
+    if (!aligned_to(d_out, 4)) return fail(h, GYMNET_ERR_INVALID_ARG, "d_out must be 4-byte aligned");
+    if (out_stride < h->n) return fail(h, GYMNET_ERR_INVALID_ARG, "out_stride %lld < num_envs %lld", (long long)out_stride, (long long)h->n);
+    if (!actor_current(h))
+        return fail(h, GYMNET_ERR_INVALID_ARG, "the actor's history is stale: push after every single vector step (or reset the actor; after a reset, "
+                    "seed, set_tick or set_state of the handle only a reset of the actor serves)");
+    const ActorHist &hs = h->actor->hist;
+    if (hs.n > 0) {
+        hipLaunchKernelGGL(actor_history_kernel, lane_grid(hs.n), dim3(256), 0, h->stream, hs, d_out, out_stride);
+        HIP_TRY(h, hipGetLastError());
+    }
     return GYMNET_OK;
     });
 }

@@ -525,6 +525,70 @@ class VectorEnv:
         capi.check(self._lib.gymnet_gae_device(int(dev), C.c_void_p(stream), T, n, n, _ptr(reward), _ptr(done), v_ptr, lv_ptr, _ptr(boot),
                                                float(gamma), float(lam), _ptr(advantage), _ptr(returns)))
 
+    def RolloutInputsDevice(self, rec_obs, rec_done, history0, history, rows=None, out=None, history_out=None):
+        """The network inputs a recorded rollout's actions were chosen from, on the handle's device and stream (gymnet_rollout_inputs_device:
+        the rule is written out there), so it is ordered after the rollout with no synchronise.  For step t of a lane: the lane's last
+        `history` observations before the step, oldest first, clamped to the episode's first — what Actor.Act read.
+          rec_obs    RolloutFusedDevice's rec_obs, [T, obs_dim, n] float32, or float64 (a float64 handle's; each value is rounded to float32)
+          rec_done   its rec_done, uint8 [T, n]
+          history0   float32 [history, obs_dim, n]: Actor.HistoryDevice() taken before the rollout (or a previous call's history_out)
+          rows       None: every row, the result is float32 [T, n, history * obs_dim]; or a device int64 tensor [m] of flat row indices
+                     t * n + lane (a PPO minibatch; duplicates allowed): the result is [m, history * obs_dim].  An index outside
+                     [0, T * n) gives a row of NaN.
+          out        the result's tensor, caller-allocated (contiguous, of exactly that shape); None: a new one.  Returned.
+          history_out  optional float32 [history, obs_dim, n]: the history after the last step, the next call's history0
+        Every argument is checked here, before any native call."""
+        dev, n = self.Device, self.NumberOfEnvironments
+        S = _count(history, "history", 1, 64)
+        if not hasattr(rec_obs, "data_ptr") or str(getattr(rec_obs, "dtype", None)) not in ("torch.float32", "torch.float64"):
+            raise ValueError(f"rec_obs must be a device float32 or float64 tensor [T, obs_dim, {n}], got {getattr(rec_obs, 'dtype', type(rec_obs).__name__)}")
+        f64 = str(rec_obs.dtype) == "torch.float64"
+        shape = tuple(int(v) for v in rec_obs.shape)
+        if len(shape) != 3 or shape[2] != n or shape[1] < 1:
+            raise ValueError(f"rec_obs must have shape (T, obs_dim, {n}), got {shape}")
+        T, O = shape[0], shape[1]
+        if S * O > 64:
+            raise ValueError(f"history * obs_dim = {S * O} is beyond 64, the widest input an actor can have")
+
+        def device_tensor(x, want, dtype, name):
+            if not hasattr(x, "data_ptr") or str(getattr(x, "dtype", None)) != dtype:
+                raise ValueError(f"{name} must be a device {dtype[6:]} tensor of shape {want}, got {getattr(x, 'dtype', type(x).__name__)}")
+            if want is not None and tuple(int(v) for v in x.shape) != tuple(want):
+                raise ValueError(f"{name} must have shape {tuple(want)}, got {tuple(x.shape)}")
+            if not getattr(x, "is_cuda", False) or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous tensor on the handle's device")
+            index = getattr(getattr(x, "device", None), "index", None)
+            if dev is not None and index is not None and int(index) != int(dev):
+                raise ValueError(f"{name} is on device {index}, the handle on {dev}")
+            return x
+        device_tensor(rec_obs, shape, str(rec_obs.dtype), "rec_obs")
+        device_tensor(rec_done, (T, n), "torch.uint8", "rec_done")
+        device_tensor(history0, (S, O, n), "torch.float32", "history0")
+        if history_out is not None:
+            device_tensor(history_out, (S, O, n), "torch.float32", "history_out")
+        m = 0
+        if rows is not None:
+            device_tensor(rows, None, "torch.int64", "rows")
+            if len(rows.shape) != 1:
+                raise ValueError(f"rows must be one-dimensional, got shape {tuple(rows.shape)}")
+            m = int(rows.shape[0])
+        want = (T, n, S * O) if rows is None else (m, S * O)
+        if dev is None:
+            dev = getattr(getattr(rec_obs, "device", None), "index", None)
+            if dev is None:
+                raise ValueError("the handle's device is not known and rec_obs does not name one")
+        if out is None:
+            import torch
+            out = torch.empty(want, dtype=torch.float32, device=f"cuda:{int(dev)}")
+        else:
+            device_tensor(out, want, "torch.float32", "out")
+        if rows is not None and m == 0:
+            return out                                        # the gathered form with no row is a no-op (an empty tensor has no pointer)
+        stream = self.DeviceView().stream
+        capi.check(self._lib.gymnet_rollout_inputs_device(int(dev), C.c_void_p(stream), T, n, n, O, S, 1 if f64 else 0, _ptr(rec_obs), _ptr(rec_done),
+                                                          _ptr(history0), n, _ptr(rows), m, _ptr(out), S * O, _ptr(history_out), n))
+        return out
+
     def SampleActionsDevice(self, d_actions, seed=0, tick=0):
         capi.check(self._lib.gymnet_vecenv_sample_actions_device(self._h, _ptr(d_actions), int(seed), int(tick)))
 
@@ -1344,6 +1408,21 @@ class Actor:
         raw = torch.as_tensor(_View(), device=f"cuda:{env.Device}").cpu().numpy()[:, :, :n]
         order = [(int(slot.value) + 1 + s) % S for s in range(S)]
         return np.ascontiguousarray(raw[order].transpose(2, 0, 1))
+
+    def HistoryDevice(self, out=None):
+        """The history as a torch float32 [history, obs_dim, N] on the device, oldest first (gymnet_vecenv_actor_history_device): a copy
+        on the handle's stream that does not block, and that a later Push or rollout does not overwrite.  Taken before
+        RolloutFusedDevice(actions="actor") it is the history0 of VectorEnv.RolloutInputsDevice.  out: a caller-allocated tensor of
+        that shape; None: a new one.  The history must be current, as for Act."""
+        env = self._env
+        shape = (self.History_, env.ObsDim, env.NumberOfEnvironments)
+        if out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{env.Device}")
+        else:
+            _logp_buffer(out, shape, "out", env.Device)
+        capi.check(self._lib.gymnet_vecenv_actor_history_device(self._handle(), _ptr(out), env.NumberOfEnvironments))
+        return out
 
     def Step(self, epsilon=0.0, seed=0, tick=0, repeat=0, logp=None, value=None, logd=None, boot=None):
         """Act(epsilon, seed, tick, logp=logp, value=value, logd=logd), StepDevice — with repeat > 0 StepRepeatDevice: the action held for repeat + 1 env steps —,

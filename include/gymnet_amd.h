@@ -670,6 +670,14 @@ int gymnet_vecenv_actor_reset_device(gymnet_vecenv *h, const uint8_t *d_mask);
 int gymnet_vecenv_actor_push_device(gymnet_vecenv *h, const uint8_t *d_done);
 int gymnet_vecenv_actor_act_device(gymnet_vecenv *h, int32_t *d_actions, float *d_logits, float epsilon, uint64_t seed, uint64_t tick);
 int gymnet_vecenv_actor_view(gymnet_vecenv *h, float **d_history, int64_t *lane_stride, int32_t *slot);
+/* A snapshot of the history on the device (an added export: the ABI version stays 6): d_out float32 [S][obs_dim][out_stride], unrolled —
+ * row s = 0 is the oldest observation, ring slot (slot + 1 + s) % S of actor_view —, lane i in column i; columns [num_envs, out_stride) are
+ * not touched.  One kernel on the handle's stream, non-blocking: unlike the ring actor_view hands out, the copy is the caller's and a later
+ * push or actor rollout does not overwrite it.  Taken before a fused actor rollout it is the d_history0 of gymnet_rollout_inputs_device.
+ * Serves Discrete and Box actors and float64 handles (the history is float32 everywhere).  GYMNET_ERR_INVALID_ARG, nothing written, where
+ * actor_value_device is refused for the same reason — no actor configured, a stale history, a NULL or not 4-byte aligned pointer — and
+ * for out_stride < num_envs.  No critic is needed.  Changes no state, no staleness mark and no tick. */
+int gymnet_vecenv_actor_history_device(gymnet_vecenv *h, float *d_out, int64_t out_stride);
 /* A Discrete actor's exploration setting (additive in ABI 6): (explore, temperature), read by act_device and by the fused rollout with
  * GYMNET_ACTIONS_ACTOR, which stays bit-identical to steps x (act_device, step_device, actor_push_device) under every setting.
  * The coin is unchanged — a lane explores if and only if word B of the aux stream is <= coin_threshold(epsilon) — and a lane that does
@@ -1018,6 +1026,45 @@ int gymnet_vecenv_compose_actions_device(gymnet_vecenv *h, const int32_t *d_poli
 int gymnet_gae_device(int device, void *stream, int64_t steps, int64_t count, int64_t stride,
                       const float *d_reward, const uint8_t *d_done, const float *d_value, const float *d_last_value,
                       const float *d_boot, float gamma, float lambda, float *d_advantage, float *d_return);
+
+/* ---- the network inputs of a recorded rollout (what the actions were chosen from: the input of an on-policy update) ----------
+ * For step t of a lane: the lane's last S = `history` observations before the step, oldest first, clamped to the episode's first
+ * observation — what gymnet_vecenv_actor_act_device read when it chose the action of step t.  Rebuilt from the rows a fused rollout
+ * recorded (d_rec_obs, d_rec_done) and the history the rollout started from (gymnet_vecenv_actor_history_device, taken before it).
+ * Handle-less like gymnet_gae_device: on `stream` of `device`, stream-ordered, non-blocking, capturable (no allocation, copy or
+ * synchronise).  An added export: the ABI version stays 6.  Pure data movement, specified bit for bit.
+ *     d_rec_obs  [steps][obs_dim][stride] float32, or float64 where obs_f64 != 0 (each value is then rounded to float32, to nearest even);
+ *     d_rec_done [steps][stride] uint8;  stride >= count, lane i is column i;
+ *     d_history0 [history][obs_dim][history0_stride] float32, oldest first: the input of step 0;
+ *     d_x        output rows of history * obs_dim float32, x_row_stride floats apart (>= history * obs_dim; the floats between rows are
+ *                not touched);  d_history_out (optional) [history][obs_dim][history_out_stride]: the history after the last step.
+ * Per lane i: H_0 = column i of d_history0.  For t = 0 .. steps-1, with o = f32(d_rec_obs[t][:, i]) and d = d_rec_done[t][i]:
+ *     the input of step t:  x[t][i][s * obs_dim + k] = H_t[s][k]                       s < history, k < obs_dim
+ *     d != 0 (either bit):  every row of H_{t+1} = o
+ *     otherwise:            H_{t+1}[s] = H_t[s+1] for s < history-1,  H_{t+1}[history-1] = o
+ * This is the rule of gymnet_vecenv_actor_push_device: on a GYMNET_FLAG_AUTORESET handle d_rec_obs[t] is the new episode's first
+ * observation on a done row, on any other handle the terminal one.  d_history_out = H_steps, so a rollout cut into two calls chains
+ * (the second call's d_history0 is the first's d_history_out and its arrays start at row steps_1).
+ * Values are copied as bit patterns: NaN payloads, -0.0 and denormals pass unchanged (float64 observations: one conversion).
+ * Dense form (d_rows NULL; num_rows is not read): steps * count rows, row t * count + i at d_x + (t * count + i) * x_row_stride.
+ * Gathered form (d_rows int64 [num_rows] on the device, flat row indices t * count + i): row d_rows[j] at d_x + j * x_row_stride.
+ *   Duplicates are allowed.  The host cannot see the indices: one outside [0, steps * count) writes a row of canonical NaNs (0x7FC00000),
+ *   and nothing outside row j is touched.  d_history_out is written as in the dense form.  num_rows == 0 is a no-op.
+ * Accepted: obs_dim >= 1, history >= 1, history * obs_dim <= 64 (exactly the inputs an actor can have).  steps == 0 or count == 0 writes
+ * only d_history_out = H_0 (in either form).
+ * GYMNET_ERR_INVALID_ARG (message "rollout_inputs: ...": gymnet_last_error), nothing written: a negative size or stride; obs_dim,
+ * history or their product outside the range; stride, history0_stride or (with d_history_out) history_out_stride below count;
+ * x_row_stride below history * obs_dim where rows are to be written; a NULL d_rec_obs, d_rec_done or d_history0 with steps > 0, a NULL
+ * d_history0 with d_history_out; a NULL d_x where rows are to be written; a pointer that is not 4-byte aligned (d_rec_obs with obs_f64
+ * and d_rows: 8-byte; d_rec_done: any); d_x or d_history_out equal to an input pointer or to each other; sizes whose product leaves an
+ * int64. */
+int gymnet_rollout_inputs_device(int device, void *stream, int64_t steps, int64_t count, int64_t stride,
+                                 int32_t obs_dim, int32_t history, int32_t obs_f64,
+                                 const void *d_rec_obs, const uint8_t *d_rec_done,
+                                 const float *d_history0, int64_t history0_stride,
+                                 const int64_t *d_rows, int64_t num_rows,
+                                 float *d_x, int64_t x_row_stride,
+                                 float *d_history_out, int64_t history_out_stride);
 
 /* ---- multi-GPU group: ONE process (e.g. a C# host) driving G members, one per GPU ----------------------------
  * The reference has no multi-device code; what shards is the independence of VecEnvWrapper's map (VecEnvWrapper.cs:22-24).

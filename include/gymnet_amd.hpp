@@ -439,6 +439,18 @@ public:
                           float *d_advantage, float *d_return, float gamma = 0.99f, float lambda = 0.95f, const float *d_boot = nullptr) {
         check(gymnet_gae_device(device_, DeviceView().stream, steps, n_, n_, d_reward, d_done, d_value, d_last_value, d_boot, gamma, lambda, d_advantage, d_return));
     }
+    // The actor's history as the caller's own float32 [history][obs_dim][N], oldest first (gymnet_vecenv_actor_history_device): one kernel
+    // on the handle's stream.  Taken before a fused actor rollout it is the d_history0 of RolloutInputsDevice.
+    void ActorHistoryDevice(float *d_out) { check(gymnet_vecenv_actor_history_device(h_, d_out, n_)); }
+    // The network inputs a recorded rollout's actions were chosen from (gymnet_rollout_inputs_device: the rule is written out there), on
+    // the handle's device and stream: ordered after the rollout, no synchronise.  d_rec_obs [steps][obs_dim][N] float32 (obs_f64: float64,
+    // a float64 handle's records), d_rec_done uint8 [steps][N], d_history0 float32 [history][obs_dim][N].  d_rows null: d_x is float32
+    // [steps][N][history * obs_dim]; else d_rows int64 [num_rows] flat indices t * N + lane and d_x is [num_rows][history * obs_dim].
+    // d_history_out (optional) float32 [history][obs_dim][N]: the history after the last step, the next call's d_history0.
+    void RolloutInputsDevice(int64_t steps, int32_t history, const void *d_rec_obs, const uint8_t *d_rec_done, const float *d_history0, float *d_x,
+                             const int64_t *d_rows = nullptr, int64_t num_rows = 0, float *d_history_out = nullptr, bool obs_f64 = false) {
+        check(gymnet_rollout_inputs_device(device_, DeviceView().stream, steps, n_, n_, info_.obs_dim, history, obs_f64 ? 1 : 0, d_rec_obs, d_rec_done, d_history0, n_, d_rows, num_rows, d_x, (int64_t)history * info_.obs_dim, d_history_out, n_));
+    }
     // The Box actor (gymnet_vecenv_actor_box_config): the same network on Pendulum / MountainCarContinuous; its one output, clamped to the
     // env's bounds, is the action.  Empty widths release the actor.  LoadActorWeights / ResetActor / PushActor serve both kinds.
     void ConfigureBoxActor(int32_t history, const std::vector<int32_t> &widths, const std::vector<float> &weights) {
