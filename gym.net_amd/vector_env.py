@@ -320,6 +320,14 @@ class VectorEnv:
         return a
 
     # ---- device-resident path (device pointers: ints, ctypes pointers or torch tensors) -------------
+    # The stream contract of every *Device method, of this class and of PixelFrameStack, EpisodeMemory and Actor (include/gymnet_amd.h,
+    # "device-resident path"): all of the call's work is queued on the handle's stream (stream= at construction, or the library's own), in
+    # call order, and the call returns without waiting for it.  With validate_actions=True StepDevice, StepRepeatDevice and RolloutDevice
+    # block (one readback answers Discrete.Contains before any state changes); a call may block the first time it needs storage the handle
+    # allocates on demand (a fused rollout's episode records).  None of them may be captured by the caller into a graph of its own
+    # (torch.cuda.graph): the handle keeps host-side counters a replay would not advance.  The handle-less exports behind AdvantagesDevice
+    # and RolloutInputsDevice (gymnet_gae_device, gymnet_rollout_inputs_device), the gymnet_sample_*_device samplers and
+    # gymnet_push_obs_device keep nothing and are capturable when called through the C ABI with the capturing stream.
     def ResetDevice(self):
         capi.check(self._lib.gymnet_vecenv_reset_device(self._h))
 

@@ -277,7 +277,19 @@ int gymnet_vecenv_host_buffers(gymnet_vecenv *h, void **actions, void **obs, flo
 /* Copy the results of the most recent step/reset again (Step record, Step.cs:8-10). */
 int gymnet_vecenv_read(gymnet_vecenv *h, void *obs_out, float *reward_out, uint8_t *done_out);
 
-/* ---- device-resident path (no PCIe on the hot path; everything stream-ordered, non-blocking) -- */
+/* ---- device-resident path (no PCIe on the hot path; everything stream-ordered, non-blocking) --
+ * The stream contract of every gymnet_vecenv_*_device call, here and in the sections below (render, pixel stack, episode memory, actor,
+ * episode bookkeeping, sampling): all of its work — kernels, memsets, graph replays — is queued on the handle's stream
+ * (gymnet_config.stream, or the library's own), in call order, and the call returns without waiting for it.  Two exceptions, both on the
+ * host side of the call.  On a GYMNET_FLAG_VALIDATE_ACTIONS handle the calls that read the caller's Discrete actions
+ * (gymnet_vecenv_step_device, gymnet_vecenv_step_repeat_device, gymnet_vecenv_rollout_device) block: Discrete.Contains is answered by one
+ * readback before any state changes.  And a call may block the FIRST time it needs storage the handle allocates on demand (the episode-record
+ * segments of gymnet_vecenv_rollout_fused_ex_device and its kin, a graph of gymnet_vecenv_rollout_device that evicts an older one); at
+ * steady state none does.
+ * Handle calls must not be captured by the caller into a graph of its own (hipStreamBeginCapture, torch.cuda.graph): they keep host-side
+ * counters (the tick, the buffer parity, the attachments' marks) that a replay would not advance.  gymnet_vecenv_rollout_device replays
+ * graphs of its own.  The handle-less exports below (gymnet_sample_*_device, gymnet_gae_device, gymnet_rollout_inputs_device,
+ * gymnet_push_obs_device) keep nothing and are capturable. */
 int gymnet_vecenv_reset_device(gymnet_vecenv *h);
 int gymnet_vecenv_reset_where_device(gymnet_vecenv *h, const uint8_t *d_mask);   /* NULL = own done flags */
 /* One vector step = ONE kernel launch.  d_actions: device int32[num_envs] / float32[num_envs]. */
@@ -956,24 +968,29 @@ int gymnet_vecenv_final_obs(gymnet_vecenv *h, void *final_obs_out);
  * the GLOBAL lane only, so a sharded batch samples what the whole batch would (any lane_offset, aligned to a group or not).
  * (Version 1, ABI <= 5: a whole call per lane, counter (L, t), words 0 and 1.  The reference's own stream is NumSharp's
  * un-vendored generator — CartPoleEnv.cs:49, Discrete.cs:17-28 — and is pinned by nothing)
+ * The four handle-less samplers run on `stream` (a hipStream_t of `device`; NULL = default): stream-ordered, non-blocking, capturable (no
+ * allocation, copy or synchronise) — seed, lane_offset and tick are kernel arguments, so a captured call replays the same draw.
  * Discrete.Sample() without mask (Discrete.cs:17-28): start + randint(0, n).  Element i = start + hi32(word A * n). */
 int gymnet_sample_discrete_device(int device, void *stream, int32_t *d_out, int64_t count, int32_t n, int32_t start,
                                   uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* Discrete.Sample(mask) (Discrete.cs:18-26): valid = {k : mask[k] == 1}; none -> start, else start + valid[hi32(word A * |valid|)].
- * d_mask: device uint8, one row of n bytes per element (mask_stride = n) or ONE row shared by all elements (mask_stride = 0). */
+ * d_mask: device uint8, one row of n bytes per element (mask_stride = n) or ONE row shared by all elements (mask_stride = 0).
+ * On `stream`: stream-ordered, non-blocking, capturable (no allocation, copy or synchronise). */
 int gymnet_sample_discrete_masked_device(int device, void *stream, int32_t *d_out, int64_t count, int32_t n, int32_t start,
                                          const uint8_t *d_mask, int64_t mask_stride, uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* Box.Sample() (Box.cs:69-90), the reference's four regimes per element: bounded -> uniform(low, high);
  * low only -> low + Exp(1); high only -> high + Exp(1) (sic, Box.cs:84); unbounded -> Normal(0.5, 1) (sic, Box.cs:82).
  * low = -INFINITY / high = +INFINITY select the regime.  The bounded draw is low + (high - low) * u in float32; where high - low
- * overflows float32 (bounds as wide as CartPole's +-float.MaxValue velocities) it is low * (1 - u) + high * u: finite, inside the bounds. */
+ * overflows float32 (bounds as wide as CartPole's +-float.MaxValue velocities) it is low * (1 - u) + high * u: finite, inside the bounds.
+ * On `stream`: stream-ordered, non-blocking, capturable (no allocation, copy or synchronise). */
 int gymnet_sample_box_device(int device, void *stream, float *d_out, int64_t count, float low, float high,
                              uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* ABI 3.  Box.Sample() for a Box built from Low / High ARRAYS (Box.cs:25-51: `new Box(NDArray low, NDArray high)`), e.g. an
  * observation space whose velocity components are unbounded: `count` samples of `dim` elements each, row-major [count][dim];
  * d_low / d_high are device arrays of `dim` floats and every element picks ITS OWN regime from its own bounds, like the
  * reference's boolean masks (Box.cs:74-85).  gymnet_sample_box_device above is the scalar-bounds form (one pair for every
- * element: the four envs' action spaces); for dim = 1 both draw the same values. */
+ * element: the four envs' action spaces); for dim = 1 both draw the same values.
+ * On `stream`: stream-ordered, non-blocking, capturable (no allocation, copy or synchronise). */
 int gymnet_sample_box_elementwise_device(int device, void *stream, float *d_out, int64_t count, int32_t dim, const float *d_low,
                                          const float *d_high, uint64_t seed, uint64_t lane_offset, uint64_t tick);
 /* ActionSpace.Sample() for every lane of a handle into d_actions (int32 / float32 [num_envs]). */
@@ -1134,7 +1151,9 @@ int gymnet_peer_buffer_open(int device, const gymnet_ipc_handle *handle, void **
 int gymnet_peer_buffer_close(int device, void *d_ptr);                                               /* unmap an opened buffer */
 int gymnet_peer_buffer_destroy(int device, void *d_ptr);                                             /* free a created buffer */
 /* Stores `count` 4-byte words (floats; a float64 slice counts two per element) from d_src into the same-shaped slice d_dst[p] of every peer (p < npeers <= 15), all peers
- * concurrently (one grid row per peer = one xGMI link each), on `stream` (a hipStream_t of `device`; NULL = default). */
+ * concurrently (one grid row per peer = one xGMI link each), on `stream` (a hipStream_t of `device`; NULL = default): stream-ordered,
+ * non-blocking, capturable (no allocation, copy or synchronise) — d_dst is a HOST array, read before the call returns; the peers' addresses
+ * are kernel arguments, frozen by a capture. */
 int gymnet_push_obs_device(int device, void *stream, const float *d_src, float *const *d_dst, int32_t npeers, int64_t count);
 
 #ifdef __cplusplus
