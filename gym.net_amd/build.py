@@ -19,8 +19,9 @@ OUT = os.path.join(HERE, "lib", "libgymnet_amd.so")
 SOURCES = ["env_cartpole.hip", "env_cartpole64.hip", "env_acrobot.hip", "env_pendulum.hip", "env_mountaincar.hip",
            "env_mountaincar_continuous.hip", "kernels.hip", "capi.hip", "launch_policy.hip", "resident.hip", "step_graph.hip",
            "group.hip", "render.hip", "pixel_stack.hip", "episode_memory.hip", "actor.hip", "actor_box.hip", "actor_box_policy.hip", "actor_box_logd.hip",
-           "actor_softmax.hip", "actor_logp.hip", "actor_value.hip", "actor_boot.hip", "action_repeat.hip", "advantage.hip", "rollout_inputs.hip", "rollout_fused.hip"]
-DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "cartpole_done_filter.hpp", "cartpole64.hpp", "philox.hpp", "handle.hpp", "launch_policy.hpp", "rollout_plan.hpp", "cartpole_raster.hpp", "actor_net.hpp", "actor_compose_logp.hpp", "actor_box_compose.hpp", "exp_neg.hpp", "log_pos.hpp", "advantage.hpp", "rollout_inputs.hpp", "episode_memory_key.hpp",
+           "actor_softmax.hip", "actor_logp.hip", "actor_value.hip", "actor_boot.hip", "action_repeat.hip", "advantage.hip", "rollout_inputs.hip", "rollout_fused.hip",
+           "actor_grad.hip"]
+DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "cartpole_done_filter.hpp", "cartpole64.hpp", "philox.hpp", "handle.hpp", "launch_policy.hpp", "rollout_plan.hpp", "cartpole_raster.hpp", "actor_net.hpp", "actor_compose_logp.hpp", "actor_box_compose.hpp", "exp_neg.hpp", "log_pos.hpp", "advantage.hpp", "rollout_inputs.hpp", "episode_memory_key.hpp", "actor_grad.hpp",
                   os.path.join("..", "..", "include", "gymnet_amd.h")]
 # -fno-slp-vectorize: on gfx950 a packed FP32 instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) occupies the SIMD about
 # as long as the two scalar instructions it replaces (~5 cycles against ~2.4 each in these kernels' instruction mix:
@@ -32,6 +33,11 @@ DEPS = SOURCES + ["kernels.hpp", "step_kernels.hpp", "lanes.hpp", "envs.hpp", "c
 # first-use words that way (csrc/kernels.hpp StepKernelFn); a kernel whose first argument is a by-value struct is unaffected.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-amdgpu-kernarg-preload-count=14",
          "-fPIC", "-shared"]
+# actor_grad.hip, the one unit with matrix instructions, is compiled with the packed FP32 instructions taken out of the target outright,
+# not merely never paired by the SLP vectoriser: its listing is free of v_pk_*_f32 by construction, whatever a later pass decides about
+# accumulators that sit in consecutive registers.  (The host pass does not know the feature and says so in a note.)  The other units
+# keep exactly the flags their recorded ISA was built with.
+UNIT_FLAGS = {"actor_grad.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 LIBS = ["-ldl"]          # librccl is dlopen()ed on demand by group.hip, never linked
 # (The library never reads the process environment for its launch policy: gymnet_vecenv_set_launch_policy is the interface.  The
 # GYMNET_BUILD_PROBE_ENV probe build of rounds 1-4 went away in round 5 together with the scripts that needed it.)
@@ -62,7 +68,7 @@ def build(force=False, verbose=False):
     with tempfile.TemporaryDirectory(prefix="gymnet_build_") as tmp:
         def compile_one(src):
             obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
-            cmd = [hipcc()] + compile_flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [hipcc()] + compile_flags + UNIT_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + r.stdout + r.stderr)

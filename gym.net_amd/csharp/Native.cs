@@ -207,6 +207,8 @@ namespace Gym.Envs.Amd {
         // the critic: a second network over the actor's input whose one output is the value; d_value float [N], d_rec_value float [T][N]; IntPtr.Zero forwards
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_config(IntPtr h, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_load_device(IntPtr h, IntPtr d_weights, long count);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logp_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logp);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_target, IntPtr d_grad, IntPtr d_loss, IntPtr d_value);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_device(IntPtr h, IntPtr d_value);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_value_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, IntPtr d_value, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_value_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp, IntPtr d_rec_value);

@@ -344,6 +344,18 @@ namespace Gym.Envs.Amd {
             spec.struct_size = (uint) sizeof(GymnetRolloutSpec);
             Native.Check(Native.gymnet_vecenv_rollout_fused_value_device(_h, ref spec, dRecLogp, dRecValue));
         }
+        /// The gradient of the policy loss over m rows of inputs with respect to the caller's flat weights dWeights (float [count]), into
+        /// dGrad (float [count]; gymnet_vecenv_actor_policy_gradient: the loss is written out there).  dX: rows of widths[0] floats, xStride
+        /// floats apart (RolloutInputs' output); dActions int [m]; dCoef float [m]; dLogpOld float [m] or IntPtr.Zero (coef * logp; else
+        /// PPO's clipped ratio); dLoss (float [1]) and dLogp (float [m]) may be IntPtr.Zero.  A Discrete actor's shape and temperature come
+        /// from the handle, the weights from the caller; ordered on the handle's stream, no synchronise; the optimiser step is the caller's.
+        public void ActorPolicyGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dActions, IntPtr dCoef, IntPtr dGrad,
+                                        IntPtr dLogpOld = default, float clip = 0.2f, float entropyCoef = 0f, IntPtr dLoss = default, IntPtr dLogp = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_policy_gradient(_h, dWeights, count, dX, xStride, m, dActions, dCoef, dLogpOld, clip, entropyCoef, dGrad, dLoss, dLogp));
+        /// The same for the critic's loss (1 / 2m) sum (v_i - target_i)^2 (gymnet_vecenv_actor_value_gradient); dLoss and dValue may be IntPtr.Zero.
+        public void ActorValueGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dTarget, IntPtr dGrad,
+                                       IntPtr dLoss = default, IntPtr dValue = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_value_gradient(_h, dWeights, count, dX, xStride, m, dTarget, dGrad, dLoss, dValue));
         /// GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written
         /// out there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  dReward float [steps][N],
         /// dDone byte [steps][N] (RolloutFused's records); dValue float [steps][N] or IntPtr.Zero (every value 0), dLastValue float [N],

@@ -197,6 +197,8 @@ struct Actor {
     // allocation of its own so that it comes and goes without the actor; critic.layers == 0: none
     DeviceAllocs critic_mem; ActorNet critic{}; int64_t critic_count = 0, critic_packed = 0;
     bool has_critic() const { return critic.layers > 0; }
+    // the block partials of gymnet_vecenv_actor_policy_gradient / _value_gradient (actor_grad.hip), taken from `mem` on the first such call
+    float *grad_scratch = nullptr;
 };
 // what the kernels of actor_box_policy.hip take of it, as a kernel argument
 struct BoxPolicy { int32_t head, explore; float sigma; };

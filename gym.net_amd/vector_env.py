@@ -1401,6 +1401,93 @@ class Actor:
         capi.check(self._lib.gymnet_vecenv_actor_load_device(self._handle(), _ptr(d), self.Count))
         self._env.Sync()
 
+    def _grad_call(self, net, widths, count, x, grad, rows, what):
+        """what PolicyGradient and ValueGradient share, before any native call: the flat device weights of `net` (an nn.Sequential's
+        parameters are concatenated on the handle's stream: no host trip), x's row stride and m, grad, and the per-row tensors checked"""
+        import torch
+        env = self._env
+        dev = f"cuda:{env.Device}"
+        params = None
+        if hasattr(net, "parameters") and not hasattr(net, "data_ptr"):
+            mods = [mod for mod in net.children() if isinstance(mod, torch.nn.Linear)]
+            got = tuple([mods[0].in_features] + [mod.out_features for mod in mods]) if mods else ()
+            if got != tuple(widths) or any(mod.bias is None for mod in mods):
+                raise ValueError(f"{what}: the network's widths {got} (every Linear with a bias) must be the configured {tuple(widths)}")
+            params = [p for mod in mods for p in (mod.weight, mod.bias)]
+            if any(not p.is_cuda or p.dtype != torch.float32 for p in params):
+                raise ValueError(f"{what}: the network's parameters must be float32 on the handle's device")
+            with torch.cuda.stream(torch.cuda.ExternalStream(env.DeviceView().stream or 0, device=dev)):
+                flat = torch.cat([p.detach().reshape(-1) for p in params])
+        else:
+            flat = _logp_buffer(net, (count,), "net", env.Device)
+        if not hasattr(x, "data_ptr") or str(getattr(x, "dtype", None)) != "torch.float32" or not getattr(x, "is_cuda", False) or x.dim() != 2:
+            raise ValueError(f"{what}: x must be a device float32 tensor [m, {widths[0]}]")
+        m = int(x.shape[0])
+        if m < 1 or int(x.shape[1]) != widths[0] or x.stride(1) != 1 or x.stride(0) < widths[0]:
+            raise ValueError(f"{what}: x must be [m >= 1, {widths[0]}] with unit column stride and a row stride >= {widths[0]}, got {tuple(x.shape)} strides {tuple(x.stride())}")
+        for name, t, dtype in rows:
+            if t is None:
+                continue
+            if not hasattr(t, "data_ptr") or str(getattr(t, "dtype", None)) != dtype or not getattr(t, "is_cuda", False) or tuple(t.shape) != (m,) or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous device {dtype[6:]} tensor [{m}]")
+        if grad is None:
+            grad = torch.empty(count, dtype=torch.float32, device=dev)
+        else:
+            _logp_buffer(grad, (count,), "grad", env.Device)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        return flat, params, m, int(x.stride(0)), grad, loss
+
+    @staticmethod
+    def _set_grads(params, grad):
+        """each parameter's .grad = its slice of the flat gradient (views: no copy), for optimizer.step()"""
+        at = 0
+        for p in params or ():
+            p.grad = grad[at:at + p.numel()].view_as(p)
+            at += p.numel()
+
+    def PolicyGradient(self, net, x, actions, coef, logp_old=None, clip=0.2, entropy_coef=0.0, grad=None, logp=None):
+        """The gradient of the policy loss over the minibatch rows x with respect to `net`'s weights, on the handle's stream with no
+        synchronise (gymnet_vecenv_actor_policy_gradient: the loss is written out there).  Returns (grad, loss): device float32 [Count]
+        in the config layout and [1].
+          net       a flat device float32 tensor [Count] in the config layout (what Load takes), or an nn.Sequential of the configured
+                    widths on the device: its parameters are concatenated on the device, and each parameter's .grad is set to its
+                    slice of the result, so optimizer.step() follows as usual.  The weights are the caller's, not the ones the actor
+                    acts with: during PPO epochs the trained network runs ahead.
+          x         device float32 [m, history * obs_dim], rows at any stride: RolloutInputsDevice(rows=idx)
+          actions   device int32 [m];  coef device float32 [m] (returns or advantages)
+          logp_old  None: loss = -mean(coef * logp + entropy_coef * H) (REINFORCE, A2C); else device float32 [m], the rollout's rec_logp
+                    rows: PPO's min(r * coef, clamp(r, 1 - clip, 1 + clip) * coef) in place of coef * logp
+          logp      optional device float32 [m] that receives every row's log-probability under `net` (equal to rec_logp to rounding,
+                    not bit for bit: the matrix instruction sums in another order than Act)
+        The temperature is the actor's stored one (SetExploration).  A Discrete actor only."""
+        if self.IsBox:
+            raise ValueError("PolicyGradient belongs to a Discrete actor; this one chooses Box actions")
+        flat, params, m, stride, grad, loss = self._grad_call(net, self.Widths, self.Count, x, grad, (
+            ("actions", actions, "torch.int32"), ("coef", coef, "torch.float32"), ("logp_old", logp_old, "torch.float32"), ("logp", logp, "torch.float32")),
+            "PolicyGradient")
+        if actions is None or coef is None:
+            raise ValueError("PolicyGradient: actions and coef are required")
+        capi.check(self._lib.gymnet_vecenv_actor_policy_gradient(self._handle(), _ptr(flat), self.Count, _ptr(x), stride, m, _ptr(actions), _ptr(coef),
+                                                                 _ptr(logp_old), float(clip), float(entropy_coef), _ptr(grad), _ptr(loss), _ptr(logp)))
+        self._set_grads(params, grad)
+        return grad, loss
+
+    def ValueGradient(self, net, x, target, grad=None, value=None):
+        """The gradient of the critic's loss mean((v - target)^2) / 2 over the rows x with respect to `net`'s weights
+        (gymnet_vecenv_actor_value_gradient); returns (grad, loss) as PolicyGradient does.  net: a flat device float32 tensor
+        [CriticCount] or an nn.Sequential of the critic's widths; target: device float32 [m] (AdvantagesDevice's returns); value: optional
+        device float32 [m] that receives every row's value under `net`.  Either kind of actor, with a critic (SetCritic)."""
+        if getattr(self, "CriticWidths", None) is None:
+            raise ValueError("ValueGradient needs a critic (SetCritic)")
+        flat, params, m, stride, grad, loss = self._grad_call(net, self.CriticWidths, self.CriticCount, x, grad, (
+            ("target", target, "torch.float32"), ("value", value, "torch.float32")), "ValueGradient")
+        if target is None:
+            raise ValueError("ValueGradient: target is required")
+        capi.check(self._lib.gymnet_vecenv_actor_value_gradient(self._handle(), _ptr(flat), self.CriticCount, _ptr(x), stride, m, _ptr(target),
+                                                                _ptr(grad), _ptr(loss), _ptr(value)))
+        self._set_grads(params, grad)
+        return grad, loss
+
     def History(self):
         """numpy float32 [N, history, obs_dim], oldest first (blocks)."""
         p, stride, slot = C.c_void_p(), C.c_int64(), C.c_int32()

@@ -796,7 +796,7 @@ int gymnet_vecenv_rollout_fused_logp_device(gymnet_vecenv *h, const gymnet_rollo
  *   need 4-byte alignment only; steps == 0 writes nothing.  One kernel per form serves both exploration settings, with and without
  *   d_rec_logp (csrc/actor_value.hip).  A Box actor's values inside the fused rollout come from
  *   gymnet_vecenv_rollout_fused_box_logd_device (below).
- * Out of scope: a trunk shared between actor and critic; values carried through the episode memory; any gradient.  (V(terminal
+ * Out of scope: a trunk shared between actor and critic; values carried through the episode memory; and of the gradient (gymnet_vecenv_actor_policy_gradient, below) what its comment lists.  (V(terminal
  *   observation) for gymnet_gae_device's d_boot on time-limit rows: gymnet_vecenv_actor_boot_device and
  *   gymnet_vecenv_rollout_fused_value_boot_device, below.) */
 int gymnet_vecenv_actor_critic_config(gymnet_vecenv *h, int32_t num_layers, const int32_t *widths, const float *weights, int64_t count);
@@ -920,7 +920,7 @@ int gymnet_vecenv_rollout_fused_box_logd_device(gymnet_vecenv *h, const gymnet_r
  *   after step t: the call is bit-identical to steps x (act_value_device / box_act_logd_device + actor_value_device, step_device,
  *   actor_boot_device, actor_push_device).  GYMNET_FLAG_FINAL_OBS is not needed: o_term is taken from the kernel's registers before the
  *   fused reset.  steps == 0 writes nothing.  A wave in which no lane is truncated skips the evaluation (csrc/actor_boot.hip).
- * Out of scope: boot carried through the episode memory's rows; the fused actor rollout's frame skip; any gradient. */
+ * Out of scope: boot carried through the episode memory's rows; the fused actor rollout's frame skip; and of the gradient (gymnet_vecenv_actor_policy_gradient, below) what its comment lists. */
 int gymnet_vecenv_actor_boot_device(gymnet_vecenv *h, float *d_boot);
 int gymnet_vecenv_rollout_fused_value_boot_device(gymnet_vecenv *h, const gymnet_rollout_spec *spec, float *d_rec_logp, float *d_rec_value,
                                                   float *d_rec_boot);
@@ -1082,6 +1082,48 @@ int gymnet_rollout_inputs_device(int device, void *stream, int64_t steps, int64_
                                  const int64_t *d_rows, int64_t num_rows,
                                  float *d_x, int64_t x_row_stride,
                                  float *d_history_out, int64_t history_out_stride);
+
+/* ---- the gradient of a minibatch loss with respect to a network's weights (the backward half of an on-policy update) ----------
+ * Two handle calls (additive: the ABI version stays 6) that differentiate the configured Discrete actor's policy loss, or the configured
+ * critic's value loss, over m rows of network inputs.  All pointers are device pointers.  From the handle come the SHAPE only — the
+ * actor's widths and its stored temperature tau (gymnet_vecenv_actor_set_exploration) for the policy call, the critic's widths for the
+ * value call —, the stream, and a scratch block.  The WEIGHTS come from the caller: during PPO epochs the trained network runs ahead of
+ * the behaviour weights the actor holds.  The optimiser step stays with the caller.
+ *     d_weights [count]   the current flat parameters in the layout actor_config / actor_load_device take: per layer W [out][in]
+ *                         row-major, then b;  count must be the configured network's;
+ *     d_x                 m rows of widths[0] float32 at a stride of x_stride floats (>= widths[0]; the floats between rows are not
+ *                         read): exactly what gymnet_rollout_inputs_device writes;
+ *     d_grad [count]      the gradient of the loss in the same flat layout; overwritten, not accumulated into;
+ *     d_loss [1], d_logp [m] / d_value [m]   the loss and the per-row forward results; each may be NULL.
+ * Policy loss, float32 throughout, z = net(x_i) the last layer's values:
+ *     a_k    = (z_k - max z) * (1 / tau)         the scaled differences gymnet_vecenv_actor_act_logp_device forms
+ *     logp_i = a_{act_i} - log sum_k exp a_k,    p = softmax(a),    H_i = - sum_k p_k log p_k
+ *     d_logp_old NULL (REINFORCE, A2C):  s_i = coef_i * logp_i
+ *     otherwise (PPO):  r_i = exp(logp_i - logp_old_i),  s_i = min(r_i * coef_i, clamp(r_i, 1 - clip, 1 + clip) * coef_i); the gradient
+ *                       flows through the unclipped term wherever it is the minimum, and ties go to the unclipped term
+ *     loss   = -(1 / m) sum_i (s_i + entropy_coef * H_i)
+ *   An action outside [0, action_n) is never used as an index (the action is selected by compare): it makes that row's logp, the loss
+ *   and the gradient NaN.
+ * Value loss:  v_i = net(x_i)[0],  loss = (1 / 2m) sum_i (v_i - target_i)^2.
+ * The arithmetic: forward and backward run on the FP32 matrix instruction (float32 products and sums, no reduced-precision type), which
+ *   sums in another order than the fmaf chain of the act calls — d_logp / d_value agree with a rollout's rec_logp / rec_value to rounding
+ *   (2^-18 * max(1, |logp|)), not bit for bit.  Rows are dealt to at most 512 workgroups by a rule that reads m alone, every workgroup's
+ *   partial is summed in workgroup order and divided by m, and there is no atomic: the same inputs give the same bits on every call.
+ * Both calls are ordered on the handle's stream and do not synchronise; the first of them on a handle may block, as a call may block the
+ *   FIRST time it needs storage the handle allocates on demand (the scratch, which goes with the actor).  They change nothing else on the
+ *   handle — no tick, no history, no staleness state: a stale history does not refuse them and they do not make one stale.
+ * GYMNET_ERR_INVALID_ARG, nothing touched: no actor; a Box actor (policy call); no critic (value call); count != the configured count;
+ *   m < 1; x_stride < widths[0]; a NULL d_weights, d_x, d_actions, d_coef / d_target or d_grad; clip outside [0, 1) when d_logp_old is
+ *   given; an entropy_coef that is not finite.
+ * Out of scope: the Box actor's Gaussian log-density gradient (tanh head), PPO value clipping, a trunk shared between actor and critic,
+ *   gradients accumulated across calls, the optimiser step, fusing the d_rows gather into the gradient kernel, float64 networks. */
+int gymnet_vecenv_actor_policy_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
+                                        const float *d_x, int64_t x_stride, int64_t m, const int32_t *d_actions, const float *d_coef,
+                                        const float *d_logp_old, float clip, float entropy_coef,
+                                        float *d_grad, float *d_loss, float *d_logp);
+int gymnet_vecenv_actor_value_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
+                                       const float *d_x, int64_t x_stride, int64_t m, const float *d_target,
+                                       float *d_grad, float *d_loss, float *d_value);
 
 /* ---- multi-GPU group: ONE process (e.g. a C# host) driving G members, one per GPU ----------------------------
  * The reference has no multi-device code; what shards is the independence of VecEnvWrapper's map (VecEnvWrapper.cs:22-24).

@@ -430,6 +430,22 @@ public:
         spec.struct_size = (uint32_t)sizeof spec;
         check(gymnet_vecenv_rollout_fused_value_device(h_, &spec, d_rec_logp, d_rec_value));
     }
+    // The gradient of the policy loss over m rows of inputs with respect to the caller's flat weights d_weights [count], into d_grad [count]
+    // (gymnet_vecenv_actor_policy_gradient: the loss is written out there).  d_x: rows of widths[0] float32, x_stride floats apart
+    // (RolloutInputsDevice's output); d_actions int32 [m]; d_coef float32 [m]; d_logp_old float32 [m] or null (null: coef * logp; else
+    // PPO's clipped ratio); d_loss [1] and d_logp [m] may be null.  A Discrete actor's shape and temperature come from the handle, the
+    // weights from the caller; ordered on the handle's stream, no synchronise; the optimiser step is the caller's.
+    void ActorPolicyGradient(const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m, const int32_t *d_actions,
+                             const float *d_coef, float *d_grad, const float *d_logp_old = nullptr, float clip = 0.2f, float entropy_coef = 0.0f,
+                             float *d_loss = nullptr, float *d_logp = nullptr) {
+        check(gymnet_vecenv_actor_policy_gradient(h_, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logp_old, clip, entropy_coef, d_grad,
+                                                  d_loss, d_logp));
+    }
+    // The same for the critic's loss (1 / 2m) sum (v_i - target_i)^2 (gymnet_vecenv_actor_value_gradient); d_loss [1] and d_value [m] may be null.
+    void ActorValueGradient(const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m, const float *d_target,
+                            float *d_grad, float *d_loss = nullptr, float *d_value = nullptr) {
+        check(gymnet_vecenv_actor_value_gradient(h_, d_weights, count, d_x, x_stride, m, d_target, d_grad, d_loss, d_value));
+    }
     // GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written out
     // there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  d_reward float32 [steps][N], d_done
     // uint8 [steps][N] (the fused rollout's records); d_value float32 [steps][N] or null (every value 0), d_last_value float32 [N], d_boot
