@@ -208,6 +208,7 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_config(IntPtr h, int num_layers, int* widths, float* weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_critic_load_device(IntPtr h, IntPtr d_weights, long count);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logp_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logp);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logd_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logd, IntPtr d_grad_log_sigma);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_target, IntPtr d_grad, IntPtr d_loss, IntPtr d_value);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_device(IntPtr h, IntPtr d_value);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_value_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, IntPtr d_value, float epsilon, ulong seed, ulong tick);

@@ -352,6 +352,14 @@ namespace Gym.Envs.Amd {
         public void ActorPolicyGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dActions, IntPtr dCoef, IntPtr dGrad,
                                         IntPtr dLogpOld = default, float clip = 0.2f, float entropyCoef = 0f, IntPtr dLoss = default, IntPtr dLogp = default) =>
             Native.Check(Native.gymnet_vecenv_actor_policy_gradient(_h, dWeights, count, dX, xStride, m, dActions, dCoef, dLogpOld, clip, entropyCoef, dGrad, dLoss, dLogp));
+        /// ActorPolicyGradient for a Box actor's Gaussian policy under the handle's stored head, bounds and sigma
+        /// (gymnet_vecenv_actor_box_policy_gradient: the loss is written out there).  dActions float [m], the actions taken after the clamp;
+        /// dLogdOld float [m] (a rollout's recLogd rows) or IntPtr.Zero; dLogd (float [m]) and dGradLogSigma (float [1]), the loss's
+        /// derivative with respect to ln sigma, may be IntPtr.Zero.
+        public void ActorBoxPolicyGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dActions, IntPtr dCoef, IntPtr dGrad,
+                                           IntPtr dLogdOld = default, float clip = 0.2f, float entropyCoef = 0f, IntPtr dLoss = default, IntPtr dLogd = default,
+                                           IntPtr dGradLogSigma = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_box_policy_gradient(_h, dWeights, count, dX, xStride, m, dActions, dCoef, dLogdOld, clip, entropyCoef, dGrad, dLoss, dLogd, dGradLogSigma));
         /// The same for the critic's loss (1 / 2m) sum (v_i - target_i)^2 (gymnet_vecenv_actor_value_gradient); dLoss and dValue may be IntPtr.Zero.
         public void ActorValueGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dTarget, IntPtr dGrad,
                                        IntPtr dLoss = default, IntPtr dValue = default) =>

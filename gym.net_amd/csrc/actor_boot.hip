@@ -26,7 +26,7 @@
 // x[64] through scratch in every form and on every call, the two hot ones included; code bytes and registers of all 20 forms are in
 // profiles/kernel_resources_actor_boot.txt.
 //
-// Not built: boot carried through the episode memory's rows, frame skip inside the fused actor rollout, and of the gradient: the Box actor's Gaussian log-density gradient (tanh head), PPO value clipping, a shared trunk's gradient, gradients accumulated across calls, the optimiser step, the rows= gather fused into the gradient kernel, float64 networks (the gradient itself: gymnet_vecenv_actor_policy_gradient / _value_gradient, csrc/actor_grad.hip).
+// Not built: boot carried through the episode memory's rows, frame skip inside the fused actor rollout, and of the gradient: a Box actor's action dimensions above 1 and per-lane sigma, PPO value clipping, a shared trunk's gradient, gradients accumulated across calls, the optimiser step, the rows= gather fused into the gradient kernel, float64 networks (the gradient itself: gymnet_vecenv_actor_policy_gradient / _box_policy_gradient / _value_gradient, csrc/actor_grad.hip).
 #include "actor_box_compose.hpp"
 #include "actor_compose_logp.hpp"
 

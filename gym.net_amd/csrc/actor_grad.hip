@@ -1,6 +1,7 @@
 // actor_grad.hip — the gradient of a minibatch loss with respect to an actor's or a critic's flat weights: the one dense contraction on
 // the library's hot path, and so its one use of the matrix cores.  The contract, loss for loss, is gymnet_vecenv_actor_policy_gradient /
-// gymnet_vecenv_actor_value_gradient in include/gymnet_amd.h; what a call is refused for and how its launch is sized is actor_grad.hpp.
+// gymnet_vecenv_actor_box_policy_gradient / gymnet_vecenv_actor_value_gradient in include/gymnet_amd.h; what a call is refused for and
+// how its launch is sized is actor_grad.hpp.
 //
 // The network (at most 4 layers, widths <= 64, <= 8192 parameters) fits in LDS whole, so a workgroup keeps it there and walks row tiles:
 //   work split   256 threads = four waves; G = min(ceil(m / 16), kGradBlocks) workgroups; block b takes the tiles b, b + G, .. of R = 16
@@ -11,23 +12,36 @@
 //   forward      A_{l+1} = relu(A_l W_l^T + b_l) on v_mfma_f32_16x16x4_f32: M = the tile's 16 rows, N = 16 outputs, K = the inputs 4 at
 //                a time; the <= 4 output tiles of a layer go to the four waves; the accumulator starts as the bias.  Every A_l stays in
 //                LDS for the backward pass; the last layer's values land in the dZ tile.
-//   head         one thread per row, plain float32 (exp_neg.hpp, log_pos.hpp): the row's logp / value, its loss term, and dZ_L unscaled
-//                into LDS, as [row][out] and transposed [out][row].
+//   head         one thread per row, plain float32 (exp_neg.hpp, log_pos.hpp; the Box head float64, below): the row's logp / logd / value, its loss term, and dZ_L
+//                unscaled into LDS, as [row][out] and transposed [out][row].  Three heads, one instantiation each (GradHead): the Discrete
+//                softmax policy, the critic's squared error, and the Box actor's Gaussian policy (box_row: clamp or tanh head, the
+//                log-density of actor_box_logd.hip), whose dZ_L has one live column as the critic's and which also sums g (d^2 - 1), the
+//                row's share of d loss / d ln sigma, beside the loss.  The last layer of width 1 runs the plain MFMA path (one live column
+//                of a 16-wide tile in forward, dW and dA): the time is in the hidden layers (docs/ledger.md §46).
+//   refine       Box head only.  (a - g) / sigma^2 carries raw's error into every gradient, and a float32 raw costs more than the whole
+//                of torch's float32 gradient loses.  So the hidden layers run once more in float64 on the vector unit (v_fma_f64, 4 outputs
+//                a thread), from the float32 activations plus a float32 low part kept in the dZ tiles, which are free until the head; the
+//                head's thread forms its row's raw, the head, the log-density and the objective in float64, and the row's loss term, sigma
+//                term and dZ_L are summed in float64 over the block (db_L[0] too) and rounded once.  The backward pass stays float32 MFMA.
+//                This instantiation takes 209 + 88 registers, one wave a SIMD where the others have two, and 3.7 times a float32 head's time at
+//                m = 2^20 (docs/ledger.md §46): what the accuracy costs.
 //   backward     last layer to first: dW_l += dZ_l^T A_l (M = outputs, N = inputs, K = the 16 rows: four instructions a tile) into
 //                accumulators that stay in registers across all of the block's tiles — at most 16 tiles a layer, tile q of a layer with
 //                wave q % 4 in slot q / 4; db_l as column sums by wave 0; dA_l = dZ_l W_l (M = rows, N = inputs, K = outputs) from the
 //                transposed dZ, masked by A_l > 0 into dZ_{l-1}.
 //   reduction    each block writes its partial gradient and loss once, to scratch [b][count + 1]; actor_grad_reduce_kernel sums the G
 //                partials of a parameter in block order (in a double, rounded once), divides by m and writes d_grad / d_loss.  No
-//                atomics: the same inputs give the same bits.
+//                atomics: the same inputs give the same bits.  The Box head's sigma term goes to a [kGradBlocks] tail behind the
+//                partials (their layout is the same for every head), written once per block and summed the same way by one more
+//                thread of the reduce kernel, only where d_grad_log_sigma was given.
 // The FP32 MFMA keeps float32 products and sums (no reduced-precision type anywhere), but sums in another order than actor_forward's fmaf
 // chain: logp / value agree with the rollout's records to rounding, not bit for bit.
 //
-// Out of scope: the Box actor's Gaussian log-density gradient (tanh head), PPO value clipping, a trunk shared between actor and critic,
-// gradients accumulated across calls, the optimiser step, fusing the rows= gather of gymnet_rollout_inputs_device into this kernel, float64
-// networks.
+// Out of scope: action dimensions above 1, a per-lane sigma, noise before the tanh head (a squashed Gaussian), PPO value clipping, a trunk
+// shared between actor and critic, gradients accumulated across calls, the optimiser step, fusing the rows= gather of
+// gymnet_rollout_inputs_device into this kernel, float64 networks.
 #include "actor_grad.hpp"
-#include "actor_net.hpp"
+#include "actor_box_compose.hpp"
 #include "exp_neg.hpp"
 #include "log_pos.hpp"
 
@@ -46,12 +60,16 @@ struct GradArgs {
     const float *w, *x;
     int64_t x_stride, m, tiles;
     const int32_t *actions;                       // policy
-    const float *aux;                             // policy: coef; value: target
-    const float *logp_old;                        // policy, or null
+    const float *aux;                             // policy, box: coef; value: target
+    const float *logp_old;                        // policy: logp_old, box: logd_old; or null
     float clip, entropy_coef, inv_tau;
     int32_t action_n;
-    float *scratch;                               // [blocks][count + 1]
-    float *row_out;                               // logp / value [m], or null
+    float *scratch;                               // [blocks][count + 1]; box: the sigma terms [blocks] at kGradSigmaAt
+    float *row_out;                               // logp / logd / value [m], or null
+    const float *box_actions;                     // box: the actions taken, after the clamp
+    float low, high, entropy;                     // box: the env's bounds; H = ln sigma + (1 + ln 2 pi) / 2
+    int32_t box_head;
+    BoxLogd ld;                                   // box: inv_sigma and c (box_logd_args)
 };
 
 // D += A B for A [16][4], B [4][16], D [16][16]: lane (i, k) = (lane % 16, lane / 16) gives A[i][k] and B[k][i], and holds D[4 * k + r][i] in d[r]
@@ -59,6 +77,23 @@ __device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 d) { return __
 
 // exp(d) for either sign from exp_neg
 __device__ __forceinline__ float exp_any(float d) { return d <= 0.0f ? exp_neg(d) : 1.0f / exp_neg(-d); }
+
+// what both policy heads make of a row's log-probability (or log-density): the row's objective s_i and g = d s_i / d logp
+__device__ __forceinline__ void row_objective(const GradArgs &a, int64_t row, float logp, float &obj, float &g) {
+    const float coef = a.aux[row];
+    if (a.logp_old) {                                                        // wave-uniform
+        const float r = exp_any(logp - a.logp_old[row]);
+        const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
+        const float rc = r < lo ? lo : (r > hi ? hi : r);
+        const float u = r * coef, c = rc * coef;
+        const bool unclipped = u <= c;                                       // ties go to the unclipped term
+        obj = unclipped ? u : c;
+        g = unclipped ? u : 0.0f;
+    } else {
+        obj = coef * logp;
+        g = coef;
+    }
+}
 
 // one row of the policy loss: z -> dz (both [16], zeros beyond action_n), the row's loss term -(s + entropy_coef * H), its logp
 __device__ __forceinline__ float policy_row(const GradArgs &a, int64_t row, float (&z)[16], float &logp) {
@@ -91,20 +126,8 @@ __device__ __forceinline__ float policy_row(const GradArgs &a, int64_t row, floa
     for (int k = 0; k < kActorMaxActions; ++k) {
         if (k < n) ent = ent - (e[k] * inv_run) * (s[k] - lse);
     }
-    const float coef = a.aux[row];
-    float obj, g;                                                            // the row's objective s_i and d s_i / d logp
-    if (a.logp_old) {                                                        // wave-uniform
-        const float r = exp_any(logp - a.logp_old[row]);
-        const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
-        const float rc = r < lo ? lo : (r > hi ? hi : r);
-        const float u = r * coef, c = rc * coef;
-        const bool unclipped = u <= c;                                       // ties go to the unclipped term
-        obj = unclipped ? u : c;
-        g = unclipped ? u : 0.0f;
-    } else {
-        obj = coef * logp;
-        g = coef;
-    }
+    float obj, g;
+    row_objective(a, row, logp, obj, g);
     if (bad) { obj = nan; g = nan; }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -120,7 +143,47 @@ __device__ __forceinline__ float policy_row(const GradArgs &a, int64_t row, floa
     return -(obj + a.entropy_coef * ent);
 }
 
-template <bool POLICY>
+// one row of the Box actor's Gaussian policy loss, in float64 from the refined raw (see `refine` in the header): the row's loss term
+// -(s + entropy_coef * H), its logd (the five lines of actor_box_logd.hip), d loss term / d raw, and the row's share g * (d^2 - 1) of
+// d s / d ln sigma.  A NaN action or raw makes all four NaN: every factor below is a product
+__device__ __forceinline__ double box_row(const GradArgs &a, int64_t row, double raw, double &logd, double &dz, double &dsigma) {
+    const double low = a.low, high = a.high, inv_sigma = a.ld.inv_sigma;
+    double greedy, slope;                                                    // the action after the head, d greedy / d raw
+    if (a.box_head == GYMNET_BOX_HEAD_TANH) {                                // wave-uniform
+        // tanh = (1 - u) / (1 + u) and 1 - tanh^2 = 4 u / (1 + u)^2 with u = exp(-2 |raw|): one exp, and no cancellation where the
+        // head saturates.  A NaN raw makes u, and so everything below, NaN
+        const double u = exp(-2.0 * __builtin_fabs(raw));
+        greedy = 0.5 * (low + high) + 0.5 * (high - low) * __builtin_copysign((1.0 - u) / (1.0 + u), raw);
+        slope = 0.5 * (high - low) * ((4.0 * u) / ((1.0 + u) * (1.0 + u)));
+    } else {
+        greedy = raw < low ? low : (raw > high ? high : raw);
+        slope = (raw >= low ? 1.0 : 0.0) * (raw <= high ? 1.0 : 0.0);        // inclusive at both bounds
+    }
+    const double d = ((double)a.box_actions[row] - greedy) * inv_sigma;
+    logd = __builtin_fma(-0.5 * d, d, (double)a.ld.c);
+    const double coef = a.aux[row];
+    double obj = coef * logd, g = coef;                                      // row_objective, in float64
+    if (a.logp_old) {                                                        // wave-uniform
+        const double r = exp(logd - (double)a.logp_old[row]);
+        const double lo = 1.0 - (double)a.clip, hi = 1.0 + (double)a.clip;
+        const double u = r * coef, c = (r < lo ? lo : (r > hi ? hi : r)) * coef;
+        obj = u <= c ? u : c;                                                // ties go to the unclipped term
+        g = u <= c ? u : 0.0;
+    }
+    if (logd != logd) { obj = logd; g = logd; }                              // (a compare with a NaN chose the clipped term)
+    dz = -(g * ((d * inv_sigma) * slope));
+    dsigma = g * (d * d - 1.0);
+    return -(obj + (double)a.entropy_coef * (double)a.entropy);
+}
+
+// the sum over threads 0 .. 15 of a wave, in one fixed order
+__device__ __forceinline__ double sum16(double v) {
+#pragma unroll
+    for (int s = 8; s > 0; s >>= 1) v = v + __shfl_xor(v, s, 16);
+    return v;
+}
+
+template <int HEAD>                                                         // a GradHead (an int: the listing names the instantiations <0>, <1>, <2>)
 __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
     __shared__ float sW[kGradLdsWeights];
     __shared__ float sA[kL][kR * kP];
@@ -162,6 +225,7 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
         for (int s = 0; s < 4; ++s) acc[l][s] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
     float db[kL] = {0.0f, 0.0f, 0.0f, 0.0f};                                 // wave 0: db_l[tid]
     float loss = 0.0f;                                                       // threads 0 .. 15: the loss terms of row tid of every tile
+    double loss_d = 0.0, sigma_d = 0.0, db_d = 0.0;                          // box, threads 0 .. 15: its loss terms, g * (d^2 - 1) and dZ_L
 
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
         const int64_t row0 = tile * kR;
@@ -203,6 +267,41 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
                 __syncthreads();
             }
         }
+        // ---- box, refine: the hidden layers once more in float64 on the vector unit.  A_{l+1} = hi + lo, hi the float32 value the MFMA
+        // pass left in sA, lo = relu(float64 row) - hi in the dZ tiles, free until the head: lo_{l+1} in sZT for even l, in sZ for odd.
+        // Thread (row li, outputs lk + 4 * wave + 16 * q): activations along a row, four weight rows a wave, no bank conflicts
+        if constexpr (HEAD == kGradBox) {
+#pragma unroll
+            for (int l = 0; l < kL - 1; ++l) {
+                if (l + 1 < net.layers) {                                    // wave-uniform
+                    const int32_t win = net.win[l], wout = net.wout[l];
+                    const float *wl = a.w + net.off[l];
+                    const float *lo_in = (l & 1) ? sZT : sZ;
+                    float *lo_out = (l & 1) ? sZ : sZT;
+                    double z[4];
+                    const float *wrow[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int o = lk + 4 * wave + 16 * q;
+                        z[q] = o < wout ? (double)wl[wout * win + o] : 0.0;
+                        wrow[q] = sW + net.lds[l] + (o < wout ? o : 0) * net.pitch[l];
+                    }
+#pragma unroll 2
+                    for (int j = 0; j < win; ++j) {
+                        double av = (double)sA[l][li * kP + j];
+                        if (l > 0) av = av + (double)lo_in[li * kP + j];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) z[q] = __builtin_fma(av, (double)wrow[q][j], z[q]);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int o = lk + 4 * wave + 16 * q;
+                        if (o < wout) lo_out[li * kP + o] = (float)((z[q] > 0.0 ? z[q] : 0.0) - (double)sA[l + 1][li * kP + o]);
+                    }
+                    __syncthreads();
+                }
+            }
+        }
         // ---- head: one thread per row
         if (tid < kR) {
             const int64_t row = row0 + tid;
@@ -210,12 +309,31 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) z[k] = 0.0f;
             if (row < a.m) {
-                if constexpr (POLICY) {
+                if constexpr (HEAD == kGradPolicy) {
 #pragma unroll
                     for (int k = 0; k < kActorMaxActions; ++k) z[k] = sZ[tid * kP + k];
                     float logp;
                     loss = loss + policy_row(a, row, z, logp);
                     if (a.row_out) a.row_out[row] = logp;
+                } else if constexpr (HEAD == kGradBox) {
+                    // raw = A_L W_L[0] + b_L[0] in float64 from hi + lo; the other threads' lo rows are read before any dZ is written
+                    // below (one wave, in program order)
+                    const int L = net.layers - 1;
+                    const int32_t win = net.win[L];
+                    const float *lo_in = (L & 1) ? sZT : sZ;
+                    double raw = (double)a.w[net.off[L] + net.wout[L] * win];
+#pragma unroll 2
+                    for (int j = 0; j < win; ++j) {
+                        double av = (double)sA[L][tid * kP + j];
+                        if (L > 0) av = av + (double)lo_in[tid * kP + j];
+                        raw = __builtin_fma(av, (double)sW[net.lds[L] + j], raw);
+                    }
+                    double logd, dz, ds;
+                    loss_d = loss_d + box_row(a, row, raw, logd, dz, ds);
+                    sigma_d = sigma_d + ds;
+                    db_d = db_d + dz;
+                    z[0] = (float)dz;
+                    if (a.row_out) a.row_out[row] = (float)logd;
                 } else {
                     const float v = sZ[tid * kP];
                     const float d = v - a.aux[row];
@@ -307,22 +425,46 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
             if (wave == 0 && tid < wout) part[net.off[l] + wout * win + tid] = db[l];
         }
     }
-    if (tid < kR) sLoss[tid] = loss;
-    __syncthreads();
-    if (tid == 0) {
-        float sum = 0.0f;
+    if constexpr (HEAD == kGradBox) {
+        // the block's loss, sigma term and db_L[0] from the rows' float64 terms, each rounded once; thread 0 wrote db_L[0] from the
+        // float32 column sums above and replaces it here
+        if (tid < kR) {
+            const double ls = sum16(loss_d), ss = sum16(sigma_d), bs = sum16(db_d);
+            if (tid == 0) {
+                const int L = net.layers - 1;
+                part[net.count] = (float)ls;
+                part[net.off[L] + net.wout[L] * net.win[L]] = (float)bs;
+                a.scratch[kGradSigmaAt + blockIdx.x] = (float)ss;
+            }
+        }
+    } else {
+        if (tid < kR) sLoss[tid] = loss;
+        __syncthreads();
+        if (tid == 0) {
+            float sum = 0.0f;
 #pragma unroll
-        for (int r = 0; r < kR; ++r) sum = sum + sLoss[r];
-        part[net.count] = sum;
+            for (int r = 0; r < kR; ++r) sum = sum + sLoss[r];
+            part[net.count] = sum;
+        }
     }
 }
 
 // parameter i (i == count: the loss): the blocks' partials in block order, over m.  The running sum is a double, rounded to float32 once at the
-// end: up to 512 partials of either sign summed in float32 lose several units in the last place, more than torch's own float32 gradient
+// end: up to 512 partials of either sign summed in float32 lose several units in the last place, more than torch's own float32 gradient.
+// i == count + 1, where the Box call asked for it (the grid is one thread longer then): the blocks' sigma terms behind the partials, in the
+// same way, as d loss / d ln sigma = -mean(g (d^2 - 1)) - entropy_coef
 __global__ __launch_bounds__(256) void actor_grad_reduce_kernel(const float *__restrict__ scratch, int32_t blocks, int32_t count, double m,
-                                                                float *__restrict__ grad, float *__restrict__ loss) {
+                                                                float *__restrict__ grad, float *__restrict__ loss,
+                                                                float *__restrict__ grad_log_sigma, float entropy_coef) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > count) return;
+    if (i > count) {
+        if (i == count + 1 && grad_log_sigma) {
+            double sum = 0.0;
+            for (int b = 0; b < blocks; ++b) sum = sum + (double)scratch[kGradSigmaAt + b];
+            *grad_log_sigma = (float)(-(sum / m) - (double)entropy_coef);
+        }
+        return;
+    }
     double sum = 0.0;
     for (int b = 0; b < blocks; ++b) sum = sum + (double)scratch[(int64_t)b * (count + 1) + i];
     const float out = (float)(sum / m);
@@ -330,41 +472,55 @@ __global__ __launch_bounds__(256) void actor_grad_reduce_kernel(const float *__r
     else if (loss) *loss = out;
 }
 
-// the handle's scratch: kGradBlocks partials of the largest network, allocated on the first call and gone with the actor
+// the handle's scratch (actor_grad.hpp kGradScratchFloats), allocated on the first call and gone with the actor
 int grad_scratch(gymnet_vecenv *h, float *&scratch) {
     Actor &ac = *h->actor;
     if (!ac.grad_scratch) {
-        ac.grad_scratch = static_cast<float *>(ac.mem.take(sizeof(float) * (size_t)kGradBlocks * (kGradMaxParams + 1)));
+        ac.grad_scratch = static_cast<float *>(ac.mem.take(sizeof(float) * (size_t)kGradScratchFloats));
         if (!ac.grad_scratch) return fail(h, GYMNET_ERR_OOM, "hipMalloc of the gradient scratch failed");
     }
     scratch = ac.grad_scratch;
     return GYMNET_OK;
 }
 
-int actor_gradient(gymnet_vecenv *h, bool policy, const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m,
-                   const int32_t *d_actions, const float *d_aux, const float *d_logp_old, float clip, float entropy_coef, float *d_grad, float *d_loss,
-                   float *d_row_out) {
+constexpr const char *kGradCallName[] = {"actor_value_gradient", "actor_policy_gradient", "actor_box_policy_gradient"};
+
+// d_actions: int32 for the Discrete call, float32 for the Box call; d_grad_log_sigma: the Box call's, or null
+int actor_gradient(gymnet_vecenv *h, GradHead head, const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m,
+                   const void *d_actions, const float *d_aux, const float *d_logp_old, float clip, float entropy_coef, float *d_grad, float *d_loss,
+                   float *d_row_out, float *d_grad_log_sigma) {
     const Actor *ac = h->actor;
+    const bool policy = head != kGradValue;
     const ActorNet *an = !ac ? nullptr : (policy ? &ac->net : &ac->critic);
     const bool has_net = an && an->layers > 0;
-    const ActorGradCall c{policy, ac != nullptr, ac && ac->box, ac && ac->has_critic(), !ac ? 0 : (policy ? ac->count : ac->critic_count),
+    const ActorGradCall c{head, ac != nullptr, ac && ac->box, ac && ac->has_critic(), ac ? ac->sigma : 0.0f, !ac ? 0 : (policy ? ac->count : ac->critic_count),
                           has_net ? an->win[0] : 0, count, x_stride, m, (uintptr_t)d_weights, (uintptr_t)d_x, (uintptr_t)d_actions, (uintptr_t)d_aux,
                           (uintptr_t)d_logp_old, (uintptr_t)d_grad, clip, entropy_coef};
-    if (const char *why = actor_grad_refusal(c)) return fail(h, GYMNET_ERR_INVALID_ARG, "%s: %s", policy ? "actor_policy_gradient" : "actor_value_gradient", why);
+    if (const char *why = actor_grad_refusal(c)) return fail(h, GYMNET_ERR_INVALID_ARG, "%s: %s", kGradCallName[head], why);
     GradArgs a{};
     if (grad_net_shape(a.net, an->layers, an->win, an->wout) > kGradLdsWeights || a.net.count != count)
         return fail(h, GYMNET_ERR_HIP, "actor gradient: the network does not fit the kernel's LDS plan");
     const ActorGradForm f = pick_actor_grad_form(m);
     ST_TRY(grad_scratch(h, a.scratch));
     a.w = d_weights; a.x = d_x; a.x_stride = x_stride; a.m = m; a.tiles = f.tiles;
-    a.actions = d_actions; a.aux = d_aux; a.logp_old = d_logp_old;
+    a.aux = d_aux; a.logp_old = d_logp_old;
     a.clip = clip; a.entropy_coef = entropy_coef; a.inv_tau = ac->inv_tau; a.action_n = an->action_n;
     a.row_out = d_row_out;
-    if (policy) hipLaunchKernelGGL(actor_grad_kernel<true>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL(actor_grad_kernel<false>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
+    if (head == kGradBox) {
+        a.box_actions = static_cast<const float *>(d_actions);
+        a.low = h->desc->action_low; a.high = h->desc->action_high; a.box_head = ac->head;
+        a.ld = box_logd_args(ac->sigma);
+        a.entropy = (float)(std::log((double)ac->sigma) + 1.41893853320467274178);      // ln sigma + (1 + ln 2 pi) / 2
+        hipLaunchKernelGGL(actor_grad_kernel<kGradBox>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
+    } else {
+        a.actions = static_cast<const int32_t *>(d_actions);
+        if (policy) hipLaunchKernelGGL(actor_grad_kernel<kGradPolicy>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
+        else hipLaunchKernelGGL(actor_grad_kernel<kGradValue>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
+    }
     HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(actor_grad_reduce_kernel, dim3((unsigned)((count + 1 + 255) / 256)), dim3(256), 0, h->stream, a.scratch, f.blocks, (int32_t)count,
-                       (double)m, d_grad, d_loss);
+    const int64_t outputs = count + 1 + (d_grad_log_sigma ? 1 : 0);
+    hipLaunchKernelGGL(actor_grad_reduce_kernel, dim3((unsigned)((outputs + 255) / 256)), dim3(256), 0, h->stream, a.scratch, f.blocks, (int32_t)count,
+                       (double)m, d_grad, d_loss, d_grad_log_sigma, entropy_coef);
     HIP_TRY(h, hipGetLastError());
     return GYMNET_OK;
 }
@@ -382,7 +538,7 @@ int gymnet_vecenv_actor_policy_gradient(gymnet_vecenv *h, const float *d_weights
                                         float *d_grad, float *d_loss, float *d_logp) {
     return guarded([&]() -> int {
     ENTER(h);
-    return actor_gradient(h, true, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logp_old, clip, entropy_coef, d_grad, d_loss, d_logp);
+    return actor_gradient(h, kGradPolicy, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logp_old, clip, entropy_coef, d_grad, d_loss, d_logp, nullptr);
     });
 }
 
@@ -390,7 +546,17 @@ int gymnet_vecenv_actor_value_gradient(gymnet_vecenv *h, const float *d_weights,
                                        const float *d_target, float *d_grad, float *d_loss, float *d_value) {
     return guarded([&]() -> int {
     ENTER(h);
-    return actor_gradient(h, false, d_weights, count, d_x, x_stride, m, nullptr, d_target, nullptr, 0.0f, 0.0f, d_grad, d_loss, d_value);
+    return actor_gradient(h, kGradValue, d_weights, count, d_x, x_stride, m, nullptr, d_target, nullptr, 0.0f, 0.0f, d_grad, d_loss, d_value, nullptr);
+    });
+}
+
+int gymnet_vecenv_actor_box_policy_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m,
+                                            const float *d_actions, const float *d_coef, const float *d_logd_old, float clip, float entropy_coef,
+                                            float *d_grad, float *d_loss, float *d_logd, float *d_grad_log_sigma) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    return actor_gradient(h, kGradBox, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logd_old, clip, entropy_coef, d_grad, d_loss, d_logd,
+                          d_grad_log_sigma);
     });
 }
 

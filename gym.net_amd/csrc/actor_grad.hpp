@@ -1,9 +1,12 @@
-// actor_grad.hpp — what a call to gymnet_vecenv_actor_policy_gradient / gymnet_vecenv_actor_value_gradient is refused for, how its rows are
-// dealt to the workgroups of actor_grad.hip, and where that kernel keeps a network in LDS.  Host-only and pure as rollout_inputs.hpp is: no
-// HIP type, no global, nothing read but the arguments.  This is the only place that refuses a call or sizes its launch.
+// actor_grad.hpp — what a call to gymnet_vecenv_actor_policy_gradient / gymnet_vecenv_actor_box_policy_gradient /
+// gymnet_vecenv_actor_value_gradient is refused for, how its rows are dealt to the workgroups of actor_grad.hip, and where that kernel
+// keeps a network in LDS.  Host-only and pure as rollout_inputs.hpp is: no HIP type, no global, nothing read but the arguments
+// (rollout_plan.hpp, as pure, for the sigmas a log-density is defined for).  This is the only place that refuses a call or sizes its launch.
 #pragma once
 #include <cmath>
 #include <cstdint>
+
+#include "rollout_plan.hpp"
 
 namespace gymnet {
 
@@ -33,28 +36,42 @@ constexpr int kGradLdsWeights = 9472;
 constexpr int kGradLdsBytes = 4 * (kGradLdsWeights + kGradMaxLayers * kGradRows * kGradPitch + kGradRows * kGradPitch + kGradMaxWidth * kGradPitchT + kGradRows);
 static_assert(kGradLdsBytes <= 64 * 1024, "two workgroups share a CU");
 
+// the scratch of a handle in floats: kGradBlocks partials [count + 1] of the largest network, then — behind them, so that the partial
+// layout is the same for every head — one float per block for the Box head's sigma term
+constexpr int64_t kGradSigmaAt = (int64_t)kGradBlocks * (kGradMaxParams + 1);
+constexpr int64_t kGradScratchFloats = kGradSigmaAt + kGradBlocks;
+
+// the loss a call differentiates, and so the head the main kernel is instantiated for
+enum GradHead : int { kGradValue = 0, kGradPolicy = 1, kGradBox = 2 };        // _value_gradient, _policy_gradient, _box_policy_gradient
+
 struct ActorGradCall {                            // the call's arguments and what it reads of the handle; pointers as integers, 0 = NULL
-    bool policy;                                  // gymnet_vecenv_actor_policy_gradient, else _value_gradient
+    GradHead head;
     bool has_actor, box, has_critic;
+    float sigma;                                  // a Box actor's stored sigma (read by the Box call only)
     int64_t configured_count;                     // the parameters of the network the call differentiates
     int32_t win0;                                 // its input width
     int64_t count, x_stride, m;
-    uintptr_t weights, x, actions, aux, logp_old, grad;      // aux: d_coef / d_target
+    uintptr_t weights, x, actions, aux, logp_old, grad;      // aux: d_coef / d_target; logp_old: d_logp_old / d_logd_old
     float clip, entropy_coef;
 };
 
 // NULL: the call is accepted; else why it is refused (GYMNET_ERR_INVALID_ARG).  Nothing is written by a refused call.
 inline const char *actor_grad_refusal(const ActorGradCall &c) {
+    const bool policy = c.head != kGradValue;     // either policy call
     if (!c.has_actor) return "no actor configured";
-    if (c.policy && c.box) return "the policy gradient serves a Discrete actor; this handle's actor chooses Box actions";
-    if (!c.policy && !c.has_critic) return "no critic configured (gymnet_vecenv_actor_critic_config)";
-    if (c.count != c.configured_count) return c.policy ? "count != the actor's parameters" : "count != the critic's parameters";
+    if (c.head == kGradPolicy && c.box) return "the policy gradient serves a Discrete actor; this handle's actor chooses Box actions";
+    if (c.head == kGradBox && !c.box) return "the Box policy gradient serves a Box actor; this handle's actor chooses Discrete actions";
+    if (c.head == kGradBox && !box_sigma_ok(c.sigma))
+        return "the log-density needs a policy with sigma > 0 and a finite 1 / sigma (gymnet_vecenv_actor_box_set_policy)";
+    if (!policy && !c.has_critic) return "no critic configured (gymnet_vecenv_actor_critic_config)";
+    if (c.count != c.configured_count) return policy ? "count != the actor's parameters" : "count != the critic's parameters";
     if (c.m < 1) return "m < 1";
     if (c.x_stride < c.win0) return "x_stride < widths[0]";
-    if (!c.weights || !c.x || !c.aux || !c.grad || (c.policy && !c.actions))
-        return c.policy ? "d_weights / d_x / d_actions / d_coef / d_grad is null" : "d_weights / d_x / d_target / d_grad is null";
-    if (c.policy && c.logp_old && !(c.clip >= 0.0f && c.clip < 1.0f)) return "clip must be in [0, 1) with d_logp_old";
-    if (c.policy && !std::isfinite(c.entropy_coef)) return "entropy_coef is not finite";
+    if (!c.weights || !c.x || !c.aux || !c.grad || (policy && !c.actions))
+        return policy ? "d_weights / d_x / d_actions / d_coef / d_grad is null" : "d_weights / d_x / d_target / d_grad is null";
+    if (policy && c.logp_old && !(c.clip >= 0.0f && c.clip < 1.0f))
+        return c.head == kGradBox ? "clip must be in [0, 1) with d_logd_old" : "clip must be in [0, 1) with d_logp_old";
+    if (policy && !std::isfinite(c.entropy_coef)) return "entropy_coef is not finite";
     if (c.m > INT64_MAX / 4 / c.x_stride) return "m x x_stride overflows";
     return nullptr;
 }

@@ -18,7 +18,7 @@
 //
 // A Box actor's values inside the fused rollout are actor_box_logd.hip's; V(terminal observation) for gymnet_gae_device's boot rows is
 // actor_boot.hip's, for both kinds.  Out of scope: a trunk shared between actor and critic, values carried through the episode memory,
-// and of the gradient: the Box actor's Gaussian log-density gradient (tanh head), PPO value clipping, a shared trunk's gradient, gradients accumulated across calls, the optimiser step, the rows= gather fused into the gradient kernel, float64 networks (the gradient itself: gymnet_vecenv_actor_policy_gradient / _value_gradient, csrc/actor_grad.hip).
+// and of the gradient: a Box actor's action dimensions above 1 and per-lane sigma, PPO value clipping, a shared trunk's gradient, gradients accumulated across calls, the optimiser step, the rows= gather fused into the gradient kernel, float64 networks (the gradient itself: gymnet_vecenv_actor_policy_gradient / _box_policy_gradient / _value_gradient, csrc/actor_grad.hip).
 #include "actor_compose_logp.hpp"
 
 namespace gymnet {

@@ -1472,6 +1472,31 @@ class Actor:
         self._set_grads(params, grad)
         return grad, loss
 
+    def BoxPolicyGradient(self, net, x, actions, coef, logd_old=None, clip=0.2, entropy_coef=0.0, grad=None, logd=None, grad_log_sigma=None):
+        """PolicyGradient for a Box actor: the gradient of the Gaussian policy loss under the stored head, bounds and sigma (SetPolicy;
+        gymnet_vecenv_actor_box_policy_gradient: the loss is written out there).  net, x, coef, clip, entropy_coef, grad and the result
+        (grad, loss) as PolicyGradient's.
+          actions         device float32 [m]: the actions taken, after the clamp (a rollout's rec_actions rows)
+          logd_old        None, or device float32 [m]: the rollout's rec_logd rows (PPO's clipped ratio)
+          logd            optional device float32 [m] that receives every row's log-density under `net` (rec_logd to rounding)
+          grad_log_sigma  optional device float32 [1] that receives d loss / d ln sigma; the caller applies its own rule to ln sigma and
+                          stores the result with SetPolicy
+        A Box actor only, with sigma > 0."""
+        if not self.IsBox:
+            raise ValueError("BoxPolicyGradient belongs to a Box actor; this one chooses Discrete actions")
+        flat, params, m, stride, grad, loss = self._grad_call(net, self.Widths, self.Count, x, grad, (
+            ("actions", actions, "torch.float32"), ("coef", coef, "torch.float32"), ("logd_old", logd_old, "torch.float32"), ("logd", logd, "torch.float32")),
+            "BoxPolicyGradient")
+        if actions is None or coef is None:
+            raise ValueError("BoxPolicyGradient: actions and coef are required")
+        if grad_log_sigma is not None:
+            _logp_buffer(grad_log_sigma, (1,), "grad_log_sigma", self._env.Device)
+        capi.check(self._lib.gymnet_vecenv_actor_box_policy_gradient(self._handle(), _ptr(flat), self.Count, _ptr(x), stride, m, _ptr(actions), _ptr(coef),
+                                                                     _ptr(logd_old), float(clip), float(entropy_coef), _ptr(grad), _ptr(loss), _ptr(logd),
+                                                                     _ptr(grad_log_sigma)))
+        self._set_grads(params, grad)
+        return grad, loss
+
     def ValueGradient(self, net, x, target, grad=None, value=None):
         """The gradient of the critic's loss mean((v - target)^2) / 2 over the rows x with respect to `net`'s weights
         (gymnet_vecenv_actor_value_gradient); returns (grad, loss) as PolicyGradient does.  net: a flat device float32 tensor

@@ -1115,8 +1115,8 @@ int gymnet_rollout_inputs_device(int device, void *stream, int64_t steps, int64_
  * GYMNET_ERR_INVALID_ARG, nothing touched: no actor; a Box actor (policy call); no critic (value call); count != the configured count;
  *   m < 1; x_stride < widths[0]; a NULL d_weights, d_x, d_actions, d_coef / d_target or d_grad; clip outside [0, 1) when d_logp_old is
  *   given; an entropy_coef that is not finite.
- * Out of scope: the Box actor's Gaussian log-density gradient (tanh head), PPO value clipping, a trunk shared between actor and critic,
- *   gradients accumulated across calls, the optimiser step, fusing the d_rows gather into the gradient kernel, float64 networks. */
+ * Out of scope: PPO value clipping, a trunk shared between actor and critic, gradients accumulated across calls, the optimiser step,
+ *   fusing the d_rows gather into the gradient kernel, float64 networks; and of the Box call below what its comment lists. */
 int gymnet_vecenv_actor_policy_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
                                         const float *d_x, int64_t x_stride, int64_t m, const int32_t *d_actions, const float *d_coef,
                                         const float *d_logp_old, float clip, float entropy_coef,
@@ -1124,6 +1124,38 @@ int gymnet_vecenv_actor_policy_gradient(gymnet_vecenv *h, const float *d_weights
 int gymnet_vecenv_actor_value_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
                                        const float *d_x, int64_t x_stride, int64_t m, const float *d_target,
                                        float *d_grad, float *d_loss, float *d_value);
+
+/* The policy call for a Box actor (additive: the ABI version stays 6): the gradient of the Gaussian policy loss of the configured Box
+ * actor over m rows, and its derivative with respect to ln sigma.  Everything said above of the policy call holds — the weights are the
+ * caller's, the shape comes from the handle, the same kernel, order and determinism, d_grad / d_loss as there, d_logd as d_logp — with
+ * these differences.  From the handle come also the stored head and sigma (gymnet_vecenv_actor_box_set_policy) and the env's action
+ * bounds low / high.  d_actions float32 [m]: the actions taken, after the clamp (a rollout's d_rec_actions rows).  d_logd_old float32 [m]
+ * or NULL: a rollout's d_rec_logd rows.  d_grad_log_sigma float32 [1], may be NULL: with it NULL every other output keeps its bits.
+ * The loss, float32 throughout, raw = net(x_i)[0], inv_sigma and c the two constants gymnet_vecenv_actor_box_act_logd_device forms on the
+ * host (1 / sigma and -ln sigma - ln(2 pi) / 2, computed in float64 and rounded once):
+ *     head CLAMP:  g = clamp(raw, low, high),        dg/draw = 1 where low <= raw <= high (both bounds included), else 0
+ *     head TANH:   g = mid + half * tanhf(raw),      dg/draw = half * (1 - tanh(raw)^2),    mid = (low + high) / 2, half = (high - low) / 2
+ *                  (the derivative is evaluated as half * 4 u / (1 + u)^2, u = exp(-2 |raw|): the same function without the cancellation)
+ *     d = (a_i - g) * inv_sigma,   logd_i = fmaf(-0.5f * d, d, c)         the log-density that call records: d_logd equals d_rec_logd
+ *                                                                        to rounding (2^-18 * max(1, |logd|))
+ *     dlogd/dg = d * inv_sigma,    dlogd/dln sigma = d * d - 1
+ *     s_i as the policy call forms it with logd_i for logp_i and d_logd_old for d_logp_old;  w_i = ds_i/dlogd_i
+ *     H = ln sigma + (1 + ln 2 pi) / 2                                    the same for every row: no part of the weight gradient
+ *     loss = -(1 / m) sum_i s_i - entropy_coef * H
+ *     *d_grad_log_sigma = -(1 / m) sum_i w_i * (d_i * d_i - 1) - entropy_coef        (block partials summed in block order in a double)
+ *   These are the float32 functions differentiated.  The kernel evaluates raw and the lines above in float64 from the float32 inputs
+ *   (a second forward pass on the vector unit) and rounds each output once: (a - g) / sigma^2 carries an error of g into every gradient,
+ *   and a float32 raw alone cost more than torch's float32 gradient loses.  The backward pass is float32, as the policy call's.
+ *   A NaN action or a NaN raw makes that row's logd, the loss, the gradient and *d_grad_log_sigma NaN; no other row's logd changes.
+ *   The caller applies its own rule to ln sigma and stores the result with gymnet_vecenv_actor_box_set_policy.
+ * GYMNET_ERR_INVALID_ARG, nothing touched: everything the policy call refuses (with d_logd_old for d_logp_old), but a Discrete actor
+ *   where that call refuses a Box actor; a stored sigma that is not > 0 with a finite float32 reciprocal (a fresh actor's is 0).
+ * Out of scope: action dimensions above 1, a per-lane sigma, noise before the tanh head (a squashed Gaussian with its Jacobian), and
+ *   what the policy call lists. */
+int gymnet_vecenv_actor_box_policy_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
+                                            const float *d_x, int64_t x_stride, int64_t m, const float *d_actions, const float *d_coef,
+                                            const float *d_logd_old, float clip, float entropy_coef,
+                                            float *d_grad, float *d_loss, float *d_logd, float *d_grad_log_sigma);
 
 /* ---- multi-GPU group: ONE process (e.g. a C# host) driving G members, one per GPU ----------------------------
  * The reference has no multi-device code; what shards is the independence of VecEnvWrapper's map (VecEnvWrapper.cs:22-24).

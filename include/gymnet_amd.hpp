@@ -441,6 +441,16 @@ public:
         check(gymnet_vecenv_actor_policy_gradient(h_, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logp_old, clip, entropy_coef, d_grad,
                                                   d_loss, d_logp));
     }
+    // ActorPolicyGradient for a Box actor's Gaussian policy under the handle's stored head, bounds and sigma
+    // (gymnet_vecenv_actor_box_policy_gradient: the loss is written out there).  d_actions float32 [m], the actions taken after the clamp;
+    // d_logd_old float32 [m] (a rollout's rec_logd rows) or null; d_logd [m] and d_grad_log_sigma [1], the loss's derivative with respect
+    // to ln sigma, may be null.
+    void ActorBoxPolicyGradient(const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m, const float *d_actions,
+                                const float *d_coef, float *d_grad, const float *d_logd_old = nullptr, float clip = 0.2f, float entropy_coef = 0.0f,
+                                float *d_loss = nullptr, float *d_logd = nullptr, float *d_grad_log_sigma = nullptr) {
+        check(gymnet_vecenv_actor_box_policy_gradient(h_, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logd_old, clip, entropy_coef, d_grad,
+                                                      d_loss, d_logd, d_grad_log_sigma));
+    }
     // The same for the critic's loss (1 / 2m) sum (v_i - target_i)^2 (gymnet_vecenv_actor_value_gradient); d_loss [1] and d_value [m] may be null.
     void ActorValueGradient(const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m, const float *d_target,
                             float *d_grad, float *d_loss = nullptr, float *d_value = nullptr) {
