@@ -210,6 +210,8 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logp_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logp);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logd_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logd, IntPtr d_grad_log_sigma);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_target, IntPtr d_grad, IntPtr d_loss, IntPtr d_value);
+        // the optimiser step: rule 0 SGD (p0 momentum), 1 AdaDelta (p0 rho), 2 Adam (p0, p1 betas); d_state float [2][count], the caller's, zeros when fresh
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_apply_gradient(IntPtr h, int rule, IntPtr d_weights, long count, IntPtr d_grad, IntPtr d_state, long step, float lr, float p0, float p1, float eps, float weight_decay, float max_grad_norm, IntPtr d_norm);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_device(IntPtr h, IntPtr d_value);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_act_value_device(IntPtr h, IntPtr d_actions, IntPtr d_logits, IntPtr d_logp, IntPtr d_value, float epsilon, ulong seed, ulong tick);
         [DllImport(Lib)] public static extern int gymnet_vecenv_rollout_fused_value_device(IntPtr h, ref GymnetRolloutSpec spec, IntPtr d_rec_logp, IntPtr d_rec_value);

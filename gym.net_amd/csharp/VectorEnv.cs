@@ -364,6 +364,16 @@ namespace Gym.Envs.Amd {
         public void ActorValueGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dTarget, IntPtr dGrad,
                                        IntPtr dLoss = default, IntPtr dValue = default) =>
             Native.Check(Native.gymnet_vecenv_actor_value_gradient(_h, dWeights, count, dX, xStride, m, dTarget, dGrad, dLoss, dValue));
+        public const int OptSgd = 0, OptAdaDelta = 1, OptAdam = 2;             // GYMNET_OPT_*
+        /// The optimiser step on the device: dWeights (float [count], count at most 8192, any flat vector — the policy's, the critic's, the
+        /// one-element ln sigma) updated in place from dGrad under rule (OptSgd: p0 momentum; OptAdaDelta: p0 rho; OptAdam: p0, p1 the
+        /// betas, step >= 1 the update's number), after clipping the gradient's 2-norm to maxGradNorm (0: no clipping) and adding
+        /// weightDecay * w (gymnet_vecenv_actor_apply_gradient: the arithmetic is written out there; it is torch.optim's).  dState
+        /// (float [2][count]) is the caller's, zeros for a fresh optimiser, IntPtr.Zero for SGD without momentum; dNorm (float [1]) receives
+        /// the norm before clipping and may be IntPtr.Zero.  One launch, ordered on the handle's stream, no synchronise, no allocation.
+        public void ActorApplyGradient(int rule, IntPtr dWeights, long count, IntPtr dGrad, IntPtr dState, long step, float lr, float p0, float p1,
+                                       float eps, float weightDecay = 0f, float maxGradNorm = 0f, IntPtr dNorm = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_apply_gradient(_h, rule, dWeights, count, dGrad, dState, step, lr, p0, p1, eps, weightDecay, maxGradNorm, dNorm));
         /// GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written
         /// out there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  dReward float [steps][N],
         /// dDone byte [steps][N] (RolloutFused's records); dValue float [steps][N] or IntPtr.Zero (every value 0), dLastValue float [N],

@@ -1513,6 +1513,64 @@ class Actor:
         self._set_grads(params, grad)
         return grad, loss
 
+    _RULES = {"sgd": 0, "adadelta": 1, "adam": 2}                      # GYMNET_OPT_*
+
+    def ApplyGradient(self, net, grad, state, rule="adam", step=1, lr=None, momentum=0.0, rho=0.9, betas=(0.9, 0.999), eps=None, weight_decay=0.0,
+                      max_grad_norm=0.0, norm=None):
+        """The optimiser step on the device: one update of `net` from `grad` in one launch on the handle's stream, no synchronise
+        (gymnet_vecenv_actor_apply_gradient: the arithmetic is written out there; it is clip_grad_norm_ followed by torch.optim's SGD,
+        Adadelta or Adam).  Returns net.
+          net            a flat device float32 tensor of at most 8192 elements, updated in place: the policy's or the critic's flat weights,
+                         or the one-element ln sigma against BoxPolicyGradient's grad_log_sigma (its length is not tied to the actor's);
+                         or an nn.Sequential on the device: its parameters are concatenated on the handle's stream as PolicyGradient does,
+                         stepped, and copied back into the module's parameters, still on the stream
+          grad           device float32 of net's length, read only; None with an nn.Sequential: the concatenation of its parameters' .grad
+          state          device float32 [2, count] made with torch.zeros and kept by the caller from update to update (SGD uses row 0, and
+                         with momentum 0 takes None)
+          rule           "sgd" (momentum), "adadelta" (rho) or "adam" (betas; step >= 1 is the number of this update).  lr and eps default
+                         to torch's for the rule: 1e-3 / -, 1.0 / 1e-6, 1e-3 / 1e-8
+          weight_decay   coupled (L2) decay;  max_grad_norm  0: no clipping
+          norm           optional device float32 [1] that receives the gradient's 2-norm before clipping"""
+        import torch
+        env = self._env
+        if rule not in self._RULES:
+            raise ValueError(f"ApplyGradient: rule must be one of {tuple(self._RULES)}, got {rule!r}")
+        lr = {"sgd": 1e-3, "adadelta": 1.0, "adam": 1e-3}[rule] if lr is None else lr
+        eps = {"sgd": 0.0, "adadelta": 1e-6, "adam": 1e-8}[rule] if eps is None else eps
+        p0, p1 = {"sgd": (momentum, 0.0), "adadelta": (rho, 0.0), "adam": tuple(betas)}[rule]
+        params, handle_stream = None, torch.cuda.ExternalStream(env.DeviceView().stream or 0, device=f"cuda:{env.Device}")
+        if hasattr(net, "parameters") and not hasattr(net, "data_ptr"):
+            params = list(net.parameters())
+            if not params or any(not p.is_cuda or p.dtype != torch.float32 for p in params):
+                raise ValueError("ApplyGradient: the network's parameters must be float32 on the handle's device")
+            if grad is None and any(p.grad is None for p in params):
+                raise ValueError("ApplyGradient: grad is None and a parameter has no .grad")
+            with torch.cuda.stream(handle_stream):
+                flat = torch.cat([p.detach().reshape(-1) for p in params])
+                if grad is None:
+                    grad = torch.cat([p.grad.reshape(-1) for p in params])
+        else:
+            flat = net
+            if not hasattr(flat, "data_ptr") or getattr(flat, "dim", lambda: 0)() != 1:
+                raise ValueError("ApplyGradient: net must be a flat device float32 tensor or an nn.Sequential")
+        count = int(flat.shape[0])
+        _logp_buffer(flat, (count,), "net", env.Device)
+        _logp_buffer(grad, (count,), "grad", env.Device)
+        if state is not None:
+            _logp_buffer(state, (2, count), "state", env.Device)
+        if norm is not None:
+            _logp_buffer(norm, (1,), "norm", env.Device)
+        capi.check(self._lib.gymnet_vecenv_actor_apply_gradient(self._handle(), self._RULES[rule], _ptr(flat), count, _ptr(grad), _ptr(state), int(step),
+                                                                float(lr), float(p0), float(p1), float(eps), float(weight_decay), float(max_grad_norm),
+                                                                _ptr(norm)))
+        if params is not None:
+            with torch.cuda.stream(handle_stream), torch.no_grad():
+                at = 0
+                for p in params:
+                    p.copy_(flat[at:at + p.numel()].view_as(p))
+                    at += p.numel()
+        return net
+
     def History(self):
         """numpy float32 [N, history, obs_dim], oldest first (blocks)."""
         p, stride, slot = C.c_void_p(), C.c_int64(), C.c_int32()

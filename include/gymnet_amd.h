@@ -1088,7 +1088,7 @@ int gymnet_rollout_inputs_device(int device, void *stream, int64_t steps, int64_
  * critic's value loss, over m rows of network inputs.  All pointers are device pointers.  From the handle come the SHAPE only — the
  * actor's widths and its stored temperature tau (gymnet_vecenv_actor_set_exploration) for the policy call, the critic's widths for the
  * value call —, the stream, and a scratch block.  The WEIGHTS come from the caller: during PPO epochs the trained network runs ahead of
- * the behaviour weights the actor holds.  The optimiser step stays with the caller.
+ * the behaviour weights the actor holds.  The optimiser step is a call of its own (gymnet_vecenv_actor_apply_gradient, below).
  *     d_weights [count]   the current flat parameters in the layout actor_config / actor_load_device take: per layer W [out][in]
  *                         row-major, then b;  count must be the configured network's;
  *     d_x                 m rows of widths[0] float32 at a stride of x_stride floats (>= widths[0]; the floats between rows are not
@@ -1115,8 +1115,8 @@ int gymnet_rollout_inputs_device(int device, void *stream, int64_t steps, int64_
  * GYMNET_ERR_INVALID_ARG, nothing touched: no actor; a Box actor (policy call); no critic (value call); count != the configured count;
  *   m < 1; x_stride < widths[0]; a NULL d_weights, d_x, d_actions, d_coef / d_target or d_grad; clip outside [0, 1) when d_logp_old is
  *   given; an entropy_coef that is not finite.
- * Out of scope: PPO value clipping, a trunk shared between actor and critic, gradients accumulated across calls, the optimiser step,
- *   fusing the d_rows gather into the gradient kernel, float64 networks; and of the Box call below what its comment lists. */
+ * Out of scope: PPO value clipping, a trunk shared between actor and critic, gradients accumulated across calls, the optimiser step fused into
+ *   these kernels (it is gymnet_vecenv_actor_apply_gradient, below), fusing the d_rows gather into the gradient kernel, float64 networks; and of the Box call below what its comment lists. */
 int gymnet_vecenv_actor_policy_gradient(gymnet_vecenv *h, const float *d_weights, int64_t count,
                                         const float *d_x, int64_t x_stride, int64_t m, const int32_t *d_actions, const float *d_coef,
                                         const float *d_logp_old, float clip, float entropy_coef,
@@ -1156,6 +1156,52 @@ int gymnet_vecenv_actor_box_policy_gradient(gymnet_vecenv *h, const float *d_wei
                                             const float *d_x, int64_t x_stride, int64_t m, const float *d_actions, const float *d_coef,
                                             const float *d_logd_old, float clip, float entropy_coef,
                                             float *d_grad, float *d_loss, float *d_logd, float *d_grad_log_sigma);
+
+/* ---- the optimiser step: one update of one flat parameter vector from its gradient, on the device ------------------------------
+ * One handle call (additive: the ABI version stays 6) that applies d_grad to d_weights in place under one of three rules, after an
+ * optional clip of the gradient's 2-norm: what follows a gradient call, so that a host without torch trains with no trip to the host.
+ * One launch of one workgroup.  The handle gives its stream, its error slot and nothing else: it need not have an actor, and count is
+ * NOT tied to a configured network — the same call steps the policy, the critic, or the one-element ln sigma against
+ * d_grad_log_sigma.  The weights and the optimiser state are the caller's; the handle keeps neither.  All pointers are device pointers.
+ *     rule                GYMNET_OPT_SGD, GYMNET_OPT_ADADELTA or GYMNET_OPT_ADAM
+ *     d_weights [count]   float32, updated in place;  count in [1, 8192]
+ *     d_grad [count]      float32, read only (the clipped and decayed gradient lives in registers)
+ *     d_state [2][count]  float32, read and written; all zeros is a fresh optimiser.  SGD: row 0 the momentum buffer b, row 1 untouched;
+ *                         with p0 == 0 no row is touched and d_state may be NULL.  AdaDelta: rows q, a.  Adam: rows m, v.
+ *     step                the number of this update, >= 1; only Adam reads it
+ *     lr, p0, p1, eps     SGD: p0 = momentum.  AdaDelta: p0 = rho.  Adam: p0, p1 = beta1, beta2.  A rule ignores what it does not name.
+ *     weight_decay        coupled (L2) decay for every rule; 0: none
+ *     max_grad_norm       0: no clipping
+ *     d_norm [1]          float32, may be NULL: receives the gradient's 2-norm BEFORE clipping, whether or not clipping is on
+ * The arithmetic is fixed so that torch's optimisers are the reference.  Per element float32, every operation rounding on its own, / and
+ * sqrt correctly rounded.  The scalars named below — 1 - p0, 1 - p1, the two Adam bias terms — are computed once per call on the host in
+ * float64 from the float32 arguments and rounded once.
+ *     norm:   S = sum_i g_i^2 in float64 in a fixed order (per thread over the elements i, i + 1024, .. ascending; across each 64-lane
+ *             wave by a xor butterfly; the sixteen wave sums in wave order);  norm = sqrt(S);  *d_norm = (float) norm
+ *             max_grad_norm > 0:  coef = (float) min(1, max_grad_norm / (norm + 1e-6))  in float64,  g <- g * coef
+ *             (torch.nn.utils.clip_grad_norm_).  A NaN norm gives a NaN coef; an infinite one coef = 0.
+ *     decay:  weight_decay != 0:  g <- g + weight_decay * w
+ *     SGD:       b <- p0 * b + g;   w <- w - lr * b                    (torch.optim.SGD, dampening 0, no Nesterov: a zero b gives its
+ *                                                                       first step)
+ *     AdaDelta:  q <- p0 * q + (1 - p0) * (g * g);   d = sqrt(a + eps) / sqrt(q + eps) * g;   a <- p0 * a + (1 - p0) * (d * d);
+ *                w <- w - lr * d                                       (torch.optim.Adadelta)
+ *     Adam:      m <- p0 * m + (1 - p0) * g;   v <- p1 * v + (1 - p1) * (g * g);
+ *                w <- w - (lr / (1 - p0^step)) * (m / (sqrt(v) / sqrt(1 - p1^step) + eps))      (torch.optim.Adam, no amsgrad)
+ *   No atomics and one summation order: the same inputs give the same bits.  With max_grad_norm == 0 the weights and the state do not
+ *   depend on whether d_norm is given.
+ * Ordered on the handle's stream; no synchronise, no allocation.  It changes nothing on the handle.
+ * GYMNET_ERR_INVALID_ARG, nothing written: a NULL handle, d_weights or d_grad; count outside [1, 8192]; an unknown rule; p0 (Adam: p0 or
+ *   p1) outside [0, 1); a NULL d_state unless the rule is SGD with p0 == 0; a pointer that is not 4-byte aligned; d_grad, d_state (the
+ *   rows the rule uses: one for SGD, two otherwise) or d_norm overlapping d_weights or each other; step < 1 for Adam; lr, eps or
+ *   weight_decay negative or not finite; eps == 0 for AdaDelta; max_grad_norm negative or NaN.
+ * Out of scope: an epoch or minibatch loop, optimiser state in the handle or in checkpoints, a joint norm over several vectors, AdamW's
+ *   decoupled decay, Nesterov, amsgrad, learning-rate schedules (lr is per call), float64 parameters. */
+#define GYMNET_OPT_SGD 0
+#define GYMNET_OPT_ADADELTA 1
+#define GYMNET_OPT_ADAM 2
+int gymnet_vecenv_actor_apply_gradient(gymnet_vecenv *h, int32_t rule, float *d_weights, int64_t count, const float *d_grad,
+                                       float *d_state, int64_t step, float lr, float p0, float p1, float eps,
+                                       float weight_decay, float max_grad_norm, float *d_norm);
 
 /* ---- multi-GPU group: ONE process (e.g. a C# host) driving G members, one per GPU ----------------------------
  * The reference has no multi-device code; what shards is the independence of VecEnvWrapper's map (VecEnvWrapper.cs:22-24).

@@ -456,6 +456,16 @@ public:
                             float *d_grad, float *d_loss = nullptr, float *d_value = nullptr) {
         check(gymnet_vecenv_actor_value_gradient(h_, d_weights, count, d_x, x_stride, m, d_target, d_grad, d_loss, d_value));
     }
+    // The optimiser step on the device: d_weights [count] (count <= 8192; any flat vector — the policy's, the critic's, the one-element
+    // ln sigma) updated in place from d_grad under rule (GYMNET_OPT_SGD: p0 momentum; _ADADELTA: p0 rho; _ADAM: p0, p1 the betas, step >= 1
+    // the update's number), after clipping the gradient's 2-norm to max_grad_norm (0: none) and adding weight_decay * w
+    // (gymnet_vecenv_actor_apply_gradient: the arithmetic is written out there; it is torch.optim's).  d_state float32 [2][count] is the
+    // caller's, zeros for a fresh optimiser, null for SGD without momentum; d_norm [1] receives the norm before clipping and may be null.
+    // One launch, ordered on the handle's stream, no synchronise, no allocation.
+    void ActorApplyGradient(int32_t rule, float *d_weights, int64_t count, const float *d_grad, float *d_state, int64_t step, float lr, float p0,
+                            float p1, float eps, float weight_decay = 0.0f, float max_grad_norm = 0.0f, float *d_norm = nullptr) {
+        check(gymnet_vecenv_actor_apply_gradient(h_, rule, d_weights, count, d_grad, d_state, step, lr, p0, p1, eps, weight_decay, max_grad_norm, d_norm));
+    }
     // GAE(gamma, lambda) advantages and advantage + value over the rows a rollout recorded (gymnet_gae_device: the recurrence is written out
     // there), one launch on the handle's device and stream: ordered after the rollout, no synchronise.  d_reward float32 [steps][N], d_done
     // uint8 [steps][N] (the fused rollout's records); d_value float32 [steps][N] or null (every value 0), d_last_value float32 [N], d_boot
