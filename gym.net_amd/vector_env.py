@@ -55,22 +55,51 @@ def _count(value, name, low, high=None):
     return int(value)
 
 
-def _logp_buffer(x, shape, name, device=None):
-    """a device float32 tensor of exactly `shape` for log-probabilities, refused here before any native call"""
-    if not hasattr(x, "data_ptr") or not hasattr(x, "dtype") or not hasattr(x, "shape"):
-        raise ValueError(f"{name} must be a device float32 tensor of shape {tuple(shape)}, got {type(x).__name__}")
-    if str(x.dtype) != "torch.float32":
-        raise ValueError(f"{name} must be float32, got {x.dtype}")
-    if tuple(int(v) for v in x.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(x.shape)}")
-    if not getattr(x, "is_cuda", False):
-        raise ValueError(f"{name} must be on the handle's device, got a host tensor")
-    index = getattr(getattr(x, "device", None), "index", None)
-    if device is not None and index is not None and int(index) != int(device):
-        raise ValueError(f"{name} is on device {index}, the handle on {device}")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return x
+_F32, _F64, _I32, _I64, _U8 = "torch.float32", "torch.float64", "torch.int32", "torch.int64", "torch.uint8"      # str(tensor.dtype)
+
+
+def _device_tensor(x, name, dtype, shape, device=None, what=None):
+    """The one rule for a device tensor argument, refused here before any native call: `x` has data_ptr(), its dtype is `dtype` (_F32 ...;
+    a tuple: one of them), its shape is the tuple `shape` — or, where `shape` is a predicate over the tuple, passes it, `what` being its
+    words —, it is on the device, on `device` where the handle's and the tensor's are both known, and it is contiguous.  Returns x."""
+    got = None
+    if hasattr(x, "data_ptr") and hasattr(x, "dtype") and hasattr(x, "shape"):
+        have, shape_ = str(x.dtype), tuple(x.shape)
+        if (have != dtype if dtype.__class__ is str else have not in dtype) or not (shape_ == shape if shape.__class__ is tuple else shape(shape_)):
+            got = f"{have} of shape {shape_}"
+        elif not getattr(x, "is_cuda", False):
+            got = "a host tensor"
+        else:
+            if device is not None:
+                index = getattr(getattr(x, "device", None), "index", None)
+                if index is not None and int(index) != int(device):
+                    raise ValueError(f"{name} is on device {index}, the handle on {device}")
+            if x.is_contiguous():
+                return x
+            got = "one that is not contiguous"
+    kinds = " or ".join(d[6:] for d in ((dtype,) if dtype.__class__ is str else dtype))
+    raise ValueError(f"{name} must be a contiguous device {kinds} tensor of shape {what or shape}, got {got or type(x).__name__}")
+
+
+def _seed(seed):
+    """a seed as the native calls take it: the low 64 bits, so a negative int wraps"""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _one_action(action):
+    """(action, one): an Enum member becomes its int value (Env<TAction>.Step(TAction), Env.cs:43-53); `one` says the action is a single
+    int, which IVecEnv.Step(int) gives to every lane (a bool is none: it goes the per-lane way)"""
+    if isinstance(action, enum.Enum):
+        action = int(action.value)
+    return action, isinstance(action, (int, np.integer)) and not isinstance(action, (bool, np.bool_))
+
+
+def _lane_actions(action, n, dtype):
+    """one action per lane as the native calls take them: a contiguous [n] array of the action dtype"""
+    a = np.ascontiguousarray(np.asarray(action).reshape(-1).astype(dtype, copy=False))
+    if a.shape[0] != n:
+        raise ValueError("Number of actions passed should be equals to number of environments")
+    return a
 
 
 class BatchStep:
@@ -97,6 +126,11 @@ class BatchStep:
 
     def ToSteps(self):
         return list(self)
+
+
+def _batch_step(obs, rew, done):
+    """the BatchStep of a native step's outputs: `done` is the done byte, whose bit 1 says the time limit ended the episode"""
+    return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
 
 
 class PendingStep:
@@ -134,7 +168,7 @@ class VectorEnv:
                  | (capi.FLAG_RESIDENT if resident else 0))
         cfg = capi.Config(struct_size=C.sizeof(capi.Config), env_id=env_id, num_envs=int(num_envs),
                           lane_offset=int(lane_offset), device=int(device), flags=flags,
-                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF, stream=_ptr(stream), d_ext_obs=_ptr(ext_obs),
+                          seed=_seed(seed), stream=_ptr(stream), d_ext_obs=_ptr(ext_obs),
                           ext_obs_stride=int(ext_obs_stride), max_episode_steps=int(max_episode_steps), reserved=0,
                           d_ext_obs_alt=_ptr(ext_obs_alt))
         self._h = C.c_void_p()
@@ -211,7 +245,7 @@ class VectorEnv:
 
     def Seed(self, seed):                                                            # VecEnv.cs:44-53
         if isinstance(seed, (int, np.integer)):
-            capi.check(self._lib.gymnet_vecenv_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+            capi.check(self._lib.gymnet_vecenv_seed(self._h, _seed(seed)))
         else:
             s = np.ascontiguousarray(np.asarray(seed, dtype=np.int64).astype(np.uint64))
             capi.check(self._lib.gymnet_vecenv_seed_lanes(self._h, _host(s), s.shape[0]))
@@ -235,24 +269,17 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_reset_where(self._h, None if m is None else _host(m), _host(obs)))
         return obs
 
-    def _actions(self, action):
-        a = np.ascontiguousarray(np.asarray(action).reshape(-1).astype(self._adtype, copy=False))
-        if a.shape[0] != self.NumberOfEnvironments:
-            raise ValueError("Number of actions passed should be equals to number of environments")
-        return a
-
     def Step(self, action):
         """IVecEnv.Step(int action) (IVecEnv.cs:15, VecEnvWrapper.cs:22-24) broadcasts ONE scalar action;
         an array-like gives one action per lane (extension)."""
         obs, rew, done = self._outs()
-        if isinstance(action, enum.Enum):                                            # Env<TAction>.Step(TAction), Env.cs:43-53
-            action = int(action.value)
-        if isinstance(action, (int, np.integer)) and not isinstance(action, (bool, np.bool_)):
+        action, one = _one_action(action)
+        if one:
             capi.check(self._lib.gymnet_vecenv_step_broadcast(self._h, int(action), _host(obs), _host(rew), _host(done)))
         else:
-            a = self._actions(action)
+            a = _lane_actions(action, self.NumberOfEnvironments, self._adtype)
             capi.check(self._lib.gymnet_vecenv_step(self._h, _host(a), _host(obs), _host(rew), _host(done)))
-        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+        return _batch_step(obs, rew, done)
 
     def StepRepeat(self, action, repeat):
         """Frame skip at the host boundary (gymnet_vecenv_step_repeat): one action per lane, held for repeat + 1 env steps in one launch.
@@ -260,9 +287,9 @@ class VectorEnv:
         lane that finishes inside the decision stops there (see StepRepeatDevice).  repeat = 0 is Step(action) with an array."""
         repeat = _repeat(repeat)
         obs, rew, done = self._outs()
-        a = self._actions(action)
+        a = _lane_actions(action, self.NumberOfEnvironments, self._adtype)
         capi.check(self._lib.gymnet_vecenv_step_repeat(self._h, _host(a), repeat, _host(obs), _host(rew), _host(done)))
-        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+        return _batch_step(obs, rew, done)
 
     def HostBuffers(self):
         """(actions, obs, reward, done): numpy views over the library's page-locked, device-mapped host buffers
@@ -295,23 +322,22 @@ class VectorEnv:
         capi.check(self._lib.gymnet_vecenv_reset(self._h, _host(obs_out)))
 
     def StepAsync(self, action):                                                     # VecEnv.cs:63-65
-        if isinstance(action, enum.Enum):
-            action = int(action.value)
-        if isinstance(action, (int, np.integer)):
+        action, one = _one_action(action)
+        if one or isinstance(action, bool):                   # (a Python bool broadcasts here, as it always has)
             action = np.full(self.NumberOfEnvironments, action, dtype=self._adtype)
-        a = self._actions(action)
+        a = _lane_actions(action, self.NumberOfEnvironments, self._adtype)
         capi.check(self._lib.gymnet_vecenv_step_async(self._h, _host(a)))
         return PendingStep(self)
 
     def StepWait(self):
         obs, rew, done = self._outs()
         capi.check(self._lib.gymnet_vecenv_step_wait(self._h, _host(obs), _host(rew), _host(done)))
-        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+        return _batch_step(obs, rew, done)
 
     def Read(self):
         obs, rew, done = self._outs()
         capi.check(self._lib.gymnet_vecenv_read(self._h, _host(obs), _host(rew), _host(done)))
-        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+        return _batch_step(obs, rew, done)
 
     def SampleActions(self, seed=0, tick=0):
         """ActionSpace.Sample() for every lane, on the device (TrainingPlaySession.cs:46-49 batched)."""
@@ -382,62 +408,46 @@ class VectorEnv:
                     _box_boot_device).  Needs rec_value (on a Box actor rec_logd too), actions="actor", repeat = 0 and a handle with
                     max_episode_steps > 0; final_obs is not needed."""
         repeat = _repeat(repeat)
-        value_rows = None
-        if rec_boot is not None:
-            if actions != "actor":
-                raise ValueError(f"rec_boot records the critic's value of terminal observations where the actor chooses: it needs actions=\"actor\", got {actions!r}")
-            if rec_value is None:
-                raise ValueError("rec_boot needs rec_value (V(terminal observation) is recorded beside the values)")
-            if repeat:
-                raise ValueError("rec_boot: the fused actor rollout has no frame skip (repeat must be 0)")
-            _logp_buffer(rec_boot, (_count(steps, "steps", 0), self.NumberOfEnvironments), "rec_boot", self.Device)
         box_logd = rec_logd is not None
-        if box_logd:
-            actor = getattr(self, "_actor", None)
-            if actions != "actor":
-                raise ValueError(f"rec_logd records the actor's log-densities: it needs actions=\"actor\", got {actions!r}")
-            if actor is None:
-                raise ValueError("rec_logd needs an actor (VectorEnv.Actor)")
-            if not actor.IsBox:
-                raise ValueError("rec_logd belongs to a Box actor; this handle's actor chooses Discrete actions (rec_logp)")
-            if rec_logp is not None:
-                raise ValueError("rec_logp belongs to a Discrete actor; this handle's actor chooses Box actions (rec_logd)")
-            if repeat:
-                raise ValueError("rec_logd: the fused actor rollout has no frame skip (repeat must be 0)")
-            T = _count(steps, "steps", 0)
-            _logp_buffer(rec_logd, (T, self.NumberOfEnvironments), "rec_logd", self.Device)
-            if rec_value is not None:
-                if getattr(actor, "CriticWidths", None) is None:
-                    raise ValueError("rec_value needs a critic (Actor.SetCritic)")
-                value_rows = T + 1 if tuple(getattr(rec_value, "shape", ()))[:1] == (T + 1,) else T
-                _logp_buffer(rec_value, (value_rows, self.NumberOfEnvironments), "rec_value", self.Device)
-        if rec_value is not None and not box_logd:
-            actor = getattr(self, "_actor", None)
-            if actions != "actor":
-                raise ValueError(f"rec_value records the critic's values where the actor chooses: it needs actions=\"actor\", got {actions!r}")
-            if actor is None:
-                raise ValueError("rec_value needs an actor (VectorEnv.Actor)")
-            if actor.IsBox:
-                raise ValueError("rec_value alone belongs to a Discrete actor's fused rollout; this handle's actor chooses Box actions: pass "
-                                 "rec_logd with it (Actor.Value serves a single step)")
-            if getattr(actor, "CriticWidths", None) is None:
-                raise ValueError("rec_value needs a critic (Actor.SetCritic)")
-            if repeat:
-                raise ValueError("rec_value: the fused actor rollout has no frame skip (repeat must be 0)")
-            T = _count(steps, "steps", 0)
-            value_rows = T + 1 if tuple(getattr(rec_value, "shape", ()))[:1] == (T + 1,) else T
-            _logp_buffer(rec_value, (value_rows, self.NumberOfEnvironments), "rec_value", self.Device)
-        if rec_logp is not None and not box_logd:
-            actor = getattr(self, "_actor", None)
-            if actions != "actor":
-                raise ValueError(f"rec_logp records the actor's log-probabilities: it needs actions=\"actor\", got {actions!r}")
-            if actor is None:
-                raise ValueError("rec_logp needs an actor (VectorEnv.Actor)")
-            if actor.IsBox:
-                raise ValueError("rec_logp belongs to a Discrete actor; this handle's actor chooses Box actions")
-            if repeat:
-                raise ValueError("rec_logp: the fused actor rollout has no frame skip (repeat must be 0)")
-            _logp_buffer(rec_logp, (_count(steps, "steps", 0), self.NumberOfEnvironments), "rec_logp", self.Device)
+        records = rec_logp is not None or rec_value is not None or box_logd or rec_boot is not None
+        if records:
+            n, T, row_T = self.NumberOfEnvironments, None, False
+            logp_on_box ="rec_logp belongs to a Discrete actor; this handle's actor chooses Box actions (rec_logd)"
+            # One row per record argument, in the order they are checked: what it records, the kind of actor it belongs to (True: Box; None:
+            # rec_boot rides on rec_value, whose row asks for the actor), the refusal of the other kind, whether it needs a critic.  rec_value
+            # is the one that goes with either kind, on a Box actor beside rec_logd, and the one that may carry a row T.
+            for name, x, records, box, other_kind, critic in (
+                    ("rec_boot", rec_boot, "the critic's value of terminal observations where the actor chooses", None, None, False),
+                    ("rec_logd", rec_logd, "the actor's log-densities", True,
+                     "rec_logd belongs to a Box actor; this handle's actor chooses Discrete actions (rec_logp)", False),
+                    ("rec_value", rec_value, "the critic's values where the actor chooses", box_logd,
+                     "rec_value alone belongs to a Discrete actor's fused rollout; this handle's actor chooses Box actions: pass "
+                     "rec_logd with it (Actor.Value serves a single step)", True),
+                    ("rec_logp", rec_logp, "the actor's log-probabilities", False, logp_on_box, False)):
+                if x is None:
+                    continue
+                if actions != "actor":
+                    raise ValueError(f"{name} records {records}: it needs actions=\"actor\", got {actions!r}")
+                if box is None:
+                    if rec_value is None:
+                        raise ValueError("rec_boot needs rec_value (V(terminal observation) is recorded beside the values)")
+                else:
+                    actor = getattr(self, "_actor", None)
+                    if actor is None:
+                        raise ValueError(f"{name} needs an actor (VectorEnv.Actor)")
+                    if actor.IsBox != box:
+                        raise ValueError(other_kind)
+                    if box and rec_logp is not None:
+                        raise ValueError(logp_on_box)
+                    if critic and getattr(actor, "CriticWidths", None) is None:
+                        raise ValueError(f"{name} needs a critic (Actor.SetCritic)")
+                if repeat:
+                    raise ValueError(f"{name}: the fused actor rollout has no frame skip (repeat must be 0)")
+                if T is None:
+                    T = _count(steps, "steps", 0)
+                if critic and tuple(getattr(x, "shape", ()))[:1] == (T + 1,):
+                    row_T = True
+                _device_tensor(x, name, _F32, (T + 1 if critic and row_T else T, n), self.Device)
         src = {"ring": capi.ACTIONS_RING, "sample": capi.ACTIONS_SAMPLE, "epsilon_greedy": capi.ACTIONS_EPSILON_GREEDY,
                "actor": capi.ACTIONS_ACTOR}[actions]
         ep = episodes or {}
@@ -445,33 +455,36 @@ class VectorEnv:
         if unknown:
             raise TypeError(f"unknown episode record field(s): {sorted(unknown)}")
         spec = capi.RolloutSpec(struct_size=C.sizeof(capi.RolloutSpec), action_source=src, d_actions=_ptr(d_actions), steps=int(steps),
-                                action_stride=int(action_stride), ring=int(ring), action_seed=int(action_seed) & 0xFFFFFFFFFFFFFFFF,
+                                action_stride=int(action_stride), ring=int(ring), action_seed=_seed(action_seed),
                                 action_tick0=int(action_tick0), epsilon=float(epsilon), record_flags=capi.RECORDS_NO_OVERFLOW if ep.get("no_overflow") else 0,
                                 d_rec_obs=_ptr(rec_obs), d_rec_reward=_ptr(rec_reward), d_rec_done=_ptr(rec_done), d_rec_actions=_ptr(rec_actions),
                                 d_ep_step=_ptr(ep.get("step")), d_ep_lane=_ptr(ep.get("lane")), d_ep_return=_ptr(ep.get("ret")),
                                 d_ep_length=_ptr(ep.get("length")), ep_capacity=int(ep.get("capacity", 0)), d_ep_count=_ptr(ep.get("count")))
         if repeat:
             capi.check(self._lib.gymnet_vecenv_rollout_repeat_device(self._h, C.byref(spec), repeat))
-        elif box_logd:
-            if rec_boot is not None:
-                capi.check(self._lib.gymnet_vecenv_rollout_fused_box_boot_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value), _ptr(rec_boot)))
-            else:
-                capi.check(self._lib.gymnet_vecenv_rollout_fused_box_logd_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value)))
-            if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
-                last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
-                capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
-        elif rec_value is not None:
-            if rec_boot is not None:
-                capi.check(self._lib.gymnet_vecenv_rollout_fused_value_boot_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value), _ptr(rec_boot)))
-            else:
-                capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
-            if value_rows == int(steps) + 1:                  # row T: the value of the history the rollout leaves
-                last = C.c_void_p(rec_value.data_ptr() + 4 * int(steps) * self.NumberOfEnvironments)
-                capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, last))
-        elif rec_logp is not None:
-            capi.check(self._lib.gymnet_vecenv_rollout_fused_logp_device(self._h, C.byref(spec), _ptr(rec_logp)))
-        else:
+        elif not records:
             capi.check(self._lib.gymnet_vecenv_rollout_fused_ex_device(self._h, C.byref(spec)))
+        elif box_logd and rec_boot is not None:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_box_boot_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value), _ptr(rec_boot)))
+        elif box_logd:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_box_logd_device(self._h, C.byref(spec), _ptr(rec_logd), _ptr(rec_value)))
+        elif rec_boot is not None:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_value_boot_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value), _ptr(rec_boot)))
+        elif rec_value is not None:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_value_device(self._h, C.byref(spec), _ptr(rec_logp), _ptr(rec_value)))
+        else:
+            capi.check(self._lib.gymnet_vecenv_rollout_fused_logp_device(self._h, C.byref(spec), _ptr(rec_logp)))
+        if records and row_T:                                 # row T: the value of the history the rollout leaves
+            capi.check(self._lib.gymnet_vecenv_actor_value_device(self._h, C.c_void_p(rec_value.data_ptr() + 4 * T * n)))
+
+    def _device_or(self, x, name):
+        """the handle's device index; where it is not known (a group member's view), the one the tensor `x` names"""
+        dev = self.Device
+        if dev is None:
+            dev = getattr(getattr(x, "device", None), "index", None)
+            if dev is None:
+                raise ValueError(f"the handle's device is not known and {name} does not name one")
+        return int(dev)
 
     def AdvantagesDevice(self, reward, done, values, advantage, returns, gamma=0.99, lam=0.95, last_value=None, boot=None):
         """GAE(gamma, lam) advantages and advantage + value over the rows a rollout recorded, in one kernel launch on the handle's
@@ -486,51 +499,37 @@ class VectorEnv:
           advantage, returns   caller-allocated float32 [T, n]; either may be None, not both.  advantage may be the reward tensor while
                      returns is values' first T rows, or the other way round: each element is read before it is written.
         Every argument is checked here, before any native call."""
-        dev = self.Device
-        reward = _logp_buffer(reward, getattr(reward, "shape", ()), "reward", dev)
-        if len(reward.shape) != 2 or int(reward.shape[1]) != self.NumberOfEnvironments:
-            raise ValueError(f"reward must have shape (T, {self.NumberOfEnvironments}), got {tuple(reward.shape)}")
-        T, n = int(reward.shape[0]), self.NumberOfEnvironments
-        if not hasattr(done, "data_ptr") or str(getattr(done, "dtype", None)) != "torch.uint8":
-            raise ValueError(f"done must be a device uint8 tensor of shape ({T}, {n}), got {getattr(done, 'dtype', type(done).__name__)}")
-        if tuple(int(v) for v in done.shape) != (T, n) or not getattr(done, "is_cuda", False) or not done.is_contiguous():
-            raise ValueError(f"done must be a contiguous device tensor of shape ({T}, {n}), got {tuple(done.shape)}")
-        index = getattr(getattr(done, "device", None), "index", None)
-        if dev is not None and index is not None and int(index) != int(dev):
-            raise ValueError(f"done is on device {index}, the handle on {dev}")
+        dev, n = self.Device, self.NumberOfEnvironments
+        _device_tensor(reward, "reward", _F32, lambda s: len(s) == 2 and s[1] == n, dev, ("T", n))
+        T = int(reward.shape[0])
+        _device_tensor(done, "done", _U8, (T, n), dev)
         v_ptr = lv_ptr = None
         if values is not None:
             rows = int(values.shape[0]) if len(getattr(values, "shape", ())) == 2 else -1
             if rows == T + 1:
                 if last_value is not None:
                     raise ValueError("values has T + 1 rows (row T is the last value): last_value must be None")
-                _logp_buffer(values, (T + 1, n), "values", dev)
+                _device_tensor(values, "values", _F32, (T + 1, n), dev)
                 lv_ptr = C.c_void_p(values.data_ptr() + 4 * T * n)
             else:
-                _logp_buffer(values, (T, n), "values", dev)
+                _device_tensor(values, "values", _F32, (T, n), dev)
             v_ptr = _ptr(values)
         if last_value is not None:
-            lv_ptr = _ptr(_logp_buffer(last_value, (n,), "last_value", dev))
+            lv_ptr = _ptr(_device_tensor(last_value, "last_value", _F32, (n,), dev))
         if boot is not None:
-            _logp_buffer(boot, (T, n), "boot", dev)
+            _device_tensor(boot, "boot", _F32, (T, n), dev)
         if advantage is None and returns is None:
             raise ValueError("advantage and returns are both None")
         if advantage is not None:
-            _logp_buffer(advantage, (T, n), "advantage", dev)
-        if returns is not None:
-            if values is not None and returns is values and int(values.shape[0]) == T + 1:
-                pass                                          # in place over the first T rows of a [T + 1, n] values tensor
-            else:
-                _logp_buffer(returns, (T, n), "returns", dev)
+            _device_tensor(advantage, "advantage", _F32, (T, n), dev)
+        if returns is not None and not (returns is values and int(values.shape[0]) == T + 1):    # (in place over the first T rows of a [T + 1, n] values)
+            _device_tensor(returns, "returns", _F32, (T, n), dev)
         for name, g in (("gamma", gamma), ("lam", lam)):
             if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, float, np.integer, np.floating)) or not 0.0 <= float(g) <= 1.0:
                 raise ValueError(f"{name} must be a number in [0, 1], got {g!r}")
-        if dev is None:
-            dev = getattr(getattr(reward, "device", None), "index", None)
-            if dev is None:
-                raise ValueError("the handle's device is not known and reward does not name one")
+        dev = self._device_or(reward, "reward")
         stream = self.DeviceView().stream
-        capi.check(self._lib.gymnet_gae_device(int(dev), C.c_void_p(stream), T, n, n, _ptr(reward), _ptr(done), v_ptr, lv_ptr, _ptr(boot),
+        capi.check(self._lib.gymnet_gae_device(dev, C.c_void_p(stream), T, n, n, _ptr(reward), _ptr(done), v_ptr, lv_ptr, _ptr(boot),
                                                float(gamma), float(lam), _ptr(advantage), _ptr(returns)))
 
     def RolloutInputsDevice(self, rec_obs, rec_done, history0, history, rows=None, out=None, history_out=None):
@@ -548,52 +547,28 @@ class VectorEnv:
         Every argument is checked here, before any native call."""
         dev, n = self.Device, self.NumberOfEnvironments
         S = _count(history, "history", 1, 64)
-        if not hasattr(rec_obs, "data_ptr") or str(getattr(rec_obs, "dtype", None)) not in ("torch.float32", "torch.float64"):
-            raise ValueError(f"rec_obs must be a device float32 or float64 tensor [T, obs_dim, {n}], got {getattr(rec_obs, 'dtype', type(rec_obs).__name__)}")
-        f64 = str(rec_obs.dtype) == "torch.float64"
-        shape = tuple(int(v) for v in rec_obs.shape)
-        if len(shape) != 3 or shape[2] != n or shape[1] < 1:
-            raise ValueError(f"rec_obs must have shape (T, obs_dim, {n}), got {shape}")
-        T, O = shape[0], shape[1]
+        _device_tensor(rec_obs, "rec_obs", (_F32, _F64), lambda s: len(s) == 3 and s[2] == n and s[1] >= 1, dev, ("T", "obs_dim", n))
+        f64, T, O = str(rec_obs.dtype) == _F64, int(rec_obs.shape[0]), int(rec_obs.shape[1])
         if S * O > 64:
             raise ValueError(f"history * obs_dim = {S * O} is beyond 64, the widest input an actor can have")
-
-        def device_tensor(x, want, dtype, name):
-            if not hasattr(x, "data_ptr") or str(getattr(x, "dtype", None)) != dtype:
-                raise ValueError(f"{name} must be a device {dtype[6:]} tensor of shape {want}, got {getattr(x, 'dtype', type(x).__name__)}")
-            if want is not None and tuple(int(v) for v in x.shape) != tuple(want):
-                raise ValueError(f"{name} must have shape {tuple(want)}, got {tuple(x.shape)}")
-            if not getattr(x, "is_cuda", False) or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous tensor on the handle's device")
-            index = getattr(getattr(x, "device", None), "index", None)
-            if dev is not None and index is not None and int(index) != int(dev):
-                raise ValueError(f"{name} is on device {index}, the handle on {dev}")
-            return x
-        device_tensor(rec_obs, shape, str(rec_obs.dtype), "rec_obs")
-        device_tensor(rec_done, (T, n), "torch.uint8", "rec_done")
-        device_tensor(history0, (S, O, n), "torch.float32", "history0")
+        _device_tensor(rec_done, "rec_done", _U8, (T, n), dev)
+        _device_tensor(history0, "history0", _F32, (S, O, n), dev)
         if history_out is not None:
-            device_tensor(history_out, (S, O, n), "torch.float32", "history_out")
+            _device_tensor(history_out, "history_out", _F32, (S, O, n), dev)
         m = 0
         if rows is not None:
-            device_tensor(rows, None, "torch.int64", "rows")
-            if len(rows.shape) != 1:
-                raise ValueError(f"rows must be one-dimensional, got shape {tuple(rows.shape)}")
-            m = int(rows.shape[0])
+            m = int(_device_tensor(rows, "rows", _I64, lambda s: len(s) == 1, dev, ("m",)).shape[0])
         want = (T, n, S * O) if rows is None else (m, S * O)
-        if dev is None:
-            dev = getattr(getattr(rec_obs, "device", None), "index", None)
-            if dev is None:
-                raise ValueError("the handle's device is not known and rec_obs does not name one")
+        dev = self._device_or(rec_obs, "rec_obs")
         if out is None:
             import torch
-            out = torch.empty(want, dtype=torch.float32, device=f"cuda:{int(dev)}")
+            out = torch.empty(want, dtype=torch.float32, device=f"cuda:{dev}")
         else:
-            device_tensor(out, want, "torch.float32", "out")
+            _device_tensor(out, "out", _F32, want, dev)
         if rows is not None and m == 0:
             return out                                        # the gathered form with no row is a no-op (an empty tensor has no pointer)
         stream = self.DeviceView().stream
-        capi.check(self._lib.gymnet_rollout_inputs_device(int(dev), C.c_void_p(stream), T, n, n, O, S, 1 if f64 else 0, _ptr(rec_obs), _ptr(rec_done),
+        capi.check(self._lib.gymnet_rollout_inputs_device(dev, C.c_void_p(stream), T, n, n, O, S, 1 if f64 else 0, _ptr(rec_obs), _ptr(rec_done),
                                                           _ptr(history0), n, _ptr(rows), m, _ptr(out), S * O, _ptr(history_out), n))
         return out
 
@@ -1222,35 +1197,40 @@ class Actor:
         float32 tensor in the config layout is copied device to device, anything else goes through actor_pack and the host."""
         if getattr(self, "CriticWidths", None) is None:
             raise ValueError("this actor has no critic (SetCritic)")
+        self._load(net, self.CriticWidths, self.CriticCount, self._critic_pack, "critic",
+                   lambda *args: self._lib.gymnet_vecenv_actor_critic_load_device(*args))
+
+    def _load(self, net, widths, count, pack, whose, load):
+        """what Load and LoadCritic share: a device tensor of `count` float32 values, in any shape, is copied device to device; anything
+        else goes through `pack` and the host, and must come out with the configured `widths`"""
         if hasattr(net, "data_ptr") and getattr(net, "is_cuda", False):
-            if net.numel() != self.CriticCount or str(net.dtype) != "torch.float32" or not net.is_contiguous():
-                raise ValueError(f"a device weight tensor must be {self.CriticCount} contiguous float32 values")
-            capi.check(self._lib.gymnet_vecenv_actor_critic_load_device(self._handle(), _ptr(net), self.CriticCount))
+            _device_tensor(net, "net", _F32, lambda s: np.prod(s) == count, what=f"({count},), or any other of {count} values,")
+            capi.check(load(self._handle(), _ptr(net), count))
             return
-        widths, flat = self._critic_pack(net)
-        if tuple(int(w) for w in widths) != self.CriticWidths:
-            raise ValueError(f"widths {tuple(int(w) for w in widths)} != the critic's {self.CriticWidths}")
+        got, flat = pack(net)
+        if tuple(int(w) for w in got) != widths:
+            raise ValueError(f"widths {tuple(int(w) for w in got)} != the {whose}'s {widths}")
         import torch
         d = torch.from_numpy(flat).to(f"cuda:{self._env.Device}")
-        capi.check(self._lib.gymnet_vecenv_actor_critic_load_device(self._handle(), _ptr(d), self.CriticCount))
+        capi.check(load(self._handle(), _ptr(d), count))
         self._env.Sync()
 
-    def _value_buffer(self, value, name="value"):
+    def _value_buffer(self, value, name="value", what=None):
+        """a device float32 [N] for the critic to write, checked; None (Value's and Boot's `out`): a new one.  `what` names the caller in the
+        refusal of an actor without a critic."""
+        env = self._env
         if getattr(self, "CriticWidths", None) is None:
-            raise ValueError(f"{name} needs a critic (SetCritic)")
-        return _logp_buffer(value, (self._env.NumberOfEnvironments,), name, self._env.Device)
+            raise ValueError(f"{what or name} needs a critic (SetCritic)")
+        if value is not None:
+            return _device_tensor(value, name, _F32, (env.NumberOfEnvironments,), env.Device)
+        import torch
+        return torch.empty(env.NumberOfEnvironments, dtype=torch.float32, device=f"cuda:{env.Device}")
 
     def Value(self, out=None):
         """The critic's value of every lane's current history into `out` (device float32 [N]; None: a new torch tensor, returned), one
         kernel on the handle's stream (gymnet_vecenv_actor_value_device).  Serves Box actors and float64 handles too; the history must be
         current, as for Act.  After a rollout this is the last value."""
-        if out is None:
-            if getattr(self, "CriticWidths", None) is None:
-                raise ValueError("value needs a critic (SetCritic)")
-            import torch
-            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.float32, device=f"cuda:{self._env.Device}")
-        else:
-            self._value_buffer(out, "out")
+        out = self._value_buffer(out, "out", "value")
         capi.check(self._lib.gymnet_vecenv_actor_value_device(self._handle(), _ptr(out)))
         return out
 
@@ -1260,13 +1240,7 @@ class Actor:
         Call it after a vector step and before Push.  The terminal observation is read from the dense final observations on an
         auto_reset handle (final_obs=True) and from the current observation otherwise; the handle needs max_episode_steps > 0.  Changes
         neither the history nor what Push does next."""
-        if out is None:
-            if getattr(self, "CriticWidths", None) is None:
-                raise ValueError("boot needs a critic (SetCritic)")
-            import torch
-            out = torch.empty(self._env.NumberOfEnvironments, dtype=torch.float32, device=f"cuda:{self._env.Device}")
-        else:
-            self._value_buffer(out, "out")
+        out = self._value_buffer(out, "out", "boot")
         capi.check(self._lib.gymnet_vecenv_actor_boot_device(self._handle(), _ptr(out)))
         return out
 
@@ -1284,35 +1258,40 @@ class Actor:
         (gymnet_vecenv_actor_act_value_device); actions, logits and logp are the same bits with and without it.  logd (a Box actor whose
         policy has sigma > 0): an optional device float32 [N] for the log-density log N(action; greedy action, sigma^2) of the action each
         lane takes (gymnet_vecenv_actor_box_act_logd_device); actions and the unclamped outputs are the same bits with and without it."""
-        if logd is not None:
-            if not self.IsBox:
-                raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
-            _logp_buffer(logd, (self._env.NumberOfEnvironments,), "logd", self._env.Device)
-        if logp is not None:
-            if self.IsBox:
-                raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
-            _logp_buffer(logp, (self._env.NumberOfEnvironments,), "logp", self._env.Device)
-        if value is not None:
-            if self.IsBox:
-                raise ValueError("Act(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
-            self._value_buffer(value)
+        records = logp is not None or value is not None or logd is not None
+        if records:
+            self._records_kind("Act", logp, value, logd)
+            lanes, dev = (self._env.NumberOfEnvironments,), self._env.Device
+            if logd is not None:
+                _device_tensor(logd, "logd", _F32, lanes, dev)
+            if logp is not None:
+                _device_tensor(logp, "logp", _F32, lanes, dev)
+            if value is not None:
+                self._value_buffer(value)
         if out is None:
             out = self._actions()
-        if logd is not None:
+        if not records:
+            act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
+            capi.check(act(self._handle(), _ptr(out), _ptr(logits), float(epsilon), _seed(seed), int(tick)))
+        elif logd is not None:
             capi.check(self._lib.gymnet_vecenv_actor_box_act_logd_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logd), float(epsilon),
-                                                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
-            return out
-        if value is not None:
+                                                                         _seed(seed), int(tick)))
+        elif value is not None:
             capi.check(self._lib.gymnet_vecenv_actor_act_value_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), _ptr(value), float(epsilon),
-                                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
-            return out
-        if logp is not None:
+                                                                      _seed(seed), int(tick)))
+        else:
             capi.check(self._lib.gymnet_vecenv_actor_act_logp_device(self._handle(), _ptr(out), _ptr(logits), _ptr(logp), float(epsilon),
-                                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
-            return out
-        act = self._lib.gymnet_vecenv_actor_box_act_device if self.IsBox else self._lib.gymnet_vecenv_actor_act_device
-        capi.check(act(self._handle(), _ptr(out), _ptr(logits), float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tick)))
+                                                                     _seed(seed), int(tick)))
         return out
+
+    def _records_kind(self, method, logp, value, logd):
+        """the refusals Act and Step share: logp and value are a Discrete actor's, logd a Box actor's"""
+        if logp is not None and self.IsBox:
+            raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
+        if value is not None and self.IsBox:
+            raise ValueError(f"{method}(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
+        if logd is not None and not self.IsBox:
+            raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
 
     _HEADS = {"clamp": capi.BOX_HEAD_CLAMP, "tanh": capi.BOX_HEAD_TANH}
     _EXPLORES = {"sample": capi.BOX_EXPLORE_SAMPLE, "gaussian": capi.BOX_EXPLORE_GAUSSIAN}
@@ -1388,18 +1367,19 @@ class Actor:
     def Load(self, net):
         """New weights of the same widths, history kept: a flat device float32 tensor in the config layout is copied device to device,
         anything else goes through actor_pack and the host."""
-        if hasattr(net, "data_ptr") and getattr(net, "is_cuda", False):
-            if net.numel() != self.Count or str(net.dtype) != "torch.float32" or not net.is_contiguous():
-                raise ValueError(f"a device weight tensor must be {self.Count} contiguous float32 values")
-            capi.check(self._lib.gymnet_vecenv_actor_load_device(self._handle(), _ptr(net), self.Count))
-            return
-        widths, flat = actor_pack(net)
-        if tuple(int(w) for w in widths) != self.Widths:
-            raise ValueError(f"widths {tuple(int(w) for w in widths)} != the actor's {self.Widths}")
+        self._load(net, self.Widths, self.Count, actor_pack, "actor", lambda *args: self._lib.gymnet_vecenv_actor_load_device(*args))
+
+    def _handle_stream(self):
+        """the handle's stream as torch sees it: what is queued under torch.cuda.stream(...) of it is ordered with the handle's own work"""
         import torch
-        d = torch.from_numpy(flat).to(f"cuda:{self._env.Device}")
-        capi.check(self._lib.gymnet_vecenv_actor_load_device(self._handle(), _ptr(d), self.Count))
-        self._env.Sync()
+        return torch.cuda.ExternalStream(self._env.DeviceView().stream or 0, device=f"cuda:{self._env.Device}")
+
+    @staticmethod
+    def _concat(stream, tensors):
+        """the tensors' values as one flat tensor, concatenated on `stream`: no host trip"""
+        import torch
+        with torch.cuda.stream(stream):
+            return torch.cat([t.detach().reshape(-1) for t in tensors])
 
     def _grad_call(self, net, widths, count, x, grad, rows, what):
         """what PolicyGradient and ValueGradient share, before any native call: the flat device weights of `net` (an nn.Sequential's
@@ -1416,24 +1396,21 @@ class Actor:
             params = [p for mod in mods for p in (mod.weight, mod.bias)]
             if any(not p.is_cuda or p.dtype != torch.float32 for p in params):
                 raise ValueError(f"{what}: the network's parameters must be float32 on the handle's device")
-            with torch.cuda.stream(torch.cuda.ExternalStream(env.DeviceView().stream or 0, device=dev)):
-                flat = torch.cat([p.detach().reshape(-1) for p in params])
+            flat = self._concat(self._handle_stream(), params)
         else:
-            flat = _logp_buffer(net, (count,), "net", env.Device)
+            flat = _device_tensor(net, "net", _F32, (count,), env.Device)
         if not hasattr(x, "data_ptr") or str(getattr(x, "dtype", None)) != "torch.float32" or not getattr(x, "is_cuda", False) or x.dim() != 2:
             raise ValueError(f"{what}: x must be a device float32 tensor [m, {widths[0]}]")
         m = int(x.shape[0])
         if m < 1 or int(x.shape[1]) != widths[0] or x.stride(1) != 1 or x.stride(0) < widths[0]:
             raise ValueError(f"{what}: x must be [m >= 1, {widths[0]}] with unit column stride and a row stride >= {widths[0]}, got {tuple(x.shape)} strides {tuple(x.stride())}")
         for name, t, dtype in rows:
-            if t is None:
-                continue
-            if not hasattr(t, "data_ptr") or str(getattr(t, "dtype", None)) != dtype or not getattr(t, "is_cuda", False) or tuple(t.shape) != (m,) or not t.is_contiguous():
-                raise ValueError(f"{what}: {name} must be a contiguous device {dtype[6:]} tensor [{m}]")
+            if t is not None:
+                _device_tensor(t, f"{what}: {name}", dtype, (m,))           # (no device: these rows were never held to the handle's)
         if grad is None:
             grad = torch.empty(count, dtype=torch.float32, device=dev)
         else:
-            _logp_buffer(grad, (count,), "grad", env.Device)
+            _device_tensor(grad, "grad", _F32, (count,), env.Device)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         return flat, params, m, int(x.stride(0)), grad, loss
 
@@ -1462,13 +1439,24 @@ class Actor:
         The temperature is the actor's stored one (SetExploration).  A Discrete actor only."""
         if self.IsBox:
             raise ValueError("PolicyGradient belongs to a Discrete actor; this one chooses Box actions")
+        return self._policy_gradient("PolicyGradient", net, x, actions, coef, logp_old, clip, entropy_coef, grad, logp)
+
+    def _policy_gradient(self, what, net, x, actions, coef, old, clip, entropy_coef, grad, new, grad_log_sigma=None):
+        """PolicyGradient's and BoxPolicyGradient's body: `old` and `new` are logp_old and logp on a Discrete actor, logd_old and logd on a
+        Box actor, whose call takes grad_log_sigma as one more pointer"""
+        log = "logd" if self.IsBox else "logp"
         flat, params, m, stride, grad, loss = self._grad_call(net, self.Widths, self.Count, x, grad, (
-            ("actions", actions, "torch.int32"), ("coef", coef, "torch.float32"), ("logp_old", logp_old, "torch.float32"), ("logp", logp, "torch.float32")),
-            "PolicyGradient")
+            ("actions", actions, _F32 if self.IsBox else _I32), ("coef", coef, _F32), (log + "_old", old, _F32), (log, new, _F32)), what)
         if actions is None or coef is None:
-            raise ValueError("PolicyGradient: actions and coef are required")
-        capi.check(self._lib.gymnet_vecenv_actor_policy_gradient(self._handle(), _ptr(flat), self.Count, _ptr(x), stride, m, _ptr(actions), _ptr(coef),
-                                                                 _ptr(logp_old), float(clip), float(entropy_coef), _ptr(grad), _ptr(loss), _ptr(logp)))
+            raise ValueError(f"{what}: actions and coef are required")
+        if grad_log_sigma is not None:
+            _device_tensor(grad_log_sigma, "grad_log_sigma", _F32, (1,), self._env.Device)
+        args = (self._handle(), _ptr(flat), self.Count, _ptr(x), stride, m, _ptr(actions), _ptr(coef), _ptr(old), float(clip), float(entropy_coef),
+                _ptr(grad), _ptr(loss), _ptr(new))
+        if self.IsBox:
+            capi.check(self._lib.gymnet_vecenv_actor_box_policy_gradient(*args, _ptr(grad_log_sigma)))
+        else:
+            capi.check(self._lib.gymnet_vecenv_actor_policy_gradient(*args))
         self._set_grads(params, grad)
         return grad, loss
 
@@ -1484,18 +1472,7 @@ class Actor:
         A Box actor only, with sigma > 0."""
         if not self.IsBox:
             raise ValueError("BoxPolicyGradient belongs to a Box actor; this one chooses Discrete actions")
-        flat, params, m, stride, grad, loss = self._grad_call(net, self.Widths, self.Count, x, grad, (
-            ("actions", actions, "torch.float32"), ("coef", coef, "torch.float32"), ("logd_old", logd_old, "torch.float32"), ("logd", logd, "torch.float32")),
-            "BoxPolicyGradient")
-        if actions is None or coef is None:
-            raise ValueError("BoxPolicyGradient: actions and coef are required")
-        if grad_log_sigma is not None:
-            _logp_buffer(grad_log_sigma, (1,), "grad_log_sigma", self._env.Device)
-        capi.check(self._lib.gymnet_vecenv_actor_box_policy_gradient(self._handle(), _ptr(flat), self.Count, _ptr(x), stride, m, _ptr(actions), _ptr(coef),
-                                                                     _ptr(logd_old), float(clip), float(entropy_coef), _ptr(grad), _ptr(loss), _ptr(logd),
-                                                                     _ptr(grad_log_sigma)))
-        self._set_grads(params, grad)
-        return grad, loss
+        return self._policy_gradient("BoxPolicyGradient", net, x, actions, coef, logd_old, clip, entropy_coef, grad, logd, grad_log_sigma)
 
     def ValueGradient(self, net, x, target, grad=None, value=None):
         """The gradient of the critic's loss mean((v - target)^2) / 2 over the rows x with respect to `net`'s weights
@@ -1505,7 +1482,7 @@ class Actor:
         if getattr(self, "CriticWidths", None) is None:
             raise ValueError("ValueGradient needs a critic (SetCritic)")
         flat, params, m, stride, grad, loss = self._grad_call(net, self.CriticWidths, self.CriticCount, x, grad, (
-            ("target", target, "torch.float32"), ("value", value, "torch.float32")), "ValueGradient")
+            ("target", target, _F32), ("value", value, _F32)), "ValueGradient")
         if target is None:
             raise ValueError("ValueGradient: target is required")
         capi.check(self._lib.gymnet_vecenv_actor_value_gradient(self._handle(), _ptr(flat), self.CriticCount, _ptr(x), stride, m, _ptr(target),
@@ -1538,28 +1515,22 @@ class Actor:
         lr = {"sgd": 1e-3, "adadelta": 1.0, "adam": 1e-3}[rule] if lr is None else lr
         eps = {"sgd": 0.0, "adadelta": 1e-6, "adam": 1e-8}[rule] if eps is None else eps
         p0, p1 = {"sgd": (momentum, 0.0), "adadelta": (rho, 0.0), "adam": tuple(betas)}[rule]
-        params, handle_stream = None, torch.cuda.ExternalStream(env.DeviceView().stream or 0, device=f"cuda:{env.Device}")
+        params, flat, handle_stream = None, net, self._handle_stream()
         if hasattr(net, "parameters") and not hasattr(net, "data_ptr"):
             params = list(net.parameters())
             if not params or any(not p.is_cuda or p.dtype != torch.float32 for p in params):
                 raise ValueError("ApplyGradient: the network's parameters must be float32 on the handle's device")
             if grad is None and any(p.grad is None for p in params):
                 raise ValueError("ApplyGradient: grad is None and a parameter has no .grad")
-            with torch.cuda.stream(handle_stream):
-                flat = torch.cat([p.detach().reshape(-1) for p in params])
-                if grad is None:
-                    grad = torch.cat([p.grad.reshape(-1) for p in params])
-        else:
-            flat = net
-            if not hasattr(flat, "data_ptr") or getattr(flat, "dim", lambda: 0)() != 1:
-                raise ValueError("ApplyGradient: net must be a flat device float32 tensor or an nn.Sequential")
-        count = int(flat.shape[0])
-        _logp_buffer(flat, (count,), "net", env.Device)
-        _logp_buffer(grad, (count,), "grad", env.Device)
+            flat = self._concat(handle_stream, params)
+            if grad is None:
+                grad = self._concat(handle_stream, [p.grad for p in params])
+        count = int(_device_tensor(flat, "net", _F32, lambda s: len(s) == 1, env.Device, "(count,), or an nn.Sequential,").shape[0])
+        _device_tensor(grad, "grad", _F32, (count,), env.Device)
         if state is not None:
-            _logp_buffer(state, (2, count), "state", env.Device)
+            _device_tensor(state, "state", _F32, (2, count), env.Device)
         if norm is not None:
-            _logp_buffer(norm, (1,), "norm", env.Device)
+            _device_tensor(norm, "norm", _F32, (1,), env.Device)
         capi.check(self._lib.gymnet_vecenv_actor_apply_gradient(self._handle(), self._RULES[rule], _ptr(flat), count, _ptr(grad), _ptr(state), int(step),
                                                                 float(lr), float(p0), float(p1), float(eps), float(weight_decay), float(max_grad_norm),
                                                                 _ptr(norm)))
@@ -1598,7 +1569,7 @@ class Actor:
             import torch
             out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{env.Device}")
         else:
-            _logp_buffer(out, shape, "out", env.Device)
+            _device_tensor(out, "out", _F32, shape, env.Device)
         capi.check(self._lib.gymnet_vecenv_actor_history_device(self._handle(), _ptr(out), env.NumberOfEnvironments))
         return out
 
@@ -1607,12 +1578,8 @@ class Actor:
         Push(): one closed-loop decision; returns the device actions taken.  boot: an optional device float32 [N] that takes Boot()
         between the step and the push."""
         repeat = _repeat(repeat)
-        if logp is not None and self.IsBox:
-            raise ValueError("logp belongs to a Discrete actor; this one chooses Box actions")
-        if value is not None and self.IsBox:
-            raise ValueError("Step(value=) belongs to a Discrete actor; this one chooses Box actions (Value() serves it)")
-        if logd is not None and not self.IsBox:
-            raise ValueError("logd belongs to a Box actor; this one chooses Discrete actions (logp)")
+        if logp is not None or value is not None or logd is not None:
+            self._records_kind("Step", logp, value, logd)
         if boot is not None:
             self._value_buffer(boot, "boot")
         if self._out is None:
@@ -1660,7 +1627,7 @@ class GroupVectorEnv:
                 raise ValueError("len(devices) must equal num_members")
             devs = (C.c_int32 * num_members)(*[int(d) for d in devices])
         cfg = capi.GroupConfig(struct_size=C.sizeof(capi.GroupConfig), env_id=env_id, global_num_envs=int(global_num_envs),
-                               num_members=int(num_members), flags=flags, seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                               num_members=int(num_members), flags=flags, seed=_seed(seed),
                                devices=devs, gather=mode, max_episode_steps=int(max_episode_steps))
         self._g = C.c_void_p()
         capi.check(self._lib.gymnet_group_create(C.byref(cfg), C.byref(self._g)))
@@ -1702,7 +1669,7 @@ class GroupVectorEnv:
             pass
 
     def Seed(self, seed):
-        capi.check(self._lib.gymnet_group_seed(self._g, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        capi.check(self._lib.gymnet_group_seed(self._g, _seed(seed)))
 
     # host-boundary path over the whole batch
     def Reset(self):
@@ -1712,16 +1679,11 @@ class GroupVectorEnv:
 
     def Step(self, action):
         n = self.NumberOfEnvironments
-        if isinstance(action, enum.Enum):
-            action = int(action.value)
-        if isinstance(action, (int, np.integer)) and not isinstance(action, (bool, np.bool_)):
-            action = np.full(n, action, dtype=self._adtype)                          # IVecEnv.Step(int): broadcast
-        a = np.ascontiguousarray(np.asarray(action).reshape(-1).astype(self._adtype, copy=False))
-        if a.shape[0] != n:
-            raise ValueError("Number of actions passed should be equals to number of environments")
+        action, one = _one_action(action)
+        a = _lane_actions(np.full(n, action, dtype=self._adtype) if one else action, n, self._adtype)
         obs, rew, done = np.empty((n, self.ObsDim), self._dtype), np.empty(n, np.float32), np.empty(n, np.uint8)
         capi.check(self._lib.gymnet_group_step(self._g, _host(a), _host(obs), _host(rew), _host(done)))
-        return BatchStep(obs, rew, done.astype(bool), None, truncated=(done & 2) != 0)
+        return _batch_step(obs, rew, done)
 
     # device-resident path
     def ResetDevice(self):

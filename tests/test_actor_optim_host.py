@@ -22,6 +22,18 @@ def test_one_arity_in_every_binding(gymnet):
     assert callable(importlib.import_module(gymnet.__name__ + ".vector_env").Actor.ApplyGradient)
 
 
+def test_an_unknown_rule_is_refused_before_any_native_call(gymnet):
+    """the one refusal of ApplyGradient that needs no device (the handle's stream is asked for next)"""
+    import pytest
+    from test_actor_grad_host import NoNativeCalls
+    ve = importlib.import_module(gymnet.__name__ + ".vector_env")
+    actor = ve.Actor.__new__(ve.Actor)
+    actor.__dict__.update(_lib=NoNativeCalls(), _h=1, _env=None)
+    for rule in ("rmsprop", "Adam", None, 2):
+        with pytest.raises(ValueError, match="rule"):
+            actor.ApplyGradient(None, None, None, rule=rule)
+
+
 def test_additive_in_abi_6_a_null_handle_is_refused_and_the_unit_is_a_build_input(gymnet):
     capi, build = gymnet._capi, importlib.import_module(gymnet.__name__ + ".build")
     lib = capi.load_library()

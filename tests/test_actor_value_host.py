@@ -197,6 +197,18 @@ def test_value_arguments_are_checked_before_any_native_call(gymnet):
             actor.LoadCritic(_pairs(widths))
     with pytest.raises(ValueError, match="critic"):
         actor.LoadCritic(_pairs([9, 16, 1]))
+
+    class _Weights(_Tensor):                                         # a device tensor as Load / LoadCritic ask it: its element count too
+        def numel(self):
+            return int(np.prod(self.shape))
+    actor.Count, count = 154, actor.CriticCount                      # (8 * 16 + 16 + 16 * 2 + 2; the critic's: 8 * 16 + 16 + 16 + 1)
+    for load, n, call in ((actor.Load, 154, "gymnet_vecenv_actor_load_device"), (actor.LoadCritic, count, "gymnet_vecenv_actor_critic_load_device")):
+        for net in (_Weights((n + 1,)), _Weights((n - 1,)), _Weights((n,), "torch.float64"), _Weights((n,), "torch.float16"), _Weights((n,), contiguous=False)):
+            with pytest.raises(ValueError):
+                load(net)
+        for net in (_Weights((n,)), _Weights((n // 7, 7))):         # any shape of that many values
+            with pytest.raises(AssertionError, match="native call: " + call + "$"):
+                load(net)
     for value in bad:
         with pytest.raises(ValueError):
             actor.Value(out=value)

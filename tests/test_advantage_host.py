@@ -205,6 +205,23 @@ def test_advantage_arguments_are_checked_before_any_native_call(gymnet):
                    dict(returns=None), dict(last_value=None), dict(boot=None)):
         with pytest.raises(AssertionError, match=reach):
             env.AdvantagesDevice(**dict(good, **change))
+    # a tensor that names its device: another one than the handle's is refused; a handle that does not know its own takes the reward's
+    import types
+
+    def on(t, index):
+        t.device = types.SimpleNamespace(index=index)
+        return t
+    for name in ("reward", "done", "values", "last_value", "boot", "advantage", "returns"):
+        with pytest.raises(ValueError, match=name + " is on device 1, the handle on 0"):
+            env.AdvantagesDevice(**dict(good, **{name: on(_Tensor(good[name].shape, good[name].dtype), 1)}))
+    with pytest.raises(AssertionError, match=reach):
+        env.AdvantagesDevice(**dict(good, reward=on(f(T, N), 0)))
+    member = ve.VectorEnv.__new__(ve.VectorEnv)                     # a group member's view: Device is None
+    member.__dict__.update(_lib=OnlyTheView(), _h=1, _owns_handle=False, NumberOfEnvironments=N, Device=None)
+    with pytest.raises(ValueError, match="device is not known"):
+        member.AdvantagesDevice(**good)
+    with pytest.raises(AssertionError, match=reach):
+        member.AdvantagesDevice(**dict(good, reward=on(f(T, N), 1), done=on(u8(T, N), 0)))     # (nothing to compare a tensor's device with)
     import inspect
     sig = inspect.signature(ve.VectorEnv.AdvantagesDevice)
     assert list(sig.parameters)[1:] == ["reward", "done", "values", "advantage", "returns", "gamma", "lam", "last_value", "boot"]

@@ -264,6 +264,23 @@ def test_arguments_are_checked_before_any_native_call(gymnet):
         env.RolloutInputsDevice(**dict(good, rows=f(7, dtype="torch.int64")))
     empty = f(0, S * O)
     assert env.RolloutInputsDevice(**dict(good, rows=f(0, dtype="torch.int64", ptr=0), out=empty)) is empty          # no row: no native call
+    # a tensor that names its device: another one than the handle's is refused; a handle that does not know its own takes rec_obs's
+    import types
+
+    def on(t, index):
+        t.device = types.SimpleNamespace(index=index)
+        return t
+    for name in ("rec_obs", "rec_done", "history0", "out", "history_out"):
+        with pytest.raises(ValueError, match=name + " is on device 1, the handle on 0"):
+            env.RolloutInputsDevice(**dict(good, **{name: on(_Tensor(good[name].shape, good[name].dtype), 1)}))
+    with pytest.raises(ValueError, match="rows is on device 1, the handle on 0"):
+        env.RolloutInputsDevice(**dict(good, rows=on(f(7, dtype="torch.int64"), 1), out=f(7, S * O)))
+    member = ve.VectorEnv.__new__(ve.VectorEnv)                     # a group member's view: Device is None
+    member.__dict__.update(_lib=OnlyTheView(), _h=1, _owns_handle=False, NumberOfEnvironments=N, Device=None, ObsDim=O)
+    with pytest.raises(ValueError, match="device is not known"):
+        member.RolloutInputsDevice(**good)
+    with pytest.raises(AssertionError, match=reach):
+        member.RolloutInputsDevice(**dict(good, rec_obs=on(f(T, O, N), 1)))
     import inspect
     sig = inspect.signature(ve.VectorEnv.RolloutInputsDevice)
     assert list(sig.parameters)[1:] == ["rec_obs", "rec_done", "history0", "history", "rows", "out", "history_out"]
