@@ -242,6 +242,8 @@ PROTOTYPES = {
     "gymnet_vecenv_actor_policy_gradient": (C.c_int, [_H, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     "gymnet_vecenv_actor_box_policy_gradient": (C.c_int, [_H, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     "gymnet_vecenv_actor_value_gradient": (C.c_int, [_H, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "gymnet_vecenv_actor_q_gradient": (C.c_int, [_H, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_float, C.c_float,
+                                                 C.c_int32, _P, _P, _P, _P]),
     "gymnet_vecenv_actor_apply_gradient": (C.c_int, [_H, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                                      C.c_float, C.c_float, _P]),
     "gymnet_peer_buffer_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(IpcHandle)]),

@@ -210,6 +210,7 @@ namespace Gym.Envs.Amd {
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logp_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logp);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_box_policy_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_actions, IntPtr d_coef, IntPtr d_logd_old, float clip, float entropy_coef, IntPtr d_grad, IntPtr d_loss, IntPtr d_logd, IntPtr d_grad_log_sigma);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_gradient(IntPtr h, IntPtr d_weights, long count, IntPtr d_x, long x_stride, long m, IntPtr d_target, IntPtr d_grad, IntPtr d_loss, IntPtr d_value);
+        [DllImport(Lib)] public static extern int gymnet_vecenv_actor_q_gradient(IntPtr h, IntPtr d_weights, IntPtr d_target_weights, long count, IntPtr d_x, long x_stride, IntPtr d_x_next, long x_next_stride, long m, IntPtr d_actions, IntPtr d_reward, IntPtr d_done, float gamma, float huber_delta, int double_q, IntPtr d_y, IntPtr d_grad, IntPtr d_loss, IntPtr d_q);
         // the optimiser step: rule 0 SGD (p0 momentum), 1 AdaDelta (p0 rho), 2 Adam (p0, p1 betas); d_state float [2][count], the caller's, zeros when fresh
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_apply_gradient(IntPtr h, int rule, IntPtr d_weights, long count, IntPtr d_grad, IntPtr d_state, long step, float lr, float p0, float p1, float eps, float weight_decay, float max_grad_norm, IntPtr d_norm);
         [DllImport(Lib)] public static extern int gymnet_vecenv_actor_value_device(IntPtr h, IntPtr d_value);

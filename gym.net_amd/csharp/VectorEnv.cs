@@ -364,7 +364,15 @@ namespace Gym.Envs.Amd {
         public void ActorValueGradient(IntPtr dWeights, long count, IntPtr dX, long xStride, long m, IntPtr dTarget, IntPtr dGrad,
                                        IntPtr dLoss = default, IntPtr dValue = default) =>
             Native.Check(Native.gymnet_vecenv_actor_value_gradient(_h, dWeights, count, dX, xStride, m, dTarget, dGrad, dLoss, dValue));
-        public const int OptSgd = 0, OptAdaDelta = 1, OptAdam = 2;             // GYMNET_OPT_*
+        /// The Q-learning gradient of a Discrete actor's network (gymnet_vecenv_actor_q_gradient: the target and the Huber TD loss are
+        /// written out there): y = done ? reward : reward + gamma * max Q_T(xNext) (doubleQ: Q_T at the online argmax) into dY (float [m],
+        /// required, the call's workspace), the gradient of mean huber(Q(x)[a] - y) into dGrad.  dTargetWeights IntPtr.Zero: dWeights;
+        /// dLoss (float [1]) and dQ (float [m]) may be IntPtr.Zero.  dActions int [m], dReward float [m], dDone byte [m].
+        public void ActorQGradient(IntPtr dWeights, IntPtr dTargetWeights, long count, IntPtr dX, long xStride, IntPtr dXNext, long xNextStride, long m,
+                                   IntPtr dActions, IntPtr dReward, IntPtr dDone, IntPtr dY, IntPtr dGrad, float gamma = 0.99f, float huberDelta = 1f,
+                                   bool doubleQ = false, IntPtr dLoss = default, IntPtr dQ = default) =>
+            Native.Check(Native.gymnet_vecenv_actor_q_gradient(_h, dWeights, dTargetWeights, count, dX, xStride, dXNext, xNextStride, m, dActions, dReward, dDone, gamma, huberDelta, doubleQ ? 1 : 0, dY, dGrad, dLoss, dQ));
+        public const int OptSgd = 0, OptAdaDelta = 1, OptAdam = 2;            // GYMNET_OPT_*
         /// The optimiser step on the device: dWeights (float [count], count at most 8192, any flat vector — the policy's, the critic's, the
         /// one-element ln sigma) updated in place from dGrad under rule (OptSgd: p0 momentum; OptAdaDelta: p0 rho; OptAdam: p0, p1 the
         /// betas, step >= 1 the update's number), after clipping the gradient's 2-norm to maxGradNorm (0: no clipping) and adding

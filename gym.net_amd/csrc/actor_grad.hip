@@ -1,6 +1,6 @@
 // actor_grad.hip — the gradient of a minibatch loss with respect to an actor's or a critic's flat weights: the one dense contraction on
 // the library's hot path, and so its one use of the matrix cores.  The contract, loss for loss, is gymnet_vecenv_actor_policy_gradient /
-// gymnet_vecenv_actor_box_policy_gradient / gymnet_vecenv_actor_value_gradient in include/gymnet_amd.h; what a call is refused for and
+// gymnet_vecenv_actor_box_policy_gradient / gymnet_vecenv_actor_value_gradient / gymnet_vecenv_actor_q_gradient in include/gymnet_amd.h; what a call is refused for and
 // how its launch is sized is actor_grad.hpp.
 //
 // The network (at most 4 layers, widths <= 64, <= 8192 parameters) fits in LDS whole, so a workgroup keeps it there and walks row tiles:
@@ -25,6 +25,10 @@
 //                term and dZ_L are summed in float64 over the block (db_L[0] too) and rounded once.  The backward pass stays float32 MFMA.
 //                This instantiation takes 209 + 88 registers, one wave a SIMD where the others have two, and 3.7 times a float32 head's time at
 //                m = 2^20 (docs/ledger.md §46): what the accuracy costs.
+//   q targets    Q head only (gymnet_vecenv_actor_q_gradient), ahead of everything above: the block's own tiles of x_next forward-only under
+//                the online weights (double DQN's argmax) and under the target weights (y), the weights restaged in between, each row's
+//                index and target kept in d_y by the one thread that owns the row (q_targets).  Then the passes above run over x, the
+//                head being Huber's of Q(x)[a] - y: one live column of dZ_L, plain float32.  162 registers, two waves a SIMD.
 //   backward     last layer to first: dW_l += dZ_l^T A_l (M = outputs, N = inputs, K = the 16 rows: four instructions a tile) into
 //                accumulators that stay in registers across all of the block's tiles — at most 16 tiles a layer, tile q of a layer with
 //                wave q % 4 in slot q / 4; db_l as column sums by wave 0; dA_l = dZ_l W_l (M = rows, N = inputs, K = outputs) from the
@@ -39,7 +43,8 @@
 //
 // Out of scope: action dimensions above 1, a per-lane sigma, noise before the tanh head (a squashed Gaussian), PPO value clipping, a trunk
 // shared between actor and critic, gradients accumulated across calls, the optimiser step, fusing the rows= gather of
-// gymnet_rollout_inputs_device into this kernel, float64 networks.
+// gymnet_rollout_inputs_device into this kernel, float64 networks; and of the Q head: per-row importance weights (prioritised replay), a
+// soft (Polyak) target update, dueling heads, bootstrapping through a time limit (there is no boot for Q), a Box actor.
 #include "actor_grad.hpp"
 #include "actor_box_compose.hpp"
 #include "exp_neg.hpp"
@@ -71,6 +76,20 @@ struct GradArgs {
     int32_t box_head;
     BoxLogd ld;                                   // box: inv_sigma and c (box_logd_args)
 };
+
+// what the Q instantiation alone takes behind GradArgs (w: the online weights; x, actions, row_out = d_q as above)
+struct GradQArgs : GradArgs {
+    const float *w_target;                        // the target network's weights (== w: one network)
+    const float *x_next;
+    int64_t x_next_stride;
+    const float *reward;
+    const uint8_t *done;
+    float gamma, delta;
+    int32_t double_q;
+    float *y;                                     // [m]: row i is written and read by one thread of one block only (see `target`)
+};
+template <int HEAD> struct GradArgsOf { typedef GradArgs type; };
+template <> struct GradArgsOf<kGradQ> { typedef GradQArgs type; };
 
 // D += A B for A [16][4], B [4][16], D [16][16]: lane (i, k) = (lane % 16, lane / 16) gives A[i][k] and B[k][i], and holds D[4 * k + r][i] in d[r]
 __device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 d) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, d, 0, 0, 0); }
@@ -183,8 +202,143 @@ __device__ __forceinline__ double sum16(double v) {
     return v;
 }
 
-template <int HEAD>                                                         // a GradHead (an int: the listing names the instantiations <0>, <1>, <2>)
-__global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
+// the caller's flat W_l [out][in] at `w` into LDS at their pitch, and the thread's four bias values (output 16 * wave + li of each layer).
+// Only weight positions are written: the zeros between rows and behind the last matrix stay from the kernel's entry
+__device__ __forceinline__ void stage_weights(const GradNet &net, const float *w, float *sW, float (&bias)[kL], int tid, int wave, int li) {
+#pragma unroll
+    for (int l = 0; l < kL; ++l) {
+        bias[l] = 0.0f;
+        if (l < net.layers) {                                                // wave-uniform
+            const int32_t win = net.win[l], wout = net.wout[l];
+            const float *wl = w + net.off[l];
+            for (int e = tid; e < wout * win; e += 256) {
+                const int o = e / win, j = e - o * win;
+                sW[net.lds[l] + o * net.pitch[l] + j] = wl[e];
+            }
+            const int o = 16 * wave + li;
+            if (o < wout) bias[l] = wl[wout * win + o];
+        }
+    }
+    __syncthreads();
+}
+
+// A_0 = the tile of x that starts at row0, +0 beyond m and beyond win
+__device__ __forceinline__ void load_tile(const GradNet &net, const float *x, int64_t x_stride, int64_t row0, int64_t m, float *sA0, int tid) {
+#pragma unroll
+    for (int q = 0; q < kR * kGradMaxWidth / 256; ++q) {
+        const int e = tid + 256 * q, r = e >> 6, c = e & 63;
+        const int64_t row = row0 + r;
+        sA0[r * kP + c] = (row < m && c < net.win[0]) ? x[row * x_stride + c] : 0.0f;
+    }
+    __syncthreads();
+}
+
+// the forward pass over the tile in sA[0] under the weights in sW: A_{l+1} into sA[l + 1], the last layer's values into sZ
+__device__ __forceinline__ void forward_tile(const GradNet &net, const float *sW, float (*sA)[kR * kP], float *sZ, const float (&bias)[kL], int wave,
+                                             int li, int lk) {
+#pragma unroll
+    for (int l = 0; l < kL; ++l) {
+        if (l < net.layers) {                                                // wave-uniform
+            const int32_t win = net.win[l], wout = net.wout[l];
+            const bool hidden = l + 1 < net.layers;
+            if (16 * wave < wout) {                                          // wave-uniform: output tile `wave`
+                const int o = 16 * wave + li;
+                const bool ok = o < wout;
+                const float *wrow = sW + net.lds[l] + (ok ? o : 0) * net.pitch[l] + lk;
+                const float *arow = sA[l] + li * kP + lk;
+                const int nch = (win + 3) >> 2;
+                floatx4 z = floatx4{bias[l], bias[l], bias[l], bias[l]};
+#pragma unroll
+                for (int c = 0; c < kGradMaxWidth / 4; ++c) {
+                    if (c < nch) {                                           // wave-uniform
+                        const float wv = wrow[4 * c];
+                        z = mfma(arow[4 * c], ok ? wv : 0.0f, z);
+                    }
+                }
+                float *dst = (hidden && l + 1 < kL) ? sA[(l + 1) & (kL - 1)] : sZ;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = z[r];
+                    dst[(4 * lk + r) * kP + o] = hidden ? (v > 0.0f ? v : 0.0f) : v;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// the Q head's target passes over the block's own tiles, before its gradient pass: y_i into a.y (the contract: gymnet_vecenv_actor_q_gradient).
+//   select   double_q only, under the online weights: the forward over the x_next tiles; thread t < 16 of a tile takes the argmax of its
+//            row of sZ and leaves the index, as an int's bits, in a.y[row]
+//   target   under the target weights: the forward over the x_next tiles again; the same thread forms qn — the max, or the entry at the
+//            index it left, selected by compare — and writes y over it
+// Block b walks the tiles b, b + G, .. in every pass and thread t takes row t of a tile, so a.y[row] is written and read back by one thread
+// only, in program order: no fence, no grid sync, no second launch, nothing sized by m.  Weights are restaged (<= 38 KB from L2) only where
+// the next pass runs under another vector; `staged` names the one in LDS on return.  A done row's x_next may hold NaN: a row of the
+// MFMA forward reads its own row of A only, max and argmax let no NaN win, and y is a select
+__device__ __forceinline__ void q_targets(const GradQArgs &a, float *sW, float (*sA)[kR * kP], float *sZ, float (&bias)[kL], const float *&staged,
+                                          int tid, int wave, int li, int lk) {
+    const GradNet &net = a.net;
+    const int32_t n = a.action_n;
+    for (int pass = a.double_q ? 0 : 1; pass < 2; ++pass) {                  // block-uniform
+        const float *w = pass == 0 ? a.w : a.w_target;
+        if (w != staged) {                                                   // (every read of sW is behind a barrier: forward_tile ends on one)
+            stage_weights(net, w, sW, bias, tid, wave, li);
+            staged = w;
+        }
+        for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+            const int64_t row0 = tile * kR;
+            load_tile(net, a.x_next, a.x_next_stride, row0, a.m, sA[0], tid);
+            forward_tile(net, sW, sA, sZ, bias, wave, li, lk);
+            // the next tile's forward writes sZ only behind load_tile's barrier, which these threads reach after their reads
+            const int64_t row = row0 + tid;
+            if (tid < kR && row < a.m) {
+                float best = sZ[tid * kP];
+                int32_t at = 0;
+#pragma unroll
+                for (int k = 1; k < kActorMaxActions; ++k) {
+                    const float v = sZ[tid * kP + k];
+                    if (k < n && v > best) { best = v; at = k; }             // strict >, from index 0: the lowest index wins a tie, a NaN never
+                }
+                if (pass == 0) {
+                    a.y[row] = __builtin_bit_cast(float, at);
+                } else {
+                    float qn = best;
+                    if (a.double_q) {
+                        const int32_t pick = __builtin_bit_cast(int32_t, a.y[row]);
+#pragma unroll
+                        for (int k = 0; k < kActorMaxActions; ++k) qn = k == pick ? sZ[tid * kP + k] : qn;
+                    }
+                    const float r = a.reward[row];
+                    a.y[row] = a.done[row] != 0 ? r : __builtin_fmaf(a.gamma, qn, r);
+                }
+            }
+        }
+    }
+}
+
+// one row of the Huber TD loss: z -> dz (one live column, or NaN in every column of an action outside the space), the row's loss term, its q
+__device__ __forceinline__ float q_row(const GradQArgs &a, int64_t row, float (&z)[16], float &q) {
+    const int32_t n = a.action_n;
+    const int32_t act = a.actions[row];
+    const bool bad = act < 0 || act >= n;                                    // never an index: selected by compare below
+    const float nan = __builtin_bit_cast(float, 0x7FC00000u);
+    float qa = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kActorMaxActions; ++k) qa = k == act ? z[k] : qa;
+    q = bad ? nan : qa;
+    const float td = q - a.y[row];
+    const float mag = __builtin_fabsf(td);
+    // a NaN td fails the compare and stays NaN in the linear branch; delta = +inf takes the square for every finite td
+    const float term = mag <= a.delta ? 0.5f * (td * td) : a.delta * (mag - 0.5f * a.delta);
+    const float g = td > a.delta ? a.delta : (td < -a.delta ? -a.delta : td);                  // a NaN td passes both compares
+#pragma unroll
+    for (int k = 0; k < 16; ++k) z[k] = (k < kActorMaxActions && k < n) ? (bad ? nan : (k == act ? g : 0.0f)) : 0.0f;
+    return term;
+}
+
+template <int HEAD>                                                         // a GradHead (an int: the listing names the instantiations <0>, <1>, <2>, <3>)
+__global__ __launch_bounds__(256) void actor_grad_kernel(const typename GradArgsOf<HEAD>::type a) {
     __shared__ float sW[kGradLdsWeights];
     __shared__ float sA[kL][kR * kP];
     __shared__ float sZ[kR * kP];                                            // the last layer's values, then dZ_l [row][out]
@@ -202,21 +356,14 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
     for (int e = tid; e < kGradMaxWidth * kPT; e += 256) sZT[e] = 0.0f;
     __syncthreads();
     float bias[kL];
-#pragma unroll
-    for (int l = 0; l < kL; ++l) {
-        bias[l] = 0.0f;
-        if (l < net.layers) {                                                // wave-uniform
-            const int32_t win = net.win[l], wout = net.wout[l];
-            const float *wl = a.w + net.off[l];
-            for (int e = tid; e < wout * win; e += 256) {
-                const int o = e / win, j = e - o * win;
-                sW[net.lds[l] + o * net.pitch[l] + j] = wl[e];
-            }
-            const int o = 16 * wave + li;
-            if (o < wout) bias[l] = wl[wout * win + o];
-        }
+    if constexpr (HEAD == kGradQ) {
+        // the target passes first (q_targets), then the online weights for the gradient pass, restaged unless they are the ones in LDS
+        const float *staged = nullptr;
+        q_targets(a, sW, sA, sZ, bias, staged, tid, wave, li, lk);
+        if (staged != a.w) stage_weights(net, a.w, sW, bias, tid, wave, li);
+    } else {
+        stage_weights(net, a.w, sW, bias, tid, wave, li);
     }
-    __syncthreads();
 
     floatx4 acc[kL][4];                                                      // dW_l tile q = wave + 4 * slot, across all of the block's tiles
 #pragma unroll
@@ -229,44 +376,9 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
 
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
         const int64_t row0 = tile * kR;
-        // ---- A_0 = the tile of x, +0 beyond m and beyond win
-#pragma unroll
-        for (int q = 0; q < kR * kGradMaxWidth / 256; ++q) {
-            const int e = tid + 256 * q, r = e >> 6, c = e & 63;
-            const int64_t row = row0 + r;
-            sA[0][r * kP + c] = (row < a.m && c < net.win[0]) ? a.x[row * a.x_stride + c] : 0.0f;
-        }
-        __syncthreads();
-        // ---- forward
-#pragma unroll
-        for (int l = 0; l < kL; ++l) {
-            if (l < net.layers) {                                            // wave-uniform
-                const int32_t win = net.win[l], wout = net.wout[l];
-                const bool hidden = l + 1 < net.layers;
-                if (16 * wave < wout) {                                      // wave-uniform: output tile `wave`
-                    const int o = 16 * wave + li;
-                    const bool ok = o < wout;
-                    const float *wrow = sW + net.lds[l] + (ok ? o : 0) * net.pitch[l] + lk;
-                    const float *arow = sA[l] + li * kP + lk;
-                    const int nch = (win + 3) >> 2;
-                    floatx4 z = floatx4{bias[l], bias[l], bias[l], bias[l]};
-#pragma unroll
-                    for (int c = 0; c < kGradMaxWidth / 4; ++c) {
-                        if (c < nch) {                                       // wave-uniform
-                            const float wv = wrow[4 * c];
-                            z = mfma(arow[4 * c], ok ? wv : 0.0f, z);
-                        }
-                    }
-                    float *dst = (hidden && l + 1 < kL) ? sA[(l + 1) & (kL - 1)] : sZ;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float v = z[r];
-                        dst[(4 * lk + r) * kP + o] = hidden ? (v > 0.0f ? v : 0.0f) : v;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        // ---- A_0 = the tile of x, then the forward pass
+        load_tile(net, a.x, a.x_stride, row0, a.m, sA[0], tid);
+        forward_tile(net, sW, sA, sZ, bias, wave, li, lk);
         // ---- box, refine: the hidden layers once more in float64 on the vector unit.  A_{l+1} = hi + lo, hi the float32 value the MFMA
         // pass left in sA, lo = relu(float64 row) - hi in the dZ tiles, free until the head: lo_{l+1} in sZT for even l, in sZ for odd.
         // Thread (row li, outputs lk + 4 * wave + 16 * q): activations along a row, four weight rows a wave, no bank conflicts
@@ -315,6 +427,12 @@ __global__ __launch_bounds__(256) void actor_grad_kernel(const GradArgs a) {
                     float logp;
                     loss = loss + policy_row(a, row, z, logp);
                     if (a.row_out) a.row_out[row] = logp;
+                } else if constexpr (HEAD == kGradQ) {
+#pragma unroll
+                    for (int k = 0; k < kActorMaxActions; ++k) z[k] = sZ[tid * kP + k];
+                    float q;
+                    loss = loss + q_row(a, row, z, q);
+                    if (a.row_out) a.row_out[row] = q;
                 } else if constexpr (HEAD == kGradBox) {
                     // raw = A_L W_L[0] + b_L[0] in float64 from hi + lo; the other threads' lo rows are read before any dZ is written
                     // below (one wave, in program order)
@@ -483,7 +601,7 @@ int grad_scratch(gymnet_vecenv *h, float *&scratch) {
     return GYMNET_OK;
 }
 
-constexpr const char *kGradCallName[] = {"actor_value_gradient", "actor_policy_gradient", "actor_box_policy_gradient"};
+constexpr const char *kGradCallName[] = {"actor_value_gradient", "actor_policy_gradient", "actor_box_policy_gradient", "actor_q_gradient"};
 
 // d_actions: int32 for the Discrete call, float32 for the Box call; d_grad_log_sigma: the Box call's, or null
 int actor_gradient(gymnet_vecenv *h, GradHead head, const float *d_weights, int64_t count, const float *d_x, int64_t x_stride, int64_t m,
@@ -525,6 +643,34 @@ int actor_gradient(gymnet_vecenv *h, GradHead head, const float *d_weights, int6
     return GYMNET_OK;
 }
 
+// the Q-learning call: the same launch form, partials and reduce kernel as the calls above; the stored temperature is not read
+int actor_q_gradient(gymnet_vecenv *h, const float *d_weights, const float *d_target_weights, int64_t count, const float *d_x, int64_t x_stride,
+                     const float *d_x_next, int64_t x_next_stride, int64_t m, const int32_t *d_actions, const float *d_reward, const uint8_t *d_done,
+                     float gamma, float huber_delta, int32_t double_q, float *d_y, float *d_grad, float *d_loss, float *d_q) {
+    const Actor *ac = h->actor;
+    const bool has_net = ac && ac->net.layers > 0;
+    const ActorQGradCall c{ac != nullptr, ac && ac->box, ac ? ac->count : 0, has_net ? ac->net.win[0] : 0, count, x_stride, x_next_stride, m,
+                           (uintptr_t)d_weights, (uintptr_t)d_x, (uintptr_t)d_x_next, (uintptr_t)d_actions, (uintptr_t)d_reward, (uintptr_t)d_done,
+                           (uintptr_t)d_y, (uintptr_t)d_grad, gamma, huber_delta};
+    if (const char *why = actor_q_grad_refusal(c)) return fail(h, GYMNET_ERR_INVALID_ARG, "%s: %s", kGradCallName[kGradQ], why);
+    GradQArgs a{};
+    if (grad_net_shape(a.net, ac->net.layers, ac->net.win, ac->net.wout) > kGradLdsWeights || a.net.count != count)
+        return fail(h, GYMNET_ERR_HIP, "actor gradient: the network does not fit the kernel's LDS plan");
+    const ActorGradForm f = pick_actor_grad_form(m);
+    ST_TRY(grad_scratch(h, a.scratch));
+    a.w = d_weights; a.x = d_x; a.x_stride = x_stride; a.m = m; a.tiles = f.tiles;
+    a.actions = d_actions; a.action_n = ac->net.action_n; a.row_out = d_q;
+    a.w_target = d_target_weights ? d_target_weights : d_weights;
+    a.x_next = d_x_next; a.x_next_stride = x_next_stride; a.reward = d_reward; a.done = d_done;
+    a.gamma = gamma; a.delta = huber_delta; a.double_q = double_q != 0; a.y = d_y;
+    hipLaunchKernelGGL(actor_grad_kernel<kGradQ>, dim3((unsigned)f.blocks), dim3(256), 0, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(actor_grad_reduce_kernel, dim3((unsigned)((count + 1 + 255) / 256)), dim3(256), 0, h->stream, a.scratch, f.blocks, (int32_t)count,
+                       (double)m, d_grad, d_loss, (float *)nullptr, 0.0f);
+    HIP_TRY(h, hipGetLastError());
+    return GYMNET_OK;
+}
+
 }  // namespace
 
 }  // namespace gymnet
@@ -557,6 +703,17 @@ int gymnet_vecenv_actor_box_policy_gradient(gymnet_vecenv *h, const float *d_wei
     ENTER(h);
     return actor_gradient(h, kGradBox, d_weights, count, d_x, x_stride, m, d_actions, d_coef, d_logd_old, clip, entropy_coef, d_grad, d_loss, d_logd,
                           d_grad_log_sigma);
+    });
+}
+
+int gymnet_vecenv_actor_q_gradient(gymnet_vecenv *h, const float *d_weights, const float *d_target_weights, int64_t count, const float *d_x,
+                                   int64_t x_stride, const float *d_x_next, int64_t x_next_stride, int64_t m, const int32_t *d_actions,
+                                   const float *d_reward, const uint8_t *d_done, float gamma, float huber_delta, int32_t double_q, float *d_y,
+                                   float *d_grad, float *d_loss, float *d_q) {
+    return guarded([&]() -> int {
+    ENTER(h);
+    return actor_q_gradient(h, d_weights, d_target_weights, count, d_x, x_stride, d_x_next, x_next_stride, m, d_actions, d_reward, d_done, gamma,
+                            huber_delta, double_q, d_y, d_grad, d_loss, d_q);
     });
 }
 

@@ -1,5 +1,5 @@
 // actor_grad.hpp — what a call to gymnet_vecenv_actor_policy_gradient / gymnet_vecenv_actor_box_policy_gradient /
-// gymnet_vecenv_actor_value_gradient is refused for, how its rows are dealt to the workgroups of actor_grad.hip, and where that kernel
+// gymnet_vecenv_actor_value_gradient / gymnet_vecenv_actor_q_gradient is refused for, how its rows are dealt to the workgroups of actor_grad.hip, and where that kernel
 // keeps a network in LDS.  Host-only and pure as rollout_inputs.hpp is: no HIP type, no global, nothing read but the arguments
 // (rollout_plan.hpp, as pure, for the sigmas a log-density is defined for).  This is the only place that refuses a call or sizes its launch.
 #pragma once
@@ -42,7 +42,7 @@ constexpr int64_t kGradSigmaAt = (int64_t)kGradBlocks * (kGradMaxParams + 1);
 constexpr int64_t kGradScratchFloats = kGradSigmaAt + kGradBlocks;
 
 // the loss a call differentiates, and so the head the main kernel is instantiated for
-enum GradHead : int { kGradValue = 0, kGradPolicy = 1, kGradBox = 2 };        // _value_gradient, _policy_gradient, _box_policy_gradient
+enum GradHead : int { kGradValue = 0, kGradPolicy = 1, kGradBox = 2, kGradQ = 3 };        // _value_gradient, _policy_gradient, _box_policy_gradient, _q_gradient
 
 struct ActorGradCall {                            // the call's arguments and what it reads of the handle; pointers as integers, 0 = NULL
     GradHead head;
@@ -73,6 +73,33 @@ inline const char *actor_grad_refusal(const ActorGradCall &c) {
         return c.head == kGradBox ? "clip must be in [0, 1) with d_logd_old" : "clip must be in [0, 1) with d_logp_old";
     if (policy && !std::isfinite(c.entropy_coef)) return "entropy_coef is not finite";
     if (c.m > INT64_MAX / 4 / c.x_stride) return "m x x_stride overflows";
+    return nullptr;
+}
+
+// the Q-learning call (gymnet_vecenv_actor_q_gradient): its arguments and what it reads of the handle, as ActorGradCall
+struct ActorQGradCall {
+    bool has_actor, box;
+    int64_t configured_count;                     // the parameters of the Discrete actor's network
+    int32_t win0;                                 // its input width
+    int64_t count, x_stride, x_next_stride, m;
+    uintptr_t weights, x, x_next, actions, reward, done, y, grad;            // (d_target_weights, d_loss and d_q may be NULL)
+    float gamma, huber_delta;
+};
+
+// NULL: the call is accepted; else why it is refused (GYMNET_ERR_INVALID_ARG).  Nothing is written by a refused call.
+inline const char *actor_q_grad_refusal(const ActorQGradCall &c) {
+    if (!c.has_actor) return "no actor configured";
+    if (c.box) return "the Q gradient serves a Discrete actor; this handle's actor chooses Box actions";
+    if (c.count != c.configured_count) return "count != the actor's parameters";
+    if (c.m < 1) return "m < 1";
+    if (c.x_stride < c.win0) return "x_stride < widths[0]";
+    if (c.x_next_stride < c.win0) return "x_next_stride < widths[0]";
+    if (!c.weights || !c.x || !c.x_next || !c.actions || !c.reward || !c.done || !c.y || !c.grad)
+        return "d_weights / d_x / d_x_next / d_actions / d_reward / d_done / d_y / d_grad is null";
+    if (!(c.gamma >= 0.0f && c.gamma <= 1.0f)) return "gamma must be in [0, 1]";
+    if (!(c.huber_delta > 0.0f)) return "huber_delta must be > 0 (+inf: the squared error)";
+    if (c.m > INT64_MAX / 4 / c.x_stride) return "m x x_stride overflows";
+    if (c.m > INT64_MAX / 4 / c.x_next_stride) return "m x x_next_stride overflows";
     return nullptr;
 }
 

@@ -1381,13 +1381,10 @@ class Actor:
         with torch.cuda.stream(stream):
             return torch.cat([t.detach().reshape(-1) for t in tensors])
 
-    def _grad_call(self, net, widths, count, x, grad, rows, what):
-        """what PolicyGradient and ValueGradient share, before any native call: the flat device weights of `net` (an nn.Sequential's
-        parameters are concatenated on the handle's stream: no host trip), x's row stride and m, grad, and the per-row tensors checked"""
+    def _flat_net(self, net, widths, count, what, name="net"):
+        """(flat device weights, the parameters or None) of `net`: a flat device float32 tensor [count], or an nn.Sequential of `widths`,
+        whose parameters are concatenated on the handle's stream: no host trip"""
         import torch
-        env = self._env
-        dev = f"cuda:{env.Device}"
-        params = None
         if hasattr(net, "parameters") and not hasattr(net, "data_ptr"):
             mods = [mod for mod in net.children() if isinstance(mod, torch.nn.Linear)]
             got = tuple([mods[0].in_features] + [mod.out_features for mod in mods]) if mods else ()
@@ -1396,14 +1393,27 @@ class Actor:
             params = [p for mod in mods for p in (mod.weight, mod.bias)]
             if any(not p.is_cuda or p.dtype != torch.float32 for p in params):
                 raise ValueError(f"{what}: the network's parameters must be float32 on the handle's device")
-            flat = self._concat(self._handle_stream(), params)
-        else:
-            flat = _device_tensor(net, "net", _F32, (count,), env.Device)
+            return self._concat(self._handle_stream(), params), params
+        return _device_tensor(net, name, _F32, (count,), self._env.Device), None
+
+    @staticmethod
+    def _input_rows(x, widths, what, name="x"):
+        """(m, row stride) of a tensor of network inputs: device float32 [m, widths[0]], rows at any stride"""
         if not hasattr(x, "data_ptr") or str(getattr(x, "dtype", None)) != "torch.float32" or not getattr(x, "is_cuda", False) or x.dim() != 2:
-            raise ValueError(f"{what}: x must be a device float32 tensor [m, {widths[0]}]")
+            raise ValueError(f"{what}: {name} must be a device float32 tensor [m, {widths[0]}]")
         m = int(x.shape[0])
         if m < 1 or int(x.shape[1]) != widths[0] or x.stride(1) != 1 or x.stride(0) < widths[0]:
-            raise ValueError(f"{what}: x must be [m >= 1, {widths[0]}] with unit column stride and a row stride >= {widths[0]}, got {tuple(x.shape)} strides {tuple(x.stride())}")
+            raise ValueError(f"{what}: {name} must be [m >= 1, {widths[0]}] with unit column stride and a row stride >= {widths[0]}, got {tuple(x.shape)} strides {tuple(x.stride())}")
+        return m, int(x.stride(0))
+
+    def _grad_call(self, net, widths, count, x, grad, rows, what):
+        """what PolicyGradient and ValueGradient share, before any native call: the flat device weights of `net` (an nn.Sequential's
+        parameters are concatenated on the handle's stream: no host trip), x's row stride and m, grad, and the per-row tensors checked"""
+        import torch
+        env = self._env
+        dev = f"cuda:{env.Device}"
+        flat, params = self._flat_net(net, widths, count, what)
+        m, _ = self._input_rows(x, widths, what)
         for name, t, dtype in rows:
             if t is not None:
                 _device_tensor(t, f"{what}: {name}", dtype, (m,))           # (no device: these rows were never held to the handle's)
@@ -1490,7 +1500,40 @@ class Actor:
         self._set_grads(params, grad)
         return grad, loss
 
-    _RULES = {"sgd": 0, "adadelta": 1, "adam": 2}                      # GYMNET_OPT_*
+    def QGradient(self, net, x, actions, reward, done, x_next, target_net=None, gamma=0.99, huber_delta=1.0, double=False, grad=None, y=None, q=None):
+        """The Q-learning update's gradient for the actor that acts by epsilon-greedy argmax (DQN; double=True: double DQN), on the handle's
+        stream with no synchronise (gymnet_vecenv_actor_q_gradient: the target and the loss are written out there).  Per row
+        y = done ? reward : reward + gamma * max_k Q_T(x_next)[k] (double: Q_T at the argmax of the online Q(x_next)), a constant of the
+        loss mean(huber(Q(x)[action] - y, huber_delta)); huber_delta = inf is the squared error.  Returns (grad, loss) as PolicyGradient.
+          net         the online network: a flat device float32 tensor [Count] or an nn.Sequential, whose parameters get .grad
+          target_net  the target network in either form (it never gets .grad); None: net
+          x, x_next   device float32 [m, history * obs_dim], rows at any stride: RolloutInputsDevice(rows=idx) and (rows=idx + N)
+          actions     device int32 [m];  reward device float32 [m];  done device uint8 [m] (a rollout's records at idx; either done bit
+                      ends the bootstrap).  For an n-step target pass the summed discounted reward and gamma ** n
+          y           device float32 [m] that receives the targets (the call's workspace: it must not overlap an input); None: a new one
+          q           optional device float32 [m] that receives Q(x)[action]
+        A Discrete actor only."""
+        if self.IsBox:
+            raise ValueError("QGradient belongs to a Discrete actor; this one chooses Box actions")
+        import torch
+        what = "QGradient"
+        if actions is None or reward is None or done is None:
+            raise ValueError(f"{what}: actions, reward and done are required")
+        m_next, stride_next = self._input_rows(x_next, self.Widths, what, "x_next")
+        target = None if target_net is None else self._flat_net(target_net, self.Widths, self.Count, what, "target_net")[0]
+        flat, params, m, stride, grad, loss = self._grad_call(net, self.Widths, self.Count, x, grad, (
+            ("actions", actions, _I32), ("reward", reward, _F32), ("done", done, _U8), ("y", y, _F32), ("q", q, _F32)), what)
+        if m_next != m:
+            raise ValueError(f"{what}: x_next must have x's {m} rows, got {m_next}")
+        if y is None:
+            y = torch.empty(m, dtype=torch.float32, device=grad.device)
+        capi.check(self._lib.gymnet_vecenv_actor_q_gradient(self._handle(), _ptr(flat), _ptr(target), self.Count, _ptr(x), stride, _ptr(x_next), stride_next, m,
+                                                            _ptr(actions), _ptr(reward), _ptr(done), float(gamma), float(huber_delta), int(bool(double)),
+                                                            _ptr(y), _ptr(grad), _ptr(loss), _ptr(q)))
+        self._set_grads(params, grad)
+        return grad, loss
+
+    _RULES = {"sgd": 0, "adadelta": 1, "adam": 2}                    # GYMNET_OPT_*
 
     def ApplyGradient(self, net, grad, state, rule="adam", step=1, lr=None, momentum=0.0, rho=0.9, betas=(0.9, 0.999), eps=None, weight_decay=0.0,
                       max_grad_norm=0.0, norm=None):

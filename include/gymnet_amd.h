@@ -1157,6 +1157,47 @@ int gymnet_vecenv_actor_box_policy_gradient(gymnet_vecenv *h, const float *d_wei
                                             const float *d_logd_old, float clip, float entropy_coef,
                                             float *d_grad, float *d_loss, float *d_logd, float *d_grad_log_sigma);
 
+/* The Q-learning call (additive: the ABI version stays 6): the temporal-difference target from a target network and the gradient of the
+ * Huber TD loss through the online network, for the Discrete actor whose behaviour policy is the epsilon-greedy argmax of the act calls
+ * (DQN; double DQN with double_q != 0).  Everything said above of the policy call holds — the shape (the actor's widths and action_n)
+ * and the stream come from the handle, both weight vectors are the caller's in the config layout, the same kernel, launch rule, order
+ * and determinism, d_grad / d_loss as there — with these differences.  The stored temperature is not used.
+ *     d_target_weights [count]   the target network; NULL means d_weights
+ *     d_x, d_x_next              m rows each, at x_stride and x_next_stride floats: gymnet_rollout_inputs_device at d_rows = idx and at
+ *                                idx + count-of-lanes (the next step's row of the same lane)
+ *     d_actions int32 [m], d_reward float32 [m], d_done uint8 [m]    the recorded rollout's rows at idx
+ *     d_y float32 [m]            REQUIRED: receives the targets y_i, and is the call's workspace before that; it must not overlap any input
+ *     d_q float32 [m]            may be NULL: receives q_i
+ * Per row i, float32 with every operation rounding on its own; Q = the network under d_weights, Q_T under d_target_weights:
+ *     double_q == 0:  qn = max_k Q_T(x_next_i)[k]
+ *     double_q != 0:  k* = argmax_k Q(x_next_i)[k],  qn = Q_T(x_next_i)[k*]
+ *                     max and argmax scan k = 0 .. action_n - 1 with a strict > from index 0: the lowest index wins a tie (the act
+ *                     calls' IndexOf(Max())) and a NaN never wins
+ *     y_i  = d_done[i] != 0 ? reward_i : fmaf(gamma, qn, reward_i)       a select, not a product: a done row's x_next may hold anything,
+ *                     NaN included.  Either done bit stops the bootstrap — a time limit counts as a termination, as for
+ *                     gymnet_advantages_device without d_boot; under GYMNET_FLAG_AUTORESET the row after a done belongs to the next
+ *                     episode.  y is a constant of the loss (semi-gradient).
+ *     q_i  = Q(x_i)[a_i]      selected by compare, never used as an index: an action outside [0, action_n) makes that row's q, the
+ *                     loss and the whole gradient NaN; no other row's q and no y changes
+ *     td   = q_i - y_i
+ *     term = |td| <= huber_delta ? td * td / 2 : huber_delta * (|td| - huber_delta / 2);   d term / d q = clamp(td, -huber_delta, huber_delta);
+ *                     a NaN td stays NaN in both; huber_delta = +inf is the plain squared error
+ *     loss = (1 / m) sum_i term_i
+ *   An n-step target needs nothing more: the caller passes the summed discounted reward and gamma^n.
+ *   The three forward passes (two with double_q == 0, one where the target weights are also d_weights) run inside the one launch: a
+ *   workgroup walks its own row tiles under each weight vector in turn, and d_y[i] is written and read by one thread only.
+ * GYMNET_ERR_INVALID_ARG, nothing touched: no actor; a Box actor; count != the actor's count; m < 1; x_stride or x_next_stride <
+ *   widths[0]; a NULL d_weights, d_x, d_x_next, d_actions, d_reward, d_done, d_y or d_grad; gamma outside [0, 1] or not finite;
+ *   huber_delta not > 0 (NaN included); m * x_stride or m * x_next_stride leaving an int64.
+ * Out of scope: per-row importance weights (prioritised replay), a soft (Polyak) target update — the hard update is a device-to-device
+ *   copy of the weights —, dueling heads, bootstrapping through a time limit (there is no d_boot for Q), a Box actor, and what the
+ *   policy call lists. */
+int gymnet_vecenv_actor_q_gradient(gymnet_vecenv *h, const float *d_weights, const float *d_target_weights, int64_t count,
+                                   const float *d_x, int64_t x_stride, const float *d_x_next, int64_t x_next_stride, int64_t m,
+                                   const int32_t *d_actions, const float *d_reward, const uint8_t *d_done,
+                                   float gamma, float huber_delta, int32_t double_q,
+                                   float *d_y, float *d_grad, float *d_loss, float *d_q);
+
 /* ---- the optimiser step: one update of one flat parameter vector from its gradient, on the device ------------------------------
  * One handle call (additive: the ABI version stays 6) that applies d_grad to d_weights in place under one of three rules, after an
  * optional clip of the gradient's 2-norm: what follows a gradient call, so that a host without torch trains with no trip to the host.

@@ -456,6 +456,17 @@ public:
                             float *d_grad, float *d_loss = nullptr, float *d_value = nullptr) {
         check(gymnet_vecenv_actor_value_gradient(h_, d_weights, count, d_x, x_stride, m, d_target, d_grad, d_loss, d_value));
     }
+    // The Q-learning gradient of a Discrete actor's network (gymnet_vecenv_actor_q_gradient: the target and the Huber TD loss are written
+    // out there): y_i = done_i ? reward_i : reward_i + gamma * max_k Q_T(x_next_i)[k] (double_q: Q_T at the online argmax) into d_y [m],
+    // which is required and is the call's workspace, and the gradient of mean huber(Q(x_i)[a_i] - y_i) into d_grad.  d_target_weights null:
+    // d_weights; d_loss [1] and d_q [m] may be null.  One launch on the handle's stream, no synchronise.
+    void ActorQGradient(const float *d_weights, const float *d_target_weights, int64_t count, const float *d_x, int64_t x_stride, const float *d_x_next,
+                        int64_t x_next_stride, int64_t m, const int32_t *d_actions, const float *d_reward, const uint8_t *d_done, float *d_y,
+                        float *d_grad, float gamma = 0.99f, float huber_delta = 1.0f, bool double_q = false, float *d_loss = nullptr,
+                        float *d_q = nullptr) {
+        check(gymnet_vecenv_actor_q_gradient(h_, d_weights, d_target_weights, count, d_x, x_stride, d_x_next, x_next_stride, m, d_actions, d_reward,
+                                             d_done, gamma, huber_delta, double_q ? 1 : 0, d_y, d_grad, d_loss, d_q));
+    }
     // The optimiser step on the device: d_weights [count] (count <= 8192; any flat vector — the policy's, the critic's, the one-element
     // ln sigma) updated in place from d_grad under rule (GYMNET_OPT_SGD: p0 momentum; _ADADELTA: p0 rho; _ADAM: p0, p1 the betas, step >= 1
     // the update's number), after clipping the gradient's 2-norm to max_grad_norm (0: none) and adding weight_decay * w
